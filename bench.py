@@ -1,7 +1,7 @@
 """iRTF benchmark of the LF-MMI training step (BASELINE.json: 3x512 BLSTM LF-MMI, LibriSpeech-shaped
 utterances, batch 4 x var-len per GPU, train_chain.py semantics) on N MI355X.
 
-    python bench.py --gpus 1 --steps 20 --warmup 3
+    python bench.py --gpus 1 --steps 20 --warmup 3 [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -902,6 +902,44 @@ def run_secondaries():
     return out
 
 
+def dump_outputs(tr, out_dir, n_cols=512, n_rows=8192, n_flat=1 << 20):
+    """--dump-outputs: what the last timed step handed its caller, as float32 / float64 .npy files: the loss, the global
+    gradient norm and the optimiser step that produced them; the logits of the real (unpadded) frames on a fixed, seeded
+    set of n_cols output columns (all frames in order, or a seeded sample of n_rows of them when there are more); the
+    updated parameters and their gradients on a fixed, seeded set of n_flat positions of the model's flat buffers.
+    About 22 MB at the default batch, 33 MB at most whatever the batch.  The inputs are seeded, so two builds run with the
+    same arguments can be compared file by file."""
+    os.makedirs(out_dir, exist_ok=True)
+    last = tr.last
+    logits = last["logits"]                                     # [T, B, P] time-major
+    cols = np.sort(np.random.default_rng(0).choice(logits.shape[2], min(n_cols, logits.shape[2]), replace=False))
+    ci = torch.from_numpy(cols).to(logits.device)
+    real = torch.cat([logits[:s.frames_per_sequence, n].index_select(1, ci) for n, s in enumerate(last["sups"])])
+    rows = np.arange(real.shape[0])
+    if rows.size > n_rows:
+        rows = np.sort(np.random.default_rng(2).choice(rows.size, n_rows, replace=False))
+        real = real.index_select(0, torch.from_numpy(rows).to(real.device))
+    p, g = tr.model.flat_parameters()
+    idx = np.sort(np.random.default_rng(1).choice(p.numel(), min(n_flat, p.numel()), replace=False))
+    ii = torch.from_numpy(idx).to(p.device)
+    arrays = {
+        "loss": np.array([float(last["loss"].item())], dtype=np.float64),
+        "grad_norm": np.array([float(last["norm"].item())], dtype=np.float64),
+        "step": np.array([tr.step_no], dtype=np.float64),
+        "logits_sample": real.detach().float().cpu().numpy(),
+        "logits_sample_rows": rows.astype(np.float64),
+        "logits_sample_columns": cols.astype(np.float64),
+        "params_sample": p.detach().index_select(0, ii).float().cpu().numpy(),
+        "grads_sample": g.detach().index_select(0, ii).float().cpu().numpy(),
+        "flat_sample_positions": idx.astype(np.float64),
+    }
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= 64 << 20, total
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    log("outputs of the last timed step (optimiser step %d, %.1f MB) written to %s" % (tr.step_no, total / 2 ** 20, out_dir))
+
+
 def log(msg):
     sys.stderr.write("[bench %.1fs] %s\n" % (time.time() - T_START, msg))
     sys.stderr.flush()
@@ -945,7 +983,14 @@ def main():
                     "(PK2_SE_CRITERION=smbr|mpfe for the other criteria)")
     ap.add_argument("--ce", action="store_true", help="secondary workload configs[1]: 3x512 BLSTM CE, 256 x 80-frame "
                     "chunks per step (not the headline metric)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one "
+                    "computed (loss, gradient norm, seeded samples of logits, parameters and gradients) as DIR/<name>.npy; "
+                    "LF-MMI workload only (the default BLSTM or --transformer)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and (args.ce or args.se or args.gemm_only or args.lstm_only or args.den_only):
+        ap.error("--dump-outputs: only the LF-MMI training step (default or --transformer) writes its outputs")
     global DEN_TOPOLOGY, S_DEN, A_DEN
     if args.den_states:
         S_DEN = args.den_states
@@ -1089,6 +1134,8 @@ def main():
     dt = time.perf_counter() - t0
     device_allocs = int(torch.cuda.memory_stats(dev).get("num_device_alloc", 0) - allocs0)      # hipMalloc calls inside the timed region
     log("timed region done: %.3f s (%d device allocations inside it)" % (dt, device_allocs))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(tr, args.dump_outputs)
     exchange_timing, tr.opt.timing = tr.opt.timing, None
     scaling = scaling_report(step_events, exchange_timing, audio, dev, rank, world)
     irtf_bucketed = None

@@ -492,9 +492,14 @@ __global__ void __launch_bounds__(kDenBwdThreads) den_bwd_step(const DenParams* 
           for (int n = 0; n < NG; ++n) sum[n] += prob * xv[n] * (gat[n] ? bv[j][n] + lB[n] : cst[n]);
         } else {
           // rec = {src, dst, prob, pi*prob}: acc[pdf-row] += alpha'[t][src] * prob * beta[t+1][dst]
+          // An arc out of a state the sequence cannot be in yet (alpha' = 0) adds exactly nothing: skipped, because the
+          // scaled beta of such a state may have overflowed to inf in float32, and 0 * inf would be NaN.  (Only the exact
+          // zero is handled: an overflowed beta behind a tiny nonzero weight still gives inf, as in Kaldi's scaling.)
 #pragma unroll
-          for (int n = 0; n < NG; ++n)
-            sum[n] += (av[j][n] * prob + lk[n] * pr) * (gat[n] ? bv[j][n] + lB[n] : cst[n]);
+          for (int n = 0; n < NG; ++n) {
+            const float w = av[j][n] * prob + lk[n] * pr;
+            if (w != 0.f) sum[n] += w * (gat[n] ? bv[j][n] + lB[n] : cst[n]);
+          }
         }
         if ((mask >> (jg * KG + j)) & 1u) {
 #pragma unroll
@@ -522,7 +527,10 @@ __global__ void __launch_bounds__(kDenBwdThreads) den_bwd_step(const DenParams* 
       float v[NG];
       const float pis = p.pi[row0 + r];
 #pragma unroll
-      for (int n = 0; n < NG; ++n) { v[n] = acc[r * NG + n] * inv_as[n]; loc[n] += pis * v[n]; }
+      for (int n = 0; n < NG; ++n) {
+        v[n] = acc[r * NG + n] * inv_as[n];
+        if (pis != 0.f) loc[n] += pis * v[n];     // (pi = 0: no term; v may be inf, see the occupancy half)
+      }
       float* o = beta_t + (size_t)(row0 + r) * NG;
       if (atomic) {
 #pragma unroll

@@ -339,10 +339,15 @@ def test_overlap_schedule_survives_a_cu_hogging_peer():
 
 
 def test_bench_eight_ranks_on_one_gpu_over_gloo():
-    """The driver's N = 8 line (`torch.distributed.run --nproc-per-node 8 ... bench.py --gpus 8`) with all ranks on this GPU
-    over gloo: rendezvous, parameter broadcast, the start-up trial of the two exchange schedules, the same number of
-    collectives on every rank, one JSON line from rank 0 with the whole-job aggregate."""
+    """The driver's N = 8 line (`torch.distributed.run --nproc-per-node 8 ... bench.py --gpus 8`) over gloo: rendezvous,
+    parameter broadcast, the start-up trial of the two exchange schedules, the same number of collectives on every rank,
+    one JSON line from rank 0 with the whole-job aggregate.  The ranks take one GPU each (hvd: local rank % devices):
+    eight ranks stacked on one GPU are more processes than a shared device may have open at once, so a node with fewer
+    than 8 GPUs skips the test."""
     import json
+    n_dev = torch.cuda.device_count()
+    if n_dev < 8:
+        pytest.skip("needs 8 GPUs (one per rank), found %d" % n_dev)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr", "127.0.0.1",
            "--master-port", "29553", os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1",
            "--no-cpu-baseline"]
@@ -356,3 +361,57 @@ def test_bench_eight_ranks_on_one_gpu_over_gloo():
     assert d["scaling"] == "weak" and d["value"] > 0 and d["exchange"]["calibration_steps"] == 14
     assert d["persistent_health"]["lstm_persist_abort"] == 0
     _check_scaling_fields(d, 8)
+
+
+def test_bench_four_ranks_on_one_gpu_over_gloo():
+    """The N > 2 launch line on the one GPU a node may have (`torch.distributed.run --nproc-per-node 4 ... bench.py --gpus 4`)
+    over gloo: rendezvous of four ranks, parameter broadcast, the start-up trial of the two exchange schedules, the same
+    number of collectives on every rank, one JSON line from rank 0 with the whole-job aggregate.  Four ranks and this
+    process stay within the processes a shared device may have open at once (the N = 8 line needs 8 GPUs, above)."""
+    import json
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "4", "--master-addr", "127.0.0.1",
+           "--master-port", "29559", os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "2", "--warmup", "1",
+           "--no-cpu-baseline"]
+    out = subprocess.run(cmd, capture_output=True, text=True, timeout=1500, cwd=ROOT,
+                         env=dict(os.environ, PK2_HVD_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="2"))
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, out.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["n_gpus"] == 4 and d["config"]["parallelism"] == "dp4" and d["config"]["global_batch"] == 16
+    assert d["scaling"] == "weak" and d["value"] > 0 and d["exchange"]["calibration_steps"] == 14
+    assert d["persistent_health"]["lstm_persist_abort"] == 0
+    _check_scaling_fields(d, 4)
+
+def test_bench_dump_outputs_repeat(tmp_path):
+    """bench.py --dump-outputs DIR: the last timed step's outputs as float32 / float64 .npy files, 64 MB at most, and the
+    same arguments give the same inputs -- two runs agree output for output (split-K GEMMs accumulate with float atomics:
+    equal up to summation order).  The dump is the LAST timed step's: its optimiser step is the priming step + the
+    warm-up steps + the timed steps, not one of the untimed steps that follow the timed window."""
+    import json
+    runs = []
+    for tag in ("a", "b"):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                              "--no-cpu-baseline", "--dump-outputs", str(tmp_path / tag)],
+                             capture_output=True, text=True, timeout=900, cwd=ROOT)
+        assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
+        d = json.loads(out.stdout.strip().splitlines()[-1])
+        assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0
+        files = sorted(os.listdir(tmp_path / tag))
+        assert files and all(f.endswith(".npy") for f in files), files
+        assert sum(os.path.getsize(tmp_path / tag / f) for f in files) <= 64 << 20
+        arrs = {f[:-4]: np.load(tmp_path / tag / f) for f in files}
+        for k, a in arrs.items():
+            assert a.dtype in (np.float32, np.float64) and a.size > 0 and np.isfinite(a).all(), k
+        assert arrs["step"][0] == 1 + 1 + 3, arrs["step"]          # priming + warm-up + timed steps
+        runs.append(arrs)
+    a, b = runs
+    assert a.keys() == b.keys() and {"loss", "grad_norm", "logits_sample", "params_sample", "grads_sample"} <= a.keys()
+    for k in a:
+        assert a[k].shape == b[k].shape, k
+    for k in ("step", "logits_sample_rows", "logits_sample_columns", "flat_sample_positions"):
+        assert np.array_equal(a[k], b[k])
+    assert abs(a["loss"][0] - b["loss"][0]) <= 2e-3 * abs(b["loss"][0]) + 1e-3
+    assert abs(a["grad_norm"][0] - b["grad_norm"][0]) <= 1e-2 * abs(b["grad_norm"][0]) + 1e-3
+    for k in ("logits_sample", "params_sample", "grads_sample"):
+        assert np.abs(a[k] - b[k]).max() <= 1e-2 * max(1.0, np.abs(b[k]).max()), k
