@@ -380,9 +380,12 @@ int pk2_lstm_layer_fwd(const float* gx, const float* whh, const float* bhh, int3
 /* dy: device f32 [T][B][D*H] gradient wrt y.  dgx: device f32 [T][B][D*4H]
  * receives the gradient wrt the pre-activations (= gradient wrt gx).
  * scratch: device f32, at least pk2_lstm_bwd_scratch_floats(B,H,D). */
-/* Batches of <= 4 rows at H = 512 run the whole recurrence of a layer in ONE persistent launch (csrc/lstm_persist.hip;
- * PK2_LSTM_PERSIST=0 keeps the launch-per-step kernels).  A poll of that kernel that times out leaves NaNs in the
- * outputs and raises this flag (the call synchronises the device). */
+/* At H = 512 the whole recurrence of a layer runs in ONE persistent launch: lstm_fwd_seq2 / lstm_bwd_seq2 with a
+ * (sequence, direction) pair per XCD for B*D <= 32 (csrc/lstm_persist_seq.hip; PK2_LSTM_SEQ=0 keeps the launch-per-step
+ * kernels), lstm_fwd_big_persist / lstm_bwd_big_persist2 (lstm_bwd_big_persist for tensors that are not 16-byte aligned)
+ * for B >= 32 (csrc/lstm_persist_big.hip; PK2_LSTM_BIG_PERSIST=0).
+ * A poll of those kernels that times out leaves NaNs in the outputs and raises this flag (the call synchronises the
+ * device). */
 int pk2_lstm_persist_status(uint32_t* abort_flag);
 size_t pk2_lstm_bwd_scratch_floats(int32_t B, int32_t H, int32_t num_dirs);
 int pk2_lstm_layer_bwd(const float* dy, const float* whh, const float* gates, const float* cells,

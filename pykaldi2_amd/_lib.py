@@ -209,7 +209,7 @@ def check_persist_guard(where, raised=None):
         raise Pk2Error("%s: a persistent kernel (one-launch LSTM recurrence / denominator / lattice decoder) timed out on "
                        "this device; its output was poisoned with NaN and the optimiser kernels have been leaving the "
                        "weights untouched since.  Typical causes: the GPU is shared with another process, or fewer than "
-                       "256 CUs are available to the launch.  PK2_LSTM_SEQ=0 PK2_LSTM_PERSIST=0 PK2_DEN_PERSIST=0 "
+                       "256 CUs are available to the launch.  PK2_LSTM_SEQ=0 PK2_LSTM_BIG_PERSIST=0 PK2_DEN_PERSIST=0 "
                        "PK2_LAT_DECODER=frames select the launch-per-step kernels." % where)
 
 

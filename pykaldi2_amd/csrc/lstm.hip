@@ -15,13 +15,12 @@
 //    activations, c_t and h_t are computed in the same kernel (fused pointwise).  The pointwise
 //    operands (input projection, bias, c_{t-1}) are fetched before the MFMA phase so their
 //    latency hides behind it.
-//  * backward: a workgroup owns 4 hidden units (4 live columns of the N tile) and splits K = 4H
-//    over 16 wavefronts; d h_{t-1} = dgates_t W_hh is fused with the gate derivative of step t-1.
+//  * backward: a workgroup owns 4 hidden units and splits K = 4H over 4 wavefronts on the 4x4x1 MFMA
+//    (lstm_bwd_step_x4); d h_{t-1} = dgates_t W_hh is fused with the gate derivative of step t-1.
 // W_hh slices are re-read from L2 every step (4 MB per direction stays L2 resident; each
 // workgroup always reads the same slice, and consecutive launches place block b on XCD b%8).
 // All activations are time-major ([T][B][...]) so "previous step" is a constant row offset.
 #include <algorithm>
-#include <cstdlib>
 
 #include "common.h"
 #include "gemm_tile.h"
@@ -34,10 +33,6 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kFwdThreads = 256;    // 4 waves, K = H split 4 ways
 constexpr int kFwdUnits = 4;        // hidden units per workgroup (x4 gates = 16 MFMA columns)
-constexpr int kBwdWavesDefault = 16; // K = 4H split over this many wavefronts (PK2_LSTM_BWD_WAVES = 8 | 16)
-constexpr int kBwdUnits = 4;        // hidden units per workgroup (4 of the 16 MFMA columns carry data:
-                                    // the matrix work is negligible at these batch sizes, and 4x more
-                                    // workgroups spread the W_hh^T read over the whole chip)
 
 // Gate nonlinearities on v_exp_f32 / v_rcp_f32 (about 1 ulp each): sigmoid(x) = 1 / (1 + 2^(-x log2 e)),
 // tanh(x) = 1 - 2 / (1 + 2^(2 x log2 e)); absolute error ~1e-7 (libm's expf / tanhf cost 0.27 us of a 4.2 us step, measured).
@@ -188,104 +183,10 @@ struct LstmBwdParams {
   float* dh_part;      // [kBigSplitK][D][B][H] split-K partial sums of dgates W_hh (large-batch kernels)
 };
 
-// KS = 4-wide MFMA k-steps per wave (4H / 16 waves / 4).  Batch rows in groups of kBwdTileGroup M-tiles.
-constexpr int kBwdTileGroup = 2;
-
-template <int KS, int WAVES>
-__global__ void __launch_bounds__(WAVES * 64) lstm_bwd_step(const LstmBwdParams* __restrict__ pp,
-                                                            const StepCounter* __restrict__ cnt, int local) {
-  __shared__ float part[kBwdTileGroup][WAVES][16][17];
-  const int step = cnt->base + local;
-  if (step >= cnt->T) return;
-  const LstmBwdParams p = *pp;
-  const int d = blockIdx.y;
-  const int k0 = blockIdx.x * kBwdUnits;
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int H = p.H, B = p.B, T = p.T, D = p.D;
-  // backward visits the forward steps in reverse order
-  const int fstep = T - 1 - step;                  // forward step index being differentiated
-  const int t = d == 0 ? fstep : T - 1 - fstep;    // its frame
-  const int tn = d == 0 ? t + 1 : t - 1;           // frame of the step after it (already done)
-  const int tp = d == 0 ? t - 1 : t + 1;           // frame of the step before it
-  const bool last_fwd = step == 0;                 // no recurrent gradient flows in
-  const bool first_fwd = fstep == 0;               // c_{prev} = 0
-  const int li = lane & 15, kq = lane >> 4;
-  const int G4 = 4 * H;
-
-  f32x4 wf[KS / 4];
-  const int rbase = w * (KS * 4) + kq * KS;        // run of gate rows r handled by this lane
-#pragma unroll
-  for (int q = 0; q < KS / 4; ++q) wf[q] = f32x4{0.f, 0.f, 0.f, 0.f};
-  if (!last_fwd && li < kBwdUnits) {
-    const float* wrow = p.whhT + ((size_t)d * H + k0 + li) * G4 + rbase;
-#pragma unroll
-    for (int q = 0; q < KS / 4; ++q) wf[q] = *reinterpret_cast<const f32x4*>(wrow + q * 4);
-  }
-  const int ntiles = (B + 15) / 16;
-  {
-    const int mt0 = blockIdx.z * kBwdTileGroup;   // one group of M-tiles per workgroup
-    const int ng = min(kBwdTileGroup, ntiles - mt0);
-    // pointwise operands of thread (tile tg, row i, unit j) fetched before the MFMA phase
-    const int tg = tid >> 6, pi_ = (tid >> 2) & 15, pj = tid & 3;
-    const int pb = (mt0 + tg) * 16 + pi_, pk = k0 + pj;
-    const bool pw_active = tg < ng && pb < B;
-    float dh = 0.f, ig = 0.f, fg = 0.f, gg = 0.f, og = 0.f, c = 0.f, cprev = 0.f, dcin = 0.f;
-    if (pw_active) {
-      dh = p.dy[((size_t)t * B + pb) * ((size_t)D * H) + (size_t)d * H + pk];
-      const float* gr = p.gates + (((size_t)d * T + t) * B + pb) * G4 + pk;
-      ig = gr[0]; fg = gr[(size_t)H]; gg = gr[(size_t)2 * H]; og = gr[(size_t)3 * H];
-      c = p.cells[(((size_t)d * T + t) * B + pb) * H + pk];
-      if (!first_fwd) cprev = p.cells[(((size_t)d * T + tp) * B + pb) * H + pk];
-      if (!last_fwd) dcin = p.dc[((size_t)d * B + pb) * H + pk];
-    }
-    if (!last_fwd) {
-      for (int g2 = 0; g2 < ng; ++g2) {
-        const int b = (mt0 + g2) * 16 + li;
-        f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-        f32x4 af[KS / 4];
-        if (b < B) {
-          const float* grow = p.dgx + ((size_t)tn * B + b) * ((size_t)D * G4) + (size_t)d * G4 + rbase;
-#pragma unroll
-          for (int q = 0; q < KS / 4; ++q) af[q] = *reinterpret_cast<const f32x4*>(grow + q * 4);
-        } else {
-#pragma unroll
-          for (int q = 0; q < KS / 4; ++q) af[q] = f32x4{0.f, 0.f, 0.f, 0.f};
-        }
-#pragma unroll
-        for (int q = 0; q < KS / 4; ++q) {
-          acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(af[q][0], wf[q][0], acc0, 0, 0, 0);
-          acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(af[q][1], wf[q][1], acc1, 0, 0, 0);
-          acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(af[q][2], wf[q][2], acc0, 0, 0, 0);
-          acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(af[q][3], wf[q][3], acc1, 0, 0, 0);
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) part[g2][w][kq * 4 + r][li] = acc0[r] + acc1[r];
-      }
-    }
-    __syncthreads();
-    if (pw_active) {
-      if (!last_fwd) {
-        float s = 0.f;
-#pragma unroll
-        for (int ww = 0; ww < WAVES; ++ww) s += part[tg][ww][pi_][pj];
-        dh += s;
-      }
-      const float tc = fast_tanh(c);
-      const float dcv = dcin + dh * og * (1.f - tc * tc);
-      p.dc[((size_t)d * B + pb) * H + pk] = dcv * fg;
-      float* o = p.dgx + ((size_t)t * B + pb) * ((size_t)D * G4) + (size_t)d * G4 + pk;
-      o[0] = dcv * gg * ig * (1.f - ig);
-      o[(size_t)H] = dcv * cprev * fg * (1.f - fg);
-      o[(size_t)2 * H] = dcv * ig * (1.f - gg * gg);
-      o[(size_t)3 * H] = dh * tc * og * (1.f - og);
-    }
-  }
-}
-
 // ----------------------------------------------------------------------------------------
 // Small-batch backward step on v_mfma_f32_4x4x1_16b_f32.
 // With a batch of 4 and 4 hidden units per workgroup the product dh[b][k] = sum_r dgates[b][r] W_hh[r][k] is a
-// 4 x 2048 x 4 job: a 16x16x4 MFMA tile would be 15/16 padding (the 16-wave kernel above spends 1.7 us per step in
+// 4 x 2048 x 4 job: a 16x16x4 MFMA tile would be 15/16 padding (a 16-wave kernel on it spent 1.7 us per step in
 // the matrix pipe at 1/16 utilisation).  The 4x4x1 instruction computes 16 INDEPENDENT 4x4 outer products per
 // issue (lane l feeds block l/4: row/column l%4; layout verified with tools/ubench/mfma4x4_layout.hip), so the 16
 // blocks take 16 different gate rows r: every lane streams its own run of H/16 consecutive r's of one batch row
@@ -590,12 +491,6 @@ extern "C" int pk2_lstm_layer_fwd(const float* gx, const float* whh, const float
     if (prc) return prc;
     if (ran) return PK2_OK;
   }
-  if (lstm_persist_wanted(B, H, D)) {       // one launch for the whole sequence (lstm_persist.hip)
-    bool ran = false;
-    int prc = lstm_fwd_persist_launch(gx, whh, bhh, B, T, H, D, y, gates, cells, stream, &ran);
-    if (prc) return prc;
-    if (ran) return PK2_OK;
-  }
   if (lstm_big_wanted(B, H, D)) {           // large batches: one launch, W_hh slices resident in LDS (lstm_persist_big.hip)
     bool ran = false;
     int prc = lstm_fwd_big_launch(gx, whh, bhh, B, T, H, D, y, gates, cells, stream, &ran);
@@ -646,17 +541,15 @@ extern "C" int pk2_lstm_layer_fwd(const float* gx, const float* whh, const float
   return PK2_OK;
 }
 
-// Test / monitoring hook: 1 in *abort_flag when a poll of the persistent recurrence (lstm_persist.hip) has timed out
-// (synchronises the device).
+// Test / monitoring hook: 1 in *abort_flag when a poll of a persistent recurrence (lstm_persist_seq.hip,
+// lstm_persist_big.hip) has timed out (synchronises the device).
 extern "C" int pk2_lstm_persist_status(uint32_t* abort_flag) {
   PK2_REQUIRE(abort_flag, "lstm_persist_status: null pointer");
-  unsigned f = 0;
-  int rc = lstm_persist_status(&f);
-  unsigned f2 = 0, f3 = 0;
-  if (!rc) rc = lstm_seq_status(&f2);
-  if (!rc) rc = lstm_big_status(&f3);
-  f |= f2 | f3;
-  *abort_flag = f;
+  PK2_HIP(hipDeviceSynchronize());
+  unsigned f = 0, f2 = 0;
+  int rc = lstm_seq_status(&f);
+  if (!rc) rc = lstm_big_status(&f2);
+  *abort_flag = f | f2;
   return rc;
 }
 
@@ -693,19 +586,13 @@ static int lstm_layer_bwd_impl(const float* dy, const float* whh, const float* g
   PK2_REQUIRE(lstm_h_ok(H), "lstm_bwd: hidden size %d unsupported (64,128,256,512,1024)", H);
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   if (bias_done) *bias_done = 0;
-  if (lstm_seq_wanted(B, H, D) && !getenv("PK2_LSTM_PERSIST_FWD_ONLY")) {
+  if (lstm_seq_wanted(B, H, D)) {           // one launch, a (sequence, direction) pair per XCD (lstm_persist_seq.hip)
     bool ran = false, bdone = false;
     int prc = lstm_bwd_seq_launch(dy, whh, gates, cells, B, T, H, D, dgx, stream, &ran, dbias_ih, dbias_hh, &bdone);
     if (prc) return prc;
     if (ran) { if (bias_done) *bias_done = bdone ? 1 : 0; return PK2_OK; }
   }
-  if (lstm_persist_wanted(B, H, D) && !getenv("PK2_LSTM_PERSIST_FWD_ONLY")) {   // one launch for the whole sequence (lstm_persist.hip)
-    bool ran = false;      // the mailboxes (1 MB) live where the step kernels keep W_hh^T
-    int prc = lstm_bwd_persist_launch(dy, whh, gates, cells, B, T, H, D, dgx, scratch, stream, &ran);
-    if (prc) return prc;
-    if (ran) return PK2_OK;
-  }
-  if (lstm_big_wanted(B, H, D) && !getenv("PK2_LSTM_PERSIST_FWD_ONLY")) {   // large batches, one launch (lstm_persist_big.hip)
+  if (lstm_big_wanted(B, H, D)) {           // large batches, one launch (lstm_persist_big.hip)
     bool ran = false;
     int prc = lstm_bwd_big_launch(dy, whh, gates, cells, B, T, H, D, dgx, stream, &ran);
     if (prc) return prc;
@@ -736,45 +623,21 @@ static int lstm_layer_bwd_impl(const float* dy, const float* whh, const float* g
     PK2_LAUNCH_CHECK();
     return PK2_OK;
   }
-  // batches below 32 rows: the 4x4x1-MFMA kernel (PK2_LSTM_BWD_X4=0 keeps the 16x16x4 one)
-  static const bool use_x4 = [] { const char* e = getenv("PK2_LSTM_BWD_X4"); return !(e && atoi(e) == 0); }();
-  if (use_x4 && B <= 4 * kX4MaxGroups) {
-    dim3 gridx(H / 4, D, 1);
-    const LstmBwdParams* pbx = slot->params;
-    const StepCounter* cx = slot->counter;
-    char keyx[64];
-    snprintf(keyx, sizeof(keyx), "lstm_bwd_x4_H%d_D%d_%p", H, D, (void*)stream);
-    rc = g_graphs.run(keyx, T, slot->counter, stream, [&](hipStream_t s, int j) {
-      switch (H) {
-        case 64: launch_step(lstm_bwd_step_x4<64>, gridx, dim3(256), s, pbx, cx, j); break;
-        case 128: launch_step(lstm_bwd_step_x4<128>, gridx, dim3(256), s, pbx, cx, j); break;
-        case 256: launch_step(lstm_bwd_step_x4<256>, gridx, dim3(256), s, pbx, cx, j); break;
-        case 512: launch_step(lstm_bwd_step_x4<512>, gridx, dim3(256), s, pbx, cx, j); break;
-        default: launch_step(lstm_bwd_step_x4<1024>, gridx, dim3(256), s, pbx, cx, j); break;
-      }
-    });
-    if (rc) return rc;
-    PK2_LAUNCH_CHECK();
-    return PK2_OK;
-  }
-  const int zb = ((B + 15) / 16 + kBwdTileGroup - 1) / kBwdTileGroup;
-  const char* wenv = getenv("PK2_LSTM_BWD_WAVES");
-  const int waves = (wenv && atoi(wenv) == 8) ? 8 : kBwdWavesDefault;
-  dim3 grid(H / kBwdUnits, D, zb), block(waves * 64);
-  const LstmBwdParams* pb = slot->params;
-  const StepCounter* c = slot->counter;
-  char key[64];
-  snprintf(key, sizeof(key), "lstm_bwd_H%d_D%d_Z%d_W%d_%p", H, D, zb, waves, (void*)stream);
-  rc = g_graphs.run(key, T, slot->counter, stream, [&](hipStream_t s, int j) {
-#define PK2_BWD(HH)                                                                                  \
-  case HH:                                                                                           \
-    if (waves == 8) launch_step(lstm_bwd_step<HH / 8, 8>, grid, block, s, pb, c, j);                 \
-    else launch_step(lstm_bwd_step<HH / 16, 16>, grid, block, s, pb, c, j);                          \
-    break;
+  // batches below kBigBatch rows (every supported H is a multiple of 64): the 4x4x1-MFMA kernel
+  static_assert(kBigBatch - 1 <= 4 * kX4MaxGroups, "lstm_bwd_step_x4 covers every batch below kBigBatch");
+  dim3 gridx(H / 4, D, 1);
+  const LstmBwdParams* pbx = slot->params;
+  const StepCounter* cx = slot->counter;
+  char keyx[64];
+  snprintf(keyx, sizeof(keyx), "lstm_bwd_x4_H%d_D%d_%p", H, D, (void*)stream);
+  rc = g_graphs.run(keyx, T, slot->counter, stream, [&](hipStream_t s, int j) {
     switch (H) {
-      PK2_BWD(64) PK2_BWD(128) PK2_BWD(256) PK2_BWD(512) PK2_BWD(1024)
+      case 64: launch_step(lstm_bwd_step_x4<64>, gridx, dim3(256), s, pbx, cx, j); break;
+      case 128: launch_step(lstm_bwd_step_x4<128>, gridx, dim3(256), s, pbx, cx, j); break;
+      case 256: launch_step(lstm_bwd_step_x4<256>, gridx, dim3(256), s, pbx, cx, j); break;
+      case 512: launch_step(lstm_bwd_step_x4<512>, gridx, dim3(256), s, pbx, cx, j); break;
+      default: launch_step(lstm_bwd_step_x4<1024>, gridx, dim3(256), s, pbx, cx, j); break;
     }
-#undef PK2_BWD
   });
   if (rc) return rc;
   PK2_LAUNCH_CHECK();

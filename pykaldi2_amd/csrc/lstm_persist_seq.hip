@@ -1,18 +1,15 @@
 // Persistent LSTM recurrence, one (sequence, direction) per XCD (gfx950, H = 512).
 //
-// lstm_persist.hip runs a direction of a layer on one XCD for ALL sequences of the minibatch: at batch 4 that keeps 2 of
-// the 8 XCDs busy, and a step pays for 4 batch rows on the 4x4x1 MFMA (128 instructions per wave: 0.85 of a step's 2.2 us).
-// The recurrences of different sequences do not depend on each other, so here every (sequence, direction) pair is its own
+// The recurrences of different sequences do not depend on each other, so every (sequence, direction) pair is its own
 // recurrence on its own XCD -- 4 sequences x 2 directions = the 8 XCDs of the part; more pairs queue up behind them:
 //  * 32 workgroups (one per CU of the XCD; teams form by arrival order, pairs are handed out from a queue), workgroup r
 //    owns hidden units 16r..16r+15, its 64 gate rows of W_hh (128 KB) stay in VGPRs;
-//  * one batch row makes the recurrent product a matrix-VECTOR product: plain FMAs.  Forward: a lane owns a quarter of one
-//    gate row (128 k's; the four quarters are added with two DPP moves), 128 FMAs per lane and step.  Backward: a lane
-//    owns two columns k of the workgroup's 64 rows, 128 FMAs per lane, no cross-lane reduction at all;
-//  * h_t (2 KB) / the partial products (a 2 KB mailbox per workgroup) are exchanged through the XCD's own L2 exactly as in
-//    lstm_persist.hip: agent-scope stores over a NaN sentinel, polled with L1-bypassing 16-byte loads, no flags.
-// Tensors and their layouts are those of lstm_persist.hip (y pre-filled with the sentinel, gates / cells kept for the
-// backward pass), so the two implementations are interchangeable behind pk2_lstm_layer_fwd / _bwd.
+//  * one batch row makes the recurrent product a matrix-VECTOR product: plain FMAs (the layout of the lanes is described
+//    with the kernels below);
+//  * h_t (2 KB) / the partial products (a 2 KB mailbox per workgroup) are exchanged through the XCD's own L2: plain stores
+//    over a NaN sentinel, polled with L1-bypassing 16-byte loads, no flags.
+// Tensors and their layouts are those of the step kernels (lstm.hip; y pre-filled with the sentinel, gates / cells kept for
+// the backward pass), so the two implementations are interchangeable behind pk2_lstm_layer_fwd / _bwd.
 // Replaces the same cuDNN RNN (reference models/lstm.py:49-58).
 #include <algorithm>
 #include <cstdlib>
@@ -33,9 +30,9 @@ constexpr int kSWgs = 32;                   // workgroups of a team = CUs of an 
 constexpr int kSeqTeams = 8;                // teams per XCD the control block has room for
 constexpr int kSeqMaxTasks = 64;
 constexpr long long kSeqSpinTicks = 1000LL * 1000 * 100;     // 1 s of the 100 MHz wall clock
-// per team: [step % depth][reader][writer][16 units].  The round-2 kernel uses three slots; the round-4 kernel, whose
-// hand-over stores are plain (XCD-local) ones, walks all eight: a slot's reset by its reader then has seven steps and as
-// many dependent exchanges to land before a writer stores to the slot again.
+// per team: [step % depth][reader][writer][16 units].  The hand-over stores are plain (XCD-local) ones, so the backward
+// kernel walks all eight slots: a slot's reset by its reader then has seven steps and as many dependent exchanges to land
+// before a writer stores to the slot again.
 constexpr int kSeqMailDepth = 8;
 constexpr int kSeqMailFloats = kSeqMailDepth * kSWgs * kSWgs * 16;
 
@@ -59,22 +56,13 @@ __device__ __forceinline__ u32x4 seq_load16(const float* p) {
   asm volatile("global_load_dwordx4 %0, %1, off sc1\n\ts_waitcnt vmcnt(0)" : "=v"(v) : "v"(p) : "memory");
   return v;
 }
-// (the s_nop: ">8-byte VMEM store data followed by a VALU write of the same VGPRs" hazard, invisible to the compiler
-// inside an asm statement)
+// The hand-over stores: plain ones (see the notes on the kernels below).  (the s_nop: ">8-byte VMEM store data followed by
+// a VALU write of the same VGPRs" hazard, invisible to the compiler inside an asm statement)
 __device__ __forceinline__ void seq_store16(float* p, u32x4 v) {
-  asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" : : "v"(p), "v"(v) : "memory");
+  asm volatile("global_store_dwordx4 %0, %1, off\n\ts_nop 1" : : "v"(p), "v"(v) : "memory");
 }
-__device__ __forceinline__ void seq_store16_mode(float* p, u32x4 v, int mode) {
-  if (mode == 1) asm volatile("global_store_dwordx4 %0, %1, off\n\ts_nop 1" : : "v"(p), "v"(v) : "memory");
-  else if (mode == 2) asm volatile("global_store_dwordx4 %0, %1, off sc0\n\ts_nop 1" : : "v"(p), "v"(v) : "memory");
-  else asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" : : "v"(p), "v"(v) : "memory");
-}
-__device__ __forceinline__ void seq_store(float* p, float v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-// The hand-over stores of the round-4 kernels by cache policy (experiment switch; 0 = agent scope as everywhere else).
-__device__ __forceinline__ void seq_store_mode(float* p, float v, int mode) {
-  if (mode == 1) asm volatile("global_store_dword %0, %1, off" : : "v"(p), "v"(v) : "memory");
-  else if (mode == 2) asm volatile("global_store_dword %0, %1, off sc0" : : "v"(p), "v"(v) : "memory");
-  else asm volatile("global_store_dword %0, %1, off sc1" : : "v"(p), "v"(v) : "memory");
+__device__ __forceinline__ void seq_store(float* p, float v) {
+  asm volatile("global_store_dword %0, %1, off" : : "v"(p), "v"(v) : "memory");
 }
 __device__ __forceinline__ unsigned seq_load_u(const unsigned* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ bool seq_has_sentinel(u32x4 v) {
@@ -183,127 +171,7 @@ struct SeqFwdParams {
   float* gates;       // [D][T][B][4H]
   float* cells;       // [D][T][B][H]
   int B, T, D;
-  int pre_sleep, loop_sleep;   // round-4 kernels: s_sleep units (64 clocks) before the first poll of a step / between polls
-  int store_mode;
 };
-
-__global__ void __launch_bounds__(256) lstm_fwd_seq(SeqFwdParams p, SeqCtl* ctl) {
-  constexpr int H = kSH;
-  constexpr int kPhasePitch = 132;          // 128 + 4: the four k-quarters the lanes of a quad read start 16 bytes apart mod the banks
-  __shared__ __attribute__((aligned(16))) float hs[2][4 * kPhasePitch];
-  __shared__ int s_i[8];
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  SeqRole role;
-  if (!seq_register(ctl, s_i, &role)) return;
-  const int rank = role.rank, B = p.B, T = p.T, D = p.D;
-  // lane roles: quad = one gate row, lane % 4 = its k-quarter; the 4 gates of a unit sit in one 16-lane DPP row
-  const int ul = lane >> 4, g = (lane >> 2) & 3, q = lane & 3;
-  const int gu = 16 * rank + 4 * w + ul;                 // hidden unit of this lane's row
-  const bool unit_lane = (lane & 15) == 0;
-  const bool poll_lane = (lane & 15) >= 1 && (lane & 15) <= 8;
-  const int gran = w * 32 + (lane >> 4) * 8 + ((lane & 15) - 1);      // granule of h this lane polls (128 per step)
-  const size_t yrow = (size_t)D * H;
-  unsigned nbar = 0;
-  for (int iter = 0; iter <= kSeqMaxTasks; ++iter) {
-    const int task = seq_next_task(ctl, role, iter, B * D, s_i);
-    if (task < 0) return;
-    const int b = task / D, d = task % D;
-    float wa[128];                                       // W_hh[d][g*H + gu][128 q + i]
-    {
-      const float* wrow = p.whh + ((size_t)d * 4 * H + (size_t)g * H + gu) * H + 128 * q;
-#pragma unroll
-      for (int i = 0; i < 32; ++i) {
-        const f32x4 v = *reinterpret_cast<const f32x4*>(wrow + i * 4);
-        wa[i * 4] = v[0]; wa[i * 4 + 1] = v[1]; wa[i * 4 + 2] = v[2]; wa[i * 4 + 3] = v[3];
-      }
-    }
-    float bias[4] = {0.f, 0.f, 0.f, 0.f};
-    if (unit_lane && p.bhh) {
-#pragma unroll
-      for (int k = 0; k < 4; ++k) bias[k] = p.bhh[(size_t)d * 4 * H + (size_t)k * H + gu];
-    }
-    float cstate = 0.f;
-    bool timed_out = false;
-    float gxn[4] = {0.f, 0.f, 0.f, 0.f};
-    auto load_gx = [&](int step_) {
-      if (unit_lane && step_ < T) {
-        const int t_ = d == 0 ? step_ : T - 1 - step_;
-        const float* gxr = p.gx + ((size_t)t_ * B + b) * ((size_t)D * 4 * H) + (size_t)d * 4 * H + gu;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) gxn[k] = gxr[(size_t)k * H];
-      }
-    };
-    load_gx(0);
-    float gxm[4];                      // the input projections of step s+1; gxn: those of step s+2, in flight
-#pragma unroll
-    for (int k = 0; k < 4; ++k) gxm[k] = gxn[k];
-    load_gx(1);
-    SeqSpin spin(ctl);
-    SQ_T0();
-    for (int step = 0; step < T; ++step) {
-      const int t = d == 0 ? step : T - 1 - step;
-      const int tp = d == 0 ? t - 1 : t + 1;
-      const int buf = step & 1;
-      float pre[4];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) { pre[k] = gxm[k] + bias[k]; gxm[k] = gxn[k]; }
-      // ---- gather h_{t-1} of this (sequence, direction): 512 floats = 128 granules of 16 bytes -----------------------
-      // (by lanes 1..8 of every 16-lane row: a poll waits for ALL of the thread's outstanding memory operations, and the
-      // unit lanes -- lane % 16 == 0 -- still have the previous step's gate / cell stores and the gx prefetch in flight)
-      if (step > 0 && poll_lane) {
-        const float* src = p.y + ((size_t)tp * B + b) * yrow + (size_t)d * H + 4 * gran;
-        u32x4 v = seq_load16(src);
-        while (seq_has_sentinel(v)) {
-          if (spin.expired()) { timed_out = true; break; }
-          v = seq_load16(src);
-        }
-        *reinterpret_cast<u32x4*>(&hs[buf][(gran >> 5) * kPhasePitch + 4 * (gran & 31)]) = v;
-      }
-      SQ_T(0);
-      if (timed_out) s_i[3] = 1;
-      seq_lds_barrier();
-      SQ_T(1);
-      if (s_i[3]) return;
-      load_gx(step + 2);
-      // ---- recurrent product: this lane's quarter of its gate row ------------------------------------------------------
-      float s = 0.f;
-      if (step > 0) {
-        const float* hq = &hs[buf][q * kPhasePitch];
-        float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-#pragma unroll
-        for (int i = 0; i < 32; ++i) {
-          const f32x4 hv = *reinterpret_cast<const f32x4*>(hq + 4 * i);
-          a0 = fmaf(wa[4 * i], hv[0], a0);
-          a1 = fmaf(wa[4 * i + 1], hv[1], a1);
-          a2 = fmaf(wa[4 * i + 2], hv[2], a2);
-          a3 = fmaf(wa[4 * i + 3], hv[3], a3);
-        }
-        s = (a0 + a1) + (a2 + a3);
-        s += seq_dpp<0xB1>(s);        // quad_perm [1,0,3,2]
-        s += seq_dpp<0x4E>(s);        // quad_perm [2,3,0,1]
-      }
-      // the four gates of a unit: lanes +0, +4, +8, +12 of its 16-lane row
-      const float sf = seq_dpp<0x104>(s), sg = seq_dpp<0x108>(s), so = seq_dpp<0x10C>(s);
-#ifdef PK2_SEQ_PROFILE
-      asm volatile("" : "+v"(s));
-#endif
-      SQ_T(2);
-      if (unit_lane) {
-        const float ig = seq_sig(pre[0] + s), fg = seq_sig(pre[1] + sf), gg = seq_tanh(pre[2] + sg), og = seq_sig(pre[3] + so);
-        cstate = fg * cstate + ig * gg;
-        const float h = og * seq_tanh(cstate);
-        seq_store(p.y + ((size_t)t * B + b) * yrow + (size_t)d * H + gu, h);
-        p.cells[(((size_t)d * T + t) * B + b) * H + gu] = cstate;
-        float* gr = p.gates + (((size_t)d * T + t) * B + b) * 4 * H + gu;
-        gr[0] = ig; gr[(size_t)H] = fg; gr[(size_t)2 * H] = gg; gr[(size_t)3 * H] = og;
-      }
-      SQ_T(3);
-    }
-    SQ_PRINT("lstm_fwd_seq", "(poll | lds + barrier | product | gates + stores)", T);
-    if (tid == 0 && rank == 0) __hip_atomic_fetch_add(&ctl->done, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (!seq_team_barrier(ctl, role, &nbar, s_i)) return;     // (the LDS buffers and the team's pace are per pair)
-  }
-}
 
 struct SeqBwdParams {
   const float* dy;     // [T][B][D*H]
@@ -311,160 +179,21 @@ struct SeqBwdParams {
   const float* gates;  // [D][T][B][4H]
   const float* cells;  // [D][T][B][H]
   float* dgx;          // [T][B][D*4H]
-  float* mail;         // [teams][3][32 readers][32 writers][16 units], all sentinel
+  float* mail;         // [teams][kSeqMailDepth][32 readers][32 writers][16 units], all sentinel
   int B, T, D;
-  int pre_sleep, loop_sleep, store_mode;
-  float* dbias_ih;     // round-4 kernel: [D][4H] += sum over frames and sequences of d gx (null: not wanted), likewise dbias_hh
+  float* dbias_ih;     // [D][4H] += sum over frames and sequences of d gx (null: not wanted), likewise dbias_hh
   float* dbias_hh;
 };
 
-__global__ void __launch_bounds__(256) lstm_bwd_seq(SeqBwdParams p, SeqCtl* ctl) {
-  constexpr int H = kSH, G4 = 4 * kSH;
-  __shared__ __attribute__((aligned(16))) float pl[kSWgs][16 + 4];    // gathered partials [writer][unit]
-  __shared__ __attribute__((aligned(16))) float dgl[64];              // this workgroup's dgates [gate * 16 + unit]
-  __shared__ int s_i[8];
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  SeqRole role;
-  if (!seq_register(ctl, s_i, &role)) return;
-  const int rank = role.rank, B = p.B, T = p.T, D = p.D;
-  float* mail0 = p.mail + (size_t)role.team_index * kSeqMailFloats;
-  const u32x4 sent = {kSeqSentinel, kSeqSentinel, kSeqSentinel, kSeqSentinel};
-  const int unit = 16 * rank + tid;                     // pointwise role of threads 0..15
-  const bool pw = tid < 16;
-  unsigned nbar = 0;
-  for (int iter = 0; iter <= kSeqMaxTasks; ++iter) {
-    const int task = seq_next_task(ctl, role, iter, B * D, s_i);
-    if (task < 0) return;
-    const int b = task / D, d = task % D;
-    // W_hh[d][(r/16)*H + 16*rank + r%16][k] for the 64 own rows r and the lane's two columns k = 128 w + lane (+ 64)
-    float wb[128];
-    {
-      const float* wbase = p.whh + (size_t)d * G4 * H + 128 * w + lane;
-#pragma unroll
-      for (int r = 0; r < 64; ++r) {
-        const float* row = wbase + ((size_t)(r >> 4) * H + 16 * rank + (r & 15)) * H;
-        wb[2 * r] = row[0];
-        wb[2 * r + 1] = row[64];
-      }
-    }
-    float dcarry = 0.f;
-    bool timed_out = false;
-    float n_dy = 0.f, n_i = 0.f, n_f = 0.f, n_g = 0.f, n_o = 0.f, n_c = 0.f, n_cp = 0.f;          // operands of step s+2 (in flight)
-    float m_dy = 0.f, m_i = 0.f, m_f = 0.f, m_g = 0.f, m_o = 0.f, m_c = 0.f, m_cp = 0.f;          // operands of step s+1
-    auto load_pw = [&](int step_) {
-      if (pw && step_ < T) {
-        const int fs = T - 1 - step_;
-        const int t_ = d == 0 ? fs : T - 1 - fs;
-        const int tp_ = d == 0 ? t_ - 1 : t_ + 1;
-        n_dy = p.dy[((size_t)t_ * B + b) * ((size_t)D * H) + (size_t)d * H + unit];
-        const float* gr = p.gates + (((size_t)d * T + t_) * B + b) * G4 + unit;
-        n_i = gr[0]; n_f = gr[(size_t)H]; n_g = gr[(size_t)2 * H]; n_o = gr[(size_t)3 * H];
-        n_c = p.cells[(((size_t)d * T + t_) * B + b) * H + unit];
-        n_cp = fs == 0 ? 0.f : p.cells[(((size_t)d * T + tp_) * B + b) * H + unit];
-      }
-    };
-    load_pw(0);
-    m_dy = n_dy; m_i = n_i; m_f = n_f; m_g = n_g; m_o = n_o; m_c = n_c; m_cp = n_cp;
-    load_pw(1);
-    SeqSpin spin(ctl);
-    SQ_T0();
-    for (int step = 0; step < T; ++step) {
-      const int fstep = T - 1 - step;
-      const int t = d == 0 ? fstep : T - 1 - fstep;
-      // (loaded two steps ahead: a step is shorter than a round trip to memory; the rotation below only touches values whose
-      // loads were issued a whole step ago)
-      const float c_dy = m_dy, c_i = m_i, c_f = m_f, c_g = m_g, c_o = m_o, c_c = m_c, c_cp = m_cp;
-      m_dy = n_dy; m_i = n_i; m_f = n_f; m_g = n_g; m_o = n_o; m_c = n_c; m_cp = n_cp;
-      // ---- gather the 32 partials of d h for the own 16 units (written by the peers during the previous step) ----------
-      float rec = 0.f;
-      if (step > 0) {
-        // (threads 128..255 poll: the pointwise threads 0..15 have prefetches and gradient stores in flight, which a poll
-        // -- it waits for all of a thread's outstanding memory operations -- would wait for)
-        if (tid >= 128) {
-          const int gt = tid - 128;
-          float* src = mail0 + ((size_t)(step % 3) * kSWgs + rank) * (kSWgs * 16) + 4 * gt;      // [writer = gt/4][4 units]
-          u32x4 v = seq_load16(src);
-          while (seq_has_sentinel(v)) {
-            if (spin.expired()) { timed_out = true; break; }
-            v = seq_load16(src);
-          }
-          seq_store16(src, sent);               // free again (ordered before this step's own stores by the wait below)
-          *reinterpret_cast<u32x4*>(&pl[gt >> 2][4 * (gt & 3)]) = v;
-        }
-        if (timed_out) s_i[3] = 1;
-        __syncthreads();
-        SQ_T(0);
-        if (s_i[3]) {            // loud failure: the gradient of this layer turns NaN
-          if (tid == 0) p.dgx[(size_t)d * G4 + 16 * rank] = __int_as_float(0x7fc00000);
-          return;
-        }
-        if (pw) {
-          float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-#pragma unroll
-          for (int k = 0; k < kSWgs; k += 4) { s0 += pl[k][tid]; s1 += pl[k + 1][tid]; s2 += pl[k + 2][tid]; s3 += pl[k + 3][tid]; }
-          rec = (s0 + s1) + (s2 + s3);
-        }
-      }
-      // ---- gate derivatives of the own units ------------------------------------------------------------------------------
-      float dgi = 0.f, dgf = 0.f, dgg = 0.f, dgo = 0.f;
-      if (pw) {
-        const float dh = c_dy + rec;
-        const float tc = seq_tanh(c_c);
-        const float dcv = dcarry + dh * c_o * (1.f - tc * tc);
-        dcarry = dcv * c_f;
-        dgi = dcv * c_g * c_i * (1.f - c_i);
-        dgf = dcv * c_cp * c_f * (1.f - c_f);
-        dgg = dcv * c_i * (1.f - c_g * c_g);
-        dgo = dh * tc * c_o * (1.f - c_o);
-        dgl[tid] = dgi; dgl[16 + tid] = dgf; dgl[32 + tid] = dgg; dgl[48 + tid] = dgo;
-      }
-      auto store_dgx = [&]() {        // (to HBM; nothing waits for these)
-        if (pw) {
-          float* o = p.dgx + ((size_t)t * B + b) * ((size_t)D * G4) + (size_t)d * G4 + unit;
-          o[0] = dgi; o[(size_t)H] = dgf; o[(size_t)2 * H] = dgg; o[(size_t)3 * H] = dgo;
-        }
-      };
-      SQ_T(1);
-      if (step == T - 1) { store_dgx(); break; }
-      // Three mailbox buffers: the one read (and reset) in step s is written again by the peers in their step s+2, after they
-      // have read this workgroup's partials of step s+2 -- which go out behind the barrier of step s+1, and the polling
-      // threads reach that barrier only after their reset stores have been acknowledged (a poll waits for the thread's
-      // outstanding stores).  So no wait for the resets here (with two buffers it cost an L2 round trip per step).
-      seq_lds_barrier();
-      SQ_T(2);
-      store_dgx();
-      load_pw(step + 2);             // the pointwise operands of the step after next
-      // ---- own 64 rows of dgates x own W_hh rows: the lane's two columns ---------------------------------------------------
-      float a0 = 0.f, a1 = 0.f, b0 = 0.f, b1 = 0.f;
-#pragma unroll
-      for (int r4 = 0; r4 < 16; ++r4) {
-        const f32x4 dv = *reinterpret_cast<const f32x4*>(&dgl[4 * r4]);
-        a0 = fmaf(dv[0], wb[8 * r4], a0);     b0 = fmaf(dv[0], wb[8 * r4 + 1], b0);
-        a1 = fmaf(dv[1], wb[8 * r4 + 2], a1); b1 = fmaf(dv[1], wb[8 * r4 + 3], b1);
-        a0 = fmaf(dv[2], wb[8 * r4 + 4], a0); b0 = fmaf(dv[2], wb[8 * r4 + 5], b0);
-        a1 = fmaf(dv[3], wb[8 * r4 + 6], a1); b1 = fmaf(dv[3], wb[8 * r4 + 7], b1);
-      }
-      // peer k/16 reads [writer = rank][unit k%16] from its mailbox of the next step
-      float* box = mail0 + (size_t)((step + 1) % 3) * kSWgs * (kSWgs * 16);
-      const int k0 = 128 * w + lane, k1 = k0 + 64;
-      seq_store(box + ((size_t)(k0 >> 4) * kSWgs + rank) * 16 + (k0 & 15), a0 + a1);
-      seq_store(box + ((size_t)(k1 >> 4) * kSWgs + rank) * 16 + (k1 & 15), b0 + b1);
-      SQ_T(3);
-    }
-    SQ_PRINT("lstm_bwd_seq", "(mailbox poll by waves 2, 3 + barrier | partial sums + gate derivatives | lds barrier | product + mailbox stores)", T);
-    if (tid == 0 && rank == 0) __hip_atomic_fetch_add(&ctl->done, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (!seq_team_barrier(ctl, role, &nbar, s_i)) return;     // nobody writes a mailbox of the next pair before everybody has read the last of this one
-  }
-}
-
-// ---- Round 4: the same recurrences with the step's critical path cut down (lstm_fwd_seq2 / lstm_bwd_seq2) ---------------
-// What the phase timers (-DPK2_SEQ_PROFILE, profiles/r04_seq_phases.txt) charged a step of the kernels above besides the
-// round trip through L2, and what changed (forward 1.47 -> 0.97 us, backward 1.79 -> 1.14 us per step, T = 589, B = 4):
+// ---- The kernels (round 4: lstm_fwd_seq2 / lstm_bwd_seq2), the step's critical path cut down ---------------------------
+// What the phase timers (-DPK2_SEQ_PROFILE, profiles/r04_seq_phases.txt) charged a step of the round-2 kernels (since
+// retired) besides the round trip through L2, and what changed (forward 1.47 -> 0.97 us, backward 1.79 -> 1.14
+// us per step, T = 589, B = 4):
 //  * The hand-over stores were agent-scope (sc1) stores.  On this multi-XCD part an agent-scope store is written THROUGH
 //    the XCD's L2 to the fabric; a team lives on one XCD, whose L2 is the coherence point of its 32 CUs, so plain stores
 //    (which the write-through vector L1 forwards to L2, and which vmcnt acknowledges there) are enough as long as the
 //    readers poll with L1-bypassing loads: backward 1.95 -> 1.22 us per step by that alone (its 2 KB of scattered partial
-//    sums per workgroup and step), forward 1.09 -> 0.98.  (PK2_SEQ_STORE_MODE=0 restores sc1 for A/B.)  The data is
+//    sums per workgroup and step), forward 1.09 -> 0.98.  The data is
 //    polled on itself over a sentinel, so no ordering between stores is assumed; the backward mailboxes are a ring of
 //    eight step slots, so that a slot's reset has seven steps to land before the slot is written again.
 //  * `s_waitcnt vmcnt(0)` counts the WAVE's operations, not the lane's: a poll waits for every vector-memory operation the
@@ -618,11 +347,9 @@ __device__ __forceinline__ void lstm_fwd_seq2_body(const SeqFwdParams& p, SeqCtl
       const float pre = gxs[step % 3][pre_idx] + bias;
       // ---- gather h_{t-1} of this (sequence, direction): 512 floats = 128 granules of 16 bytes -----------------------
       if (step > 0 && poller) {
-        for (int i = 0; i < p.pre_sleep; ++i) __builtin_amdgcn_s_sleep(1);
         u32x4 v = seq_load16(y_poll);
         while (seq_has_sentinel(v)) {
           if (spin.expired()) { timed_out = true; break; }
-          for (int i = 0; i < p.loop_sleep; ++i) __builtin_amdgcn_s_sleep(1);
           v = seq_load16(y_poll);
         }
         *reinterpret_cast<u32x4*>(&hs[buf][(gran >> 3) * kSlicePitch + 4 * (gran & 7)]) = v;
@@ -667,7 +394,7 @@ __device__ __forceinline__ void lstm_fwd_seq2_body(const SeqFwdParams& p, SeqCtl
       const float fg = seq_dpp<0x101>(act), gg = seq_dpp<0x102>(act), og = seq_dpp<0x103>(act);     // row_shl 1, 2, 3
       cstate = fg * cstate + act * gg;                    // (meaningful in the row's lane 0 only)
       const float h = og * seq_tanh(cstate);
-      if (unit_lane) seq_store_mode(y_out, h, p.store_mode);
+      if (unit_lane) seq_store(y_out, h);
       y_out += y_stride;
       SQ_T(3);
       // ---- behind the hand-over: what the backward pass needs goes to HBM through wave 3, the input projections of the
@@ -799,7 +526,6 @@ __device__ __forceinline__ void lstm_bwd_seq2_body(const SeqBwdParams& p, SeqCtl
         if (step > 0) {
           float* src = mail_rd + m8 * kBox;
           u32x4 v0, v1;
-          for (int i = 0; i < p.pre_sleep; ++i) __builtin_amdgcn_s_sleep(1);
 #ifdef PK2_SEQ_PROFILE
           { const long long c0_ = clock64(); asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); sq_acc_[4] += clock64() - c0_; }   // own stores acknowledged
           bool first_ = true; const long long c1_ = clock64();
@@ -812,7 +538,6 @@ __device__ __forceinline__ void lstm_bwd_seq2_body(const SeqBwdParams& p, SeqCtl
 #endif
             if (!seq_has_sentinel(v0) && !seq_has_sentinel(v1)) break;
             if (spin.expired()) { timed_out = true; break; }
-            for (int i = 0; i < p.loop_sleep; ++i) __builtin_amdgcn_s_sleep(1);
           }
 #ifdef PK2_SEQ_PROFILE
           sq_acc_[6] += clock64() - c1_;           // the whole poll loop
@@ -869,15 +594,15 @@ __device__ __forceinline__ void lstm_bwd_seq2_body(const SeqBwdParams& p, SeqCtl
           const f32x4 gv = {g0, g1, g2, g3};
           u32x4 gu4;
           __builtin_memcpy(&gu4, &gv, 16);
-          seq_store16_mode(mail_wr + m8n * kBox, gu4, p.store_mode);
+          seq_store16(mail_wr + m8n * kBox, gu4);
         }
       }
       // The mailbox slot read in this step is free again: its reset goes out behind the step's own partials (issuing the
       // two stores takes ~300 clocks, which the poll of the next step has to spare) and has until the slot's next use, seven
       // steps on, to land.
       if (w == 0 && step > 0) {
-        seq_store16_mode(mail_rd + m8 * kBox, sent, p.store_mode);
-        seq_store16_mode(mail_rd + m8 * kBox + 256, sent, p.store_mode);
+        seq_store16(mail_rd + m8 * kBox, sent);
+        seq_store16(mail_rd + m8 * kBox + 256, sent);
       }
       SQ_T(3);
       if (io) {                  // behind the hand-over: d gx of the step to HBM, the factors two steps ahead, the prefetch
@@ -905,26 +630,25 @@ __device__ __forceinline__ void lstm_bwd_seq2_body(const SeqBwdParams& p, SeqCtl
 // pass keeps its NaN sentinels in y, but the backward pass would leave dgx -- freshly allocated memory -- partly
 // unwritten.  One workgroup after every persistent launch turns the launch's output into NaN in that case and raises a
 // sticky flag (the control block itself is cleared by the next launch) that pk2_lstm_persist_status reports.
-// `mail` (backward pass): an aborted launch leaves consumed and unconsumed hand-overs in the mailboxes, which the next
-// launch would read as valid ones (ADVICE r4) -- the same workgroup fills them with sentinels again, so that a caller who
-// lowers the guard (pk2_persist_guard_clear) and carries on does not compute on stale words.
 // (round 5: the check also leaves the control block zeroed for the next launch on this stream -- one hipMemsetAsync, i.e.
 // one fill kernel, less per recurrence launch: six per LF-MMI step)
-__global__ void lstm_seq_check(SeqCtl* ctl, unsigned pairs, float* out, size_t n, unsigned* sticky, unsigned* guard_dev, unsigned* guard_host,
-                               float* mail, size_t mail_n) {
+// This separate kernel checks the first forward launch on a device; every other launch folds the check in (seq_exit_check).
+__global__ void lstm_seq_check(SeqCtl* ctl, unsigned pairs, float* out, size_t n, unsigned* sticky, unsigned* guard_dev, unsigned* guard_host) {
   const bool good = ctl->abort == 0u && ctl->done == pairs;
   __syncthreads();
   for (unsigned i = threadIdx.x; i < sizeof(SeqCtl) / sizeof(unsigned); i += blockDim.x) reinterpret_cast<unsigned*>(ctl)[i] = 0u;
   if (good) return;
   if (threadIdx.x == 0) { *sticky = 1u; persist_guard_raise(guard_dev, guard_host); }
   for (size_t i = threadIdx.x; i < n; i += blockDim.x) out[i] = __uint_as_float(0x7fc00000u);
-  for (size_t i = threadIdx.x; i < mail_n; i += blockDim.x) mail[i] = __uint_as_float(kSeqSentinel);
 }
 
 // Round 6: the check rides in the recurrence launch.  Every workgroup counts itself out; the last one to leave sees the
 // control block in its final state (every other workgroup's atomics are in L2 before its exit count), does what
 // lstm_seq_check does -- verdict, control block zeroed for the next launch, on failure the sticky flag, the guard and the NaN
 // poison -- and the step has six launches less.  (first use on a device: `fold` = 0, the host reads the control block itself)
+// `mail` (backward pass): an aborted launch leaves consumed and unconsumed hand-overs in the mailboxes, which the next
+// launch would read as valid ones (ADVICE r4) -- the same workgroup fills them with sentinels again, so that a caller who
+// lowers the guard (pk2_persist_guard_clear) and carries on does not compute on stale words.
 struct SeqExit { unsigned pairs; int fold; float* out; size_t n; unsigned* sticky; unsigned* guard_dev; unsigned* guard_host; float* mail; size_t mail_n; };
 __device__ __forceinline__ void seq_exit_check(SeqCtl* ctl, const SeqExit& x) {
   if (!x.fold) return;
@@ -958,7 +682,7 @@ static std::map<DevStream, SeqScratch> g_seq_scratch;
 static PerDevice<int> g_seq_state_pd(-1);             // -1 untested, 0 unusable, 1 verified on this device
 
 // pk2_persist_guard_clear: whatever an aborted launch left behind, the next backward launch fills every mailbox again
-// (belt and braces next to the refill by lstm_seq_check: a launch that was killed never reached its check kernel).
+// (belt and braces next to the refill by the folded check: a launch that was killed never reached it).
 static void seq_mail_dirty() { for (auto& kv : g_seq_scratch) { kv.second.mail_clean_teams = 0; kv.second.ctl_clean = false; } }
 
 static int seq_scratch(hipStream_t stream, SeqScratch** out) {
@@ -978,21 +702,7 @@ static int seq_scratch(hipStream_t stream, SeqScratch** out) {
 
 // Teams per XCD of a launch: with more than 8 pairs a second team per XCD takes its own pairs from the queue at the same
 // time (two workgroups per CU; a recurrence is latency-bound, two of them interleave almost for free).
-static int seq_teams(int pairs) {
-  const char* env = getenv("PK2_LSTM_SEQ_TEAMS");
-  const int most = env ? std::max(1, std::min(atoi(env), kSeqTeams)) : 2;
-  return std::max(1, std::min(most, (pairs + 7) / 8));
-}
-
-// PK2_LSTM_SEQ_FORM=1 keeps the round-2 kernels (lstm_fwd_seq / lstm_bwd_seq) for A/B runs; default: the round-4 forms.
-static int seq_form() {
-  static int form = -1;
-  if (form < 0) {
-    const char* env = getenv("PK2_LSTM_SEQ_FORM");
-    form = (env && atoi(env) == 1) ? 1 : 2;
-  }
-  return form;
-}
+static int seq_teams(int pairs) { return std::max(1, std::min(2, (pairs + 7) / 8)); }
 
 bool lstm_seq_wanted(int B, int H, int D) {
   const char* env = getenv("PK2_LSTM_SEQ");
@@ -1017,18 +727,14 @@ int lstm_fwd_seq_launch(const float* gx, const float* whh, const float* bhh, int
   if (!sc->ctl_clean) PK2_HIP(hipMemsetAsync(sc->ctl, 0, sizeof(SeqCtl), stream));
   sc->ctl_clean = false;
   PK2_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(y), (int)kSeqSentinel, (size_t)T * B * D * H, stream));
-  static const int pre = getenv("PK2_SEQ_FWD_PRESLEEP") ? atoi(getenv("PK2_SEQ_FWD_PRESLEEP")) : 0;
-  static const int lps = getenv("PK2_SEQ_FWD_LOOPSLEEP") ? atoi(getenv("PK2_SEQ_FWD_LOOPSLEEP")) : 0;
-  static const int smode = getenv("PK2_SEQ_STORE_MODE") ? atoi(getenv("PK2_SEQ_STORE_MODE")) : 1;
-  SeqFwdParams p{gx, whh, bhh, y, gates, cells, B, T, D, pre, lps, smode};
-  static const bool fold_env = [] { const char* e = getenv("PK2_LSTM_SEQ_FOLD_CHECK"); return !(e && atoi(e) == 0); }();
-  const bool fold = fold_env && seq_form() != 1 && g_seq_state_pd.ref() == 1;
+  SeqFwdParams p{gx, whh, bhh, y, gates, cells, B, T, D};
+  // (the first launch on a device is checked by the host below and by the separate check kernel: no folded check)
+  const bool fold = g_seq_state_pd.ref() == 1;
   // (test hook, read per call: PK2_LSTM_SEQ_TEST_FAIL=1 makes the folded check of a forward launch behave as if a poll had timed out)
   const char* tf_e = getenv("PK2_LSTM_SEQ_TEST_FAIL");
   const int fold_mode = fold ? ((tf_e && atoi(tf_e) == 1) ? 2 : 1) : 0;
   const SeqExit ex{(unsigned)(B * D), fold_mode, y, (size_t)T * B * D * H, sc->sticky, sc->guard.dev, sc->guard.host_dev, nullptr, (size_t)0};
-  if (seq_form() == 1) hipLaunchKernelGGL(lstm_fwd_seq, dim3(8 * kSWgs * seq_teams(B * D)), dim3(256), 0, stream, p, sc->ctl);
-  else hipLaunchKernelGGL(lstm_fwd_seq2, dim3(8 * kSWgs * seq_teams(B * D)), dim3(256), 0, stream, p, sc->ctl, ex);
+  hipLaunchKernelGGL(lstm_fwd_seq2, dim3(8 * kSWgs * seq_teams(B * D)), dim3(256), 0, stream, p, sc->ctl, ex);
   PK2_LAUNCH_CHECK();
   if (g_seq_state_pd.ref() < 0) {                 // first use on this device: every pair done, nobody timed out?
     SeqCtl* h = new SeqCtl;
@@ -1041,8 +747,7 @@ int lstm_fwd_seq_launch(const float* gx, const float* whh, const float* bhh, int
     if (!ok) return PK2_OK;              // the caller falls back (and keeps doing so)
   }
   if (!fold)
-    hipLaunchKernelGGL(lstm_seq_check, dim3(1), dim3(1024), 0, stream, sc->ctl, (unsigned)(B * D), y, (size_t)T * B * D * H, sc->sticky, sc->guard.dev, sc->guard.host_dev,
-                       nullptr, (size_t)0);
+    hipLaunchKernelGGL(lstm_seq_check, dim3(1), dim3(1024), 0, stream, sc->ctl, (unsigned)(B * D), y, (size_t)T * B * D * H, sc->sticky, sc->guard.dev, sc->guard.host_dev);
   sc->ctl_clean = true;
   *ran = true;
   return PK2_OK;
@@ -1065,21 +770,11 @@ int lstm_bwd_seq_launch(const float* dy, const float* whh, const float* gates, c
     PK2_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(sc->mail), (int)kSeqSentinel, (size_t)8 * seq_teams(B * D) * kSeqMailFloats, stream));
     sc->mail_clean_teams = seq_teams(B * D);
   }
-  static const int pre = getenv("PK2_SEQ_BWD_PRESLEEP") ? atoi(getenv("PK2_SEQ_BWD_PRESLEEP")) : 0;
-  static const int lps = getenv("PK2_SEQ_BWD_LOOPSLEEP") ? atoi(getenv("PK2_SEQ_BWD_LOOPSLEEP")) : 0;
-  static const int smode = getenv("PK2_SEQ_STORE_MODE") ? atoi(getenv("PK2_SEQ_STORE_MODE")) : 1;
-  const bool with_bias = seq_form() != 1 && dbias_ih != nullptr;
-  SeqBwdParams p{dy, whh, gates, cells, dgx, sc->mail, B, T, D, pre, lps, smode, with_bias ? dbias_ih : nullptr, with_bias ? dbias_hh : nullptr};
-  if (bias_done) *bias_done = with_bias;
-  static const bool fold_env = [] { const char* e = getenv("PK2_LSTM_SEQ_FOLD_CHECK"); return !(e && atoi(e) == 0); }();
-  const bool fold = fold_env && seq_form() != 1;
-  const SeqExit ex{(unsigned)(B * D), fold ? 1 : 0, dgx, (size_t)T * B * D * 4 * H, sc->sticky, sc->guard.dev, sc->guard.host_dev, sc->mail,
+  SeqBwdParams p{dy, whh, gates, cells, dgx, sc->mail, B, T, D, dbias_ih, dbias_hh};
+  if (bias_done) *bias_done = dbias_ih != nullptr;
+  const SeqExit ex{(unsigned)(B * D), 1, dgx, (size_t)T * B * D * 4 * H, sc->sticky, sc->guard.dev, sc->guard.host_dev, sc->mail,
                    (size_t)8 * kSeqTeams * kSeqMailFloats};
-  if (seq_form() == 1) hipLaunchKernelGGL(lstm_bwd_seq, dim3(8 * kSWgs * seq_teams(B * D)), dim3(256), 0, stream, p, sc->ctl);
-  else hipLaunchKernelGGL(lstm_bwd_seq2, dim3(8 * kSWgs * seq_teams(B * D)), dim3(256), 0, stream, p, sc->ctl, ex);
-  if (!fold)
-    hipLaunchKernelGGL(lstm_seq_check, dim3(1), dim3(1024), 0, stream, sc->ctl, (unsigned)(B * D), dgx, (size_t)T * B * D * 4 * H, sc->sticky, sc->guard.dev, sc->guard.host_dev,
-                       sc->mail, (size_t)8 * kSeqTeams * kSeqMailFloats);
+  hipLaunchKernelGGL(lstm_bwd_seq2, dim3(8 * kSWgs * seq_teams(B * D)), dim3(256), 0, stream, p, sc->ctl, ex);
   PK2_LAUNCH_CHECK();
   sc->ctl_clean = true;
   *ran = true;

@@ -104,7 +104,7 @@ def _ranks_share_a_device(local_world, devices):
     launch-per-step kernels, which need no co-residency; explicit settings of the caller win."""
     if local_world is None or devices <= 0 or local_world <= devices:
         return
-    changed = [k for k, v in (("PK2_LSTM_SEQ", "0"), ("PK2_LSTM_PERSIST", "0"), ("PK2_LSTM_BIG_PERSIST", "0"), ("PK2_DEN_PERSIST", "0"),
+    changed = [k for k, v in (("PK2_LSTM_SEQ", "0"), ("PK2_LSTM_BIG_PERSIST", "0"), ("PK2_DEN_PERSIST", "0"),
                               ("PK2_LAT_DECODER", "frames")) if os.environ.setdefault(k, v) == v]
     if changed and os.environ.get("RANK", "0") == "0":
         sys.stderr.write("[hvd] %d local ranks on %d device(s): ranks share a GPU, persistent kernels off (%s)\n"
