@@ -228,7 +228,7 @@ __global__ void scale_vec_kernel(float* v, int n, float beta) {
 
 using namespace pk2;
 
-// PK2_GEMM_ARITH = f32 (v_mfma_f32_32x32x2_f32, an f32 fmaf chain) | bf16x3 (three-way bf16 split, six products per k-step
+// PK2_GEMM_ARITH = f32 (v_mfma_f32_32x32x2_f32, a k-ordered f32 fmaf chain, bit for bit) | bf16x3 (three-way bf16 split, six products per k-step
 // on v_mfma_f32_32x32x16_bf16, f32 accumulation: gemm_bf16x3.h).  Read once per process; pk2_gemm_set_arith overrides.
 #ifndef PK2_GEMM_ARITH_DEFAULT
 #define PK2_GEMM_ARITH_DEFAULT 1

@@ -5,6 +5,7 @@ import pytest
 import torch
 
 from oracle import frontend_ref as F
+from oracle import gemm_ref as G
 from pykaldi2_amd import _lib, fbank, lstm, ops, optim
 
 pytestmark = pytest.mark.gpu
@@ -113,6 +114,11 @@ def test_gemm_f32_matches_float64(ta, tb, M, N, K, arith, gemm_arith):
     got = c.cpu().numpy()
     err = np.abs(got - want).max()
     assert err < 2e-4 * np.sqrt(K), err
+    # the same error in units of sum_k |alpha a b| + |beta C| + |bias| (oracle/gemm_ref.py: a dropped bf16x3 part product or
+    # lo plane costs rms >= 1.1e-7 there at K <= 1024; these bounds are 2x above the correct arithmetic's CPU model)
+    rms_b, max_b = G.STAT_BOUND[arith]
+    rms, mx = G.err_units(got, A.T if ta else A, B.T if tb else B, 0.5, 2.0, C0, bias)
+    assert rms <= rms_b and mx <= 2 * max_b, (rms, mx)
     # the same call again gives the same bits (partial tiles are added in part order, whoever arrives last)
     c2 = torch.from_numpy(C0.copy()).cuda()
     lstm._gemm(ta, tb, M, N, K, lstm._p(a), A.shape[1], lstm._p(b), B.shape[1], lstm._p(c2), N, bias=lstm._p(bs),
@@ -472,6 +478,9 @@ def test_weight_and_bias_gradient_in_one_launch(M, N, K, arith, gemm_arith):
     want_b = A.astype(np.float64).sum(0) + b0
     assert np.abs(c.cpu().numpy() - want_c).max() < 2e-4 * np.sqrt(K)
     assert np.abs(bs.cpu().numpy() - want_b).max() < 2e-5 * np.sqrt(K), np.abs(bs.cpu().numpy() - want_b).max()
+    rms_b, max_b = G.STAT_BOUND[arith]
+    rms, mx = G.err_units(c.cpu().numpy(), A.T, B, 1.0, 1.0, C0)
+    assert rms <= rms_b and mx <= 2 * max_b, (rms, mx)
 
 
 def test_check_inside_the_recurrence_launch_poisons_and_raises_the_guard(monkeypatch):

@@ -8,6 +8,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from oracle import gemm_ref as G
 from pykaldi2_amd import transformer
 
 pytestmark = pytest.mark.gpu
@@ -314,6 +315,9 @@ def test_gemm_act_epilogues_equal_the_product_followed_by_the_row_pass(M, N, K, 
         assert torch.equal(one, two)
         ref = torch.relu(A.double().cpu() @ W.double().cpu().t() + b.double().cpu())
         assert (one.cpu().double() - ref).abs().max().item() < 2e-5 * max(1.0, ref.abs().max().item())
+        rms_b, max_b = G.STAT_BOUND["f32" if arith == 0 else "bf16x3"]
+        rms, mx = G.err_units(one.cpu().numpy(), A.cpu().numpy(), W.cpu().numpy().T, bias=b.cpu().numpy(), want=ref.numpy())
+        assert rms <= rms_b and mx <= 2 * max_b, (rms, mx)
         # backward mask, beta = 0 and beta = 1 (the residual sum the attention block's last dX product adds into)
         Wd = torch.randn(K, N, device="cuda", generator=g) / K ** 0.5
         gate = torch.randn(M, N, device="cuda", generator=g)
@@ -408,6 +412,13 @@ def test_segmented_product_is_the_three_tap_convolution(R, B, C, arith):
         _lib.check(L.pk2_gemm_f32_seg(0, 1, R, C, C, 3, 1.0, p(xp), C, B * C, p(Wp), C, C * C, 0.0, p(y), C, p(bias), 1, None, 0, sp))
         scale = max(1.0, want.abs().max().item())
         assert (y.cpu().double() - want.detach().reshape(R, C)).abs().max().item() < 2e-5 * scale
+        # in units of sum |x w| + |bias| over the three taps, against the float32 operands the device multiplied
+        xh, Wh, bh = xp.cpu().numpy(), Wp.cpu().numpy(), bias.cpu().numpy()
+        Acat = np.concatenate([xh[j * B:j * B + R] for j in range(3)], 1)
+        Bcat = np.concatenate([Wh[j].T for j in range(3)], 0)
+        rms_b, max_b = G.STAT_BOUND["f32" if arith == 0 else "bf16x3"]
+        rms, mx = G.err_units(y.cpu().numpy(), Acat, Bcat, bias=bh, want=np.maximum(G.gemm_exact(Acat, Bcat, bias=bh), 0.0))
+        assert rms <= rms_b and mx <= 2 * max_b, (rms, mx)
         dcp = torch.zeros(R + 2 * B, C, device="cuda")
         dcp[B:B + R] = dy.reshape(R, C).float().cuda()
         dx = torch.empty(R, C, device="cuda")
