@@ -217,6 +217,54 @@ int pk2_supervision_copy(const pk2_supervision* s, int32_t* arc_src, int32_t* ar
                          float* final_weight, int32_t* allowed_off, int32_t* allowed_phones);
 
 /* ------------------------------------------------------------------ *
+ * Forced alignment (kaldi.alignment.MappedAligner.align, reference bin/train_se2.py:192-199,263): training graphs
+ * compiled on the host (csrc/align_graph.hip: transcript x L.fst x tree x H with reordered self-loops, built directly),
+ * one Viterbi launch for a minibatch on the device (csrc/align_viterbi.hip).
+ * ------------------------------------------------------------------ */
+/* L.fst: input labels are phones, output labels words; input labels listed in `disambig` count as epsilon. */
+typedef struct pk2_lexicon pk2_lexicon;
+pk2_lexicon* pk2_lexicon_create(int32_t num_states, int32_t start, int64_t num_arcs, const int32_t* src, const int32_t* dst,
+                                const int32_t* ilabel, const int32_t* olabel, const float* weight, const float* final_cost,
+                                const int32_t* disambig, int32_t num_disambig);
+pk2_lexicon* pk2_lexicon_from_openfst(const char* path, const int32_t* disambig, int32_t num_disambig);
+void pk2_lexicon_destroy(pk2_lexicon* lexicon);
+/* The tree and topologies of `m` (copied), the transition model's tuples in its order (they number the transition-ids),
+ * log_probs[num_tids + 1] (entry 0 unused) and the two graph scales.  Fails for a context window other than N = 1,
+ * N = 2 (P = 0 or 1), N = 3 (P = 1). */
+typedef struct pk2_align_model pk2_align_model;
+pk2_align_model* pk2_align_model_create(const pk2_sup_model* m, int32_t num_tuples, const int32_t* tuples, int32_t num_tids,
+                                        const double* log_probs, double transition_scale, double self_loop_scale);
+void pk2_align_model_destroy(pk2_align_model* model);
+/* Training graphs of a batch: transcript n = words[word_off[n] .. word_off[n+1]), frames[n] frames.  Per utterance a
+ * status: 0 = compiled, 2 = no path of that many frames, 3 = error (unknown word, no lexicon path, epsilon cycle, a
+ * phone the model lacks; pk2_align_graphs_error has the reason).  Null only for bad arguments. */
+typedef struct pk2_align_graphs pk2_align_graphs;
+pk2_align_graphs* pk2_align_compile(const pk2_align_model* model, const pk2_lexicon* lexicon, int32_t num_utts,
+                                    const int32_t* word_off, const int32_t* words, const int32_t* frames);
+void pk2_align_graphs_destroy(pk2_align_graphs* graphs);
+int pk2_align_graphs_info(const pk2_align_graphs* graphs, int32_t utt, int32_t* status, int32_t* num_states, int32_t* num_arcs);
+const char* pk2_align_graphs_error(const pk2_align_graphs* graphs, int32_t utt);
+/* One graph: in-arcs of state s are in_off[s] .. in_off[s+1], ordered by (source, transition-id); arc_src = -1 marks an
+ * arc from the start state.  final_cost = +inf for non-final states.  Null pointers are skipped. */
+int pk2_align_graphs_copy(const pk2_align_graphs* graphs, int32_t utt, int32_t* in_off, int32_t* arc_src, int32_t* arc_tid,
+                          int32_t* arc_pdf, float* arc_weight, float* final_cost);
+/* The batch as one int32 buffer (copy it to the device in one transfer) and the workspace pk2_align_viterbi needs. */
+int64_t pk2_align_graphs_packed_words(const pk2_align_graphs* graphs);
+int pk2_align_graphs_pack(const pk2_align_graphs* graphs, int32_t* out);
+size_t pk2_align_workspace_bytes(const pk2_align_graphs* graphs);
+/* 1 when the next pk2_align_viterbi keeps costs and graph in LDS (the graph fits and PK2_ALIGN_LDS is not 0). */
+int pk2_align_use_lds(const pk2_align_graphs* graphs);
+/* Viterbi of every utterance, one workgroup each, on `stream`.  packed_dev: the pk2_align_graphs_pack buffer on the device.
+ * loglikes: device f32, frame t of utterance n at loglikes[n * seq_stride + t * frame_stride], num_pdfs columns, already
+ * prior-subtracted; only frames < frames[n] are read.  Outputs (device): alignment i32[N][Tmax] (transition-ids, 0 past
+ * the end and for failed utterances), costs f32[N][3] = {total, graph, acoustic} (+inf when failed), status i32[N] =
+ * 0 ok, 1 no final state within the beam, 2 / 3 as compiled.  The arithmetic is specified in csrc/align_viterbi.hip. */
+int pk2_align_viterbi(const pk2_align_graphs* graphs, const int32_t* packed_dev, const float* loglikes, int64_t seq_stride,
+                      int64_t frame_stride, int32_t num_pdfs, int32_t Tmax, float acoustic_scale, float beam,
+                      int32_t* alignment, float* costs, int32_t* status, void* workspace, size_t workspace_bytes,
+                      void* stream);
+
+/* ------------------------------------------------------------------ *
  * Reverberation + additive noise of one utterance (single channel), device arrays throughout.
  * Replaces the numpy arithmetic of the reference's dynamic data simulation: Distorter.apply_rir /
  * Distorter.add_noise (reference simulation/_distorter.py:86-154) as _Simulator.simulate uses them for one

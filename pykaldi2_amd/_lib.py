@@ -70,6 +70,21 @@ SIGNATURES = {
     "pk2_supervision_sizes": (None, [_vp, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32),
                                      C.POINTER(_i32)]),
     "pk2_supervision_copy": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pk2_lexicon_create": (_vp, [_i32, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32]),
+    "pk2_lexicon_from_openfst": (_vp, [C.c_char_p, _vp, _i32]),
+    "pk2_lexicon_destroy": (None, [_vp]),
+    "pk2_align_model_create": (_vp, [_vp, _i32, _vp, _i32, _vp, C.c_double, C.c_double]),
+    "pk2_align_model_destroy": (None, [_vp]),
+    "pk2_align_compile": (_vp, [_vp, _vp, _i32, _vp, _vp, _vp]),
+    "pk2_align_graphs_destroy": (None, [_vp]),
+    "pk2_align_graphs_info": (C.c_int, [_vp, _i32, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32)]),
+    "pk2_align_graphs_error": (C.c_char_p, [_vp, _i32]),
+    "pk2_align_graphs_copy": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pk2_align_graphs_packed_words": (_i64, [_vp]),
+    "pk2_align_graphs_pack": (C.c_int, [_vp, _vp]),
+    "pk2_align_workspace_bytes": (_sz, [_vp]),
+    "pk2_align_use_lds": (C.c_int, [_vp]),
+    "pk2_align_viterbi": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i32, _i32, _f32, _f32, _vp, _vp, _vp, _vp, _sz, _vp]),
     "pk2_decode_graph_create": (C.c_int, [_i32, _i32, _i64, _vp, _vp, _vp, _vp, _vp, C.POINTER(_vp)]),
     "pk2_decode_graph_create_words": (C.c_int, [_i32, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_vp)]),
     "pk2_decode_graph_link_words": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp]),

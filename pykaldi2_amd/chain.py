@@ -6,6 +6,7 @@
   SupervisionOptions                         bin/train_chain.py:184-188
   Supervision                                bin/train_chain.py:271-272
   MappedAligner.to_phone_alignment           bin/train_chain.py:195-200,263
+  MappedAligner.align / align_batch          bin/train_se2.py:192-199,263
   alignment_to_proto_supervision             bin/train_chain.py:271
   proto_supervision_to_supervision           bin/train_chain.py:272
   compute_chain_objf_and_deriv(...)          ops/ops.py:265
@@ -322,23 +323,288 @@ def supervision_from_alignment(aligner, tree, trans_model, opts, trans_ids):
     return proto_supervision_to_supervision(tree, trans_model, proto, opts.convert_to_pdfs)
 
 
+def read_disambig(path):
+    """phones/disambig.int: one integer per line (empty file or None -> [])."""
+    if not path:
+        return []
+    with open(path) as f:
+        return [int(tok) for line in f for tok in line.split()[:1]]
+
+
+def read_symbols(path):
+    """words.txt: `<word> <id>` per line -> {word: id}."""
+    with open(path) as f:
+        return {p[0]: int(p[1]) for p in (line.split() for line in f) if len(p) >= 2}
+
+
+class Lexicon:
+    """L.fst for the aligner (pk2_lexicon): a path to an OpenFst binary or a dict of arc arrays (num_states, start, src, dst,
+    ilabel, olabel, weight, final; pykaldi2_amd.synth.lexicon_arcs).  Input labels in `disambig` count as epsilon."""
+
+    def __init__(self, fst, disambig=()):
+        L = _lib.lib()
+        dis = np.ascontiguousarray(list(disambig), np.int32)
+        if isinstance(fst, (str, bytes)):
+            h = L.pk2_lexicon_from_openfst(fst.encode() if isinstance(fst, str) else fst, _lib.ptr(dis), dis.shape[0])
+        else:
+            a = {k: np.ascontiguousarray(fst[k], np.int32) for k in ("src", "dst", "ilabel", "olabel")}
+            w = np.ascontiguousarray(fst["weight"], np.float32)
+            fin = np.ascontiguousarray(fst["final"], np.float32)
+            assert fin.shape[0] == int(fst["num_states"])
+            h = L.pk2_lexicon_create(int(fst["num_states"]), int(fst.get("start", 0)), a["src"].shape[0], _lib.ptr(a["src"]),
+                                     _lib.ptr(a["dst"]), _lib.ptr(a["ilabel"]), _lib.ptr(a["olabel"]), _lib.ptr(w), _lib.ptr(fin),
+                                     _lib.ptr(dis), dis.shape[0])
+        if not h:
+            raise _lib.Pk2Error(L.pk2_last_error().decode())
+        self._h = h
+
+    def __del__(self):
+        try:
+            if self._h:
+                _lib.lib().pk2_lexicon_destroy(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+
+class AlignModel:
+    """pk2_align_model: tree + transition model (topology, tuples, log_probs) + the two graph scales."""
+
+    def __init__(self, tree, trans_model, transition_scale=1.0, self_loop_scale=1.0):
+        lp = getattr(trans_model, "log_probs", None)
+        if lp is None:
+            raise ValueError("the transition model has no <LogProbs> (read it from final.mdl): the aligner needs them")
+        if lp.shape[0] != trans_model.num_transition_ids() + 1:
+            raise ValueError("<LogProbs> holds %d values for %d transition-ids" % (lp.shape[0], trans_model.num_transition_ids()))
+        self._sup = _SupModel(tree, trans_model)      # keeps the tree / topology handle alive
+        tuples = np.ascontiguousarray(trans_model.tuples, np.int32)
+        lp = np.ascontiguousarray(lp, np.float64)
+        L = _lib.lib()
+        self._h = L.pk2_align_model_create(self._sup._h, tuples.shape[0], _lib.ptr(tuples), trans_model.num_transition_ids(),
+                                           _lib.ptr(lp), float(transition_scale), float(self_loop_scale))
+        if not self._h:
+            raise _lib.Pk2Error(L.pk2_last_error().decode())
+
+    def __del__(self):
+        try:
+            if self._h:
+                _lib.lib().pk2_align_model_destroy(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+
+ALIGN_OK, ALIGN_BEAM, ALIGN_NO_PATH, ALIGN_ERROR = 0, 1, 2, 3
+
+
+class AlignmentGraphs:
+    """Training graphs of a batch of transcripts (one pk2_align_compile call).  status[n]: 0 compiled, 2 no path of
+    frames[n] frames, 3 error (errors[n] says why)."""
+
+    def __init__(self, model, lexicon, texts, frames):
+        word_off = np.cumsum([0] + [len(t) for t in texts]).astype(np.int32)
+        words = np.ascontiguousarray([int(w) for t in texts for w in t] or [0], np.int32)
+        self.frames = np.ascontiguousarray(frames, np.int32)
+        assert self.frames.shape[0] == len(texts)
+        L = _lib.lib()
+        self._h = L.pk2_align_compile(model._h, lexicon._h, len(texts), _lib.ptr(word_off), _lib.ptr(words), _lib.ptr(self.frames))
+        if not self._h:
+            raise _lib.Pk2Error(L.pk2_last_error().decode())
+        self._keep = (model, lexicon)
+        self.n = len(texts)
+        self.status, self.num_states, self.num_arcs, self.errors = [], [], [], []
+        for i in range(self.n):
+            v = [C.c_int32() for _ in range(3)]
+            _lib.check(L.pk2_align_graphs_info(self._h, i, *[C.byref(x) for x in v]))
+            self.status.append(v[0].value); self.num_states.append(v[1].value); self.num_arcs.append(v[2].value)
+            self.errors.append(L.pk2_align_graphs_error(self._h, i).decode())
+
+    def export(self, i):
+        """Graph i as arrays: in_off[S+1], per in-arc src (-1 = from the start state), tid, pdf, weight (f32); final (f32)."""
+        S, A = self.num_states[i], self.num_arcs[i]
+        out = dict(in_off=np.empty(S + 1, np.int32), src=np.empty(A, np.int32), tid=np.empty(A, np.int32),
+                   pdf=np.empty(A, np.int32), weight=np.empty(A, np.float32), final=np.empty(S, np.float32))
+        _lib.check(_lib.lib().pk2_align_graphs_copy(self._h, i, *[_lib.ptr(out[k]) for k in
+                                                                 ("in_off", "src", "tid", "pdf", "weight", "final")]))
+        out["dst"] = np.repeat(np.arange(S, dtype=np.int32), np.diff(out["in_off"]))
+        return out
+
+    def workspace_bytes(self):
+        return int(_lib.lib().pk2_align_workspace_bytes(self._h))
+
+    def uses_lds(self):
+        return bool(_lib.lib().pk2_align_use_lds(self._h))
+
+    def to_device(self, device):
+        """The packed batch in one pinned host-to-device copy."""
+        L = _lib.lib()
+        host = torch.empty(int(L.pk2_align_graphs_packed_words(self._h)), dtype=torch.int32).pin_memory()
+        _lib.check(L.pk2_align_graphs_pack(self._h, _lib.ptr(host)))
+        self._host = host
+        return host.to(device, non_blocking=True)
+
+    def __del__(self):
+        try:
+            if self._h:
+                _lib.lib().pk2_align_graphs_destroy(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+
+_align_ws = {}
+
+
+def align_viterbi(graphs, loglikes, acoustic_scale, beam):
+    """One pk2_align_viterbi launch on the current stream.  loglikes: f32 device tensor [N, Tmax, P] (any row strides, unit
+    column stride), prior already subtracted.  Returns device tensors (alignment i32[N, Tmax], costs f32[N, 3] = total,
+    graph, acoustic, status i32[N])."""
+    _lib.require_gpu()
+    x = loglikes
+    assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and x.stride(2) == 1
+    N, Tmax, P = x.shape
+    assert N == graphs.n and int(graphs.frames.max()) <= Tmax
+    dev = graphs.to_device(x.device)
+    key = x.device.index if x.device.index is not None else torch.cuda.current_device()
+    need = graphs.workspace_bytes()
+    ws = _align_ws.get(key)
+    if ws is None or ws.numel() < need:      # grow-only
+        _align_ws[key] = None
+        ws = _align_ws[key] = torch.empty(int(need * 1.25) + 4096, dtype=torch.uint8, device=x.device)
+    ali = torch.empty(N, Tmax, dtype=torch.int32, device=x.device)
+    costs = torch.empty(N, 3, dtype=torch.float32, device=x.device)
+    status = torch.empty(N, dtype=torch.int32, device=x.device)
+    _lib.check(_lib.lib().pk2_align_viterbi(graphs._h, _lib.ptr(dev), _lib.ptr(x), x.stride(0), x.stride(1), P, Tmax,
+                                            float(acoustic_scale), float(beam), _lib.ptr(ali), _lib.ptr(costs), _lib.ptr(status),
+                                            _lib.ptr(ws), ws.numel(), _lib.stream_ptr(x.device)))
+    ali._pk2_keepalive = (graphs, dev)
+    return ali, costs, status
+
+
 class MappedAligner:
-    """The one use the reference makes of kaldi.alignment.MappedAligner (bin/train_chain.py:195-200,263):
-    to_phone_alignment on the transition-ids of the label files.  The decoding side of the aligner (tree, L.fst,
-    beams) is not needed for that and is ignored."""
+    """kaldi.alignment.MappedAligner.  to_phone_alignment (reference bin/train_chain.py:195-200,263) splits the
+    transition-ids of the label files into phones.  align / align_batch (reference bin/train_se2.py:192-199,263) make the
+    transition-id alignment of a word transcript on the device: the training graph transcript x L.fst x tree x H is
+    compiled on the host (csrc/align_graph.hip), the Viterbi pass aligns a whole minibatch in one launch
+    (csrc/align_viterbi.hip).  The tree and L.fst of from_files are read at the first align."""
+
+    _tree = _lexicon = _model = _symbols = None
+    _tree_path = _lexicon_path = _disambig_path = _symbols_path = None
+    beam, retry_beam, transition_scale, self_loop_scale, acoustic_scale = 200.0, None, 1.0, 1.0, 0.1
 
     def __init__(self, trans_model):
         self.transition_model = trans_model
 
     @classmethod
     def from_files(cls, model_rxfilename, tree_rxfilename=None, lexicon_rxfilename=None, symbols_filename=None,
-                   disambig_rxfilename=None, **unused):
+                   disambig_rxfilename=None, graph_compiler_opts=None, beam=200.0, transition_scale=1.0, self_loop_scale=1.0,
+                   acoustic_scale=0.1, retry_beam=None, **unused):
         from .lattice import TransitionModel
-        return cls(TransitionModel.read(model_rxfilename))
+        a = cls(TransitionModel.read(model_rxfilename))
+        a._tree_path, a._lexicon_path = tree_rxfilename, lexicon_rxfilename
+        a._disambig_path, a._symbols_path = disambig_rxfilename, symbols_filename
+        a._set_options(beam, transition_scale, self_loop_scale, acoustic_scale, retry_beam)
+        return a
+
+    @classmethod
+    def from_models(cls, trans_model, tree, lexicon, disambig=(), symbols=None, beam=200.0, transition_scale=1.0,
+                    self_loop_scale=1.0, acoustic_scale=0.1, retry_beam=None):
+        """Same as from_files with objects: tree = ContextDependency, lexicon = Lexicon / path / arc dict, symbols = {word: id}."""
+        a = cls(trans_model)
+        a._tree = tree
+        a._lexicon = lexicon if isinstance(lexicon, Lexicon) else Lexicon(lexicon, disambig)
+        a._symbols = symbols
+        a._set_options(beam, transition_scale, self_loop_scale, acoustic_scale, retry_beam)
+        return a
+
+    def _set_options(self, beam, transition_scale, self_loop_scale, acoustic_scale, retry_beam):
+        self.beam, self.transition_scale, self.self_loop_scale = float(beam), float(transition_scale), float(self_loop_scale)
+        self.acoustic_scale, self.retry_beam = float(acoustic_scale), None if retry_beam is None else float(retry_beam)
 
     def to_phone_alignment(self, alignment, phones=None):
         """-> [(phone, start frame, duration)]."""
         return split_to_phones(self.transition_model, alignment)[1]
+
+    def _graph_model(self):
+        if self._model is None:
+            if self._lexicon is None:
+                if not self._lexicon_path:
+                    raise RuntimeError("MappedAligner.align needs a lexicon: build the aligner with from_files(model, tree, "
+                                       "L.fst, ...) or from_models")
+                from .tree import ContextDependency
+                if not self._tree_path:
+                    raise RuntimeError("MappedAligner.align needs the tree")
+                self._tree = ContextDependency.read(self._tree_path)
+                self._lexicon = Lexicon(self._lexicon_path, read_disambig(self._disambig_path))
+                if self._symbols_path:
+                    self._symbols = read_symbols(self._symbols_path)
+            self._model = AlignModel(self._tree, self.transition_model, self.transition_scale, self.self_loop_scale)
+        return self._model, self._lexicon
+
+    def _words(self, text):
+        if isinstance(text, str):
+            text = text.split()
+        out = []
+        for w in text:
+            if isinstance(w, str) and self._symbols is not None:
+                if w not in self._symbols:
+                    raise RuntimeError("word %r is not in the symbol table" % w)
+                out.append(self._symbols[w])
+            else:
+                out.append(int(w))
+        return out
+
+    def compile(self, texts, frames):
+        """Training graphs of transcripts for utterances of frames[n] frames (AlignmentGraphs)."""
+        model, lexicon = self._graph_model()
+        return AlignmentGraphs(model, lexicon, [self._words(t) for t in texts], frames)
+
+    def _viterbi(self, x, lengths, texts, beam):
+        graphs = self.compile(texts, lengths)
+        ali, costs, status = align_viterbi(graphs, x, self.acoustic_scale, beam)
+        return graphs, ali.cpu().numpy(), costs.cpu().numpy(), status.cpu().numpy()
+
+    @staticmethod
+    def _as_device(loglikes, dims):
+        x = torch.from_numpy(np.ascontiguousarray(loglikes)) if isinstance(loglikes, np.ndarray) else loglikes
+        if not x.is_cuda:
+            _lib.require_gpu()
+            x = x.to("cuda")
+        x = x.detach().to(torch.float32)
+        if x.dim() != dims:
+            raise ValueError("log-likelihoods of shape %s, expected %d dimensions" % (tuple(x.shape), dims))
+        return x if x.stride(-1) == 1 else x.contiguous()
+
+    @staticmethod
+    def _result(ali, cost, T):
+        return {"alignment": [int(v) for v in ali[:T]], "likelihood": -float(cost[0]),
+                "weight": (float(cost[1]), float(cost[2])), "best_path": None}
+
+    def align(self, loglikes, text):
+        """loglikes [T, P] (prior subtracted), text = word ids (list or whitespace string; words with a symbol table) ->
+        {"alignment": [transition-ids], "likelihood": -cost, "weight": (graph cost, acoustic cost), "best_path": None}.
+        Raises RuntimeError when the utterance cannot be aligned (after a retry at retry_beam, when set)."""
+        self._graph_model()      # a missing lexicon / tree is reported before anything touches the device
+        x = self._as_device(loglikes, 2)[None]
+        T = int(x.shape[1])
+        for beam in [self.beam] + ([self.retry_beam] if self.retry_beam else []):
+            graphs, ali, costs, status = self._viterbi(x, [T], [text], beam)
+            if status[0] == ALIGN_OK:
+                return self._result(ali[0], costs[0], T)
+            if status[0] != ALIGN_BEAM:
+                break
+        why = {ALIGN_BEAM: "no final state within the beam", ALIGN_NO_PATH: graphs.errors[0],
+               ALIGN_ERROR: graphs.errors[0]}[int(status[0])]
+        raise RuntimeError("alignment failed: %s" % why)
+
+    def align_batch(self, loglikes, lengths, texts, beam=None):
+        """loglikes [N, Tmax, P] (device, prior subtracted), lengths[N], texts[N]: one compile call and one launch on the
+        current stream.  Returns a list of align() results, None where an utterance failed."""
+        self._graph_model()
+        x = self._as_device(loglikes, 3)
+        lengths = [int(t) for t in lengths]
+        _, ali, costs, status = self._viterbi(x, lengths, texts, self.beam if beam is None else beam)
+        return [self._result(ali[n], costs[n], lengths[n]) if status[n] == ALIGN_OK else None for n in range(len(lengths))]
 
 
 class _SupervisionBatch:

@@ -26,43 +26,14 @@
 #include <set>
 #include <vector>
 
-#include "common.h"
-
-struct pk2_sup_model {
-  int32_t N = 0, P = 0;
-  std::vector<int32_t> phone2entry, entry_off, fwd_class, loop_class, trans_off, trans_dst;
-  std::vector<int32_t> kind, key, a, b, pool;
-  std::set<std::array<int32_t, 4>> tuples;
-};
+#include "sup_model.h"
 
 struct pk2_supervision {
   int32_t frames = 0, num_states = 0;
   std::vector<int32_t> src, dst, pdf, frame_off, state_time, finals, allowed_off, allowed;
 };
 
-namespace {
-
-// EventMap::Map on the flattened tree.
-bool tree_answer(const pk2_sup_model& m, const int32_t* window, int32_t pdf_class, int32_t* ans) {
-  int32_t node = 0;
-  for (size_t guard = 0; guard <= m.kind.size(); ++guard) {
-    if (node < 0 || node >= (int32_t)m.kind.size()) return false;
-    if (m.kind[node] == 0) { *ans = m.a[node]; return true; }
-    const int32_t k = m.key[node];
-    if (k < -1 || k >= m.N) return false;
-    const int32_t v = k == -1 ? pdf_class : window[k];
-    const int32_t* p = m.pool.data() + m.a[node];
-    if (m.kind[node] == 1) {
-      if (v < 0 || v >= m.b[node]) return false;
-      node = p[v];
-    } else {
-      node = p[m.b[node] + (std::binary_search(p, p + m.b[node], v) ? 0 : 1)];
-    }
-  }
-  return false;   // cycle in a malformed tree
-}
-
-}  // namespace
+using pk2::tree_answer;
 
 extern "C" {
 

@@ -44,6 +44,7 @@ class TransitionModel:
         assert self.tid2pdf.shape == self.tid2phone.shape and self.tid2pdf.ndim == 1
         self._dev = {}
         self.phone2entry = self.entries = self.tuples = self.tid2tstate = self.tid_flags = None
+        self.log_probs = None     # float64[num_tids + 1] (entry 0 unused) when read from a file with <LogProbs>
 
     @classmethod
     def from_arrays(cls, d):
@@ -75,7 +76,9 @@ class TransitionModel:
     @classmethod
     def read(cls, path):
         """Kaldi transition model, text (`copy-transition-model --binary=false`) or binary (`final.mdl`) form
-        [upstream knowledge of the formats: <TransitionModel> <Topology> ... </Topology> <Triples>|<Tuples> n ... ].
+        [upstream knowledge of the formats: <TransitionModel> <Topology> ... </Topology> <Triples>|<Tuples> n ...
+        </Tuples> <LogProbs> vector </LogProbs>; a binary vector is "FV ", an int32 count and raw floats].
+        <LogProbs> becomes `log_probs` (indexed by transition-id, entry 0 unused); None when the file has none.
         Transition ids enumerate, for every tuple in file order, the transitions of its HMM state in topology order."""
         with open(path, "rb") as f:
             head = f.read(2)
@@ -127,7 +130,13 @@ class TransitionModel:
             vals = [int(x) for x in toks[i:i + width]]
             i += width
             tuples.append((vals[0], vals[1], vals[2], vals[-1]))
-        return cls.from_topology(phone_entry, entries, tuples)
+        m = cls.from_topology(phone_entry, entries, tuples)
+        if "<LogProbs>" in toks[i:]:
+            j = toks.index("<LogProbs>", i) + 1
+            assert toks[j] == "[", "%s: <LogProbs> is not followed by a vector" % path
+            end = toks.index("]", j)
+            m.log_probs = np.asarray([float(v) for v in toks[j + 1:end]], np.float64)
+        return m
 
     @classmethod
     def _read_binary(cls, raw, path):
@@ -192,7 +201,15 @@ class TransitionModel:
             phone, hmm_state, fwd_pdf = i32(), i32(), i32()
             tuples.append((phone, hmm_state, fwd_pdf, i32() if tag == "<Tuples>" else fwd_pdf))
         token("</Triples>" if tag == "<Triples>" else "</Tuples>")
-        return cls.from_topology({ph: phone2idx[ph] for ph in phones}, entries, tuples)
+        m = cls.from_topology({ph: phone2idx[ph] for ph in phones}, entries, tuples)
+        if raw.startswith(b"<LogProbs> ", pos):
+            token("<LogProbs>")
+            kind = token()
+            if kind not in ("FV", "DV"):
+                raise ValueError("%s: <LogProbs> holds %s, not a vector" % (path, kind))
+            n = i32()
+            m.log_probs = np.frombuffer(raw, "<f4" if kind == "FV" else "<f8", n, pos).astype(np.float64)
+        return m
 
     def num_transition_ids(self):
         return int(self.tid2pdf.shape[0] - 1)

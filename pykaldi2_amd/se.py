@@ -66,3 +66,36 @@ def sequence_loss(model, fb, batch, asr_decoder, trans_model, log_prior, criteri
     se = ops.LatticeBatchFunction.apply(loglikes, [int(t) for t in frames], asr_decoder, trans_model, batch["aux"],
                                         criterion, silence_ids)
     return se + ce_ratio * ce_loss, se, ce_loss, frames
+
+
+def sequence_loss_aligned(model, fb, batch, texts, aligner, asr_decoder, trans_model, log_prior, criterion, silence_ids,
+                          ce_ratio, ce_criterion, forward=None, transform=None):
+    """The step of the reference's bin/train_se2.py:240-273: the numerator alignment of every utterance is made on the fly
+    from its word transcript (`texts`) with the current model -- one MappedAligner.align_batch on prediction - log_prior
+    for the whole minibatch -- instead of being read from the label files.  Utterances that fail to align are left out of
+    the sequence term.  loss = ce_ratio * ce_loss + sum of the sequence criterion.  Returns (loss, se_value, ce_loss,
+    frames, indices of the utterances that failed)."""
+    feats, frames, row_off = fb(batch["wav"], batch["lens"])
+    if transform is not None:
+        feats = transform(feats)
+    x = fb.pad_roll_subsample(feats, row_off, frames, shift=0, subsample=1, time_major=True)
+    prediction = forward(model, x, frames) if forward is not None else model.forward_time_major(x).transpose(0, 1)
+    N, Tmax = prediction.shape[0], prediction.shape[1]
+    y = np.full((N, Tmax), -100, np.int64)
+    for n, lab in enumerate(batch["y"]):
+        y[n, :frames[n]] = np.asarray(lab)[:frames[n]]
+    ce_loss = ce_criterion(prediction, torch.from_numpy(y).to(prediction.device))
+    loglikes = prediction - log_prior
+    lengths = [int(t) for t in frames]
+    ali = aligner.align_batch(loglikes.detach(), lengths, texts)
+    keep = [n for n, r in enumerate(ali) if r is not None]
+    failed = [n for n, r in enumerate(ali) if r is None]
+    if keep:
+        sub = loglikes if len(keep) == N else loglikes[keep]
+        lens = [lengths[n] for n in keep]
+        sub = sub[:, :max(lens)]
+        se = ops.LatticeBatchFunction.apply(sub, lens, asr_decoder, trans_model, [ali[n]["alignment"] for n in keep],
+                                            criterion, silence_ids)
+    else:
+        se = torch.zeros((), dtype=torch.float32, device=prediction.device)
+    return ce_ratio * ce_loss + se, se, ce_loss, frames, failed

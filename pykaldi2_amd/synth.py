@@ -372,3 +372,62 @@ def phone_tid_alignment(rng, num_frames, trans_model, reorder=True):
             piece.extend([first_tid[ts] + k] + loops if reorder else loops + [first_tid[ts] + k])
         tids.extend(piece); phones.append(p); durs.append(len(piece))
     return np.asarray(tids, np.int64), phones, durs
+
+
+# ----------------------------------------------------------------------------------------
+# Forced alignment (train_se2): lexicon and monophone model consistent with decoding_graph_arcs
+# ----------------------------------------------------------------------------------------
+def lexicon_arcs(num_words=2000, num_pdfs=5768, seed=0, max_phones=5):
+    """The word pronunciations of decoding_graph_arcs(num_words, num_pdfs, seed, max_phones) -- the same RNG draws, in the
+    same order -- as an L.fst-shaped arc list: from the loop state 0 a chain of phone arcs per word, the word id (1-based) on
+    the first arc's output, back to state 0 after the last phone; state 0 is the start and the only final state.  Returns
+    dict(num_states, start, src, dst, ilabel, olabel, weight, final) (weights 0)."""
+    rng = np.random.default_rng(seed)
+    num_phones = num_pdfs // 3
+    src, dst, ilab, olab = [], [], [], []
+    n_states = 1
+    for wd in range(num_words):
+        k = int(rng.integers(2, max_phones + 1))
+        phones = rng.integers(1, num_phones + 1, size=k)
+        if wd == 0:
+            phones = np.array([1, 1])
+        prev = 0
+        for j, ph in enumerate(phones):
+            nxt = 0 if j + 1 == len(phones) else n_states
+            if nxt:
+                n_states += 1
+            src.append(prev); dst.append(nxt); ilab.append(int(ph)); olab.append(wd + 1 if j == 0 else 0)
+            prev = nxt
+    final = np.full(n_states, np.inf, np.float32)
+    final[0] = 0.0
+    return dict(num_states=n_states, start=0, src=np.asarray(src, np.int32), dst=np.asarray(dst, np.int32),
+                ilabel=np.asarray(ilab, np.int32), olabel=np.asarray(olab, np.int32),
+                weight=np.zeros(len(src), np.float32), final=final)
+
+
+def alignment_model(num_pdfs):
+    """(tree, trans_model) of transition_model_arrays(num_pdfs) with its topology: a monophone tree (N = 1) mapping
+    (phone, HMM state) to pdf 3 (phone - 1) + state, 3-state Bakis phones, and the log-probabilities of the synthetic
+    HCLG (self-loop 0.6, forward 0.4).  The transition-ids equal transition_model_arrays'."""
+    from .lattice import TransitionModel
+    from .tree import ContextDependency
+    num_phones = num_pdfs // 3
+    tree = ContextDependency.from_nested(1, 0, ("TE", 0, [None] + [("TE", -1, [("CE", 3 * (p - 1) + c) for c in range(3)])
+                                                                   for p in range(1, num_phones + 1)]))
+    tm = TransitionModel.from_topology({p: 0 for p in range(1, num_phones + 1)}, [BAKIS_TOPO],
+                                       [(p, hs, 3 * (p - 1) + hs, 3 * (p - 1) + hs) for p in range(1, num_phones + 1)
+                                        for hs in range(3)])
+    lp = np.empty(tm.num_transition_ids() + 1)
+    lp[0] = 0.0
+    lp[1::2], lp[2::2] = np.log(0.6), np.log(0.4)
+    tm.log_probs = lp
+    return tree, tm
+
+
+def word_transcript(rng, num_frames, num_words, max_words=None):
+    """Random word ids (1-based, the silence word 1 excluded) for an utterance of num_frames frames: one word per 40
+    frames at most, so that even max_phones-phone words of 3-state phones fit."""
+    n = max(1, num_frames // 40)
+    if max_words:
+        n = min(n, max_words)
+    return [int(w) for w in rng.integers(2, num_words + 1, size=n)]
