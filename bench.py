@@ -1,9 +1,14 @@
 """iRTF benchmark of the LF-MMI training step (BASELINE.json: 3x512 BLSTM LF-MMI, LibriSpeech-shaped
 utterances, batch 4 x var-len per GPU, train_chain.py semantics) on N MI355X.
 
-    python bench.py --gpus 1 --steps 20 --warmup 3 [--dump-outputs DIR]
+    python bench.py --gpus 1 --steps 20 --warmup 3 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints its line: the headline figure and
+what the timed steps themselves recorded.  --full adds everything that takes runs of its own after the timed region:
+the f32-GEMM window, the per-phase breakdown, the rooflines, the CPU baseline with its parity check, the length-bucketed
+window (N > 1) and the secondary configurations (one GPU).
 
 One step = one pass of the hot path over one minibatch of raw waveforms already resident in HBM:
 fbank+CMN+subsample -> 3x512 BLSTM forward -> LF-MMI (numerator + denominator forward-backward)
@@ -607,48 +612,55 @@ def ce_workload(args, dev, rank, world):
     dt = time.perf_counter() - t0
     audio = args.steps * BATCH * CH * 0.01
     if rank == 0:
-        base = parity = None
-        # whole-step MFMA utilisation (125.5 MFLOP per network frame forward + backward at P = 5768, all of it
-        # MFMA-eligible) and the dominant GEMM of the step measured alone, events on the launch stream
-        ms_step = 1e3 * dt / args.steps
-        flops = 3.0 * lstm_flops_per_frame(pdfs=PC) * BATCH * CH
-        tf = flops / (ms_step * 1e-3) / 1e12
-        roof = dict(bound="mfma", achieved=round(tf, 1), peak=157.3, unit="TFLOP/s", frac=round(tf / 157.3, 4), traffic=None,
-                    gemm_arith=gemm_arith_name(), frac_of_bf16x3_peak=round(6.0 * tf / 2500.0, 4),
-                    kernel="whole CE step (3x512 BLSTM + output layer forward + backward: GEMMs pk2::gemm_f32_kernel in the arithmetic "
-                    "`gemm_arith` + the persistent recurrences pk2::lstm_*_big_persist on the f32 MFMA) over the step's wall time; "
-                    "FLOPs are f32-equivalent; peak / frac = the f32 MFMA peak (what the step is priced against since round 1), "
-                    "frac_of_bf16x3_peak = the same FLOPs against 2.5 PFLOP/s dense bf16 / 6 executed products",
-                    flops_per_step=flops, ms=round(ms_step, 3),
-                    input_projection_gemm=gemm_mfma_roofline(dev, BATCH * CH))
-        if world == 1 and not args.no_cpu_baseline:
-            import tempfile
-            with tempfile.TemporaryDirectory() as td:
-                # posteriors of the first 32 chunks of one minibatch, model in eval mode (dropout off), for the child
-                path = os.path.join(td, "ce_parity.pt")
-                mb = batches[0]
-                model.eval()
-                with torch.no_grad():
-                    feats, frames, row_off = fb(mb["wav"], mb["lens"])
-                    off = np.concatenate([[0], np.cumsum(frames)])
-                    x = torch.cat([fbank.utt2seg(feats[off[n]:off[n + 1]], CH, CH) for n in range(len(frames))])[:BATCH]
-                    lg = model.forward_time_major(x.transpose(0, 1).contiguous()).transpose(0, 1)[:32]
-                model.train()
-                torch.save(dict(state_dict={k: v.cpu() for k, v in model.state_dict().items()}, x=x[:32].cpu(),
-                                logits=lg.contiguous().cpu()), path)
-                base = cpu_baseline(0, worker="--cpu-ce-worker", parity_path=path)
-            parity = base.pop("parity", None)
-        print(json.dumps({"metric": "iRTF (hrs audio/hr) 3x512 BLSTM CE, 256x80 chunks (secondary workload, configs[1])",
-                          "value": round(audio / dt * world, 2), "n_gpus": world, "steps": args.steps,
-                          "unit": "hours of audio per wall-clock hour", "higher_is_better": True,
-                          "config": {"workload": "SECONDARY configs[1]: 3x512 BLSTM CE, batch 256 x 80 x 80 fbank from raw waveforms in "
-                                     "HBM, P=5768, dropout 0.2, Adam(amsgrad)+clip 5"},
-                          "ms_per_step": round(1e3 * dt / args.steps, 3), "dtype": dtype_string(), "loss": round(float(loss.item()), 4),
-                          "roofline": roof, "cpu_baseline": base, "parity": parity,
-                          "hbm_peak_allocated_gb": round(torch.cuda.max_memory_allocated() / 2 ** 30, 2),
-                          "reference_published": "README.md:43-45: 190 iRTF (64x80, 1 V100), 520 iRTF (256x80, 4 V100)"}),
-              flush=True)
+        line = {"metric": "iRTF (hrs audio/hr) 3x512 BLSTM CE, 256x80 chunks (secondary workload, configs[1])",
+                "value": round(audio / dt * world, 2), "n_gpus": world, "steps": args.steps,
+                "unit": "hours of audio per wall-clock hour", "higher_is_better": True,
+                "config": {"workload": "SECONDARY configs[1]: 3x512 BLSTM CE, batch 256 x 80 x 80 fbank from raw waveforms in "
+                           "HBM, P=5768, dropout 0.2, Adam(amsgrad)+clip 5"},
+                "ms_per_step": round(1e3 * dt / args.steps, 3), "dtype": dtype_string(), "loss": round(float(loss.item()), 4)}
+        if args.full:
+            line.update(ce_extras(args, dev, world, dt, model, fb, batches))
+        line.update(hbm_peak_allocated_gb=round(torch.cuda.max_memory_allocated() / 2 ** 30, 2),
+                    reference_published="README.md:43-45: 190 iRTF (64x80, 1 V100), 520 iRTF (256x80, 4 V100)")
+        print(json.dumps(line), flush=True)
     hvd.shutdown()
+
+
+def ce_extras(args, dev, world, dt, model, fb, batches):
+    """--full, configs[1]: the roofline of the CE step and, on one GPU, the reference's torch CPU CE path with its parity check."""
+    PC, CH, BATCH = 5768, 80, 256
+    base = parity = None
+    # whole-step MFMA utilisation (SURVEY 8(d): 125.5 MFLOP per network frame forward + backward at P = 5768, all of it
+    # MFMA-eligible) and the dominant GEMM of the step measured alone, events on the launch stream
+    ms_step = 1e3 * dt / args.steps
+    flops = 3.0 * lstm_flops_per_frame(pdfs=PC) * BATCH * CH
+    tf = flops / (ms_step * 1e-3) / 1e12
+    roof = dict(bound="mfma", achieved=round(tf, 1), peak=157.3, unit="TFLOP/s", frac=round(tf / 157.3, 4), traffic=None,
+                gemm_arith=gemm_arith_name(), frac_of_bf16x3_peak=round(6.0 * tf / 2500.0, 4),
+                kernel="whole CE step (3x512 BLSTM + output layer forward + backward: GEMMs pk2::gemm_f32_kernel in the arithmetic "
+                "`gemm_arith` + the persistent recurrences pk2::lstm_*_big_persist on the f32 MFMA) over the step's wall time; "
+                "FLOPs are f32-equivalent; peak / frac = the f32 MFMA peak (what the step is priced against since round 1), "
+                "frac_of_bf16x3_peak = the same FLOPs against 2.5 PFLOP/s dense bf16 / 6 executed products",
+                flops_per_step=flops, ms=round(ms_step, 3),
+                input_projection_gemm=gemm_mfma_roofline(dev, BATCH * CH))
+    if world == 1 and not args.no_cpu_baseline:
+        import tempfile
+        with tempfile.TemporaryDirectory() as td:
+            # posteriors of the first 32 chunks of one minibatch, model in eval mode (dropout off), for the child
+            path = os.path.join(td, "ce_parity.pt")
+            mb = batches[0]
+            model.eval()
+            with torch.no_grad():
+                feats, frames, row_off = fb(mb["wav"], mb["lens"])
+                off = np.concatenate([[0], np.cumsum(frames)])
+                x = torch.cat([fbank.utt2seg(feats[off[n]:off[n + 1]], CH, CH) for n in range(len(frames))])[:BATCH]
+                lg = model.forward_time_major(x.transpose(0, 1).contiguous()).transpose(0, 1)[:32]
+            model.train()
+            torch.save(dict(state_dict={k: v.cpu() for k, v in model.state_dict().items()}, x=x[:32].cpu(),
+                            logits=lg.contiguous().cpu()), path)
+            base = cpu_baseline(0, worker="--cpu-ce-worker", parity_path=path)
+        parity = base.pop("parity", None)
+    return dict(roofline=roof, cpu_baseline=base, parity=parity)
 
 
 def se_workload(args, dev, rank, world):
@@ -711,6 +723,27 @@ def se_workload(args, dev, rank, world):
     mem_gb = dict(device_total=round(total_b / 2 ** 30, 1), device_free=round(free_b / 2 ** 30, 1),
                   reserved_peak=round(mstat.get("reserved_bytes.all.peak", 0) / 2 ** 30, 1),
                   allocated_peak=round(mstat.get("allocated_bytes.all.peak", 0) / 2 ** 30, 1), alloc_retries=int(mstat.get("num_alloc_retries", 0)))
+    if rank == 0:
+        line = {"metric": "iRTF (hrs audio/hr) 3x512 BLSTM lattice-%s, on-the-fly lattices (secondary workload, configs[3])" % crit_name.upper(),
+                "value": round(audio / dt * world, 2), "unit": "hours of audio per wall-clock hour", "higher_is_better": True,
+                "config": {"workload": "SECONDARY configs[3]: 3x512 BLSTM lattice-%s (train_se.py), on-the-fly lattices, batch %d x "
+                           "var-len per GPU at 100 fps, P=5768, %d-word HCLG, beam 13 / lattice_beam 7 / max_active 7000, "
+                           "CE regulariser 0.1, SGD+clip 5" % (crit_name.upper(), batch, words)},
+                "n_gpus": world, "steps": args.steps,
+                "ms_per_step": round(1e3 * dt / args.steps, 3), "dtype": "f32", "batch_per_gpu": batch,
+                "step_host_ms": step_ms, "device_allocs_in_timed_region": device_allocs, "memory_gb": mem_gb,
+                "hclg": {"states": rec.graph.num_states, "arcs": rec.graph.num_arcs}}
+        if args.full:
+            line.update(se_extras(args, world, model, fb, batches, rec, tm, log_prior, crit_name, words))
+        line.update(loss=round(float(loss.item()), 2), hbm_peak_allocated_gb=round(torch.cuda.max_memory_allocated() / 2 ** 30, 2),
+                    reference_published="README.md:47-49: lattice MMI 16.7 iRTF (1 V100, 4 utterances), 34.5 iRTF (4 V100)")
+        print(json.dumps(line), flush=True)
+    hvd.shutdown()
+
+
+def se_extras(args, world, model, fb, batches, rec, tm, log_prior, crit_name, words):
+    """--full, configs[3]: decode-and-prune and lattice forward-backward of the last minibatch timed alone, the roofline of the
+    decoder, and on one GPU the host's C port of the decoder with its parity check against the oracle."""
     # breakdown of the lattice part on the last minibatch (outside the timed region)
     mb = batches[(args.steps - 1) % 3]
     with torch.no_grad():
@@ -727,62 +760,47 @@ def se_workload(args, dev, rank, world):
             lat.mpe(mb["aux"], crit_name, tm["silence_phones"], True)
         ev[2].record()
         torch.cuda.synchronize()
-    if rank == 0:
-        # Dominant kernel: the persistent lattice decoder (integer / pointer work on HBM-resident graphs; no MFMA).  Algorithmic
-        # bytes per decode call: per link created 56 B (16 B HCLG arc record + 4 B log-likelihood read, 16 B of
-        # the per-state {cost, token} table read and written, 16 B link record + 4 B acoustic cost written), per token 48 B
-        # (20 B token fields written, read again by the next frame, 8 B arc-range lookup) -- over the kept links / tokens
-        # the call reports, so a lower bound of what the search touched.
-        dec_ms = ev[0].elapsed_time(ev[1])
-        toks, links = float(lat.num_tokens.sum()), float(lat.num_links.sum())
-        byts = 56.0 * links + 48.0 * toks
-        ach = byts / (dec_ms * 1e-3) / 1e9
-        roof = dict(bound="hbm", achieved=round(ach, 2), peak=HBM_PEAK_GBS, unit="GB/s", frac=round(ach / HBM_PEAK_GBS, 5), traffic=None,
-                    kernel="pk2::lat_frames_persist + the pruning kernels behind it (one decode-and-prune call of the minibatch: "
-                    "a team of workgroups per utterance, all frames in one launch); latency-bound token passing, see DESIGN.md 4.4",
-                    ms_per_launch=round(dec_ms, 2), algorithmic_bytes=int(byts),
-                    us_per_frame=round(1e3 * dec_ms / float(np.max(frames)), 2))
-        base = parity = None
-        if world == 1 and not args.no_cpu_baseline and crit_name == "mmi":
-            import tempfile
-            F = min(120, int(frames[0]))       # bounded sample: the first 1.2 s of utterance 0 of this minibatch
-            with torch.no_grad():
-                ll0 = ll[0, :F].contiguous()
-                lat0 = rec.decode(ll0)
-                ali0 = np.asarray(mb["aux"][0])[:F]
-                like0, post0 = lat0.mmi([ali0], 1.0, 0.2, True)
-                torch.cuda.synchronize()
-                exp0 = lat0.export(0)          # the kept (pruned) lattice as arrays
-            with tempfile.TemporaryDirectory() as td:
-                path = os.path.join(td, "se_parity.npz")
-                np.savez(path, ll=ll0.cpu().numpy(), ali=ali0, words=words, wav=mb["wav"][:401 + 160 * (F - 1)].cpu().numpy(),
-                         best_cost=np.float32(lat0.best_cost[0]), num_links=int(len(exp0["link_src"])), num_tokens=int(lat0.num_tokens[0]),
-                         like=float(like0.item()), post=post0[0].cpu().numpy(),
-                         # the whole minibatch for the timed CPU leg (waveforms, their lengths, transition-id alignments)
-                         mb_wav=mb["wav"].cpu().numpy(), mb_lens=np.asarray(mb["lens"], np.int64),
-                         mb_ali=np.concatenate([np.asarray(a, np.int32) for a in mb["aux"]]),
-                         mb_ali_lens=np.asarray([len(a) for a in mb["aux"]], np.int64))
-                base = cpu_baseline(0, timeout=420, worker="--cpu-se-worker", parity_path=path)
-            parity = base.pop("parity", None)
-        print(json.dumps({"metric": "iRTF (hrs audio/hr) 3x512 BLSTM lattice-%s, on-the-fly lattices (secondary workload, configs[3])" % crit_name.upper(),
-                          "value": round(audio / dt * world, 2), "unit": "hours of audio per wall-clock hour", "higher_is_better": True,
-                          "config": {"workload": "SECONDARY configs[3]: 3x512 BLSTM lattice-%s (train_se.py), on-the-fly lattices, batch %d x "
-                                     "var-len per GPU at 100 fps, P=5768, %d-word HCLG, beam 13 / lattice_beam 7 / max_active 7000, "
-                                     "CE regulariser 0.1, SGD+clip 5" % (crit_name.upper(), batch, words)},
-                          "n_gpus": world, "steps": args.steps,
-                          "ms_per_step": round(1e3 * dt / args.steps, 3), "dtype": "f32", "batch_per_gpu": batch,
-                          "step_host_ms": step_ms, "device_allocs_in_timed_region": device_allocs, "memory_gb": mem_gb,
-                          "hclg": {"states": rec.graph.num_states, "arcs": rec.graph.num_arcs},
-                          "lattice_ms": {"decode_and_prune": round(ev[0].elapsed_time(ev[1]), 2),
-                                         "forward_backward": round(ev[1].elapsed_time(ev[2]), 2)},
-                          "lattice_tokens_per_frame": round(float(lat.num_tokens.sum()) / float(np.sum(frames)), 1),
-                          "lattice_links_per_frame": round(float(lat.num_links.sum()) / float(np.sum(frames)), 1),
-                          "loss": round(float(loss.item()), 2),
-                          "roofline": roof, "cpu_baseline": base, "parity": parity,
-                          "hbm_peak_allocated_gb": round(torch.cuda.max_memory_allocated() / 2 ** 30, 2),
-                          "reference_published": "README.md:47-49: lattice MMI 16.7 iRTF (1 V100, 4 utterances), 34.5 iRTF (4 V100)"}),
-              flush=True)
-    hvd.shutdown()
+    # Dominant kernel: the persistent lattice decoder (integer / pointer work on HBM-resident graphs; no MFMA).  Algorithmic
+    # bytes per decode call: per link created 56 B (16 B HCLG arc record + 4 B log-likelihood read, 16 B of
+    # the per-state {cost, token} table read and written, 16 B link record + 4 B acoustic cost written), per token 48 B
+    # (20 B token fields written, read again by the next frame, 8 B arc-range lookup) -- over the kept links / tokens
+    # the call reports, so a lower bound of what the search touched.
+    dec_ms = ev[0].elapsed_time(ev[1])
+    toks, links = float(lat.num_tokens.sum()), float(lat.num_links.sum())
+    byts = 56.0 * links + 48.0 * toks
+    ach = byts / (dec_ms * 1e-3) / 1e9
+    roof = dict(bound="hbm", achieved=round(ach, 2), peak=HBM_PEAK_GBS, unit="GB/s", frac=round(ach / HBM_PEAK_GBS, 5), traffic=None,
+                kernel="pk2::lat_frames_persist + the pruning kernels behind it (one decode-and-prune call of the minibatch: "
+                "a team of workgroups per utterance, all frames in one launch); latency-bound token passing, see DESIGN.md 4.4",
+                ms_per_launch=round(dec_ms, 2), algorithmic_bytes=int(byts),
+                us_per_frame=round(1e3 * dec_ms / float(np.max(frames)), 2))
+    base = parity = None
+    if world == 1 and not args.no_cpu_baseline and crit_name == "mmi":
+        import tempfile
+        F = min(120, int(frames[0]))       # bounded sample: the first 1.2 s of utterance 0 of this minibatch
+        with torch.no_grad():
+            ll0 = ll[0, :F].contiguous()
+            lat0 = rec.decode(ll0)
+            ali0 = np.asarray(mb["aux"][0])[:F]
+            like0, post0 = lat0.mmi([ali0], 1.0, 0.2, True)
+            torch.cuda.synchronize()
+            exp0 = lat0.export(0)          # the kept (pruned) lattice as arrays
+        with tempfile.TemporaryDirectory() as td:
+            path = os.path.join(td, "se_parity.npz")
+            np.savez(path, ll=ll0.cpu().numpy(), ali=ali0, words=words, wav=mb["wav"][:401 + 160 * (F - 1)].cpu().numpy(),
+                     best_cost=np.float32(lat0.best_cost[0]), num_links=int(len(exp0["link_src"])), num_tokens=int(lat0.num_tokens[0]),
+                     like=float(like0.item()), post=post0[0].cpu().numpy(),
+                     # the whole minibatch for the timed CPU leg (waveforms, their lengths, transition-id alignments)
+                     mb_wav=mb["wav"].cpu().numpy(), mb_lens=np.asarray(mb["lens"], np.int64),
+                     mb_ali=np.concatenate([np.asarray(a, np.int32) for a in mb["aux"]]),
+                     mb_ali_lens=np.asarray([len(a) for a in mb["aux"]], np.int64))
+            base = cpu_baseline(0, timeout=420, worker="--cpu-se-worker", parity_path=path)
+        parity = base.pop("parity", None)
+    return {"lattice_ms": {"decode_and_prune": round(ev[0].elapsed_time(ev[1]), 2),
+                           "forward_backward": round(ev[1].elapsed_time(ev[2]), 2)},
+            "lattice_tokens_per_frame": round(float(lat.num_tokens.sum()) / float(np.sum(frames)), 1),
+            "lattice_links_per_frame": round(float(lat.num_links.sum()) / float(np.sum(frames)), 1),
+            "roofline": roof, "cpu_baseline": base, "parity": parity}
 
 
 def cpu_se_worker(threads, parity_path):
@@ -868,13 +886,14 @@ def cpu_se_worker(threads, parity_path):
 
 def run_secondaries():
     """BASELINE configs[1], [3], [4] next to the headline: each runs as a short child job of its own
-    (`bench.py --ce | --se | --transformer`: own process, own HIP context, this GPU; the parent is idle meanwhile) with its own
+    (`bench.py --ce | --se | --transformer --full`: own process, own HIP context, this GPU; the parent is idle meanwhile) with its own
     timed window, roofline of its dominant kernel, CPU baseline on a bounded sample and parity check; the parent keeps the
     fields a reader needs.  Nothing of this runs inside the headline's timed region."""
     import subprocess
     out = {}
-    for name, flags in (("ce", ["--ce", "--steps", "8", "--warmup", "3"]), ("se", ["--se", "--steps", "3", "--warmup", "3"]),
-                        ("transformer", ["--transformer", "--steps", "8", "--warmup", "3"])):
+    for name, flags in (("ce", ["--ce", "--steps", "8", "--warmup", "3", "--full"]),
+                        ("se", ["--se", "--steps", "3", "--warmup", "3", "--full"]),
+                        ("transformer", ["--transformer", "--steps", "8", "--warmup", "3", "--full"])):
         t0 = time.time()
         try:
             r = subprocess.run([sys.executable, os.path.abspath(__file__)] + flags, capture_output=True, text=True, timeout=420)
@@ -960,9 +979,12 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=4)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the short child runs of configs[1], [3], [4] that the default "
-                    "one-GPU run appends to its line as `secondary`")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also measure and check what the headline figure "
+                    "does not need: rooflines, breakdowns, other precisions and configurations, CPU baselines and parity")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and its parity check "
+                    "(and the secondary configurations)")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the short child runs of configs[1], [3], [4] "
+                    "that the default one-GPU run appends to its line as `secondary`")
     ap.add_argument("--reserve-gb", type=int, default=None, help="HBM handed to the caching allocator in one piece at start-up "
                     "(0: let it grow lazily; default 12, --se 48: their runs peak at 8 / 33 GB)")
     ap.add_argument("--length-bucketed", action="store_true", help="N > 1: every rank draws the same utterance lengths "
@@ -1139,7 +1161,7 @@ def main():
     exchange_timing, tr.opt.timing = tr.opt.timing, None
     scaling = scaling_report(step_events, exchange_timing, audio, dev, rank, world)
     irtf_bucketed = None
-    if world > 1 and not args.length_bucketed:
+    if args.full and world > 1 and not args.length_bucketed:
         # the same job on minibatches whose utterance lengths are bucketed across the ranks (bin/train_chain.py
         # -length_bucketed): a second, short timed window, so that one line shows what the stragglers of the default
         # protocol (everything seeded per rank) cost
@@ -1168,11 +1190,12 @@ def main():
         torch.distributed.all_reduce(asum, op=torch.distributed.ReduceOp.SUM)
         dt, audio = float(tmax.item()), float(asum.item())
     loss_val = float(tr.last["loss"].item())
+    frames_last = [s.frames_per_sequence for s in tr.last["sups"]]      # of the last timed step, like loss_val
 
     # The same timed window once more with the GEMMs on the f32 MFMA ("carries the pure-f32 number beside it"):
     # same minibatches in the same order, same process; not part of `value`.
     f32_window = None
-    if world == 1 and gemm_arith_name() == "bf16x3" and not args.den_states and not args.den_arcs:
+    if args.full and world == 1 and gemm_arith_name() == "bf16x3" and not args.den_states and not args.den_arcs:
         from pykaldi2_amd import _lib
         _lib.check(_lib.lib().pk2_gemm_set_arith(0))
         try:
@@ -1190,44 +1213,46 @@ def main():
         finally:
             _lib.check(_lib.lib().pk2_gemm_set_arith(1))
 
-    # per-phase breakdown of one extra (untimed) step -- on EVERY rank: the step contains the gradient all-reduce
-    # The step whose phases are read follows two untimed ones WITHOUT a synchronisation in between, so that its launches are
-    # queued behind work the device still has, as in the timed loop: right behind a synchronisation the phases would
-    # hold the host's enqueue latency as well (400 launches of the TransformerAM step take the host 11.6 ms against the
-    # 12.7 ms the device needs for them; the `fbank` phase of either model read 0.4-3.9 ms for 0.1 ms of kernels).
-    events = []
-    mb = batches[0]
-    for _ in range(2):
-        tr.step(mb)
-    tr.step(mb, events=events)
-    torch.cuda.synchronize()
+    # --full: per-phase breakdown of one extra (untimed) step -- on EVERY rank: the step contains the gradient all-reduce
+    if args.full:
+        # The step whose phases are read follows two untimed ones WITHOUT a synchronisation in between, so that its launches are
+        # queued behind work the device still has, as in the timed loop: right behind a synchronisation the phases would
+        # hold the host's enqueue latency as well (400 launches of the TransformerAM step take the host 11.6 ms against the
+        # 12.7 ms the device needs for them; the `fbank` phase of either model read 0.4-3.9 ms for 0.1 ms of kernels).
+        events = []
+        mb = batches[0]
+        for _ in range(2):
+            tr.step(mb)
+        tr.step(mb, events=events)
+        torch.cuda.synchronize()
     if rank != 0:
         hvd.shutdown()
         return
-    breakdown = {events[i][0]: round(events[i - 1][1].elapsed_time(events[i][1]), 3) for i in range(1, len(events))}
-    lens = [s.frames_per_sequence for s in tr.last["sups"]]
-    roof = den_roofline(den, dev)
-    log("roofline done")
-    # whole-model MFMA utilisation of the breakdown step: all BLSTM + output-layer FLOPs (forward + backward) of the real
-    # (unpadded) frames over the time of the two model phases, against the f32 MFMA peak
-    lstm_ms = (breakdown["model_fwd"] + breakdown["model_bwd"]) if args.transformer else (breakdown["lstm_fwd"] + breakdown["lstm_bwd"])
-    if args.transformer:      # the model phases hold the 12-layer TransformerAM: its own FLOP count and label
-        flops = 3.0 * sum(transformer_flops_per_frame(T) * T for T in lens)
-        model_tf = flops / (lstm_ms * 1e-3) / 1e12
-        roof_lstm = dict(bound="mfma", achieved=round(model_tf, 2), peak=157.3, unit="TFLOP/s", frac=round(model_tf / 157.3, 4),
-                         kernel="12-layer TransformerAM (dim 512, 8 heads, FFN 2048, conv k=3) + output layer, forward + backward "
-                         "of the breakdown minibatch (GEMMs in the arithmetic `gemm_arith`, fused f32-MFMA attention, row kernels); "
-                         "FLOPs are f32-equivalent, peak = the f32 MFMA peak", gemm_arith=gemm_arith_name(), frames=int(sum(lens)),
-                         padded_rows=len(lens) * max(lens), ms=round(lstm_ms, 3), flops_fwd_bwd=flops)
-    else:
-        lstm_tf = 3.0 * lstm_flops_per_frame() * sum(lens) / (lstm_ms * 1e-3) / 1e12
-        roof_lstm = dict(bound="mfma", achieved=round(lstm_tf, 2), peak=157.3, unit="TFLOP/s", frac=round(lstm_tf / 157.3, 4),
-                         kernel="3x512 BLSTM + output layer, forward + backward of the breakdown minibatch (recurrence "
-                         "step kernels on the f32 MFMA + GEMMs in the arithmetic `gemm_arith`); FLOPs are f32-equivalent (2 per "
-                         "multiply-add of the model), peak = the f32 MFMA peak", gemm_arith=gemm_arith_name(),
-                         frames=int(sum(lens)), padded_rows=len(lens) * max(lens),
-                         ms=round(lstm_ms, 3), flops_per_frame_fwd_bwd=3 * lstm_flops_per_frame(),
-                         input_projection_gemm=gemm_mfma_roofline(dev, len(lens) * max(lens)))
+    if args.full:
+        breakdown = {events[i][0]: round(events[i - 1][1].elapsed_time(events[i][1]), 3) for i in range(1, len(events))}
+        lens = [s.frames_per_sequence for s in tr.last["sups"]]      # of the breakdown step
+        roof = den_roofline(den, dev)
+        log("roofline done")
+        # whole-model MFMA utilisation of the breakdown step: all BLSTM + output-layer FLOPs (forward + backward) of the real
+        # (unpadded) frames over the time of the two model phases, against the f32 MFMA peak
+        lstm_ms = (breakdown["model_fwd"] + breakdown["model_bwd"]) if args.transformer else (breakdown["lstm_fwd"] + breakdown["lstm_bwd"])
+        if args.transformer:      # the model phases hold the 12-layer TransformerAM: its own FLOP count and label
+            flops = 3.0 * sum(transformer_flops_per_frame(T) * T for T in lens)
+            model_tf = flops / (lstm_ms * 1e-3) / 1e12
+            roof_lstm = dict(bound="mfma", achieved=round(model_tf, 2), peak=157.3, unit="TFLOP/s", frac=round(model_tf / 157.3, 4),
+                             kernel="12-layer TransformerAM (dim 512, 8 heads, FFN 2048, conv k=3) + output layer, forward + backward "
+                             "of the breakdown minibatch (GEMMs in the arithmetic `gemm_arith`, fused f32-MFMA attention, row kernels); "
+                             "FLOPs are f32-equivalent, peak = the f32 MFMA peak", gemm_arith=gemm_arith_name(), frames=int(sum(lens)),
+                             padded_rows=len(lens) * max(lens), ms=round(lstm_ms, 3), flops_fwd_bwd=flops)
+        else:
+            lstm_tf = 3.0 * lstm_flops_per_frame() * sum(lens) / (lstm_ms * 1e-3) / 1e12
+            roof_lstm = dict(bound="mfma", achieved=round(lstm_tf, 2), peak=157.3, unit="TFLOP/s", frac=round(lstm_tf / 157.3, 4),
+                             kernel="3x512 BLSTM + output layer, forward + backward of the breakdown minibatch (recurrence "
+                             "step kernels on the f32 MFMA + GEMMs in the arithmetic `gemm_arith`); FLOPs are f32-equivalent (2 per "
+                             "multiply-add of the model), peak = the f32 MFMA peak", gemm_arith=gemm_arith_name(),
+                             frames=int(sum(lens)), padded_rows=len(lens) * max(lens),
+                             ms=round(lstm_ms, 3), flops_per_frame_fwd_bwd=3 * lstm_flops_per_frame(),
+                             input_projection_gemm=gemm_mfma_roofline(dev, len(lens) * max(lens)))
     result = {
         "metric": ("iRTF (hrs audio/hr) 12-layer TransformerAM LF-MMI (secondary workload, configs[4])" if args.transformer else
                    "iRTF (hrs audio/hr) 3x512 BLSTM LF-MMI, LibriSpeech-shaped synthetic utterances"),
@@ -1254,10 +1279,15 @@ def main():
                           "schedule": getattr(tr.opt, "_mode", "single"), "calibration_steps": calibration_steps,
                           "api": "pk2_allreduce_bucket" if hvd.comm_library() else "torch.distributed.all_reduce"},
                          **scaling["exchange"]),
-        "per_rank": scaling["per_rank"], "ideal_weak_irtf": scaling["ideal_weak_irtf"], "irtf_bucketed": irtf_bucketed,
-        "roofline": roof, ("roofline_model" if args.transformer else "roofline_lstm"): roof_lstm, "last_objf_per_frame": round(loss_val / sum(lens), 4),
-        "persistent_health": persistent_health(den, args.batch),
+        "per_rank": scaling["per_rank"], "ideal_weak_irtf": scaling["ideal_weak_irtf"],
+        "last_objf_per_frame": round(loss_val / sum(frames_last), 4), "persistent_health": persistent_health(den, args.batch),
+        "n_unique_minibatches": n_unique, "device_allocs_in_timed_region": device_allocs, "gemm_arith": gemm_arith_name(),
     }
+    if not args.full:
+        print(json.dumps(result), flush=True)
+        hvd.shutdown()
+        return
+    result.update({"irtf_bucketed": irtf_bucketed, "roofline": roof, ("roofline_model" if args.transformer else "roofline_lstm"): roof_lstm})
     if world == 1 and not args.no_cpu_baseline:
         log("cpu baseline + parity (child process, %d cores)" % usable_cores())
         import tempfile
@@ -1276,9 +1306,8 @@ def main():
         torch.cuda.empty_cache()
         result["secondary"] = run_secondaries()
     # the tail of the line (the driver keeps the last 2000 characters): the numbers a reader needs first
-    result["n_unique_minibatches"] = n_unique
-    result["device_allocs_in_timed_region"] = device_allocs
-    result["gemm_arith"] = gemm_arith_name()
+    for k in ("n_unique_minibatches", "device_allocs_in_timed_region", "gemm_arith"):
+        result[k] = result.pop(k)
     result["f32_gemm_window"] = f32_window
     result[("roofline_model" if args.transformer else "roofline_lstm") + "_frac"] = roof_lstm["frac"]
     result["roofline_frac"] = roof.get("frac")

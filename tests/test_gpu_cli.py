@@ -221,7 +221,7 @@ def test_bench_rccl_path_single_rank_group():
     side stream while the step graphs replay, barrier-bracketed timing.  With one rank the exchange is the
     identity, so the objective after the same steps must equal the run without a process group."""
     import json
-    base = [os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"]
+    base = [os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--full"]
     env = dict(os.environ, PK2_HVD_SINGLE_RANK_GROUP="1", PK2_HVD_OVERLAP="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     dist = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
                            "--master-addr", "127.0.0.1", "--master-port", "29541"] + base,
@@ -246,7 +246,7 @@ def test_bench_rccl_path_single_rank_group():
 def _check_scaling_fields(d, world):
     """an N > 1 line must explain its own scaling -- ranks of the communicator, per-rank GPU time of the
     timed steps, exchange / straggler split, the weak-scaling ideal, and the length-bucketed protocol's number from a
-    second short window (bench.py::scaling_report; DESIGN section 6 says how to read them)."""
+    second short window, which `bench.py --full` adds (bench.py::scaling_report; DESIGN section 6 says how to read them)."""
     ex = d["exchange"]
     assert ex["ranks"] == world
     for k in ("exchange_ms", "exchange_net_ms", "straggler_wait_ms", "straggler_wait_ms_worst_rank", "bytes_per_step"):
@@ -272,7 +272,7 @@ def test_bench_two_ranks_on_one_gpu_over_gloo():
     import json
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", "29547", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2",
-           "--no-cpu-baseline"]
+           "--no-cpu-baseline", "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT,
                          env=dict(os.environ, PK2_HVD_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0"))
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
@@ -350,7 +350,7 @@ def test_bench_eight_ranks_on_one_gpu_over_gloo():
         pytest.skip("needs 8 GPUs (one per rank), found %d" % n_dev)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr", "127.0.0.1",
            "--master-port", "29553", os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1",
-           "--no-cpu-baseline"]
+           "--no-cpu-baseline", "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=1500, cwd=ROOT,
                          env=dict(os.environ, PK2_HVD_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="2"))
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
@@ -371,7 +371,7 @@ def test_bench_four_ranks_on_one_gpu_over_gloo():
     import json
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "4", "--master-addr", "127.0.0.1",
            "--master-port", "29559", os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "2", "--warmup", "1",
-           "--no-cpu-baseline"]
+           "--no-cpu-baseline", "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=1500, cwd=ROOT,
                          env=dict(os.environ, PK2_HVD_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="2"))
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
@@ -415,3 +415,30 @@ def test_bench_dump_outputs_repeat(tmp_path):
     assert abs(a["grad_norm"][0] - b["grad_norm"][0]) <= 1e-2 * abs(b["grad_norm"][0]) + 1e-3
     for k in ("logits_sample", "params_sample", "grads_sample"):
         assert np.abs(a[k] - b[k]).max() <= 1e-2 * max(1.0, np.abs(b[k]).max()), k
+
+
+def test_bench_plain_run_is_lean_and_full_adds_the_rest():
+    """A plain bench run times its steps and prints the headline line with what the timed steps recorded, nothing that
+    takes runs of its own (f32-GEMM window, breakdown, rooflines, CPU baseline, secondary configurations); --full adds
+    those after the same timed region."""
+    import json
+    runs = {}
+    for tag, extra in (("plain", []), ("full", ["--full", "--no-cpu-baseline"])):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1"] + extra,
+                             capture_output=True, text=True, timeout=900, cwd=ROOT)
+        assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
+        lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, out.stdout[-2000:]
+        runs[tag] = json.loads(lines[0])
+    moved = {"f32_gemm_window", "breakdown_ms", "roofline", "roofline_lstm", "roofline_frac", "roofline_lstm_frac",
+             "cpu_baseline", "parity", "secondary", "secondary_summary", "irtf_bucketed"}
+    for tag, d in runs.items():
+        assert d["higher_is_better"] is True and d["unit"] == "hours of audio per wall-clock hour", tag
+        assert d["value"] > 0 and d["ms_per_step"] > 0 and d["steps"] == 2 and d["warmup"] == 1, tag
+        assert d["metric"].startswith("iRTF") and d["dtype"].startswith("f32"), tag
+        assert d["persistent_health"]["lstm_persist_abort"] == 0 and np.isfinite(d["last_objf_per_frame"]), tag
+    assert not moved & runs["plain"].keys(), moved & runs["plain"].keys()
+    full = runs["full"]
+    assert {"breakdown_ms", "roofline", "roofline_lstm", "cpu_baseline", "parity"} <= full.keys()
+    assert full["roofline"]["ms_per_launch"] > 0 and full["roofline_lstm"]["achieved"] > 0 and full["breakdown_ms"]["lstm_fwd"] > 0
+    assert "secondary" not in full         # --no-cpu-baseline skips the child runs as well

@@ -4,7 +4,7 @@ export TMPDIR=/tmp
 cd "${GRAFT_REPO_ROOT:-.}"; mkdir -p gpurun_out
 for w in --ce --transformer --se; do
   for ar in f32 bf16x3; do
-    PK2_GEMM_ARITH=$ar timeout 600 python bench.py $w --steps 10 --warmup 3 --no-cpu-baseline 2>/dev/null | tail -1 > /tmp/s.json
+    PK2_GEMM_ARITH=$ar timeout 600 python bench.py $w --steps 10 --warmup 3 --no-cpu-baseline --full 2>/dev/null | tail -1 > /tmp/s.json
     python - "$w $ar" <<'PY'
 import json, sys
 d = json.load(open("/tmp/s.json"))
