@@ -275,6 +275,10 @@ int pk2_align_viterbi(const pk2_align_graphs* graphs, const int32_t* packed_dev,
  * (delay = 0 keeps the direct path at sample 0).  out must not alias wav. */
 int pk2_sim_apply_rir(const float* wav, int64_t n, const float* rir, int32_t k, int32_t delay, float* out,
                       void* stream);
+/* pk2_sim_apply_rir with delay = *delay read from device memory (int32, clamped to [0, k)): reverberation by a RIR made
+ * on the device (pk2_rirgen writes each row's argmax) without reading the delay back to the host. */
+int pk2_sim_apply_rir_dev(const float* wav, int64_t n, const float* rir, int32_t k, const int32_t* delay, float* out,
+                          void* stream);
 /* stats (device f64[2], zeroed by the caller): stats[0] += sum x^2, stats[1] = max(stats[1], max |x|). */
 int pk2_sim_power(const float* x, int64_t n, double* stats, void* stream);
 /* mixed[i] += scale * noise_placed[i], scale = sqrt(Px / Pn * 10^(-snr_db / 10)) with Px = sig_stats[0] / n and
@@ -284,6 +288,31 @@ int pk2_sim_add_noise(float* mixed, int64_t n, const float* noise, int64_t m, in
                       const double* sig_stats, const double* noise_stats, void* stream);
 /* x *= 0.5 / stats[1]  (gain normalisation, simulation/simulation.py:170-172). */
 int pk2_sim_gain_norm(float* x, int64_t n, const double* stats, void* stream);
+
+/* ------------------------------------------------------------------ *
+ * Room impulse responses by the image method (reference simulation/_rirgen.py `xp_rirgen`, method 1), a batch of
+ * items per call; the host checks the arguments and forms the descriptors (pykaldi2_amd/rirgen.py).  All arrays are
+ * device memory.  Lengths are in samples (metres / (c / fs)).
+ *   item_f64[i][PK2_RIR_F64]: room[3], beta[6], c0 = 0.5 / c * fs, gain threshold = (1 / c0) / 1e4, c / fs,
+ *                             Habets high-pass b1, b2, a1, a2 (b0 = a0 = 1)
+ *   item_i64[i][PK2_RIR_I64]: nsrc, nmic, nsamples, htw, high-pass (0 none, 1 FIR, 2 Habets IIR), first double of the
+ *                             item's positions in `pos` (nsrc sources then nmic mics, xyz each), first float of the
+ *                             item's rows in `out`, first row (index into `delay`), lattice half-widths ax, ay, az
+ *                             (lattice points |x| <= ax ...; ax = min(int(nsamples / room[0]), int(nsamples / (2 room[0])) + 1)),
+ *                             one spare
+ *   wg[nwg][5]:               one workgroup each: item, row in the item (src * nmic + mic), part, number of parts (the
+ *                             row's lattice points are split into that many equal ranges), first sample of the segment
+ *                             (multiple of pk2_rirgen_segment_samples(); every (row, part, segment) once)
+ *   row_item[nrows][2]:       item and row in the item of every row
+ *   acc:                      workspace, int64[total] (zeroed here); out: f32[total], the rows (src, mic) of each item
+ *                             back to back at its offset; delay: int32[nrows], argmax of each row (first maximum).
+ * The result does not depend on the schedule: the taps are summed as 64-bit fixed point (bit-reproducible). */
+#define PK2_RIR_F64 16
+#define PK2_RIR_I64 12
+int32_t pk2_rirgen_segment_samples(void);
+int pk2_rirgen(const double* item_f64, const int64_t* item_i64, const double* pos, const int32_t* wg, int32_t nwg,
+               const int32_t* row_item, int32_t nrows, int64_t total, void* acc, float* out, int32_t* delay,
+               void* stream);
 
 /* ------------------------------------------------------------------ *
  * 80-dim log-mel filterbank + CMN + frame subsampling.

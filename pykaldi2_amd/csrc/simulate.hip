@@ -6,6 +6,7 @@
 //
 //   pk2_sim_apply_rir   time-domain convolution with the room impulse response, "synchronised" output
 //                       (the reference convolves by FFT in float64; float32 direct form here, LDS-tiled)
+//   pk2_sim_apply_rir_dev  the same, its delay read from device memory (RIRs made by pk2_rirgen)
 //   pk2_sim_power       sum of squares (float64) and max |x|
 //   pk2_sim_add_noise   noise scaled to the requested SNR and added at its sampled position
 //   pk2_sim_gain_norm   0.5 / max|x| gain normalisation
@@ -23,9 +24,8 @@ constexpr int kSimTile = kSimThreads * kSimOut;    // outputs per workgroup: sma
 constexpr int kSimTaps = 1024;                     // taps staged per pass (4096 FMAs per thread between two barriers)
 
 // out[i] = sum_j rir[j] * wav[i + base - j]  (wav is zero outside [0, n))
-__global__ void __launch_bounds__(kSimThreads) sim_apply_rir_kernel(const float* __restrict__ wav, int64_t n,
-                                                                    const float* __restrict__ rir, int k, int64_t base,
-                                                                    float* __restrict__ out) {
+__device__ __forceinline__ void sim_apply_rir_tile(const float* __restrict__ wav, int64_t n, const float* __restrict__ rir,
+                                                   int k, int64_t base, float* __restrict__ out) {
   __shared__ __attribute__((aligned(16))) float s_rir[kSimTaps];
   __shared__ __attribute__((aligned(16))) float s_wav[kSimTile + kSimTaps];
   const int tid = threadIdx.x;
@@ -67,6 +67,21 @@ __global__ void __launch_bounds__(kSimThreads) sim_apply_rir_kernel(const float*
     for (int r = 0; r < kSimOut; ++r)
       if (i + r < n) out[i + r] = acc[r];
   }
+}
+
+__global__ void __launch_bounds__(kSimThreads) sim_apply_rir_kernel(const float* __restrict__ wav, int64_t n,
+                                                                    const float* __restrict__ rir, int k, int64_t base,
+                                                                    float* __restrict__ out) {
+  sim_apply_rir_tile(wav, n, rir, k, base, out);
+}
+
+// the same with delay = argmax(rir) read from device memory (a RIR made on the device, pk2_rirgen)
+__global__ void __launch_bounds__(kSimThreads) sim_apply_rir_dev_kernel(const float* __restrict__ wav, int64_t n,
+                                                                        const float* __restrict__ rir, int k,
+                                                                        const int32_t* __restrict__ delay,
+                                                                        float* __restrict__ out) {
+  const int d = min(max(*delay, 0), k - 1);
+  sim_apply_rir_tile(wav, n, rir, k, d > 0 ? d - 1 : 0, out);
 }
 
 __global__ void __launch_bounds__(256) sim_power_kernel(const float* __restrict__ x, int64_t n, double* stats) {
@@ -126,6 +141,16 @@ extern "C" int pk2_sim_apply_rir(const float* wav, int64_t n, const float* rir, 
   const int64_t base = delay > 0 ? delay - 1 : 0;
   hipLaunchKernelGGL(sim_apply_rir_kernel, dim3((unsigned)((n + kSimTile - 1) / kSimTile)), dim3(kSimThreads), 0, stream,
                      wav, n, rir, k, base, out);
+  PK2_LAUNCH_CHECK();
+  return PK2_OK;
+}
+
+extern "C" int pk2_sim_apply_rir_dev(const float* wav, int64_t n, const float* rir, int32_t k, const int32_t* delay,
+                                     float* out, void* stream_) {
+  PK2_REQUIRE(wav && rir && delay && out && n > 0 && k > 0, "sim_apply_rir_dev: bad arguments");
+  PK2_REQUIRE(wav != out, "sim_apply_rir_dev: in-place operation is not supported");
+  hipLaunchKernelGGL(sim_apply_rir_dev_kernel, dim3((unsigned)((n + kSimTile - 1) / kSimTile)), dim3(kSimThreads), 0,
+                     static_cast<hipStream_t>(stream_), wav, n, rir, k, delay, out);
   PK2_LAUNCH_CHECK();
   return PK2_OK;
 }

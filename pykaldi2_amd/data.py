@@ -224,31 +224,43 @@ class SimulationPool:
     on the device.  Sources: zips of 16 kHz wav files (`dir_noise` / `rir` entries of the data yaml, first channel,
     one impulse response per file), or the synthetic generator."""
 
-    def __init__(self, noises, rirs, use_reverb=True, use_noise=True, simulation_prob=0.5, gain_norm=False, snr_range=(0, 30)):
+    def __init__(self, noises, rirs, use_reverb=True, use_noise=True, simulation_prob=0.5, gain_norm=False, snr_range=(0, 30),
+                 online_rir=False, t60_range=(0.1, 0.5)):
         from . import simulation
         self.noises = noises if use_noise else []
-        self.rirs = rirs if use_reverb else []
+        self.online_rir = bool(online_rir and use_reverb)
+        self.t60_range = (float(t60_range[0]), float(t60_range[1]))
+        self.rirs = rirs if use_reverb and not self.online_rir else []
         self.prob, self.gain_norm = float(simulation_prob), bool(gain_norm)
-        self.sim = simulation.SimpleSimulator(use_rir=bool(self.rirs), use_noise=bool(self.noises), snr_range=snr_range)
+        self.sim = simulation.SimpleSimulator(use_rir=bool(self.rirs) or self.online_rir, use_noise=bool(self.noises),
+                                              snr_range=snr_range)
         self._dev = {}
 
     @classmethod
     def from_config(cls, config, seed=0):
         """data_config keys of the reference YAMLs (use_dir_noise, use_reverb, snr_range, simulation_prob, gain_norm)
-        plus `dir_noise_paths` / `rir_paths` (bin/train_ce.py:73-76); None when the simulation is off."""
+        plus `dir_noise_paths` / `rir_paths` (bin/train_ce.py:73-76); None when the simulation is off.
+        `online_rir: true` (with `use_reverb`) makes a RIR for every simulated utterance on the device instead of
+        picking one from the pool (pykaldi2_amd.rirgen), T60 ~ U[`t60_range`] (default [0.1, 0.5]); it wins over
+        `rir_paths`."""
         dc = config.get("data_config", {})
         prob = dc.get("simulation_prob", 0)
         if not prob or not (dc.get("use_dir_noise") or dc.get("use_reverb")):
             return None
+        online = bool(dc.get("online_rir", False)) and bool(dc.get("use_reverb", False))
+        if online and config.get("rir_paths"):
+            import warnings
+            warnings.warn("data_config online_rir is set: the RIRs of rir_paths are not used, every simulated utterance "
+                          "gets a RIR generated for a sampled room")
         if config.get("synthetic") or not (config.get("dir_noise_paths") or config.get("rir_paths")):
             rng = np.random.default_rng(4321 + seed)
             noises = [synth.waveform(rng, float(d)) for d in rng.uniform(2.0, 12.0, size=8)]
-            rirs = [synth.room_impulse_response(rng) for _ in range(16)]
+            rirs = [synth.room_impulse_response(rng) for _ in range(16)] if not online else []
         else:
             noises = cls._read_zips(config.get("dir_noise_paths") or [], config.get("data_path", ""))
-            rirs = cls._read_zips(config.get("rir_paths") or [], config.get("data_path", ""))
+            rirs = cls._read_zips(config.get("rir_paths") or [], config.get("data_path", "")) if not online else []
         return cls(noises, rirs, dc.get("use_reverb", False), dc.get("use_dir_noise", False), prob, dc.get("gain_norm", False),
-                   dc.get("snr_range", (0, 30)))
+                   dc.get("snr_range", (0, 30)), online, dc.get("t60_range", (0.1, 0.5)))
 
     @staticmethod
     def _read_zips(sources, data_path):
@@ -264,7 +276,7 @@ class SimulationPool:
         key = (kind, idx, str(device))
         if key not in self._dev:
             arr = (self.noises if kind == "n" else self.rirs)[idx]
-            self._dev[key] = (torch.from_numpy(np.ascontiguousarray(arr, np.float32)).to(device), int(np.argmax(arr)))
+            self._dev[key] = (_lib.h2d(np.ascontiguousarray(arr, np.float32), device), int(np.argmax(arr)))
         return self._dev[key]
 
     def maybe_simulate(self, wav, device):
@@ -277,7 +289,9 @@ class SimulationPool:
         delays = []
         if self.noises:
             noise = self._on_device("n", int(np.random.choice(len(self.noises))), device)[0]
-        if self.rirs:
+        if self.online_rir:
+            src_rir, noise_rir, delays = self.online_rirs(2 if noise is not None else 1, device)
+        elif self.rirs:
             picks = np.random.choice(len(self.rirs), 2 if noise is not None else 1, replace=len(self.rirs) < 2)
             src_rir, d0 = self._on_device("r", int(picks[0]), device)
             delays.append(d0)
@@ -287,6 +301,16 @@ class SimulationPool:
         y, _ = self.sim(x, [noise] if noise is not None else None, src_rir, [noise_rir] if noise_rir is not None else None,
                         normalize_gain=self.gain_norm, rir_delays=delays or None)
         return y
+
+    def online_rirs(self, n_src, device):
+        """RIRs of one sampled room (rirgen.sample_online_room: room, T60, mic at the array centre, the speech source and
+        -- when n_src = 2 -- the directional-noise source), made in one launch.  Returns (speech RIR, noise RIR or None,
+        device delays); nothing is read back to the host."""
+        from . import rirgen
+        room, t60, mic, src = rirgen.sample_online_room(self.t60_range, n_src)
+        b = rirgen.rirgen_batch([dict(room=room, source_loc=src, mic_loc=mic, t60=t60)], device=device)
+        rirs, dl = b.rirs[0], b.delays[0]
+        return rirs[0, 0], (rirs[1, 0] if n_src > 1 else None), [dl[s, 0:1] for s in range(n_src)]
 
 
 def epoch_plan(source, batch_size, hours, rank=0, world=1, epoch=0, length_bucketed=False, seed=0):

@@ -34,8 +34,16 @@ class Distorter:
     @staticmethod
     def apply_rir(wav, rir, delay=None):
         """Reverberant signal, sample-synchronised with the input (sync=True): (rir * wav)[delay-1 : delay+n-1] with
-        delay = argmax(rir).  `delay` may be passed when it is known (it costs a host read otherwise)."""
+        delay = argmax(rir).  `delay` may be passed when it is known (it costs a host read otherwise): an int, or a
+        one-element CUDA int32 tensor that the kernel reads in device memory (the argmax that rirgen writes)."""
         wav, rir = _check(wav), _check(rir)
+        if isinstance(delay, torch.Tensor):
+            assert delay.is_cuda and delay.dtype == torch.int32 and delay.numel() == 1, "expected a CUDA int32 delay"
+            delay = delay.reshape(1)
+            out = torch.empty_like(wav)
+            _lib.check(_lib.lib().pk2_sim_apply_rir_dev(_lib.ptr(wav), wav.numel(), _lib.ptr(rir), rir.numel(),
+                                                        _lib.ptr(delay), _lib.ptr(out), _lib.stream_ptr(wav.device)))
+            return out
         if delay is None:
             delay = int(torch.argmax(rir).item())
         out = torch.empty_like(wav)
