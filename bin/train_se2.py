@@ -11,8 +11,11 @@ from them with the current model (reference :256-273): one pykaldi2_amd.chain.Ma
 aligns prediction - log_prior on the device (training graphs from <trans_model>/final.mdl, <trans_model>/tree,
 <lang_dir>/L.fst and <lang_dir>/phones/disambig.int; beam = decoder_config.align_beam, transition_scale 1.0,
 self_loop_scale 0.1, acoustic_scale 0.1 as in the reference).  An utterance that fails to align is left out of the
-sequence term.  The lattices, criteria and optimiser are train_se.py's.  -synthetic trains on seeded generators: the
-word-loop HCLG of train_se.py, the L.fst of its pronunciations (pykaldi2_amd.synth.lexicon_arcs), a monophone tree and
+sequence term.  The lattices, criteria and optimiser are train_se.py's.  -criterion mwe trains with N-best minimum word
+error (ops.MWEBatchFunction) against the word transcript, or with `phone_level: true` against the phones of the on-the-fly
+alignment; its settings come from an optional `mwe_config:` block of the YAML (pykaldi2_amd.se.mwe_settings: num_paths 16,
+lm_weight 1.0, am_weight = decoder_config.acoustic_scale, equal_weight / phone_level / distinct false).
+-synthetic trains on seeded generators: the word-loop HCLG of train_se.py, the L.fst of its pronunciations (pykaldi2_amd.synth.lexicon_arcs), a monophone tree and
 random word transcripts short enough for their utterances.
 """
 import argparse
@@ -37,7 +40,7 @@ def parse_config(argv=None):
     parser.add_argument("-seed_model", default='', help="the seed nerual network model")
     parser.add_argument("-exp_dir", help="the directory to save the outputs")
     parser.add_argument("-transform", help="feature transformation matrix or mvn statistics")
-    parser.add_argument("-criterion", type=str, choices=["mmi", "mpfe", "smbr"], default="mmi",
+    parser.add_argument("-criterion", type=str, choices=["mmi", "mpfe", "smbr", "mwe"], default="mmi",
                         help="set the sequence training crtierion")
     parser.add_argument("-trans_model", help="the HMM transistion model directory")
     parser.add_argument("-prior_path", help="the prior for decoder, usually named as final.occs in kaldi setup")
@@ -141,6 +144,7 @@ def main():
         transform = fbank.GlobalMeanVarianceNormalization.load(args.transform)
     fb = fbank.FbankExtractor()
 
+    args.mwe = se.mwe_settings(config, dc["acoustic_scale"]) if args.criterion == "mwe" else None
     model.train()
     for epoch in range(args.num_epochs):
         run_train_epoch(model, optimizer, log_prior.to(dev), source, fb, epoch, asr_decoder, trans_model, silence_ids, aligner,
@@ -167,9 +171,14 @@ def run_train_epoch(model, optimizer, log_prior, source, fb, epoch, asr_decoder,
             texts = [synth.word_transcript(text_rng, synth.num_fbank_frames(n), args.graph_words) for n in batch["lens"]]
         else:
             texts = [np.asarray(a).reshape(-1).astype(int).tolist() for a in batch["aux"]]
-        loss, se_val, ce_loss, frames, failed = se.sequence_loss_aligned(model, fb, batch, texts, aligner, asr_decoder, trans_model,
-                                                                         log_prior, args.criterion, silence_ids, args.ce_ratio,
-                                                                         ce_criterion, transform=transform)
+        if args.criterion == "mwe":
+            loss, se_val, ce_loss, frames, failed = se.sequence_loss_mwe(model, fb, batch, texts, aligner, asr_decoder, trans_model,
+                                                                         log_prior, args.mwe, args.ce_ratio, ce_criterion,
+                                                                         transform=transform)
+        else:
+            loss, se_val, ce_loss, frames, failed = se.sequence_loss_aligned(model, fb, batch, texts, aligner, asr_decoder,
+                                                                             trans_model, log_prior, args.criterion, silence_ids,
+                                                                             args.ce_ratio, ce_criterion, transform=transform)
         for j in failed:
             print("Warning: failed to align utterance {}, skip the utterance for SE loss".format(batch["utt_ids"][j]))
         optimizer.zero_grad()

@@ -658,6 +658,32 @@ int pk2_lattice_mpe(const pk2_lattice_batch* b, void* workspace, const int32_t* 
                     const uint8_t* phone_is_silence, int32_t criterion, int32_t one_silence_class,
                     double lm_scale, double acoustic_scale, float* post, int64_t post_seq_stride,
                     int64_t post_frame_stride, double* score, void* stream);
+/* N-best paths of the decoded lattices (reference nbest_as_fsts on convert_lattice_to_std of the lattice scaled by
+ * lattice_scale(lm_scale, acoustic_scale)).  `scratch`: device memory of pk2_lattice_nbest_bytes() bytes for the same
+ * (num_paths, total_tokens, total_links, distinct, label_cap); total_tokens / total_links = sums of pk2_lattice_summary's
+ * num_tokens / num_links.  label_mode 0 = HCLG output labels (words; the graph needs them), 1 = phones through
+ * tid2label (device i32 [num_tids + 1]: phone of a transition-id of HMM state 0 that is not a self-loop, else 0).
+ * distinct != 0: the num_paths best distinct label sequences.  Outputs (device): num_hyp [N] = M; hyp_path [N][num_paths]
+ * = path of hypothesis m (reference mode drops paths that repeat an earlier path's labels); per path cost [N][num_paths],
+ * label count path_nlab (-1: more than label_cap labels), labels [N][num_paths][label_cap], transition-ids
+ * [N][num_paths][Tmax].  num_paths must be in 1..64. */
+size_t pk2_lattice_nbest_bytes(const pk2_lattice_batch* b, int32_t num_paths, int64_t total_tokens, int64_t total_links,
+                               int32_t distinct, int32_t label_cap);
+int pk2_lattice_nbest(const pk2_lattice_batch* b, void* workspace, void* scratch, int64_t total_tokens,
+                      int64_t total_links, int32_t num_paths, int32_t distinct, int32_t label_mode,
+                      const int32_t* tid2label, int32_t num_tids, double lm_scale, double acoustic_scale,
+                      int32_t label_cap, int32_t* num_hyp, int32_t* hyp_path, float* path_cost, int32_t* path_nlab,
+                      int32_t* path_labels, int32_t* path_tids, void* stream);
+/* N-best minimum word error (reference MWEFunction): the N-best of pk2_lattice_nbest, e_k = Levenshtein distance of
+ * hypothesis k to the supervision (device i32 [N][sup_stride], sup_len [N], at most 1023 labels), p_k = 1/M
+ * (equal_weight) or softmax(-cost), loss [N] f64 = sum e_k p_k; grad (zero-filled by the caller) [n, t, tid2pdf[tid_k[t]]]
+ * = sum of (e_k - loss) p_k.  A failed utterance gives NaN and no gradient. */
+int pk2_lattice_mwe(const pk2_lattice_batch* b, void* workspace, void* scratch, int64_t total_tokens,
+                    int64_t total_links, int32_t num_paths, int32_t distinct, int32_t label_mode,
+                    const int32_t* tid2label, int32_t num_tids, double lm_scale, double acoustic_scale,
+                    int32_t label_cap, int32_t equal_weight, const int32_t* sup, int64_t sup_stride,
+                    const int32_t* sup_len, const int32_t* tid2pdf, int32_t num_pdfs, float* grad,
+                    int64_t grad_seq_stride, int64_t grad_frame_stride, double* loss, void* stream);
 /* Test / tooling hook: copies the pruned lattice of utterance n to host arrays (synchronises `stream`).
  * Call with null arrays to get the counts.  Tokens are renumbered frame by frame; link_ac is the acoustic
  * cost with the acoustic scale removed. */

@@ -100,6 +100,11 @@ SIGNATURES = {
     "pk2_lattice_mmi": (C.c_int, [_vp, _vp, _vp, _i64, _vp, C.c_double, C.c_double, _i32, _vp, _i64, _i64, _vp, _vp]),
     "pk2_lattice_mpe": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _i32, _i32, C.c_double, C.c_double, _vp, _i64, _i64,
                                   _vp, _vp]),
+    "pk2_lattice_nbest_bytes": (_sz, [_vp, _i32, _i64, _i64, _i32, _i32]),
+    "pk2_lattice_nbest": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _vp, _i32, C.c_double, C.c_double, _i32,
+                                    _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pk2_lattice_mwe": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _vp, _i32, C.c_double, C.c_double, _i32, _i32,
+                                  _vp, _i64, _vp, _vp, _i32, _vp, _i64, _i64, _vp, _vp]),
     "pk2_lattice_export": (C.c_int, [_vp, _vp, _i32, C.POINTER(_i32), C.POINTER(_i32), _vp, _vp, _vp, _vp, _vp,
                                      _vp, _vp, _vp, _vp, _vp]),
     "pk2_comm_unique_id_bytes": (_i32, []),

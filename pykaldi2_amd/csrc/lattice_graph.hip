@@ -31,6 +31,7 @@ static int build_decode_graph(int32_t S, int32_t start, int64_t A, const int32_t
   g->e_dst.resize(g->e_off[S]); g->e_tid.resize(g->e_off[S]); g->e_w.resize(g->e_off[S]);
   g->n_dst.resize(g->n_off[S]); g->n_w.resize(g->n_off[S]);
   g->e_ol.assign(g->e_off[S], 0); g->n_ol.assign(g->n_off[S], 0);
+  g->has_olabels = olabel != nullptr;
   std::vector<int32_t> ep(g->e_off.begin(), g->e_off.end() - 1), np(g->n_off.begin(), g->n_off.end() - 1);
   for (int64_t a = 0; a < A; ++a) {
     if (ilabel[a] > 0) {

@@ -1,6 +1,6 @@
 // Internal declarations of the lattice path (MMIFunction / sMBRFunction):
 // lattice_graph.hip (decoding graph, batch layout, export), lattice_decode.hip (token passing + lattice
-// pruning), lattice_fb.hip (lattice forward-backward: MMI, sMBR, MPFE).
+// pruning), lattice_fb.hip (lattice forward-backward: MMI, sMBR, MPFE), lattice_nbest.hip (N-best paths, MWE).
 //
 // MI355X design: the reference decodes every utterance on the CPU with Kaldi's LatticeFasterDecoder, copies
 // the lattice posteriors to the GPU and loops over utterances in Python (reference ops/ops.py:55-66,
@@ -109,7 +109,15 @@ struct pk2_decode_graph {
   int32_t S = 0, start = 0, max_ilabel = 0;
   int64_t A = 0;
   std::vector<int32_t> e_off, e_dst, e_tid, n_off, n_dst;
-  std::vector<int32_t> e_ol, n_ol;   // output labels (word ids) of the emitting / epsilon arcs, host only (0 when not given)
+  std::vector<int32_t> e_ol, n_ol;   // output labels (word ids) of the emitting / epsilon arcs (0 when not given)
+  bool has_olabels = false;
+  // device copies of e_ol / n_ol and per-state arc orders by destination, uploaded by the first N-best / MWE call
+  // (lattice_nbest.hip); decoding never reads them
+  bool dev_ol_uploaded = false;
+  const int32_t* dev_e_ol = nullptr;
+  const int32_t* dev_n_ol = nullptr;
+  const int32_t* dev_e_perm = nullptr;
+  const int32_t* dev_n_perm = nullptr;
   std::vector<float> e_w, n_w, final_cost;
   bool uploaded = false;
   int device = -1;

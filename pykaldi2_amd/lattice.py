@@ -229,6 +229,24 @@ class TransitionModel:
             self._dev[key] = (torch.from_numpy(self.tid2pdf).to(device), torch.from_numpy(self.tid2phone).to(device))
         return self._dev[key]
 
+    def phone_label_table(self):
+        """Kaldi's convert_lattice_to_phones rule per transition-id: the phone when the transition-id belongs to HMM state 0
+        and is not a self-loop, else 0 (index 0 unused).  Needs the topology, as split_to_phones does."""
+        if self.tid2tstate is None or self.tuples is None or self.tid_flags is None:
+            raise ValueError("the transition model carries no topology (read it from final.mdl)")
+        tab = np.zeros(self.num_transition_ids() + 1, np.int32)
+        tids = np.arange(1, tab.shape[0])
+        hmm_state = self.tuples[self.tid2tstate[tids] - 1, 1]
+        self_loop = (self.tid_flags[tids] & 1) != 0
+        tab[1:] = np.where((hmm_state == 0) & ~self_loop, self.tid2phone[tids], 0)
+        return tab
+
+    def device_phone_labels(self, device):
+        key = ("phone_labels", str(device))
+        if key not in self._dev:
+            self._dev[key] = torch.from_numpy(self.phone_label_table()).to(device)
+        return self._dev[key]
+
     def silence_mask(self, silence_phones, device):
         m = np.zeros(int(self.tid2phone.max()) + 2, np.uint8)
         for ph in silence_phones:
@@ -347,6 +365,91 @@ class LatticeBatch:
                                               _lib.stream_ptr(self.device)))
         return out, post
 
+    def _nbest_call(self, fn, num_paths, lm_scale, acoustic_scale, labels, distinct, *tail, trans_model=None):
+        """Shared arguments of pk2_lattice_nbest / pk2_lattice_mwe: the scratch lists come from torch's caching allocator,
+        sized from the token / link counts decode_batch read back (no extra read)."""
+        check_nbest_paths(num_paths)
+        if labels not in ("words", "phones"):
+            raise ValueError("labels must be 'words' or 'phones', got %r" % (labels,))
+        tm = trans_model or self.trans_model
+        tab = tm.device_phone_labels(self.device) if labels == "phones" else None
+        L = _lib.lib()
+        ttot, ltot = int(np.sum(self.num_tokens, dtype=np.int64)), int(np.sum(self.num_links, dtype=np.int64))
+        cap = 2 * max(self.lengths) + 8
+        nbytes = L.pk2_lattice_nbest_bytes(self._h, int(num_paths), ttot, ltot, int(bool(distinct)), cap)
+        scratch = torch.empty(int(nbytes), dtype=torch.uint8, device=self.device)
+        _lib.check(fn(self._h, _lib.ptr(self.workspace), _lib.ptr(scratch), ttot, ltot, int(num_paths), int(bool(distinct)),
+                      1 if labels == "phones" else 0, _lib.ptr(tab), tm.num_transition_ids(), float(lm_scale),
+                      float(acoustic_scale), cap, *tail))
+        return scratch, cap
+
+    def nbest(self, n, lm_scale=1.0, acoustic_scale=1.0, labels="words", distinct=False):
+        """The n lowest-cost paths of every lattice (reference nbest_as_fsts on the lattice scaled by
+        lattice_scale(lm_scale, acoustic_scale)); labels "words" = HCLG output labels, "phones" = convert_lattice_to_phones.
+        Paths that repeat an earlier path's labels are dropped; distinct=True: the n best distinct label sequences.
+        Returns, per utterance, a list of (labels, tids i32 [T], cost) in ascending cost (empty for a failed utterance).
+        Reads the result back to the host: for tools and tests."""
+        N, K, Tmax = len(self.lengths), int(n), max(self.lengths)
+        check_nbest_paths(K)
+        dev = self.device
+        i32 = lambda *shape: torch.empty(*shape, dtype=torch.int32, device=dev)
+        num_hyp, hyp_path, nlab = i32(N), i32(N, K), i32(N, K)
+        cost = torch.empty(N, K, dtype=torch.float32, device=dev)
+        cap = 2 * Tmax + 8
+        labs, tids = i32(N, K, cap), i32(N, K, Tmax)
+        keep, _ = self._nbest_call(_lib.lib().pk2_lattice_nbest, K, lm_scale, acoustic_scale, labels, distinct,
+                                   _lib.ptr(num_hyp), _lib.ptr(hyp_path), _lib.ptr(cost), _lib.ptr(nlab), _lib.ptr(labs),
+                                   _lib.ptr(tids), _lib.stream_ptr(dev))
+        num_hyp, hyp_path, nlab, cost = num_hyp.cpu().numpy(), hyp_path.cpu().numpy(), nlab.cpu().numpy(), cost.cpu().numpy()
+        labs, tids = labs.cpu().numpy(), tids.cpu().numpy()
+        del keep
+        out = []
+        for u in range(N):
+            hyps = []
+            for m in range(int(num_hyp[u])):
+                k = int(hyp_path[u, m])
+                if nlab[u, k] < 0:
+                    raise _lib.Pk2Error("N-best path %d of utterance %d: %s" % (
+                        k, u, "more labels than the buffer holds" if nlab[u, k] == -1 else "back-pointers do not reach frame 0"))
+                hyps.append((labs[u, k, :nlab[u, k]].tolist(), tids[u, k, :self.lengths[u]].copy(), float(cost[u, k])))
+            out.append(hyps)
+        return out
+
+    def mwe(self, supervisions, config, trans_model=None):
+        """N-best minimum word error of every utterance (reference MWEFunction, ops/ops.py:158-241) on the device.
+        supervisions: per utterance the word ids, or with config['phone_level'] the transition-id alignment (split into
+        phones on the host).  -> (loss f64 [N], grad f32 [N, Tmax, P]); a failed utterance gives NaN and no gradient."""
+        cfg = mwe_config(config)
+        tm = trans_model or self.trans_model
+        N = len(self.lengths)
+        assert len(supervisions) == N, "one supervision per utterance"
+        seqs = []
+        for sup in supervisions:
+            if cfg["phone_level"]:
+                from . import chain
+                _, pieces = chain.split_to_phones(tm, np.asarray(sup, np.int64).reshape(-1))
+                seqs.append([p for p, _, _ in pieces])
+            else:
+                seqs.append([int(w) for w in np.asarray(sup).reshape(-1)])
+        Lmax = max(1, max(len(q) for q in seqs))
+        if Lmax > 1023:
+            raise ValueError("MWE supervisions hold at most 1023 labels, got %d" % Lmax)
+        sup = np.zeros((N, Lmax), np.int32)
+        for u, q in enumerate(seqs):
+            sup[u, :len(q)] = q
+        lens = np.asarray([len(q) for q in seqs], np.int32)
+        sup_d, lens_d = _lib.h2d(sup, self.device), _lib.h2d(lens, self.device)
+        grad = self._zeros_post()
+        loss = torch.empty(N, dtype=torch.float64, device=self.device)
+        t2p, _ = tm.device_tables(self.device)
+        scratch, _ = self._nbest_call(_lib.lib().pk2_lattice_mwe, cfg["num_paths"], cfg["lm_weight"], cfg["am_weight"],
+                                      "phones" if cfg["phone_level"] else "words", cfg["distinct"],
+                                      int(bool(cfg["equal_weight"])), _lib.ptr(sup_d), sup_d.stride(0), _lib.ptr(lens_d),
+                                      _lib.ptr(t2p), int(self.num_pdfs), _lib.ptr(grad), grad.stride(0), grad.stride(1),
+                                      _lib.ptr(loss), _lib.stream_ptr(self.device), trans_model=tm)
+        self._mwe_keep = (scratch, sup_d, lens_d)     # (alive until the stream has used them)
+        return loss, grad
+
     def export(self, n):
         """Pruned lattice of utterance n as host arrays (tests / tooling)."""
         L = _lib.lib()
@@ -426,6 +529,32 @@ class LatticeBatch:
                     best_words=[int(words[l]) for l in path if words[l] > 0],
                     best_tids=[int(A["link_tid"][l]) for l in path if A["link_tid"][l] > 0],
                     best_cost=float(total[end]))
+
+
+MWE_KEYS = ("lm_weight", "am_weight", "phone_level", "rand_path", "num_paths", "equal_weight")
+
+
+def check_nbest_paths(num_paths):
+    if isinstance(num_paths, bool) or int(num_paths) != num_paths or not 1 <= int(num_paths) <= 64:
+        raise ValueError("num_paths must be an integer in 1..64, got %r" % (num_paths,))
+
+
+def mwe_config(config):
+    """Validates the reference's MWE config (ops/ops.py:158-241): every key of MWE_KEYS is required (KeyError, as the
+    reference's config[...] raises); rand_path (Kaldi's EqualAlign sampling) is not built; num_paths in 1..64.  The
+    optional key `distinct` (default False) asks for the num_paths best distinct label sequences."""
+    for k in MWE_KEYS:
+        if k not in config:
+            raise KeyError(k)
+    if config["rand_path"]:
+        raise NotImplementedError("MWE config key 'rand_path': sampling paths with Kaldi's EqualAlign is not supported")
+    check_nbest_paths(config["num_paths"])
+    cfg = {k: config[k] for k in MWE_KEYS}
+    cfg["num_paths"] = int(cfg["num_paths"])
+    cfg["lm_weight"], cfg["am_weight"] = float(cfg["lm_weight"]), float(cfg["am_weight"])
+    cfg["phone_level"], cfg["equal_weight"] = bool(cfg["phone_level"]), bool(cfg["equal_weight"])
+    cfg["distinct"] = bool(config.get("distinct", False))
+    return cfg
 
 
 def persistent_decoder_status():

@@ -13,7 +13,8 @@ modified in place.
 
 MMIFunction / sMBRFunction (lattice-based, ops/ops.py:41-75,119-156) decode on the device
 (lattice.MappedLatticeFasterRecognizer) and run the lattice forward-backward there; LatticeBatchFunction
-is the whole-minibatch form.
+is the whole-minibatch form.  MWEFunction (N-best minimum word error, ops/ops.py:158-241) and its minibatch form
+MWEBatchFunction take the N best paths of the same device lattices.
 """
 import numpy as np
 import os
@@ -21,7 +22,7 @@ import os
 import torch
 from torch.autograd import Function
 
-from . import _lib, chain
+from . import _lib, chain, lattice
 
 
 class ChainObjtiveFunction(Function):
@@ -195,3 +196,46 @@ class LatticeBatchFunction(Function):
     def backward(ctx, grad_out):
         post, = ctx.saved_tensors
         return -post, None, None, None, None, None, None
+
+
+class MWEFunction(Function):
+    """N-best minimum word error for one utterance with the reference's signature (ops/ops.py:158-241):
+    ``MWEFunction.apply(loglikes[T, P], asr_decoder, trans_model, supervision, config)``.  supervision = word ids, or
+    with config['phone_level'] the transition-id alignment; config keys lm_weight, am_weight, phone_level, rand_path
+    (must be false), num_paths (1..64), equal_weight, and optionally distinct.  Forward returns the expected edit
+    distance; backward returns the saved gradient sum_k (e_k - loss) p_k per (frame, pdf of path k) regardless of
+    grad_out, as the reference does."""
+
+    @staticmethod
+    def forward(ctx, loglikes, asr_decoder, trans_model, supervision, config):
+        lattice.mwe_config(config)
+        lat = asr_decoder.decode(loglikes.detach().contiguous())
+        loss, grad = lat.mwe([supervision], config, trans_model)
+        ctx.save_for_backward(grad[0])
+        return loss[0].to(torch.float32)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        grad, = ctx.saved_tensors
+        return grad, None, None, None, None
+
+
+class MWEBatchFunction(Function):
+    """MWE for all utterances of a minibatch in one decode and one N-best launch chain:
+    ``MWEBatchFunction.apply(prediction[N, Tmax, P], lengths, asr_decoder, trans_model, supervisions, config)``.
+    Returns the summed loss (float32); ctx.per_sequence holds the float64 loss of every utterance."""
+
+    @staticmethod
+    def forward(ctx, prediction, lengths, asr_decoder, trans_model, supervisions, config):
+        lattice.mwe_config(config)
+        lat = asr_decoder.decode_batch(prediction.detach(), lengths)
+        loss, grad = lat.mwe(supervisions, config, trans_model)
+        ctx.save_for_backward(grad)
+        ctx.per_sequence = loss
+        ctx.lattice = lat
+        return loss.sum().to(torch.float32)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        grad, = ctx.saved_tensors
+        return grad, None, None, None, None, None

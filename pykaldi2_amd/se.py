@@ -99,3 +99,48 @@ def sequence_loss_aligned(model, fb, batch, texts, aligner, asr_decoder, trans_m
     else:
         se = torch.zeros((), dtype=torch.float32, device=prediction.device)
     return ce_ratio * ce_loss + se, se, ce_loss, frames, failed
+
+
+def mwe_settings(config, acoustic_scale):
+    """The `mwe_config:` block of the YAML over its defaults (num_paths 16, lm_weight 1.0, am_weight = the decoder's
+    acoustic scale, equal_weight / phone_level / rand_path / distinct false), validated as MWEFunction does."""
+    from .lattice import mwe_config
+    cfg = dict(num_paths=16, lm_weight=1.0, am_weight=float(acoustic_scale), equal_weight=False, phone_level=False,
+               rand_path=False, distinct=False)
+    cfg.update(config.get("mwe_config") or {})
+    mwe_config(cfg)
+    return cfg
+
+
+def sequence_loss_mwe(model, fb, batch, texts, aligner, asr_decoder, trans_model, log_prior, mwe_cfg, ce_ratio, ce_criterion,
+                      forward=None, transform=None):
+    """The train_se2 step with the N-best minimum word error criterion (ops.MWEBatchFunction): the supervision is the word
+    transcript (`texts`); with mwe_cfg['phone_level'] it is the transition-id alignment made on the fly as in
+    sequence_loss_aligned (utterances that fail to align are left out).  loss = ce_ratio * ce_loss + sum of the MWE losses.
+    Returns (loss, se_value, ce_loss, frames, indices of the utterances that failed)."""
+    feats, frames, row_off = fb(batch["wav"], batch["lens"])
+    if transform is not None:
+        feats = transform(feats)
+    x = fb.pad_roll_subsample(feats, row_off, frames, shift=0, subsample=1, time_major=True)
+    prediction = forward(model, x, frames) if forward is not None else model.forward_time_major(x).transpose(0, 1)
+    N, Tmax = prediction.shape[0], prediction.shape[1]
+    y = np.full((N, Tmax), -100, np.int64)
+    for n, lab in enumerate(batch["y"]):
+        y[n, :frames[n]] = np.asarray(lab)[:frames[n]]
+    ce_loss = ce_criterion(prediction, torch.from_numpy(y).to(prediction.device))
+    loglikes = prediction - log_prior
+    lengths = [int(t) for t in frames]
+    failed, keep, sups = [], list(range(N)), list(texts)
+    if mwe_cfg["phone_level"]:
+        ali = aligner.align_batch(loglikes.detach(), lengths, texts)
+        keep = [n for n, r in enumerate(ali) if r is not None]
+        failed = [n for n, r in enumerate(ali) if r is None]
+        sups = [ali[n]["alignment"] if ali[n] is not None else None for n in range(N)]
+    if keep:
+        sub = loglikes if len(keep) == N else loglikes[keep]
+        lens = [lengths[n] for n in keep]
+        sub = sub[:, :max(lens)]
+        se = ops.MWEBatchFunction.apply(sub, lens, asr_decoder, trans_model, [sups[n] for n in keep], mwe_cfg)
+    else:
+        se = torch.zeros((), dtype=torch.float32, device=prediction.device)
+    return ce_ratio * ce_loss + se, se, ce_loss, frames, failed
