@@ -1605,14 +1605,8 @@ static int den_compute_t(pk2_den_graph* g, const float* logits, int64_t seq_stri
   if (persist) { p.fwd.n_chunks = kPR; p.bwd.n_chunks = kPR; }     // partial sums per frame: one per workgroup of a team
 
   const size_t lds = den_lds_bytes(g->P, NG);
-  struct attr_set_t { bool f[8]; }; static PerDevice<attr_set_t> attr_set_pd(attr_set_t{}); bool (&attr_set)[8] = attr_set_pd.ref().f;
-  if (!attr_set[NG]) {
-    PK2_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&den_fwd_step<NG>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    PK2_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&den_bwd_step<NG>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    attr_set[NG] = true;
-  }
+  PK2_DYN_LDS_ONCE(den_fwd_step<NG>, 160 * 1024);
+  PK2_DYN_LDS_ONCE(den_bwd_step<NG>, 160 * 1024);
   ParamSlot<DenParams>* slot;
   int rc = get_param_slot(g_den_slots, NG, stream, &slot);
   if (rc) return rc;
@@ -1661,12 +1655,7 @@ static int den_compute_t(pk2_den_graph* g, const float* logits, int64_t seq_stri
       hipLaunchKernelGGL(den_exp_rows, dim3(Tmax, G), dim3(256), 0, stream, logits, seq_stride, frame_stride, b.lengths, b.xv,
                          g->P, Tmax);
     } else if (persist || (exp_lds <= kGammaMaxLds && !getenv("PK2_DEN_EXP_GATHER"))) {
-      struct attr_e_t { bool f[8]; }; static PerDevice<attr_e_t> attr_e_pd(attr_e_t{}); bool (&attr_e)[8] = attr_e_pd.ref().f;
-      if (!attr_e[NG]) {
-        PK2_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&den_exp_states_lds<NG>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        attr_e[NG] = true;
-      }
+      PK2_DYN_LDS_ONCE(den_exp_states_lds<NG>, 160 * 1024);
       const int z = std::max(1, std::min((g->V + kExpThreads - 1) / kExpThreads, (2048 + Tmax * G - 1) / (Tmax * G)));
       hipLaunchKernelGGL(den_exp_states_lds<NG>, dim3(Tmax, G, z), dim3(kExpThreads), exp_lds, stream, logits, seq_stride,
                          frame_stride, b.lengths, g->d_vpdf, b.beta, g->V, g->d_loop_pdf, b.xl, g->S, g->P, Tmax,
@@ -1724,16 +1713,9 @@ static int den_compute_t(pk2_den_graph* g, const float* logits, int64_t seq_stri
     }
     const size_t row_lds = (size_t)g->P * NG * sizeof(float);
     const bool lds_row = row_lds <= kGammaMaxLds && !getenv("PK2_DEN_GAMMA_GATHER");
-    struct attr_n_t { bool f[8]; }; static PerDevice<attr_n_t> attr_n_pd(attr_n_t{}); bool (&attr_n)[8] = attr_n_pd.ref().f;
-    if (!attr_n[NG]) {
-      PK2_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&den_gamma_states_num<NG, false>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      PK2_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&den_gamma_states_num<NG, true>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      PK2_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&den_gamma_states_lds<NG>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      attr_n[NG] = true;
-    }
+    PK2_DYN_LDS_ONCE((den_gamma_states_num<NG, false>), 160 * 1024);
+    PK2_DYN_LDS_ONCE((den_gamma_states_num<NG, true>), 160 * 1024);
+    PK2_DYN_LDS_ONCE(den_gamma_states_lds<NG>, 160 * 1024);
     if (tail && tail->valid && !num_rode) {
       if (lds_row && std::max(row_lds, (size_t)tail->lds) <= kGammaMaxLds)
         hipLaunchKernelGGL((den_gamma_states_num<NG, true>), dim3(Tmax + tail->N, G), dim3(kGammaThreads),

@@ -527,7 +527,7 @@ __global__ void den_persist_check(const DenPersistCtl* ctl, int ntasks, float* d
 // ----------------------------------------------------------------------------------------
 // host
 // ----------------------------------------------------------------------------------------
-static PerDevice<int> g_den_persist_state_pd(-1);     // -1: not verified yet, 0: unusable on this device, 1: verified
+static PersistFamily g_den_persist("den_persist");      // (no sticky word: nothing asks this form for its status)
 struct DenPersistParams;
 struct DenPersistScratch { DenPersistParams* params = nullptr; DenPersistCtl* ctl = nullptr; float* ring = nullptr; float* pring = nullptr; int rpad = 0; int ntasks = 0; };
 static std::map<DevStream, DenPersistScratch> g_den_scratch;
@@ -547,15 +547,9 @@ bool den_persist_fits(const pk2_den_graph* g) {
 bool den_persist_wanted(const pk2_den_graph* g, int N) {
   const char* env = getenv("PK2_DEN_PERSIST");
   if (env && atoi(env) == 0) return false;
-  if (g_den_persist_state_pd.ref() == 0 || !den_persist_fits(g) || !den_use_sx(g)) return false;
+  if (!g_den_persist.usable() || !den_persist_fits(g) || !den_use_sx(g)) return false;
   if (N < 1 || 2 * N > kMaxTasks) return false;
-  static PerDevice<int> cus_pd(-1); int& cus = cus_pd.ref();
-  if (cus < 0) {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) n = 0;
-    cus = n;
-  }
-  return cus == 8 * kPR;
+  return device_cu_count() == 8 * kPR;
 }
 
 int den_persist_launch(pk2_den_graph* g, const DenParams& dp, const float* xv, const int32_t* lengths_host, int N,
@@ -588,12 +582,7 @@ int den_persist_launch(pk2_den_graph* g, const DenParams& dp, const float* xv, c
   sc.ntasks = 0;
   if (p.ntasks == 0) { *ran = true; return PK2_OK; }
   const size_t lds = den_persist_lds_bytes(g);
-  static PerDevice<bool> attr_pd(false); bool& attr = attr_pd.ref();
-  if (!attr) {
-    PK2_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&den_persist_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                160 * 1024));
-    attr = true;
-  }
+  PK2_DYN_LDS_ONCE(den_persist_kernel, 160 * 1024);
   PK2_HIP(hipMemsetAsync(sc.ctl, 0, sizeof(DenPersistCtl), stream));
   hipLaunchKernelGGL(param_block_store<DenPersistParams>, dim3(1), dim3(1), 0, stream, p, sc.params);
   hipLaunchKernelGGL(den_persist_kernel, dim3(8 * kPR), dim3(kPT), lds, stream, sc.params, sc.ctl);
@@ -602,16 +591,9 @@ int den_persist_launch(pk2_den_graph* g, const DenParams& dp, const float* xv, c
     hipLaunchKernelGGL(dp_prof_print, dim3(1), dim3(1), 0, stream, std::max(1, tot / 4), 1); }   // (rank 0 of every team adds up)
 #endif
   PK2_LAUNCH_CHECK();
-  if (g_den_persist_state_pd.ref() < 0) {     // first use on this device: every recursion done, nobody timed out?
-    DenPersistCtl* h = new DenPersistCtl;
-    hipError_t e = hipMemcpyAsync(h, sc.ctl, sizeof(DenPersistCtl), hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    const bool ok = e == hipSuccess && h->abort == 0u && h->done == (unsigned)p.ntasks;
-    delete h;
-    if (e != hipSuccess) { set_error("den_persist: %s", hipGetErrorString(e)); return PK2_ERR_HIP; }
-    g_den_persist_state_pd.ref() = ok ? 1 : 0;
-    if (!ok) return PK2_OK;
-  }
+  bool ok = false;                            // first use on this device: every recursion done, nobody timed out?
+  int rc = g_den_persist.verify_first_use(&sc.ctl->abort, &sc.ctl->done, (unsigned)p.ntasks, stream, &ok);
+  if (rc || !ok) return rc;
   sc.ntasks = p.ntasks;
   *ran = true;
   return PK2_OK;
@@ -619,8 +601,7 @@ int den_persist_launch(pk2_den_graph* g, const DenParams& dp, const float* xv, c
 
 void den_persist_check_launch(float* den_lp, int N, hipStream_t stream) {
   const DenPersistScratch& sc = g_den_scratch[dev_stream(stream)];
-  PersistGuard guard;
-  (void)persist_guard(&guard);
+  const PersistGuard guard = persist_guard_or_null();
   if (sc.ctl && sc.ntasks > 0) hipLaunchKernelGGL(den_persist_check, dim3(1), dim3(64), 0, stream, sc.ctl, sc.ntasks, den_lp, N, guard.dev, guard.host_dev);
 }
 

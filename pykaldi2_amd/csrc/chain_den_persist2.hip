@@ -1292,7 +1292,7 @@ __global__ void den_persist2_check(DenPersistCtl* ctl, int ntasks, float* den_lp
 // ----------------------------------------------------------------------------------------
 // host
 // ----------------------------------------------------------------------------------------
-static PerDevice<int> g_den_persist2_state_pd(-1);     // -1: not verified yet, 0: unusable on this device, 1: verified
+static PersistFamily g_den_persist2("den_persist2");    // (no sticky word: nothing asks this form for its status)
 struct DenPersist2Scratch { DenPersist2Params* params = nullptr; DenPersistCtl* ctl = nullptr; float* ring = nullptr; float* pring = nullptr; int rpad = 0; int ntasks = 0;
                             bool ctl_clean = false;         // the last launch's check kernel has zeroed the control block
                             std::vector<unsigned char> params_host; };      // what `params` holds (a call with the same block skips the store)
@@ -1305,25 +1305,15 @@ bool den_persist2_fits(const pk2_den_graph* g) {
   return g->h_p2fwd.ok && g->h_p2bwd.ok && g->p2_cap > 0 && den_persist2_lds_bytes(den2_tfloats(g), g->p2_cap, g->p2_rowarrays) <= kDenPersistMaxLds;
 }
 
-static bool den_is_8x32() {
-  static PerDevice<int> cus_pd(-1); int& cus = cus_pd.ref();
-  if (cus < 0) {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) n = 0;
-    cus = n;
-  }
-  return cus == 8 * kPR;
-}
-
 // Which form runs: the forced one if it fits; else the second form whenever the whole graph is resident in it (it takes
 // every graph the first form takes and is a little faster); when it has to stream pieces or rotate table chunks, whichever of
 // it and the launch-per-frame kernels the measured cost model (profiles/r03_den_sweep.txt) predicts to be faster.
 int den_persist_version(const pk2_den_graph* g, int N) {
   const char* env = getenv("PK2_DEN_PERSIST");
   const int want = env ? atoi(env) : -1;
-  if (want == 0 || !den_use_sx(g) || N < 1 || 2 * N > kMaxTasks || !den_is_8x32()) return 0;
+  if (want == 0 || !den_use_sx(g) || N < 1 || 2 * N > kMaxTasks || device_cu_count() != 8 * kPR) return 0;
   const bool ok1 = den_persist_wanted(g, N);
-  const bool ok2 = g_den_persist2_state_pd.ref() != 0 && den_persist2_fits(g);
+  const bool ok2 = g_den_persist2.usable() && den_persist2_fits(g);
   if (want == 1) return ok1 ? 1 : 0;
   if (want == 2) return ok2 ? 2 : 0;
   if (!ok2) return ok1 ? 1 : 0;
@@ -1380,7 +1370,7 @@ int den_persist2_launch(pk2_den_graph* g, const DenParams& dp, const float* xv, 
   // The numerator forward-backward of the minibatch (two waves per sequence, LDS-staged) as further tasks behind the
   // recursions: the teams of the short sequences run them while the longest recursion is still going.  Not during the
   // first, verified launch of a process (a fallback would have to undo the posteriors already added to the gradient).
-  const bool with_num = tail && tail->valid && tail->stage && num_ran && g_den_persist2_state_pd.ref() == 1 && tail->N == N &&
+  const bool with_num = tail && tail->valid && tail->stage && num_ran && g_den_persist2.verified() && tail->N == N &&
                         tail->lds <= (size_t)den2_tfloats(g) * sizeof(float) && p.ntasks + N <= kMaxTasks &&
                         !(getenv("PK2_DEN_NUM_RIDE") && atoi(getenv("PK2_DEN_NUM_RIDE")) == 0);
   if (with_num) {
@@ -1388,12 +1378,7 @@ int den_persist2_launch(pk2_den_graph* g, const DenParams& dp, const float* xv, 
     for (int n = 0; n < N; ++n) { p.task_seq[p.ntasks] = (short)n; p.task_dir[p.ntasks] = 2; ++p.ntasks; }
   }
   const size_t lds = den_persist2_lds_bytes(p.tfloats, p.cap, p.rowarrays);
-  static PerDevice<bool> attr_pd(false); bool& attr = attr_pd.ref();
-  if (!attr) {
-    PK2_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&den_persist2_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                160 * 1024));
-    attr = true;
-  }
+  PK2_DYN_LDS_ONCE(den_persist2_kernel, 160 * 1024);
   if (!sc.ctl_clean) PK2_HIP(hipMemsetAsync(sc.ctl, 0, sizeof(DenPersistCtl), stream));
   sc.ctl_clean = false;
   {
@@ -1409,16 +1394,9 @@ int den_persist2_launch(pk2_den_graph* g, const DenParams& dp, const float* xv, 
     hipLaunchKernelGGL(dp_prof_print, dim3(1), dim3(1), 0, stream, std::max(1, tot / 4), 2); }
 #endif
   PK2_LAUNCH_CHECK();
-  if (g_den_persist2_state_pd.ref() < 0) {     // first use on this device: every recursion done, nobody timed out?
-    DenPersistCtl* h = new DenPersistCtl;
-    hipError_t e = hipMemcpyAsync(h, sc.ctl, sizeof(DenPersistCtl), hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    const bool ok = e == hipSuccess && h->abort == 0u && h->done == (unsigned)p.ntasks;
-    delete h;
-    if (e != hipSuccess) { set_error("den_persist2: %s", hipGetErrorString(e)); return PK2_ERR_HIP; }
-    g_den_persist2_state_pd.ref() = ok ? 1 : 0;
-    if (!ok) return PK2_OK;
-  }
+  bool ok = false;                             // first use on this device: every recursion done, nobody timed out?
+  int rc = g_den_persist2.verify_first_use(&sc.ctl->abort, &sc.ctl->done, (unsigned)p.ntasks, stream, &ok);
+  if (rc || !ok) return rc;
   sc.ntasks = p.ntasks;
   *ran = true;
   if (with_num) *num_ran = true;
@@ -1427,8 +1405,7 @@ int den_persist2_launch(pk2_den_graph* g, const DenParams& dp, const float* xv, 
 
 void den_persist2_check_launch(float* den_lp, int N, hipStream_t stream) {
   DenPersist2Scratch& sc = g_den2_scratch[dev_stream(stream)];
-  PersistGuard guard;
-  (void)persist_guard(&guard);
+  const PersistGuard guard = persist_guard_or_null();
   if (sc.ctl && sc.ntasks > 0) {
     hipLaunchKernelGGL(den_persist2_check, dim3(1), dim3(256), 0, stream, sc.ctl, sc.ntasks, den_lp, N, guard.dev, guard.host_dev);
     sc.ctl_clean = true;
@@ -1437,8 +1414,7 @@ void den_persist2_check_launch(float* den_lp, int N, hipStream_t stream) {
 
 bool den_persist2_tail_check(hipStream_t stream, DenTailCheck* ck) {
   DenPersist2Scratch& sc = g_den2_scratch[dev_stream(stream)];
-  PersistGuard guard;
-  (void)persist_guard(&guard);
+  const PersistGuard guard = persist_guard_or_null();
   if (!sc.ctl || sc.ntasks <= 0) return false;
   ck->ctl = reinterpret_cast<unsigned*>(sc.ctl);
   ck->ctl_words = (int)(sizeof(DenPersistCtl) / sizeof(unsigned));

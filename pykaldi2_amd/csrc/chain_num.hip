@@ -17,6 +17,7 @@
 
 #include "chain_internal.h"
 #include "chain_num.h"
+#include "persist_guard.h"
 
 namespace pk2 {
 
@@ -113,12 +114,7 @@ int num_compute(const pk2_num_batch* nb, const float* logits, int64_t seq_stride
   const size_t staged = lds + ((size_t)2 * Tmax + 2 + 5 * arc_bound) * sizeof(float);
   const bool stage = staged <= 128 * 1024;
   if (stage) lds = staged;
-  static PerDevice<bool> attr_set_pd(false); bool& attr_set = attr_set_pd.ref();
-  if (!attr_set) {
-    PK2_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&num_fwd_bwd),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    attr_set = true;
-  }
+  PK2_DYN_LDS_ONCE(num_fwd_bwd, 160 * 1024);
   const int blocks_x = std::max(1, std::min(64, (Tmax + 3) / 4));
   hipLaunchKernelGGL(num_scores, dim3(blocks_x, N), dim3(kNumThreads), 0, stream, p, (int64_t)0);
   if (defer) {   // the caller launches the forward-backward together with the denominator's occupancy kernel

@@ -1730,31 +1730,23 @@ static uint64_t g_lat_clock = 0;
 // ---- host side of the persistent decoder ----
 struct LatPersistScratch { LatTeamCtl* ctl = nullptr; unsigned* sticky = nullptr; };
 static std::map<DevStream, LatPersistScratch> g_lat_persist;
-static PerDevice<int> g_lat_persist_state_pd(-1);      // -1: not tried on this device yet, 1: verified, 0: did not come back complete -> launch per frame
+static PersistFamily g_lat_family("lattice decode (persistent)");      // verdict 0: did not come back complete -> launch per frame
 
 static bool lat_persist_wanted(int team) {
   static const int mode = [] {
     const char* e = getenv("PK2_LAT_DECODER");
     return (e && strcmp(e, "frames") == 0) ? 0 : 1;
   }();
-  if (!mode || g_lat_persist_state_pd.ref() == 0 || (team != 8 && team != 16 && team != 32)) return false;
-  static PerDevice<int> cus_pd(-1); int& cus = cus_pd.ref();
-  if (cus < 0) {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) n = 0;
-    cus = n;
-  }
-  return cus == 256;                      // 8 XCDs x 32 CUs: what the team formation assumes
+  if (!mode || !g_lat_family.usable() || (team != 8 && team != 16 && team != 32)) return false;
+  return device_cu_count() == 256;                      // 8 XCDs x 32 CUs: what the team formation assumes
 }
 
 static int lat_persist_launch(const DecodeParams& p, int N, int team, hipStream_t stream, bool* ran) {
   *ran = false;
   LatPersistScratch& sc = g_lat_persist[dev_stream(stream)];
-  if (!sc.ctl) {
-    PK2_HIP(hipMalloc(reinterpret_cast<void**>(&sc.ctl), sizeof(LatTeamCtl)));
-    PK2_HIP(hipMalloc(reinterpret_cast<void**>(&sc.sticky), sizeof(unsigned)));
-    PK2_HIP(hipMemsetAsync(sc.sticky, 0, sizeof(unsigned), stream));
-  }
+  if (!sc.ctl) PK2_HIP(hipMalloc(reinterpret_cast<void**>(&sc.ctl), sizeof(LatTeamCtl)));
+  int rc = sc.sticky ? PK2_OK : g_lat_family.new_sticky(stream, &sc.sticky);
+  if (rc) return rc;
   PK2_HIP(hipMemsetAsync(sc.ctl, 0, sizeof(LatTeamCtl), stream));
   // one team per XCD while the utterances fit (an utterance then has its XCD's L2 to itself), more when there are more
   const int tpx = std::max(1, std::min({32 / team, kLatTeamsPerXcd, (N + 7) / 8}));
@@ -1765,22 +1757,15 @@ static int lat_persist_launch(const DecodeParams& p, int N, int team, hipStream_
   hipLaunchKernelGGL(lat_frames_persist, dim3(256), dim3(kLatThreads), 0, stream, p, sc.ctl, N, team, tpx, inv_mode, field_bits,
                      test_stall);
   PK2_LAUNCH_CHECK();
-  if (g_lat_persist_state_pd.ref() < 0) {          // first use on this device: every utterance done, nobody timed out?
-    LatTeamCtl* h = new LatTeamCtl;
-    hipError_t e = hipMemcpyAsync(h, sc.ctl, sizeof(LatTeamCtl), hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    const bool ok = e == hipSuccess && h->abort == 0u && h->done == (unsigned)N;
-    delete h;
-    if (e != hipSuccess) { set_error("lattice decode (persistent): %s", hipGetErrorString(e)); return PK2_ERR_HIP; }
-    g_lat_persist_state_pd.ref() = ok ? 1 : 0;
-    if (!ok) {                            // the caller decodes again, a launch per frame: give it clean state tables
-      PK2_HIP(hipMemsetAsync(p.L.st_cost, 0xFF, sizeof(uint32_t) * (size_t)N * p.g.S, stream));
-      PK2_HIP(hipMemsetAsync(p.L.st_tok, 0xFF, sizeof(int32_t) * (size_t)N * p.g.S, stream));
-      return PK2_OK;
-    }
+  bool ok = false;                                 // first use on this device: every utterance done, nobody timed out?
+  rc = g_lat_family.verify_first_use(&sc.ctl->abort, &sc.ctl->done, (unsigned)N, stream, &ok);
+  if (rc) return rc;
+  if (!ok) {                              // the caller decodes again, a launch per frame: give it clean state tables
+    PK2_HIP(hipMemsetAsync(p.L.st_cost, 0xFF, sizeof(uint32_t) * (size_t)N * p.g.S, stream));
+    PK2_HIP(hipMemsetAsync(p.L.st_tok, 0xFF, sizeof(int32_t) * (size_t)N * p.g.S, stream));
+    return PK2_OK;
   }
-  PersistGuard guard;
-  (void)persist_guard(&guard);
+  const PersistGuard guard = persist_guard_or_null();
   hipLaunchKernelGGL(lat_persist_check, dim3(1), dim3(64), 0, stream, p, sc.ctl, N, sc.sticky, guard.dev, guard.host_dev);
   PK2_LAUNCH_CHECK();
   *ran = true;
@@ -1790,13 +1775,8 @@ static int lat_persist_launch(const DecodeParams& p, int N, int team, hipStream_
 // 1: the persistent decoder is in use on this device, 0: it is not (disabled, or it failed its first launch), -1: not tried;
 // *abort_flag: some launch since start-up was marked "not decoded" by its check kernel.
 int lattice_persist_status(unsigned* abort_flag) {
-  unsigned any = 0;
-  for (auto& kv : g_lat_persist) {
-    unsigned st = 0;
-    if (kv.second.sticky && hipMemcpy(&st, kv.second.sticky, sizeof(unsigned), hipMemcpyDeviceToHost) == hipSuccess) any |= st;
-  }
-  *abort_flag = any;
-  return g_lat_persist_state_pd.ref();
+  *abort_flag = g_lat_family.any_gave_up();
+  return g_lat_family.verdict();
 }
 
 static int lattice_decode_frames_graphs(const DecodeParams& p, int N, int Tmax, int team, hipStream_t stream);
@@ -1862,12 +1842,7 @@ static int lattice_finish_and_prune(const DecodeParams& p, int N, hipStream_t st
   const dim3 thr(kLatThreads);
   // lattice-beam pruning: the per-link constants in parallel, then the serial pass with two frames' extra costs in LDS
   constexpr int kFinCap = 19456;                   // tokens of a frame the LDS arrays hold (2 x 76 KB)
-  static PerDevice<bool> attr_pd(false); bool& attr = attr_pd.ref();
-  if (!attr) {
-    PK2_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&lat_frames_finish), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                2 * kFinCap * (int)sizeof(uint32_t)));
-    attr = true;
-  }
+  PK2_DYN_LDS_ONCE(lat_frames_finish, 2 * kFinCap * (int)sizeof(uint32_t));
   hipLaunchKernelGGL(lat_link_delta, dim3(256, N), dim3(256), 0, stream, p);
   const char* cap_env = getenv("PK2_LAT_FIN_CAP");       // (test hook: 0 sends every utterance down the global-memory pass)
   const int cap = cap_env ? std::max(0, std::min(kFinCap, atoi(cap_env))) : kFinCap;

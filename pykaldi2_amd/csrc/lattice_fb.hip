@@ -18,6 +18,7 @@
 #include <cstdlib>
 
 #include "lattice_internal.h"
+#include "persist_guard.h"
 
 namespace pk2 {
 
@@ -860,14 +861,8 @@ static int fb_launch(int mode, const pk2_lattice_batch* b, void* workspace, FbPa
   lattice_carve(b, workspace, &p.L);
   const dim3 two(2, b->N), many(64, b->N), thr(kFbThreads);
   constexpr int kFbCap = 19456;                    // doubles of LDS (152 KB): two frames of kFbCap / 2 tokens each
-  static PerDevice<bool> attr_pd(false); bool& attr = attr_pd.ref();
-  if (!attr) {
-    PK2_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&lat_fb_alpha_beta), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                kFbCap * (int)sizeof(double)));
-    PK2_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&lat_fb_alpha_beta_lin), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                kFbCap * (int)sizeof(double)));
-    attr = true;
-  }
+  PK2_DYN_LDS_ONCE(lat_fb_alpha_beta, kFbCap * (int)sizeof(double));
+  PK2_DYN_LDS_ONCE(lat_fb_alpha_beta_lin, kFbCap * (int)sizeof(double));
   const char* cap_env = getenv("PK2_LAT_FIN_CAP");       // (test hook, shared with the pruning pass of the decoder)
   const int cap = cap_env ? std::max(0, std::min(kFbCap / 2, atoi(cap_env))) : kFbCap / 2;
   static const bool linear = [] { const char* e = getenv("PK2_FB_LINEAR"); return !(e && atoi(e) == 0); }();

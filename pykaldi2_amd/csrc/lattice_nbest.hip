@@ -25,6 +25,7 @@
 #include <cstdlib>
 
 #include "lattice_internal.h"
+#include "persist_guard.h"
 
 #pragma clang fp contract(off)
 
@@ -619,11 +620,7 @@ static int nb_run(const pk2_lattice_batch* b, void* workspace, void* scratch, in
   p.num_hyp = s.num_hyp; p.hyp_path = s.hyp_path; p.path_cost = s.path_cost; p.path_nlab = s.path_nlab;
   p.path_labels = s.path_labels; p.path_tids = s.path_tids; p.path_hash = s.path_hash;
   const size_t smem = lists + (size_t)(p.cap + 3 * p.lcap) * sizeof(int32_t);
-  static PerDevice<bool> attr_pd(false); bool& attr = attr_pd.ref();
-  if (!attr) {
-    PK2_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&nb_kbest), hipFuncAttributeMaxDynamicSharedMemorySize, kNbLds));
-    attr = true;
-  }
+  PK2_DYN_LDS_ONCE(nb_kbest, kNbLds);
   hipLaunchKernelGGL(nb_prep, dim3(1), dim3(64), 0, stream, p);
   hipLaunchKernelGGL(nb_labels, dim3(2 * (b->Tmax + 1), b->N), dim3(256), 0, stream, p);
   hipLaunchKernelGGL(nb_kbest, dim3(b->N), dim3(kNbThreads), smem, stream, p);

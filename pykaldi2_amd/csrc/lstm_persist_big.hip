@@ -647,15 +647,12 @@ __global__ void lstm_big_check(const BigCtl* ctl, unsigned ntasks, float* out, s
 struct BigScratch { BigCtl* ctl = nullptr; unsigned* flags = nullptr; size_t flag_words = 0; unsigned* sticky = nullptr;
                     float* mail = nullptr; size_t mail_floats = 0; PersistGuard guard; };
 static std::map<DevStream, BigScratch> g_big_scratch;
-static PerDevice<int> g_big_state_pd(-1);             // -1 untested, 0 unusable, 1 verified on this device
+static PersistFamily g_big("lstm_big");
 
 static int big_scratch(hipStream_t stream, size_t flag_words, BigScratch** out) {
   BigScratch& sc = g_big_scratch[dev_stream(stream)];
   if (!sc.ctl) PK2_HIP(hipMalloc(reinterpret_cast<void**>(&sc.ctl), sizeof(BigCtl)));
-  if (!sc.sticky) {
-    PK2_HIP(hipMalloc(reinterpret_cast<void**>(&sc.sticky), sizeof(unsigned)));
-    PK2_HIP(hipMemsetAsync(sc.sticky, 0, sizeof(unsigned), stream));
-  }
+  if (!sc.sticky) { int rc = g_big.new_sticky(stream, &sc.sticky); if (rc) return rc; }
   if (!sc.guard.dev) { int rc = persist_guard(&sc.guard); if (rc) return rc; }
   if (sc.flag_words < flag_words) {
     if (sc.flags) PK2_HIP(hipFree(sc.flags));
@@ -670,14 +667,8 @@ static int big_scratch(hipStream_t stream, size_t flag_words, BigScratch** out) 
 bool lstm_big_wanted(int B, int H, int D) {
   const char* env = getenv("PK2_LSTM_BIG_PERSIST");
   if (env && atoi(env) == 0) return false;
-  if (g_big_state_pd.ref() == 0 || H != kBgH || B < 32 || (D != 1 && D != 2) || D * ((B + 63) / 64) > kBgMaxTasks) return false;
-  static PerDevice<int> cus_pd(-1); int& cus = cus_pd.ref();
-  if (cus < 0) {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) n = 0;
-    cus = n;
-  }
-  return cus == 8 * kBgR;
+  if (!g_big.usable() || H != kBgH || B < 32 || (D != 1 && D != 2) || D * ((B + 63) / 64) > kBgMaxTasks) return false;
+  return device_cu_count() == 8 * kBgR;
 }
 
 int lstm_fwd_big_launch(const float* gx, const float* whh, const float* bhh, int B, int T, int H, int D, float* y,
@@ -693,25 +684,13 @@ int lstm_fwd_big_launch(const float* gx, const float* whh, const float* bhh, int
   if (rc) return rc;
   PK2_HIP(hipMemsetAsync(sc->ctl, 0, sizeof(BigCtl), stream));
   PK2_HIP(hipMemsetAsync(sc->flags, 0, (size_t)ntasks * T * kBgR * sizeof(unsigned), stream));
-  static PerDevice<bool> attr_pd(false); bool& attr = attr_pd.ref();
-  if (!attr) {
-    PK2_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&lstm_fwd_big_persist), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                160 * 1024));
-    attr = true;
-  }
+  PK2_DYN_LDS_ONCE(lstm_fwd_big_persist, 160 * 1024);
   BigFwdParams p{gx, whh, bhh, y, gates, cells, sc->flags, B, T, D};
   hipLaunchKernelGGL(lstm_fwd_big_persist, dim3(8 * kBgR), dim3(256), kBgLds, stream, p, sc->ctl);
   PK2_LAUNCH_CHECK();
-  if (g_big_state_pd.ref() < 0) {                 // first use on this device: every task done, nobody timed out?
-    BigCtl* h = new BigCtl;
-    hipError_t e = hipMemcpyAsync(h, sc->ctl, sizeof(BigCtl), hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    const bool ok = e == hipSuccess && h->abort == 0u && h->done == (unsigned)ntasks;
-    delete h;
-    if (e != hipSuccess) { set_error("lstm_big: %s", hipGetErrorString(e)); return PK2_ERR_HIP; }
-    g_big_state_pd.ref() = ok ? 1 : 0;
-    if (!ok) return PK2_OK;              // the caller falls back (and keeps doing so)
-  }
+  bool ok = false;                                // first use on this device: every task done, nobody timed out?
+  rc = g_big.verify_first_use(&sc->ctl->abort, &sc->ctl->done, (unsigned)ntasks, stream, &ok);
+  if (rc || !ok) return rc;
   hipLaunchKernelGGL(lstm_big_check, dim3(1), dim3(1024), 0, stream, sc->ctl, (unsigned)ntasks, y, (size_t)T * B * D * H, sc->sticky, sc->guard.dev, sc->guard.host_dev);
   *ran = true;
   return PK2_OK;
@@ -720,19 +699,14 @@ int lstm_fwd_big_launch(const float* gx, const float* whh, const float* bhh, int
 int lstm_bwd_big_launch(const float* dy, const float* whh, const float* gates, const float* cells, int B, int T, int H,
                         int D, float* dgx, hipStream_t stream, bool* ran) {
   *ran = false;
-  if (g_big_state_pd.ref() != 1) return PK2_OK;   // the forward pass verifies the device first
+  if (!g_big.verified()) return PK2_OK;           // the forward pass verifies the device first
   const int ntasks = D * ((B + 63) / 64);
   BigScratch* sc = nullptr;
   int rc = big_scratch(stream, (size_t)2 * ntasks * T * kBgR, &sc);      // "d gx stored" flags, then "partials stored" flags
   if (rc) return rc;
   PK2_HIP(hipMemsetAsync(sc->ctl, 0, sizeof(BigCtl), stream));
   PK2_HIP(hipMemsetAsync(sc->flags, 0, (size_t)2 * ntasks * T * kBgR * sizeof(unsigned), stream));
-  static PerDevice<bool> attr_pd(false); bool& attr = attr_pd.ref();
-  if (!attr) {
-    PK2_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&lstm_bwd_big_persist), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                160 * 1024));
-    attr = true;
-  }
+  PK2_DYN_LDS_ONCE(lstm_bwd_big_persist, 160 * 1024);
   // PK2_LSTM_BIG_BWD=1: the all-gather form (every rank reads all 4H d gates); default: the 4 x 8 decomposition
   static const bool form2 = [] { const char* e = getenv("PK2_LSTM_BIG_BWD"); return !(e && atoi(e) == 1); }();
   const bool aligned = ((reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(gates) | reinterpret_cast<uintptr_t>(cells) |
@@ -745,12 +719,7 @@ int lstm_bwd_big_launch(const float* dy, const float* whh, const float* gates, c
       PK2_HIP(hipMalloc(reinterpret_cast<void**>(&sc->mail), mail_floats * sizeof(float)));
       sc->mail_floats = mail_floats;
     }
-    static PerDevice<bool> attr2_pd(false); bool& attr2 = attr2_pd.ref();
-    if (!attr2) {
-      PK2_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&lstm_bwd_big_persist2), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  160 * 1024));
-      attr2 = true;
-    }
+    PK2_DYN_LDS_ONCE(lstm_bwd_big_persist2, 160 * 1024);
     BigBwd2Params p2{dy, whh, gates, cells, dgx, sc->mail, sc->flags, sc->flags + (size_t)ntasks * T * kBgR, B, T, D};
     hipLaunchKernelGGL(lstm_bwd_big_persist2, dim3(8 * kBgR), dim3(256), kBgLds, stream, p2, sc->ctl);
   } else {
@@ -764,12 +733,7 @@ int lstm_bwd_big_launch(const float* dy, const float* whh, const float* gates, c
 }
 
 int lstm_big_status(unsigned* abort_flag) {
-  unsigned any = 0;
-  for (auto& kv : g_big_scratch) {
-    unsigned st = 0;
-    if (kv.second.sticky && hipMemcpy(&st, kv.second.sticky, sizeof(unsigned), hipMemcpyDeviceToHost) == hipSuccess) any |= st;
-  }
-  *abort_flag = any;
+  *abort_flag = g_big.any_gave_up();
   return PK2_OK;
 }
 

@@ -679,7 +679,7 @@ struct SeqScratch { SeqCtl* ctl = nullptr; float* mail = nullptr; unsigned* stic
                     int mail_clean_teams = 0;         // mailboxes of that many teams per XCD are known to hold only sentinels
                     bool ctl_clean = false; };        // the last launch's check kernel has zeroed the control block
 static std::map<DevStream, SeqScratch> g_seq_scratch;
-static PerDevice<int> g_seq_state_pd(-1);             // -1 untested, 0 unusable, 1 verified on this device
+static PersistFamily g_seq("lstm_seq");
 
 // pk2_persist_guard_clear: whatever an aborted launch left behind, the next backward launch fills every mailbox again
 // (belt and braces next to the refill by the folded check: a launch that was killed never reached it).
@@ -691,10 +691,7 @@ static int seq_scratch(hipStream_t stream, SeqScratch** out) {
   SeqScratch& sc = g_seq_scratch[dev_stream(stream)];
   if (!sc.ctl) PK2_HIP(hipMalloc(reinterpret_cast<void**>(&sc.ctl), sizeof(SeqCtl)));
   if (!sc.mail) PK2_HIP(hipMalloc(reinterpret_cast<void**>(&sc.mail), (size_t)8 * kSeqTeams * kSeqMailFloats * sizeof(float)));
-  if (!sc.sticky) {
-    PK2_HIP(hipMalloc(reinterpret_cast<void**>(&sc.sticky), sizeof(unsigned)));
-    PK2_HIP(hipMemsetAsync(sc.sticky, 0, sizeof(unsigned), stream));
-  }
+  if (!sc.sticky) { int rc = g_seq.new_sticky(stream, &sc.sticky); if (rc) return rc; }
   if (!sc.guard.dev) { int rc = persist_guard(&sc.guard); if (rc) return rc; }
   *out = &sc;
   return PK2_OK;
@@ -708,14 +705,8 @@ bool lstm_seq_wanted(int B, int H, int D) {
   const char* env = getenv("PK2_LSTM_SEQ");
   if (env && atoi(env) == 0) return false;
   // (up to 4 pairs per XCD one after the other; larger batches are better served by the batched step kernels)
-  if (g_seq_state_pd.ref() == 0 || H != kSH || B < 1 || B * D > 32 || (D != 1 && D != 2)) return false;
-  static PerDevice<int> cus_pd(-1); int& cus = cus_pd.ref();
-  if (cus < 0) {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) n = 0;
-    cus = n;
-  }
-  return cus == 8 * kSWgs;
+  if (!g_seq.usable() || H != kSH || B < 1 || B * D > 32 || (D != 1 && D != 2)) return false;
+  return device_cu_count() == 8 * kSWgs;
 }
 
 int lstm_fwd_seq_launch(const float* gx, const float* whh, const float* bhh, int B, int T, int H, int D, float* y,
@@ -729,23 +720,16 @@ int lstm_fwd_seq_launch(const float* gx, const float* whh, const float* bhh, int
   PK2_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(y), (int)kSeqSentinel, (size_t)T * B * D * H, stream));
   SeqFwdParams p{gx, whh, bhh, y, gates, cells, B, T, D};
   // (the first launch on a device is checked by the host below and by the separate check kernel: no folded check)
-  const bool fold = g_seq_state_pd.ref() == 1;
+  const bool fold = g_seq.verified();
   // (test hook, read per call: PK2_LSTM_SEQ_TEST_FAIL=1 makes the folded check of a forward launch behave as if a poll had timed out)
   const char* tf_e = getenv("PK2_LSTM_SEQ_TEST_FAIL");
   const int fold_mode = fold ? ((tf_e && atoi(tf_e) == 1) ? 2 : 1) : 0;
   const SeqExit ex{(unsigned)(B * D), fold_mode, y, (size_t)T * B * D * H, sc->sticky, sc->guard.dev, sc->guard.host_dev, nullptr, (size_t)0};
   hipLaunchKernelGGL(lstm_fwd_seq2, dim3(8 * kSWgs * seq_teams(B * D)), dim3(256), 0, stream, p, sc->ctl, ex);
   PK2_LAUNCH_CHECK();
-  if (g_seq_state_pd.ref() < 0) {                 // first use on this device: every pair done, nobody timed out?
-    SeqCtl* h = new SeqCtl;
-    hipError_t e = hipMemcpyAsync(h, sc->ctl, sizeof(SeqCtl), hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    const bool ok = e == hipSuccess && h->abort == 0u && h->done == (unsigned)(B * D);
-    delete h;
-    if (e != hipSuccess) { set_error("lstm_seq: %s", hipGetErrorString(e)); return PK2_ERR_HIP; }
-    g_seq_state_pd.ref() = ok ? 1 : 0;
-    if (!ok) return PK2_OK;              // the caller falls back (and keeps doing so)
-  }
+  bool ok = false;                                // first use on this device: every pair done, nobody timed out?
+  rc = g_seq.verify_first_use(&sc->ctl->abort, &sc->ctl->done, (unsigned)(B * D), stream, &ok);
+  if (rc || !ok) return rc;
   if (!fold)
     hipLaunchKernelGGL(lstm_seq_check, dim3(1), dim3(1024), 0, stream, sc->ctl, (unsigned)(B * D), y, (size_t)T * B * D * H, sc->sticky, sc->guard.dev, sc->guard.host_dev);
   sc->ctl_clean = true;
@@ -757,7 +741,7 @@ int lstm_bwd_seq_launch(const float* dy, const float* whh, const float* gates, c
                         int D, float* dgx, hipStream_t stream, bool* ran, float* dbias_ih, float* dbias_hh, bool* bias_done) {
   *ran = false;
   if (bias_done) *bias_done = false;
-  if (g_seq_state_pd.ref() != 1) return PK2_OK;   // the forward pass verifies the device first
+  if (!g_seq.verified()) return PK2_OK;           // the forward pass verifies the device first
   SeqScratch* sc = nullptr;
   int rc = seq_scratch(stream, &sc);
   if (rc) return rc;
@@ -782,15 +766,10 @@ int lstm_bwd_seq_launch(const float* dy, const float* whh, const float* gates, c
 }
 
 int lstm_seq_status(unsigned* abort_flag) {
-  unsigned any = 0;
-  for (auto& kv : g_seq_scratch) {
-    if (!kv.second.ctl) continue;
-    SeqCtl* h = new SeqCtl;
-    hipError_t e = hipMemcpy(h, kv.second.ctl, sizeof(SeqCtl), hipMemcpyDeviceToHost);
-    if (e == hipSuccess) any |= h->abort;
-    delete h;
-    unsigned st = 0;
-    if (kv.second.sticky && hipMemcpy(&st, kv.second.sticky, sizeof(unsigned), hipMemcpyDeviceToHost) == hipSuccess) any |= st;
+  unsigned any = g_seq.any_gave_up();
+  for (auto& kv : g_seq_scratch) {           // and a launch that gave up whose check has not zeroed the control block yet
+    unsigned live = 0;
+    if (kv.second.ctl && hipMemcpy(&live, &kv.second.ctl->abort, sizeof(unsigned), hipMemcpyDeviceToHost) == hipSuccess) any |= live;
   }
   *abort_flag = any;
   return PK2_OK;

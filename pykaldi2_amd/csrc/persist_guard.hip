@@ -3,6 +3,8 @@
 // instead of reaching the weights.
 #include <map>
 #include <mutex>
+#include <set>
+#include <utility>
 #include <vector>
 
 #include "persist_guard.h"
@@ -41,6 +43,65 @@ int persist_guard(PersistGuard* out) {
   }
   *out = g;
   return PK2_OK;
+}
+
+PersistGuard persist_guard_or_null() {
+  PersistGuard g;
+  (void)persist_guard(&g);
+  return g;
+}
+
+int device_cu_count() {
+  static PerDevice<int> cus_pd(-1); int& cus = cus_pd.ref();
+  if (cus < 0) {
+    int dev = 0, n = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) n = 0;
+    cus = n;
+  }
+  return cus;
+}
+
+int raise_dyn_lds_once(const void* kernel, int bytes, const char* file, int line) {
+  static std::set<std::pair<int, const void*>> raised;       // (device, kernel)
+  const std::pair<int, const void*> key(current_device(), kernel);
+  std::lock_guard<std::mutex> lock(g_guard_mu);
+  if (raised.count(key)) return PK2_OK;
+  hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+  if (e != hipSuccess) { set_error("%s:%d: dynamic LDS limit of %d bytes -> %s", file, line, bytes, hipGetErrorString(e)); return PK2_ERR_HIP; }
+  raised.insert(key);
+  return PK2_OK;
+}
+
+int PersistFamily::verify_first_use(const unsigned* abort_dev, const unsigned* done_dev, unsigned expected_done, hipStream_t stream, bool* ok) {
+  int& verdict = verdict_.ref();
+  if (verdict < 0) {
+    unsigned h[2] = {1u, 0u};               // abort, done
+    hipError_t e = hipMemcpyAsync(&h[0], abort_dev, sizeof(unsigned), hipMemcpyDeviceToHost, stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(&h[1], done_dev, sizeof(unsigned), hipMemcpyDeviceToHost, stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+    if (e != hipSuccess) { set_error("%s: %s", name_, hipGetErrorString(e)); return PK2_ERR_HIP; }
+    verdict = (h[0] == 0u && h[1] == expected_done) ? 1 : 0;
+  }
+  *ok = verdict == 1;
+  return PK2_OK;
+}
+
+int PersistFamily::new_sticky(hipStream_t stream, unsigned** out) {
+  unsigned* w = nullptr;
+  PK2_HIP(hipMalloc(reinterpret_cast<void**>(&w), sizeof(unsigned)));
+  PK2_HIP(hipMemsetAsync(w, 0, sizeof(unsigned), stream));
+  sticky_.push_back(w);
+  *out = w;
+  return PK2_OK;
+}
+
+unsigned PersistFamily::any_gave_up() {
+  unsigned any = 0;
+  for (unsigned* w : sticky_) {
+    unsigned st = 0;
+    if (hipMemcpy(&st, w, sizeof(unsigned), hipMemcpyDeviceToHost) == hipSuccess) any |= st;
+  }
+  return any;
 }
 
 __global__ void persist_guard_raise_kernel(unsigned* dev, unsigned* host_dev) { persist_guard_raise(dev, host_dev); }
