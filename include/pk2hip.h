@@ -468,6 +468,18 @@ int pk2_lstm_layer_fwd(const float* gx, const float* whh, const float* bhh, int3
  * A poll of those kernels that times out leaves NaNs in the outputs and raises this flag (the call synchronises the
  * device). */
 int pk2_lstm_persist_status(uint32_t* abort_flag);
+/* Which kernels the most recent pk2_lstm_layer_fwd / pk2_lstm_layer_bwd[_bias] call of this process launched (host-side
+ * bookkeeping, no synchronisation): the persistent paths fall back to the step kernels without an error (first-use check
+ * failed, CU count, alignment, a backward call before a verified forward one), and this is how a caller or a test sees it.
+ * STEP_SMALL: lstm_fwd_step / lstm_bwd_step_x4 (B < 32; the forward pass also for B >= 32 with a NULL workspace);
+ * STEP_BIG: lstm_fwd_step_big / lstm_bwd_dh_big + lstm_bwd_pointwise_big; BIG_AG: the all-gather backward form. */
+#define PK2_LSTM_PATH_NONE 0
+#define PK2_LSTM_PATH_SEQ 1
+#define PK2_LSTM_PATH_BIG 2
+#define PK2_LSTM_PATH_BIG_AG 3
+#define PK2_LSTM_PATH_STEP_SMALL 4
+#define PK2_LSTM_PATH_STEP_BIG 5
+int pk2_lstm_last_path(int32_t* fwd, int32_t* bwd);
 size_t pk2_lstm_bwd_scratch_floats(int32_t B, int32_t H, int32_t num_dirs);
 int pk2_lstm_layer_bwd(const float* dy, const float* whh, const float* gates, const float* cells,
                        int32_t B, int32_t T, int32_t H, int32_t num_dirs, float* dgx,

@@ -473,6 +473,16 @@ static void launch_step(K kernel, dim3 grid, dim3 block, hipStream_t s, const P*
 
 using namespace pk2;
 
+// pk2_lstm_last_path: the path the most recent forward / backward call of this process took (host-side bookkeeping).
+static int g_last_fwd_path = PK2_LSTM_PATH_NONE, g_last_bwd_path = PK2_LSTM_PATH_NONE;
+
+extern "C" int pk2_lstm_last_path(int32_t* fwd, int32_t* bwd) {
+  PK2_REQUIRE(fwd && bwd, "lstm_last_path: null pointer");
+  *fwd = g_last_fwd_path;
+  *bwd = g_last_bwd_path;
+  return PK2_OK;
+}
+
 static bool lstm_h_ok(int H) { return H == 64 || H == 128 || H == 256 || H == 512 || H == 1024; }
 
 extern "C" size_t pk2_lstm_fwd_workspace_floats(int32_t B, int32_t H, int32_t D) {
@@ -489,13 +499,13 @@ extern "C" int pk2_lstm_layer_fwd(const float* gx, const float* whh, const float
     bool ran = false;
     int prc = lstm_fwd_seq_launch(gx, whh, bhh, B, T, H, D, y, gates, cells, stream, &ran);
     if (prc) return prc;
-    if (ran) return PK2_OK;
+    if (ran) { g_last_fwd_path = PK2_LSTM_PATH_SEQ; return PK2_OK; }
   }
   if (lstm_big_wanted(B, H, D)) {           // large batches: one launch, W_hh slices resident in LDS (lstm_persist_big.hip)
     bool ran = false;
     int prc = lstm_fwd_big_launch(gx, whh, bhh, B, T, H, D, y, gates, cells, stream, &ran);
     if (prc) return prc;
-    if (ran) return PK2_OK;
+    if (ran) { g_last_fwd_path = PK2_LSTM_PATH_BIG; return PK2_OK; }
   }
   ParamSlot<LstmFwdParams>* slot;
   int rc = get_param_slot(g_fwd_slots, H * 4 + D, stream, &slot);
@@ -516,6 +526,7 @@ extern "C" int pk2_lstm_layer_fwd(const float* gx, const float* whh, const float
     });
     if (rc) return rc;
     PK2_LAUNCH_CHECK();
+    g_last_fwd_path = PK2_LSTM_PATH_STEP_BIG;
     return PK2_OK;
   }
   const int zf = ((B + 15) / 16 + kFwdTileGroup - 1) / kFwdTileGroup;
@@ -538,6 +549,7 @@ extern "C" int pk2_lstm_layer_fwd(const float* gx, const float* whh, const float
   hipLaunchKernelGGL(lstm_prof_print, dim3(1), dim3(1), 0, stream, T - 1);
 #endif
   PK2_LAUNCH_CHECK();
+  g_last_fwd_path = PK2_LSTM_PATH_STEP_SMALL;
   return PK2_OK;
 }
 
@@ -590,13 +602,13 @@ static int lstm_layer_bwd_impl(const float* dy, const float* whh, const float* g
     bool ran = false, bdone = false;
     int prc = lstm_bwd_seq_launch(dy, whh, gates, cells, B, T, H, D, dgx, stream, &ran, dbias_ih, dbias_hh, &bdone);
     if (prc) return prc;
-    if (ran) { if (bias_done) *bias_done = bdone ? 1 : 0; return PK2_OK; }
+    if (ran) { if (bias_done) *bias_done = bdone ? 1 : 0; g_last_bwd_path = PK2_LSTM_PATH_SEQ; return PK2_OK; }
   }
   if (lstm_big_wanted(B, H, D)) {           // large batches, one launch (lstm_persist_big.hip)
-    bool ran = false;
-    int prc = lstm_bwd_big_launch(dy, whh, gates, cells, B, T, H, D, dgx, stream, &ran);
+    bool ran = false, all_gather = false;
+    int prc = lstm_bwd_big_launch(dy, whh, gates, cells, B, T, H, D, dgx, stream, &ran, &all_gather);
     if (prc) return prc;
-    if (ran) return PK2_OK;
+    if (ran) { g_last_bwd_path = all_gather ? PK2_LSTM_PATH_BIG_AG : PK2_LSTM_PATH_BIG; return PK2_OK; }
   }
   float* whhT = scratch;
   float* dc = scratch + (size_t)D * H * 4 * H;
@@ -621,6 +633,7 @@ static int lstm_layer_bwd_impl(const float* dy, const float* whh, const float* g
     });
     if (rc) return rc;
     PK2_LAUNCH_CHECK();
+    g_last_bwd_path = PK2_LSTM_PATH_STEP_BIG;
     return PK2_OK;
   }
   // batches below kBigBatch rows (every supported H is a multiple of 64): the 4x4x1-MFMA kernel
@@ -641,5 +654,6 @@ static int lstm_layer_bwd_impl(const float* dy, const float* whh, const float* g
   });
   if (rc) return rc;
   PK2_LAUNCH_CHECK();
+  g_last_bwd_path = PK2_LSTM_PATH_STEP_SMALL;
   return PK2_OK;
 }

@@ -22,8 +22,9 @@ int lstm_seq_status(unsigned* abort_flag);
 bool lstm_big_wanted(int B, int H, int D);
 int lstm_fwd_big_launch(const float* gx, const float* whh, const float* bhh, int B, int T, int H, int D, float* y,
                         float* gates, float* cells, hipStream_t stream, bool* ran);
+// *all_gather: which of the two backward forms was launched (lstm_bwd_big_persist, not lstm_bwd_big_persist2).
 int lstm_bwd_big_launch(const float* dy, const float* whh, const float* gates, const float* cells, int B, int T, int H,
-                        int D, float* dgx, hipStream_t stream, bool* ran);
+                        int D, float* dgx, hipStream_t stream, bool* ran, bool* all_gather);
 int lstm_big_status(unsigned* abort_flag);
 
 }  // namespace pk2

@@ -697,8 +697,9 @@ int lstm_fwd_big_launch(const float* gx, const float* whh, const float* bhh, int
 }
 
 int lstm_bwd_big_launch(const float* dy, const float* whh, const float* gates, const float* cells, int B, int T, int H,
-                        int D, float* dgx, hipStream_t stream, bool* ran) {
+                        int D, float* dgx, hipStream_t stream, bool* ran, bool* all_gather) {
   *ran = false;
+  *all_gather = false;
   if (!g_big.verified()) return PK2_OK;           // the forward pass verifies the device first
   const int ntasks = D * ((B + 63) / 64);
   BigScratch* sc = nullptr;
@@ -723,6 +724,7 @@ int lstm_bwd_big_launch(const float* dy, const float* whh, const float* gates, c
     BigBwd2Params p2{dy, whh, gates, cells, dgx, sc->mail, sc->flags, sc->flags + (size_t)ntasks * T * kBgR, B, T, D};
     hipLaunchKernelGGL(lstm_bwd_big_persist2, dim3(8 * kBgR), dim3(256), kBgLds, stream, p2, sc->ctl);
   } else {
+    *all_gather = true;
     BigBwdParams p{dy, whh, gates, cells, dgx, sc->flags, B, T, D};
     hipLaunchKernelGGL(lstm_bwd_big_persist, dim3(8 * kBgR), dim3(256), kBgLds, stream, p, sc->ctl);
   }

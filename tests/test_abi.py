@@ -37,6 +37,9 @@ def test_bad_arguments_fail_loudly():
     assert rc < 0 and b"null" in _lib.lib().pk2_last_error().lower()
     with pytest.raises(_lib.Pk2Error):
         _lib.check(rc)
+    fwd = C.c_int32(-1)
+    rc = _lib.lib().pk2_lstm_last_path(C.byref(fwd), None)
+    assert rc < 0 and b"null" in _lib.lib().pk2_last_error().lower() and fwd.value == -1
 
 
 def _emulate(o, nrows_total, val):

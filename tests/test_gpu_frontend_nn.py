@@ -219,6 +219,16 @@ def test_persistent_recurrence_long_sequences_match_torch_cpu(B, T, bi, layers, 
     from pykaldi2_amd import _lib
     flag = __import__("ctypes").c_uint32(7)
     assert _lib.lib().pk2_lstm_persist_status(__import__("ctypes").byref(flag)) == 0 and flag.value == 0   # no poll timed out
+    # and the kernels the test is about did run (pk2_lstm_last_path: 1 = SEQ, 4 = STEP_SMALL; every layer has the same shape)
+    assert _lstm_last_path() == ((1, 1) if impl == "pair_per_xcd" else (4, 4))
+
+
+def _lstm_last_path():
+    import ctypes
+    from pykaldi2_amd import _lib
+    f, b = ctypes.c_int32(-1), ctypes.c_int32(-1)
+    _lib.check(_lib.lib().pk2_lstm_last_path(ctypes.byref(f), ctypes.byref(b)))
+    return f.value, b.value
 
 
 @pytest.mark.parametrize("B,T,H,bi", [(70, 9, 128, True), (256, 5, 512, True), (33, 6, 64, False),
@@ -254,6 +264,15 @@ def test_large_batch_lstm_matches_torch_cpu(B, T, H, bi):
     from pykaldi2_amd import _lib
     flag = __import__("ctypes").c_uint32(7)
     assert _lib.lib().pk2_lstm_persist_status(__import__("ctypes").byref(flag)) == 0 and flag.value == 0   # no poll timed out
+    # pk2_lstm_last_path: 2 = BIG, 3 = BIG_AG (the backward form PK2_LSTM_BIG_BWD=1 selects), 4 = STEP_SMALL, 5 = STEP_BIG
+    import os
+    if B < 32:
+        want = (4, 4)
+    elif H == 512:
+        want = (2, 3 if os.environ.get("PK2_LSTM_BIG_BWD") == "1" else 2)
+    else:
+        want = (5, 5)
+    assert _lstm_last_path() == want
 
 
 def test_large_batch_backward_all_gather_form():
