@@ -13,9 +13,10 @@ inf anywhere in a result is a failure whatever the data.
 """
 import numpy as np
 
+import bound_check
 from oracle import lstm_ref
 
-FACTOR = 4.0
+FACTOR = bound_check.FACTOR
 TENSORS = ("y", "gates", "cells", "dgx", "dbias_ih", "dbias_hh")
 
 
@@ -64,35 +65,8 @@ def backward_refs(case, gates, cells, dbias_ih0=None, dbias_hh0=None):
 
 
 def compare(got, ref64, ref32, factor=FACTOR, factors=None):
-    """Holds every tensor of `got` (name -> array) to the bound above.  Returns (failures, ratios): failures is a list of
-    (tensor name, message), empty for a result that passes; ratios[name] = error / max(e32, floor), inf for a tensor that is
-    not finite everywhere.  factors: {name: factor} for tensors with a bound of their own."""
-    failures, ratios = [], {}
-    for name in TENSORS:
-        if name not in got:
-            continue
-        x = np.asarray(got[name])
-        want, model = ref64[name], ref32[name]
-        if x.shape != want.shape:
-            failures.append((name, "%s: shape %s, expected %s" % (name, x.shape, want.shape)))
-            ratios[name] = float("inf")
-            continue
-        bad = ~np.isfinite(x)
-        if bad.any():
-            at = tuple(int(v) for v in np.argwhere(bad)[0])
-            failures.append((name, "%s: %d of %d elements not finite (unwritten or NaN / inf), first at %s"
-                             % (name, int(bad.sum()), x.size, at)))
-            ratios[name] = float("inf")
-            continue
-        e32 = float(np.abs(model.astype(np.float64) - want).max())
-        floor = 2.0 ** -23 * float(np.abs(want).max())
-        unit = max(e32, floor)
-        diff = np.abs(x.astype(np.float64) - want)
-        err = float(diff.max())
-        ratios[name] = err / unit if unit > 0 else (0.0 if err == 0 else float("inf"))
-        f = (factors or {}).get(name, factor)
-        if not err <= f * unit:
-            at = tuple(int(v) for v in np.unravel_index(int(diff.argmax()), diff.shape))
-            failures.append((name, "%s: error %.3g at %s (got %.9g, float64 %.9g) > %g * max(e32 %.3g, floor %.3g): ratio %.1f"
-                             % (name, err, at, float(x[at]), float(want[at]), f, e32, floor, ratios[name])))
-    return failures, ratios
+    """Holds every tensor of `got` (name -> array) to the bound above (tests/bound_check.py, the one implementation of it).
+    Returns (failures, ratios): failures is a list of (tensor name, message), empty for a result that passes; ratios[name] =
+    error / max(e32, floor), inf for a tensor that is not finite everywhere.  factors: {name: factor} for tensors with a
+    bound of their own."""
+    return bound_check.compare(got, ref64, ref32, TENSORS, factor=factor, factors=factors)
