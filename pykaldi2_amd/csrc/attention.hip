@@ -1,4 +1,4 @@
-// Fused multi-head self-attention for gfx950 (f32 MFMA, head size 64): softmax(Q K^T / sqrt(d) + masks) V in one kernel,
+// Fused multi-head self-attention for gfx950 (f32 MFMA; head size 64 here, head size 128 in attention128.hip): softmax(Q K^T / sqrt(d) + masks) V in one kernel,
 // the scores never leave the CU; backward by recomputation from the saved log-sum-exp.
 //
 // Replaces nn.MultiheadAttention's scaled-dot-product core under nn.TransformerEncoderLayer (reference
@@ -23,44 +23,13 @@
 
 #include <cstdlib>
 
-#include "common.h"
+#include "attention_common.h"
 
 namespace pk2 {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int kAD = 64;            // head size served
-constexpr int kAT = 32;            // tile edge (queries, keys)
+constexpr int kAD = 64;            // head size served by this file (128: attention128.hip)
 constexpr int kALd = 65;           // LDS row pitch of a staged 32 x 64 tile: rows on different banks
-constexpr int kAWaves = 4;
 constexpr int kATileFloats = kAT * kALd;
-
-struct AttnParams {
-  const float* qkv; const float* ctx; const float* dctx; const float* lse_in;
-  float* ctx_out; float* lse_out; float* dqkv; float* dsum;
-  const float* src_mask; const uint8_t* key_pad; int skip_pad;
-  int T, B, H;
-  float scale;
-  uint32_t keep_threshold; float keep_scale; uint64_t seed; int dropout;
-};
-
-__device__ __forceinline__ uint32_t attn_mix32(uint64_t z) {     // dropout.hip: splitmix64 finaliser
-  z += 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  z ^= z >> 31;
-  return (uint32_t)(z >> 32);
-}
-__device__ __forceinline__ float attn_keep(const AttnParams& p, int64_t idx) {
-  const uint32_t r = attn_mix32(p.seed * 0xD1342543DE82EF95ull + (uint64_t)idx);
-  return r < p.keep_threshold ? p.keep_scale : 0.f;
-}
-
-__device__ __forceinline__ void wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // Rows [r0, r0 + 32) of a matrix with row stride `rs` floats, 64 columns from `base`, into a wave-private LDS tile
 // [32][kALd]; rows >= T read as zero.  Coalesced: an instruction covers 4 whole rows.
@@ -111,8 +80,6 @@ __device__ __forceinline__ void load_rows(const float* tile, float (&r)[32]) {
 #pragma unroll
   for (int i = 0; i < 32; ++i) r[i] = src[i];
 }
-// tile row the MFMA instruction j reads in the lanes' half hi (see the header)
-__device__ __forceinline__ int row_of(int j, int hi) { return (j & 3) + 8 * (j >> 2) + 4 * hi; }
 
 // acc[dim][n] += sum_rows tile[row][dim] * w[row][n] for the 64 dims (two 32-row blocks of the output), the weights w being
 // an accumulator-layout register set (register j <-> tile rows row_of(j, hi)).
@@ -135,33 +102,6 @@ __device__ __forceinline__ f32x16 mfma_rows(const float* tile, const float (&b)[
 #pragma unroll
   for (int i = 0; i < 32; ++i) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(src[i], b[i], acc, 0, 0, 0);
   return acc;
-}
-
-// Additive mask of (query, key): -inf outside the sequence / on padded keys.
-__device__ __forceinline__ float mask_of(const AttnParams& p, int b, int q, int k) {
-  if (k >= p.T || (p.key_pad && p.key_pad[(int64_t)b * p.T + k])) return -INFINITY;
-  return (p.src_mask && q < p.T) ? p.src_mask[(int64_t)q * p.T + k] : 0.f;
-}
-
-// Key tiles of utterance b that hold at least one key which is not padding (every wave computes it for itself: T bytes).  The
-// tiles behind the last valid key contribute exactly nothing -- every probability is 0 -- and a minibatch of utterances of
-// different lengths is mostly such tiles for its short ones (the bench minibatch, 146 / 539 / 569 / 159 frames: 45 of 72
-// (utterance, key tile) pairs are valid): the forward and dQ loops end there, a dK / dV workgroup of such a tile stores zeros.
-// PK2_ATTN_SKIP_PAD=0 (AttnParams::skip_pad) walks every tile as rounds 2-6a did.
-__device__ __forceinline__ int wave_max_i(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
-  return v;
-}
-__device__ __forceinline__ int valid_key_tiles(const AttnParams& p, int b) {
-  const int all = (p.T + kAT - 1) / kAT;
-  if (!p.key_pad || !(p.skip_pad & 1)) return all;
-  const uint8_t* kp = p.key_pad + (int64_t)b * p.T;
-  int last = -1;
-  for (int k = threadIdx.x & 63; k < p.T; k += 64)
-    if (!kp[k]) last = k;
-  last = __builtin_amdgcn_readfirstlane(wave_max_i(last));
-  return min(all, (last + kAT) / kAT);
 }
 
 // The 32 floats of dims {4 hi + (r&3) + 8 (r>>2)} (+32) of query/key row `row` held by a lane in the transposed
@@ -456,7 +396,7 @@ using namespace pk2;
 static int attn_fill(AttnParams* p, int32_t T, int32_t B, int32_t H, int32_t head_dim, float scale, const float* src_mask,
                      const uint8_t* key_pad, float dropout_p, uint64_t seed) {
   PK2_REQUIRE(T > 0 && B > 0 && H > 0 && (int64_t)B * H <= 65535, "attention: bad sizes");
-  PK2_REQUIRE(head_dim == kAD, "attention: the fused kernel serves head size %d (got %d)", kAD, head_dim);
+  PK2_REQUIRE(head_dim == kAD || head_dim == 128, "attention: the fused kernels serve head sizes %d and 128 (got %d)", kAD, head_dim);
   PK2_REQUIRE(dropout_p >= 0.f && dropout_p < 1.f, "attention: bad dropout");
   p->T = T; p->B = B; p->H = H; p->scale = scale; p->src_mask = src_mask; p->key_pad = key_pad;
   // bit 0: loops end at the last valid key tile; bit 1: the backward kernels leave all-zero dO tiles out (default: both)
@@ -478,7 +418,32 @@ extern "C" int pk2_attention_fwd(const float* qkv, int32_t T, int32_t B, int32_t
   int rc = attn_fill(&p, T, B, H, head_dim, scale, src_mask, key_padding, dropout_p, seed);
   if (rc) return rc;
   p.qkv = qkv; p.ctx_out = ctx; p.lse_out = lse;
-  hipLaunchKernelGGL(attn_fwd_kernel, dim3((T + kAT - 1) / kAT, B * H), dim3(64 * kAWaves), 0, static_cast<hipStream_t>(stream_), p);
+  if (head_dim == kAD)
+    hipLaunchKernelGGL(attn_fwd_kernel, dim3((T + kAT - 1) / kAT, B * H), dim3(64 * kAWaves), 0, static_cast<hipStream_t>(stream_), p);
+  else
+    attn128_launch_fwd(p, static_cast<hipStream_t>(stream_));
+  PK2_LAUNCH_CHECK();
+  return PK2_OK;
+}
+
+extern "C" int pk2_attention_bwd_part(int32_t parts, const float* qkv, const float* ctx, const float* dctx, const float* lse,
+                                      int32_t T, int32_t B, int32_t H, int32_t head_dim, float scale, const float* src_mask,
+                                      const uint8_t* key_padding, float dropout_p, uint64_t seed, float* dqkv, float* dsum,
+                                      void* stream_) {
+  PK2_REQUIRE(qkv && ctx && dctx && lse && dqkv && dsum, "attention_bwd: null pointer");
+  PK2_REQUIRE(parts >= 1 && parts <= 3, "attention_bwd_part: parts is 1 (dQ), 2 (dK / dV) or 3 (got %d)", parts);
+  AttnParams p{};
+  int rc = attn_fill(&p, T, B, H, head_dim, scale, src_mask, key_padding, dropout_p, seed);
+  if (rc) return rc;
+  p.qkv = qkv; p.ctx = ctx; p.dctx = dctx; p.lse_in = lse; p.dqkv = dqkv; p.dsum = dsum;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  const dim3 grid((T + kAT - 1) / kAT, B * H), block(64 * kAWaves);
+  if (head_dim == kAD) {
+    if (parts & 1) hipLaunchKernelGGL(attn_bwd_dq_kernel, grid, block, 0, stream, p);
+    if (parts & 2) hipLaunchKernelGGL(attn_bwd_dkv_kernel, grid, block, 0, stream, p);
+  } else {
+    attn128_launch_bwd(p, parts, stream);
+  }
   PK2_LAUNCH_CHECK();
   return PK2_OK;
 }
@@ -487,15 +452,6 @@ extern "C" int pk2_attention_bwd(const float* qkv, const float* ctx, const float
                                  int32_t B, int32_t H, int32_t head_dim, float scale, const float* src_mask,
                                  const uint8_t* key_padding, float dropout_p, uint64_t seed, float* dqkv, float* dsum,
                                  void* stream_) {
-  PK2_REQUIRE(qkv && ctx && dctx && lse && dqkv && dsum, "attention_bwd: null pointer");
-  AttnParams p{};
-  int rc = attn_fill(&p, T, B, H, head_dim, scale, src_mask, key_padding, dropout_p, seed);
-  if (rc) return rc;
-  p.qkv = qkv; p.ctx = ctx; p.dctx = dctx; p.lse_in = lse; p.dqkv = dqkv; p.dsum = dsum;
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
-  const dim3 grid((T + kAT - 1) / kAT, B * H), block(64 * kAWaves);
-  hipLaunchKernelGGL(attn_bwd_dq_kernel, grid, block, 0, stream, p);
-  hipLaunchKernelGGL(attn_bwd_dkv_kernel, grid, block, 0, stream, p);
-  PK2_LAUNCH_CHECK();
-  return PK2_OK;
+  return pk2_attention_bwd_part(3, qkv, ctx, dctx, lse, T, B, H, head_dim, scale, src_mask, key_padding, dropout_p, seed, dqkv,
+                                dsum, stream_);
 }

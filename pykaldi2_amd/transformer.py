@@ -12,9 +12,10 @@ methods is used**.  ``forward(x[T,B,D], src_mask, src_key_padding_mask) -> [T,B,
     -> ReLU ] -> LayerNorm -> Linear(C->P);  positional encoding disabled (models/transformer.py:90).
 
 Arithmetic: f32 MFMA GEMMs (`pk2_gemm_f32`, batched per (utterance, head) for QK^T and PV), masked
-softmax, LayerNorm(+residual), ReLU, counter-based dropout -- all HIP kernels of libpk2hip.so.  With head size 64
-(the reference's 512 / 8) the attention core is the fused kernel of csrc/attention.hip (scores never reach HBM, backward
-by recomputation); other head sizes, or PK2_ATTN_FUSED=0, take the batched-GEMM form with the scores in HBM.
+softmax, LayerNorm(+residual), ReLU, counter-based dropout -- all HIP kernels of libpk2hip.so.  The attention core is
+the fused kernel of csrc/attention.hip (head size 64, the reference model's 512 / 8) or csrc/attention128.hip (head size
+128, the command lines' default 512 / 4): scores never reach HBM, backward by recomputation.  `attention_is_fused` says
+which head sizes take it (PK2_ATTN_FUSED); every other one takes the batched-GEMM form with the scores in HBM.
 """
 import copy
 import math
@@ -97,6 +98,24 @@ def _seed():
     return int(torch.empty((), dtype=torch.int64).random_().item()) & 0x7FFFFFFFFFFFFFFF
 
 
+FUSED_HEAD_SIZES = (64, 128)              # what pk2_attention_fwd / _bwd serve
+# What runs fused when PK2_ATTN_FUSED is unset or 1.  Head size 128 is served but joins the default set only on a
+# measurement: tools/attn_time.py on the LF-MMI bench minibatch, fused forward + backward no slower than the batched-GEMM
+# form plus its spread.  Measured: 297.5 us against 284.1 + 4.3 (307.7 against 301.4 + 1.7 with dropout
+# 0.1, profiles/attn128_time.txt), so head size 128 is opt-in, PK2_ATTN_FUSED=all: the form to choose for memory (no
+# B H T^2 tensors).
+DEFAULT_FUSED_HEAD_SIZES = (64,)
+
+
+def attention_is_fused(head_dim):
+    """Whether TransformerAM's attention runs as the fused kernels at this head size.  PK2_ATTN_FUSED=0: never; unset
+    or 1: the default set; all: every head size the kernels serve."""
+    mode = os.environ.get("PK2_ATTN_FUSED", "1")
+    if mode == "0":
+        return False
+    return head_dim in (FUSED_HEAD_SIZES if mode == "all" else DEFAULT_FUSED_HEAD_SIZES)
+
+
 def _attention_bwd_unfused(L, sp, new, s, qkv, dcx, dqkv, T, B, C, H, d, drop):
     """Batched-GEMM form: dP = dctx V^T ; dV = Pd^T dctx ; dS = softmax'(P, dP) ; dQ = a dS K ; dK = a dS^T Q."""
     dP = new(B * H, T, T)
@@ -127,7 +146,7 @@ class _TransformerFunction(torch.autograd.Function):
         dev = x.device
         new = lambda *s: torch.empty(*s, device=dev, dtype=torch.float32)  # noqa: E731
         drop = m.dropout if m.training else 0.0
-        fused = d == 64 and os.environ.get("PK2_ATTN_FUSED", "1") != "0"
+        fused = attention_is_fused(d)
         ctx.fused, ctx.masks = fused, (src_mask, key_pad)
         fuse_relu, fuse_conv = _fuse_relu(), _fuse_conv()
 
