@@ -15,6 +15,16 @@ sequence term.  The lattices, criteria and optimiser are train_se.py's.  -criter
 error (ops.MWEBatchFunction) against the word transcript, or with `phone_level: true` against the phones of the on-the-fly
 alignment; its settings come from an optional `mwe_config:` block of the YAML (pykaldi2_amd.se.mwe_settings: num_paths 16,
 lm_weight 1.0, am_weight = decoder_config.acoustic_scale, equal_weight / phone_level / distinct false).
+-criterion ts distils a teacher into the model over the teacher's lattices (ops.TeacherStudentBatch: the lattices are decoded
+from the teacher's log-likelihoods and rescored with the model's); -teacher_model PATH is the teacher's checkpoint, an optional
+`teacher_config:` block of the YAML overrides `model_config` keys for it (a teacher of another size), and `ts_config:
+{lm_weight, am_weight, old_acoustic_scale}` (pykaldi2_amd.se.ts_settings: 1.0, decoder_config.acoustic_scale, 0.0) sets the
+lattice scales.  The transcripts are not used.
+
+  python bin/train_se2.py -config configs/se.yaml -data configs/data.yaml -exp_dir exp/ts -criterion ts \
+      -seed_model exp/ce/model.ce.0.tar -teacher_model exp/big/model.se.0.tar -trans_model exp/tri -lang_dir data/lang \
+      -prior_path exp/tri/final.occs -den_dir exp/tri/graph -lr 1e-5 -batch_size 8
+
 -synthetic trains on seeded generators: the word-loop HCLG of train_se.py, the L.fst of its pronunciations (pykaldi2_amd.synth.lexicon_arcs), a monophone tree and
 random word transcripts short enough for their utterances.
 """
@@ -39,8 +49,9 @@ def parse_config(argv=None):
     parser.add_argument("-dataPath", default='', type=str, help="path of data files")
     parser.add_argument("-seed_model", default='', help="the seed nerual network model")
     parser.add_argument("-exp_dir", help="the directory to save the outputs")
+    parser.add_argument("-teacher_model", default='', help="(-criterion ts) the teacher's checkpoint")
     parser.add_argument("-transform", help="feature transformation matrix or mvn statistics")
-    parser.add_argument("-criterion", type=str, choices=["mmi", "mpfe", "smbr", "mwe"], default="mmi",
+    parser.add_argument("-criterion", type=str, choices=["mmi", "mpfe", "smbr", "mwe", "ts"], default="mmi",
                         help="set the sequence training crtierion")
     parser.add_argument("-trans_model", help="the HMM transistion model directory")
     parser.add_argument("-prior_path", help="the prior for decoder, usually named as final.occs in kaldi setup")
@@ -145,10 +156,14 @@ def main():
     fb = fbank.FbankExtractor()
 
     args.mwe = se.mwe_settings(config, dc["acoustic_scale"]) if args.criterion == "mwe" else None
+    args.ts, teacher = None, None
+    if args.criterion == "ts":
+        args.ts = se.ts_settings(config, dc["acoustic_scale"])
+        teacher = load_teacher(args, config, dev)
     model.train()
     for epoch in range(args.num_epochs):
         run_train_epoch(model, optimizer, log_prior.to(dev), source, fb, epoch, asr_decoder, trans_model, silence_ids, aligner,
-                        args, dev, transform)
+                        args, dev, transform, teacher)
         hvd.finish()
         if hvd.rank() == 0 and args.exp_dir:
             th.save({'model': model.state_dict(), 'optimizer': optimizer.state_dict(), 'epoch': epoch},
@@ -156,8 +171,37 @@ def main():
     hvd.shutdown()
 
 
+def load_teacher(args, config, dev):
+    """The frozen teacher of -criterion ts: model_config with the keys of `teacher_config:` on top, weights from
+    -teacher_model; under -synthetic without a checkpoint, a second model initialised under a fixed seed of its own."""
+    tc = dict(config["model_config"])
+    tc.update(config.get("teacher_config") or {})
+    if tc["label_size"] != config["model_config"]["label_size"] or tc["feat_dim"] != config["model_config"]["feat_dim"]:
+        sys.stderr.write('ERROR: teacher_config must keep feat_dim and label_size of model_config!\n')
+        sys.exit(0)
+    if args.teacher_model:
+        if not os.path.isfile(args.teacher_model):
+            sys.stderr.write('ERROR: The teacher model file %s does not exist!\n' % (args.teacher_model))
+            sys.exit(0)
+        teacher = lstm.LSTMAM(tc["feat_dim"], tc["label_size"], tc["hidden_size"], tc["num_layers"], tc["dropout"], True)
+        sd = th.load(args.teacher_model, map_location="cpu")["model"]
+        teacher.load_state_dict({(k[7:] if k.startswith("module.") else k): v for k, v in sd.items()})
+        print("=> loaded teacher checkpoint '{}' ".format(args.teacher_model))
+    elif args.synthetic:
+        with th.random.fork_rng(devices=[]):
+            th.manual_seed(20240917)
+            teacher = lstm.LSTMAM(tc["feat_dim"], tc["label_size"], tc["hidden_size"], tc["num_layers"], tc["dropout"], True)
+    else:
+        sys.stderr.write('ERROR: -criterion ts needs -teacher_model!\n')
+        sys.exit(0)
+    teacher = teacher.to(dev).eval()
+    for q in teacher.parameters():
+        q.requires_grad_(False)
+    return teacher
+
+
 def run_train_epoch(model, optimizer, log_prior, source, fb, epoch, asr_decoder, trans_model, silence_ids, aligner, args, dev,
-                    transform=None):
+                    transform=None, teacher=None):
     batch_time = utils.AverageMeter('Time', ':6.3f')
     losses = utils.AverageMeter('Loss', ':.4e')
     grad_norm = utils.AverageMeter('grad_norm', ':.4e')
@@ -171,7 +215,10 @@ def run_train_epoch(model, optimizer, log_prior, source, fb, epoch, asr_decoder,
             texts = [synth.word_transcript(text_rng, synth.num_fbank_frames(n), args.graph_words) for n in batch["lens"]]
         else:
             texts = [np.asarray(a).reshape(-1).astype(int).tolist() for a in batch["aux"]]
-        if args.criterion == "mwe":
+        if args.criterion == "ts":
+            loss, se_val, ce_loss, frames, failed = se.sequence_loss_ts(model, teacher, fb, batch, asr_decoder, log_prior, args.ts,
+                                                                        args.ce_ratio, ce_criterion, transform=transform)
+        elif args.criterion == "mwe":
             loss, se_val, ce_loss, frames, failed = se.sequence_loss_mwe(model, fb, batch, texts, aligner, asr_decoder, trans_model,
                                                                          log_prior, args.mwe, args.ce_ratio, ce_criterion,
                                                                          transform=transform)

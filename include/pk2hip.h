@@ -704,6 +704,34 @@ int pk2_lattice_mwe(const pk2_lattice_batch* b, void* workspace, void* scratch, 
                     int32_t label_cap, int32_t equal_weight, const int32_t* sup, int64_t sup_stride,
                     const int32_t* sup_len, const int32_t* tid2pdf, int32_t num_pdfs, float* grad,
                     int64_t grad_seq_stride, int64_t grad_frame_stride, double* loss, void* stream);
+/* Kaldi's RescoreLattice on the decoded lattices, in place: the acoustic cost of every kept emitting link t -> t+1 with
+ * transition-id tid becomes  float(float(old_acoustic_scale * cost) - loglikes[n][t][tid2pdf[tid]])  (old_acoustic_scale 0:
+ * exactly -loglike; 1: the new score is added to the old one, as RescoreLattice does; Kaldi's discriminative trainers scale
+ * the old scores by 0 first).  loglikes is addressed as in pk2_lattice_decode (any model's output for the same frames;
+ * num_pdfs must be the decode's).  Epsilon links, tokens, graph and final costs, segments and the pruning result are not
+ * touched: pk2_lattice_summary's best_cost and the exported token costs stay those of the decode.  Every later call on the
+ * batch (mmi, mpe, nbest, mwe, posteriors, export) sees the rescored lattice. */
+int pk2_lattice_rescore(const pk2_lattice_batch* b, void* workspace, const float* loglikes, int64_t seq_stride,
+                        int64_t frame_stride, int32_t num_pdfs, const int32_t* tid2pdf, int32_t num_tids,
+                        float old_acoustic_scale, void* stream);
+/* Kaldi's LatticeForwardBackward + Posterior.to_pdf_matrix with no reference alignment: post[n][t][pdf] += post_sign *
+ * (sum of the posteriors of the frame's links with that pdf) on the lattice scaled by lm_scale / acoustic_scale as in
+ * pk2_lattice_mmi; lat_like: device f64[num_seq] = total log-likelihood (NaN for a failed utterance; a lattice without a
+ * path of non-zero weight adds nothing to post). */
+int pk2_lattice_posteriors(const pk2_lattice_batch* b, void* workspace, const int32_t* tid2pdf, double lm_scale,
+                           double acoustic_scale, float post_sign, float* post, int64_t post_seq_stride,
+                           int64_t post_frame_stride, double* lat_like, void* stream);
+/* Lattice teacher-student step (the intent of reference ops/ops.py:77-117) in one launch chain: forward-backward on the
+ * lattice as decoded from the teacher (like_T, gamma_T), pk2_lattice_rescore with the student's loglikes_S, forward-backward
+ * again (like_S, gamma_S).  loss [N] f64 = sum_l gamma_T(l) (like_T(l) - like_S(l)) - like_T + like_S = KL(P_T || P_S) over the
+ * lattice's paths; grad (zero-filled by the caller) [n][t][pdf] = gamma_S - gamma_T summed per pdf = d loss / d loglikes_S
+ * divided by acoustic_scale.  loss, like_T, like_S: device f64[num_seq].  The batch is left rescored.  An utterance whose
+ * rescored lattice has no path of non-zero weight gives loss NaN and a zero gradient. */
+int pk2_lattice_ts(const pk2_lattice_batch* b, void* workspace, const float* loglikes_S, int64_t seq_stride,
+                   int64_t frame_stride, int32_t num_pdfs, const int32_t* tid2pdf, int32_t num_tids,
+                   float old_acoustic_scale, double lm_scale, double acoustic_scale, float* grad,
+                   int64_t grad_seq_stride, int64_t grad_frame_stride, double* loss, double* like_T, double* like_S,
+                   void* stream);
 /* Test / tooling hook: copies the pruned lattice of utterance n to host arrays (synchronises `stream`).
  * Call with null arrays to get the counts.  Tokens are renumbered frame by frame; link_ac is the acoustic
  * cost with the acoustic scale removed. */

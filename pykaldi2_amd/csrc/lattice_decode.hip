@@ -260,6 +260,7 @@ extern "C" int pk2_lattice_decode(pk2_lattice_batch* b, const float* loglikes, i
   hipLaunchKernelGGL(lat_prune_segments, dim3(kPruneTeam, b->N), dim3(kLatThreads), 0, stream, p);
   PK2_LAUNCH_CHECK();
   b->decoded = true;
+  b->num_pdfs = num_pdfs;
   return PK2_OK;
 }
 

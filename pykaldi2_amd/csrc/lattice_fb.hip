@@ -17,18 +17,12 @@
 #include <cmath>
 #include <cstdlib>
 
+#include "lattice_fb.h"
 #include "lattice_internal.h"
 #include "persist_guard.h"
 
 namespace pk2 {
 
-constexpr int kFbThreads = 1024;
-constexpr int kFbWaves = kFbThreads / 64;
-
-template <typename T>
-__device__ __forceinline__ T ldc(const T* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
 __device__ __forceinline__ double log_add(double a, double b) {
   const double m = fmax(a, b);
   if (m == -INFINITY) return m;
@@ -45,27 +39,6 @@ __device__ __forceinline__ void atomic_log_add(double* addr, double v) {
   } while (old != assumed);
 }
 
-struct FbParams {
-  LatPtrs L;
-  const int32_t* ref_tids; int64_t ref_stride;
-  const int32_t* tid2pdf; const int32_t* tid2phone; const uint8_t* phone_sil;
-  int32_t criterion, one_silence_class, drop_frames;
-  double lm_scale, ac_scale;
-  float* post; int64_t post_seq_stride, post_frame_stride;
-  double* out;   // [N] lat_like (MMI) or expected accuracy (MPE)
-};
-
-__device__ __forceinline__ double block_sum_d(double v, double* red) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double r = 0.0;
-#pragma unroll
-  for (int k = 0; k < kFbWaves; ++k) r += red[k];
-  return r;
-}
 __device__ __forceinline__ double block_max_d(double v, double* red) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
@@ -90,40 +63,6 @@ __device__ __forceinline__ double frame_acc(const FbParams& p, int tid_arc, int 
     ok = p.one_silence_class ? (pdf == ref_pdf || both_sil) : (pdf == ref_pdf && !phone_sil);
   }
   return ok ? 1.0 : 0.0;
-}
-
-// Per-utterance views shared by the kernels below.
-struct FbView {
-  int T, nt;
-  const int32_t* ftok; const int32_t* seg; const int32_t* kept; const int32_t* maxlev;
-  const int4* lrec; const float* lac; const int32_t* tl; const float* tf;
-  double* alpha; double* beta; double* af; double* ab;
-  const int32_t* ref; double* ref_post;
-  LatFrame* F;
-  double* lw; double* sca; double* scb;       // linear-domain recursion: link weights, per-frame log scales of alpha / beta
-};
-__device__ __forceinline__ FbView fb_view(const FbParams& p, int n, const LatUtt& U) {
-  FbView v;
-  v.T = U.T; v.nt = U.n_tok;
-  v.ftok = p.L.frame_tok + U.frame_base; v.seg = p.L.seg_off + U.frame_base;
-  v.kept = p.L.seg_kept + U.frame_base; v.maxlev = p.L.frame_maxlev + U.frame_base;
-  v.lrec = p.L.link_rec + U.link_base;      // {src token, dst token, transition-id, graph cost bits}
-  v.lac = p.L.link_ac + U.link_base;
-  v.tl = p.L.tok_level + U.tok_base; v.tf = p.L.tok_final + U.tok_base;
-  v.alpha = p.L.alpha + U.tok_base; v.beta = p.L.beta + U.tok_base;
-  v.af = p.L.acc_f + U.tok_base; v.ab = p.L.acc_b + U.tok_base;
-  v.ref = p.ref_tids + (int64_t)n * p.ref_stride;
-  v.ref_post = p.L.ref_post + U.frame_base;
-  v.F = p.L.frame + n;
-  v.lw = p.L.link_w + U.link_base; v.sca = p.L.fb_scale + U.frame_base; v.scb = p.L.fb_scale + p.L.frame_total + U.frame_base;
-  return v;
-}
-// fst::ScaleLattice stores the scaled weights as floats; the forward-backward then sums them in double
-__device__ __forceinline__ double link_like(const FbParams& p, const FbView& v, const int4& r, int l) {
-  return -((double)(float)(p.lm_scale * (double)__int_as_float(r.w)) + (double)(float)(p.ac_scale * (double)v.lac[l]));
-}
-__device__ __forceinline__ double final_like(const FbParams& p, const FbView& v, int i) {
-  return -(double)(float)(p.lm_scale * (double)v.tf[i]);
 }
 
 // alpha (workgroup x = 0) and beta (x = 1) are independent recursions: they run side by side.  x = 0 also leaves the
@@ -431,9 +370,6 @@ __global__ void __launch_bounds__(256) lat_fb_prep(FbParams p, int with_acc) {
   }
   for (int64_t t = i0; t < v.T; t += step) v.ref_post[t] = 0.0;
 }
-
-// linear value x at log scale r -> its log (r is NaN when x is a log already; -inf marks a token nothing reaches)
-__device__ __forceinline__ double fb_log_of(double x, double r) { return (r == r && x != -INFINITY) ? r + log(x) : x; }
 
 // alpha / beta of the frames the recursions left linear -> logs (sMBR / MPFE: the accuracy recursions read them in chains)
 __global__ void __launch_bounds__(256) lat_fb_logs(FbParams p) {
@@ -805,7 +741,9 @@ __global__ void __launch_bounds__(kFbThreads) lat_fb_accuracy(FbParams p) {
 }
 
 // Posteriors, frame by frame in parallel (frames dealt round-robin to the workgroups of an utterance).
-// MODE 0: MMI (numerator - denominator with MergePosteriors' drop_frames test), MODE 1: sMBR / MPFE.
+// MODE 0: MMI (numerator - denominator with MergePosteriors' drop_frames test), MODE 1: sMBR / MPFE, MODE 2: the plain
+// link posteriors of Kaldi's LatticeForwardBackward, post += post_sign * gamma (no reference alignment; a lattice without a
+// path of non-zero weight adds nothing).
 template <int MODE>
 __global__ void __launch_bounds__(kFbThreads) lat_fb_posteriors(FbParams p, int lin) {
   const double kNaN = __longlong_as_double(0x7ff8000000000000LL);
@@ -815,12 +753,20 @@ __global__ void __launch_bounds__(kFbThreads) lat_fb_posteriors(FbParams p, int 
   const FbView v = fb_view(p, n, U);
   const double tot = v.F->fb_tot, tot_score = v.F->fb_score;
   float* post = p.post + (int64_t)n * p.post_seq_stride;
-  if (blockIdx.x == 0 && tid == 0) p.out[n] = MODE == 0 ? tot : tot_score;
+  if (blockIdx.x == 0 && tid == 0) p.out[n] = MODE == 1 ? tot_score : tot;
+  if (MODE == 2 && !(fabs(tot) < INFINITY)) return;
   for (int t = blockIdx.x; t < v.T; t += gridDim.x) {
     const int m0 = v.seg[2 * t + 1], m1 = m0 + v.kept[2 * t + 1];
-    const int r = v.ref[t];
+    const int r = MODE == 2 ? 0 : v.ref[t];
     float* row = post + (int64_t)t * p.post_frame_stride;
-    if (MODE == 0) {
+    if (MODE == 2) {
+      const double ra = lin ? v.sca[t] : kNaN, rb = lin ? v.scb[t + 1] : kNaN;
+      for (int l = m0 + tid; l < m1; l += kFbThreads) {
+        const int4 q = v.lrec[l];
+        const double g = exp(fb_log_of(v.alpha[q.x], ra) + link_like(p, v, q, l) + fb_log_of(v.beta[q.y], rb) - tot);
+        atomicAdd(&row[p.tid2pdf[q.z]], p.post_sign * (float)g);
+      }
+    } else if (MODE == 0) {
       // (the linear-domain recursions leave alpha of frame t / beta of frame t + 1 linear with their log scales: fb_log_of;
       // a scale of NaN = logs, which is also what the log-add kernel's fb_scale reads after lat_fb_logs or PK2_FB_LINEAR=0)
       const double ra = lin ? v.sca[t] : kNaN, rb = lin ? v.scb[t + 1] : kNaN;
@@ -856,10 +802,10 @@ __global__ void __launch_bounds__(kFbThreads) lat_fb_posteriors(FbParams p, int 
 
 using namespace pk2;
 
-static int fb_launch(int mode, const pk2_lattice_batch* b, void* workspace, FbParams& p, hipStream_t stream) {
-  PK2_REQUIRE(b->decoded, "lattice forward-backward: pk2_lattice_decode has not run on this batch");
-  lattice_carve(b, workspace, &p.L);
-  const dim3 two(2, b->N), many(64, b->N), thr(kFbThreads);
+namespace pk2 {
+
+int fb_recursions(const pk2_lattice_batch* b, const FbParams& p, int with_acc, hipStream_t stream, bool* linear_out) {
+  const dim3 two(2, b->N), thr(kFbThreads);
   constexpr int kFbCap = 19456;                    // doubles of LDS (152 KB): two frames of kFbCap / 2 tokens each
   PK2_DYN_LDS_ONCE(lat_fb_alpha_beta, kFbCap * (int)sizeof(double));
   PK2_DYN_LDS_ONCE(lat_fb_alpha_beta_lin, kFbCap * (int)sizeof(double));
@@ -868,14 +814,36 @@ static int fb_launch(int mode, const pk2_lattice_batch* b, void* workspace, FbPa
   static const bool linear = [] { const char* e = getenv("PK2_FB_LINEAR"); return !(e && atoi(e) == 0); }();
   const dim3 wide(256, b->N);
   if (linear) {
-    hipLaunchKernelGGL(lat_fb_prep, wide, dim3(256), 0, stream, p, mode == 0 ? 0 : 1);
+    hipLaunchKernelGGL(lat_fb_prep, wide, dim3(256), 0, stream, p, with_acc);
     hipLaunchKernelGGL(lat_fb_alpha_beta_lin, two, dim3(kLinThreads), kFbCap * sizeof(double), stream, p, cap);
-    if (mode != 0) hipLaunchKernelGGL(lat_fb_logs, wide, dim3(256), 0, stream, p);     // (MMI's posterior pass takes the logs of what it reads)
+    if (with_acc) hipLaunchKernelGGL(lat_fb_logs, wide, dim3(256), 0, stream, p);     // (the other posterior passes take the logs of what they read)
   } else {
     hipLaunchKernelGGL(lat_fb_alpha_beta, two, thr, kFbCap * sizeof(double), stream, p, cap);
   }
+  PK2_LAUNCH_CHECK();
+  *linear_out = linear;
+  return PK2_OK;
+}
+
+int fb_plain_posteriors(const pk2_lattice_batch* b, const FbParams& p, bool linear, hipStream_t stream) {
+  hipLaunchKernelGGL(lat_fb_posteriors<2>, dim3(64, b->N), dim3(kFbThreads), 0, stream, p, linear ? 1 : 0);
+  PK2_LAUNCH_CHECK();
+  return PK2_OK;
+}
+
+}  // namespace pk2
+
+static int fb_launch(int mode, const pk2_lattice_batch* b, void* workspace, FbParams& p, hipStream_t stream) {
+  PK2_REQUIRE(b->decoded, "lattice forward-backward: pk2_lattice_decode has not run on this batch");
+  lattice_carve(b, workspace, &p.L);
+  const dim3 two(2, b->N), many(64, b->N), thr(kFbThreads);
+  bool linear = false;
+  const int rc = fb_recursions(b, p, mode == 1 ? 1 : 0, stream, &linear);
+  if (rc) return rc;
   if (mode == 0) {
     hipLaunchKernelGGL(lat_fb_posteriors<0>, many, thr, 0, stream, p, linear ? 1 : 0);
+  } else if (mode == 2) {
+    return fb_plain_posteriors(b, p, linear, stream);
   } else {
     hipLaunchKernelGGL(lat_fb_accuracy, two, thr, 0, stream, p);
     hipLaunchKernelGGL(lat_fb_posteriors<1>, many, thr, 0, stream, p, 0);
@@ -910,4 +878,14 @@ extern "C" int pk2_lattice_mpe(const pk2_lattice_batch* b, void* workspace, cons
   p.lm_scale = lm_scale; p.ac_scale = acoustic_scale;
   p.post = post; p.post_seq_stride = post_seq_stride; p.post_frame_stride = post_frame_stride; p.out = score;
   return fb_launch(1, b, workspace, p, static_cast<hipStream_t>(stream_));
+}
+
+extern "C" int pk2_lattice_posteriors(const pk2_lattice_batch* b, void* workspace, const int32_t* tid2pdf, double lm_scale,
+                                      double acoustic_scale, float post_sign, float* post, int64_t post_seq_stride,
+                                      int64_t post_frame_stride, double* lat_like, void* stream_) {
+  PK2_REQUIRE(b && workspace && tid2pdf && post && lat_like, "lattice posteriors: null pointer");
+  FbParams p{};
+  p.tid2pdf = tid2pdf; p.lm_scale = lm_scale; p.ac_scale = acoustic_scale; p.post_sign = post_sign;
+  p.post = post; p.post_seq_stride = post_seq_stride; p.post_frame_stride = post_frame_stride; p.out = lat_like;
+  return fb_launch(2, b, workspace, p, static_cast<hipStream_t>(stream_));
 }

@@ -1,6 +1,7 @@
 // Internal declarations of the lattice path (MMIFunction / sMBRFunction):
 // lattice_graph.hip (decoding graph, batch layout, export), lattice_decode.hip (token passing + lattice
-// pruning), lattice_fb.hip (lattice forward-backward: MMI, sMBR, MPFE), lattice_nbest.hip (N-best paths, MWE).
+// pruning), lattice_fb.hip (lattice forward-backward: MMI, sMBR, MPFE, plain posteriors), lattice_nbest.hip (N-best paths,
+// MWE), lattice_rescore.hip (rescoring, teacher-student).
 //
 // MI355X design: the reference decodes every utterance on the CPU with Kaldi's LatticeFasterDecoder, copies
 // the lattice posteriors to the GPU and loops over utterances in Python (reference ops/ops.py:55-66,
@@ -133,6 +134,7 @@ struct pk2_lattice_batch {
   int64_t tok_total = 0, link_total = 0, frame_total = 0;
   size_t bytes = 0;
   bool decoded = false;
+  int32_t num_pdfs = 0;      // width of the log-likelihood rows the batch was decoded from (rescoring checks its own against it)
 };
 
 namespace pk2 {

@@ -6,6 +6,9 @@ ops/ops.py:41-75,119-156; bin/train_se.py:145-184):
   kaldi.asr.MappedLatticeFasterRecognizer           -> MappedLatticeFasterRecognizer (.decode / .decode_batch)
   kaldi.lat.functions.lattice_forward_backward_mmi  -> LatticeBatch.mmi
   ... lattice_forward_backward_mpe_variants         -> LatticeBatch.mpe
+  kaldi.lat.functions.rescore_lattice               -> LatticeBatch.rescore
+  kaldi.lat.functions.lattice_forward_backward      -> LatticeBatch.posteriors
+  (both, for ops.TeacherStudentMMI)                 -> LatticeBatch.teacher_student
 
 Everything runs on the device through the C ABI (pk2_lattice_*): one workgroup per utterance decodes and
 prunes the lattice, the lattice forward-backward reads it in place.  Nothing falls back to the CPU.
@@ -309,6 +312,8 @@ class LatticeBatch:
         self.device, self.trans_model, self.num_pdfs = device, trans_model, num_pdfs
         self.status = self.num_tokens = self.num_links = self.best_cost = None
         self.time_major = False
+        self.rescored = False          # rescore() / teacher_student() have replaced the decode's acoustic costs
+        self.like_T = self.like_S = None
         self._acoustic_scale = 1.0
         self._lattice_beam = 10.0
 
@@ -330,10 +335,11 @@ class LatticeBatch:
             ref[n, :self.lengths[n]] = ids[:self.lengths[n]]
         return torch.from_numpy(ref).to(self.device)
 
-    def _zeros_post(self):
-        # same memory layout as the log-likelihoods (time-major when the model produced them time-major)
+    def _zeros_post(self, time_major=None):
+        # same memory layout as the log-likelihoods (time-major when the model produced them time-major); time_major: the
+        # layout of another tensor (the student's log-likelihoods) instead of the decode's
         N, Tmax = len(self.lengths), max(self.lengths)
-        if self.time_major:
+        if self.time_major if time_major is None else time_major:
             return torch.zeros(Tmax, N, self.num_pdfs, device=self.device).transpose(0, 1)
         return torch.zeros(N, Tmax, self.num_pdfs, device=self.device)
 
@@ -448,6 +454,64 @@ class LatticeBatch:
                                       _lib.ptr(t2p), int(self.num_pdfs), _lib.ptr(grad), grad.stride(0), grad.stride(1),
                                       _lib.ptr(loss), _lib.stream_ptr(self.device), trans_model=tm)
         self._mwe_keep = (scratch, sup_d, lens_d)     # (alive until the stream has used them)
+        return loss, grad
+
+    def _check_loglikes(self, loglikes):
+        N, Tmax = len(self.lengths), max(self.lengths)
+        if not (isinstance(loglikes, torch.Tensor) and loglikes.is_cuda and loglikes.dtype == torch.float32 and
+                loglikes.dim() == 3 and loglikes.stride(2) == 1):
+            raise ValueError("log-likelihoods must be a CUDA f32 tensor [N, Tmax, P] with a unit pdf stride")
+        if tuple(loglikes.shape) != (N, Tmax, self.num_pdfs):
+            raise ValueError("log-likelihoods have shape %s, the batch was decoded from %s" % (
+                tuple(loglikes.shape), (N, Tmax, self.num_pdfs)))
+        return loglikes.detach()
+
+    def rescore(self, loglikes, old_acoustic_scale=0.0):
+        """Kaldi's RescoreLattice, in place: the acoustic cost of every kept emitting link t -> t+1 with transition-id tid
+        becomes f32(f32(old_acoustic_scale * cost) - loglikes[n, t, tid2pdf[tid]]); old_acoustic_scale 0 (what Kaldi's
+        discriminative trainers do, the default): exactly -loglike, 1: the new score is added to the old one.  loglikes: CUDA
+        f32 [N, Tmax, P] of any model for the same frames (unit pdf stride; batch- or time-major).  mmi / mpe / nbest / mwe /
+        posteriors / export afterwards see the rescored lattice; `best_cost` and the exported `tok_cost` remain those of
+        the decode that made the lattice.  Sets self.rescored."""
+        ll = self._check_loglikes(loglikes)
+        t2p, _ = self.trans_model.device_tables(self.device)
+        _lib.check(_lib.lib().pk2_lattice_rescore(self._h, _lib.ptr(self.workspace), _lib.ptr(ll), ll.stride(0), ll.stride(1),
+                                                  int(self.num_pdfs), _lib.ptr(t2p), self.trans_model.num_transition_ids(),
+                                                  float(old_acoustic_scale), _lib.stream_ptr(self.device)))
+        self.rescored = True
+        return self
+
+    def posteriors(self, lm_scale=1.0, acoustic_scale=1.0):
+        """Kaldi's LatticeForwardBackward + Posterior.to_pdf_matrix, no reference alignment:
+        -> (lat_like f64 [N], post f32 [N, Tmax, P] = the link posteriors of every frame summed per pdf)."""
+        N = len(self.lengths)
+        post = self._zeros_post()
+        out = torch.empty(N, dtype=torch.float64, device=self.device)
+        t2p, _ = self.trans_model.device_tables(self.device)
+        _lib.check(_lib.lib().pk2_lattice_posteriors(self._h, _lib.ptr(self.workspace), _lib.ptr(t2p), float(lm_scale),
+                                                     float(acoustic_scale), 1.0, _lib.ptr(post), post.stride(0), post.stride(1),
+                                                     _lib.ptr(out), _lib.stream_ptr(self.device)))
+        return out, post
+
+    def teacher_student(self, loglikes_S, lm_scale=1.0, acoustic_scale=1.0, old_acoustic_scale=0.0):
+        """Sequence-level distillation over this (the teacher's) lattice: forward-backward with the lattice's scores, rescore()
+        with the student's log-likelihoods, forward-backward again, in one launch chain.
+        -> (loss f64 [N] = KL(P_T || P_S) over the lattice's paths, grad f32 [N, Tmax, P] = post_S - post_T, laid out like
+        loglikes_S) -- grad is d loss / d loglikes_S divided by acoustic_scale (the convention of mmi).  Leaves the total
+        log-likelihoods in self.like_T / self.like_S and the batch rescored.  An utterance whose rescored lattice has no path
+        of non-zero weight gives NaN and a zero gradient."""
+        ll = self._check_loglikes(loglikes_S)
+        N = len(self.lengths)
+        grad = self._zeros_post(time_major=N > 1 and ll.stride(0) < ll.stride(1))
+        f64 = lambda: torch.empty(N, dtype=torch.float64, device=self.device)
+        loss, self.like_T, self.like_S = f64(), f64(), f64()
+        t2p, _ = self.trans_model.device_tables(self.device)
+        _lib.check(_lib.lib().pk2_lattice_ts(self._h, _lib.ptr(self.workspace), _lib.ptr(ll), ll.stride(0), ll.stride(1),
+                                             int(self.num_pdfs), _lib.ptr(t2p), self.trans_model.num_transition_ids(),
+                                             float(old_acoustic_scale), float(lm_scale), float(acoustic_scale), _lib.ptr(grad),
+                                             grad.stride(0), grad.stride(1), _lib.ptr(loss), _lib.ptr(self.like_T),
+                                             _lib.ptr(self.like_S), _lib.stream_ptr(self.device)))
+        self.rescored = True
         return loss, grad
 
     def export(self, n):

@@ -14,7 +14,8 @@ modified in place.
 MMIFunction / sMBRFunction (lattice-based, ops/ops.py:41-75,119-156) decode on the device
 (lattice.MappedLatticeFasterRecognizer) and run the lattice forward-backward there; LatticeBatchFunction
 is the whole-minibatch form.  MWEFunction (N-best minimum word error, ops/ops.py:158-241) and its minibatch form
-MWEBatchFunction take the N best paths of the same device lattices.
+MWEBatchFunction take the N best paths of the same device lattices.  TeacherStudentMMI (lattice teacher-student training,
+ops/ops.py:77-117) and its minibatch form TeacherStudentBatch rescore the teacher's device lattices with the student.
 """
 import numpy as np
 import os
@@ -239,3 +240,55 @@ class MWEBatchFunction(Function):
     def backward(ctx, grad_out):
         grad, = ctx.saved_tensors
         return grad, None, None, None, None, None
+
+
+class TeacherStudentMMI(Function):
+    """Sequence-level distillation of a teacher into a student over the teacher's lattice, with the reference's signature
+    (ops/ops.py:77-117): ``TeacherStudentMMI.apply(loglikes_T[T, P], loglikes_S[T, P], asr_decoder)``.  The lattice is decoded
+    from the teacher's log-likelihoods, its posteriors are taken, it is rescored with the student's (old acoustic scores
+    dropped) and its posteriors are taken again, on the unscaled lattice as in the reference (TeacherStudentBatch takes the
+    scales).  Forward returns
+    KL(P_T || P_S) over the lattice's paths as a 0-dim float32 tensor (the reference returned a Python float, and computed it
+    as a cross-entropy of two Python lists); backward returns post_S - post_T for the student regardless of grad_out and
+    None for the teacher (the reference returned post_T - post_S to an optimiser that minimises)."""
+
+    @staticmethod
+    def forward(ctx, loglikes_T, loglikes_S, asr_decoder):
+        if loglikes_T.shape != loglikes_S.shape:
+            raise ValueError("teacher and student log-likelihoods differ in shape: %s, %s" % (
+                tuple(loglikes_T.shape), tuple(loglikes_S.shape)))
+        lat = asr_decoder.decode(loglikes_T.detach().contiguous())
+        loss, grad = lat.teacher_student(loglikes_S.detach().unsqueeze(0), 1.0, 1.0, 0.0)
+        ctx.save_for_backward(grad[0])
+        return loss[0].to(torch.float32)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        grad, = ctx.saved_tensors
+        return None, grad, None
+
+
+class TeacherStudentBatch(Function):
+    """TeacherStudentMMI for all utterances of a minibatch in one decode and one launch chain:
+    ``TeacherStudentBatch.apply(prediction_T[N, Tmax, P], prediction_S[N, Tmax, P], lengths, asr_decoder, lm_scale=1.0,
+    acoustic_scale=1.0, old_acoustic_scale=0.0)``.  The two predictions agree in shape; their strides may differ (unit pdf
+    stride).  Returns the summed loss (float32); ctx.per_sequence holds the float64 loss of every utterance, ctx.lattice the
+    (rescored) lattices.  The gradient is that of the loss divided by acoustic_scale, as MMIFunction's."""
+
+    @staticmethod
+    def forward(ctx, prediction_T, prediction_S, lengths, asr_decoder, lm_scale=1.0, acoustic_scale=1.0,
+                old_acoustic_scale=0.0):
+        if prediction_T.shape != prediction_S.shape:
+            raise ValueError("teacher and student predictions differ in shape: %s, %s" % (
+                tuple(prediction_T.shape), tuple(prediction_S.shape)))
+        lat = asr_decoder.decode_batch(prediction_T.detach(), lengths)
+        loss, grad = lat.teacher_student(prediction_S.detach(), lm_scale, acoustic_scale, old_acoustic_scale)
+        ctx.save_for_backward(grad)
+        ctx.per_sequence = loss
+        ctx.lattice = lat
+        return loss.sum().to(torch.float32)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        grad, = ctx.saved_tensors
+        return None, grad, None, None, None, None, None

@@ -144,3 +144,44 @@ def sequence_loss_mwe(model, fb, batch, texts, aligner, asr_decoder, trans_model
     else:
         se = torch.zeros((), dtype=torch.float32, device=prediction.device)
     return ce_ratio * ce_loss + se, se, ce_loss, frames, failed
+
+
+TS_KEYS = ("lm_weight", "am_weight", "old_acoustic_scale")
+
+
+def ts_settings(config, acoustic_scale):
+    """The `ts_config:` block of the YAML over its defaults (lm_weight 1.0, am_weight = the decoder's acoustic scale,
+    old_acoustic_scale 0.0); a key it does not know raises KeyError."""
+    cfg = dict(lm_weight=1.0, am_weight=float(acoustic_scale), old_acoustic_scale=0.0)
+    for k, v in (config.get("ts_config") or {}).items():
+        if k not in TS_KEYS:
+            raise KeyError("ts_config: unknown key %r (known: %s)" % (k, ", ".join(TS_KEYS)))
+        cfg[k] = float(v)
+    return cfg
+
+
+def sequence_loss_ts(model, teacher, fb, batch, asr_decoder, log_prior, ts_cfg, ce_ratio, ce_criterion, forward=None,
+                     transform=None):
+    """The train_se2 step with the lattice teacher-student criterion (ops.TeacherStudentBatch): the frozen `teacher` runs
+    under torch.no_grad() in eval mode on the same features, the lattices are decoded from its log-likelihoods and rescored
+    with the student's; the log prior is subtracted from both, as the reference's docstring asks (ops/ops.py:81).
+    loss = ce_ratio * ce_loss + sum of the per-utterance divergences.  Returns (loss, ts_value, ce_loss, frames, [])."""
+    feats, frames, row_off = fb(batch["wav"], batch["lens"])
+    if transform is not None:
+        feats = transform(feats)
+    x = fb.pad_roll_subsample(feats, row_off, frames, shift=0, subsample=1, time_major=True)
+    run = (lambda m: forward(m, x, frames)) if forward is not None else (lambda m: m.forward_time_major(x).transpose(0, 1))
+    was_training = teacher.training
+    teacher.eval()
+    with torch.no_grad():
+        prediction_T = run(teacher)
+    teacher.train(was_training)
+    prediction = run(model)
+    N, Tmax = prediction.shape[0], prediction.shape[1]
+    y = np.full((N, Tmax), -100, np.int64)
+    for n, lab in enumerate(batch["y"]):
+        y[n, :frames[n]] = np.asarray(lab)[:frames[n]]
+    ce_loss = ce_criterion(prediction, torch.from_numpy(y).to(prediction.device))
+    ts = ops.TeacherStudentBatch.apply(prediction_T - log_prior, prediction - log_prior, [int(t) for t in frames], asr_decoder,
+                                       ts_cfg["lm_weight"], ts_cfg["am_weight"], ts_cfg["old_acoustic_scale"])
+    return ce_ratio * ce_loss + ts, ts, ce_loss, frames, []
