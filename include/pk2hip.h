@@ -290,6 +290,74 @@ int pk2_sim_add_noise(float* mixed, int64_t n, const float* noise, int64_t m, in
 int pk2_sim_gain_norm(float* x, int64_t n, const double* stats, void* stream);
 
 /* ------------------------------------------------------------------ *
+ * Multi-channel, multi-source simulation (reference simulation/simulation.py `_Simulator.simulate`, _mixer.py
+ * `Mixer`, _distorter.py with C > 1).  Device layout: channel-major, a signal is a contiguous f32 (C, T) array and
+ * a RIR is (C, k) (the reference uses (T, C)).  The job / segment / source tables are HOST arrays of at most
+ * PK2_SIM_MAX_SEGS entries, passed to the kernel by value; every pointer inside them is device memory.
+ * ------------------------------------------------------------------ */
+#define PK2_SIM_MAX_SEGS 16
+typedef struct {
+  const float* wav;          /* (n) dry source */
+  const float* rir;          /* (C, k) */
+  float* out;                /* (C, n) reverberant source, pk2_sim_apply_rir per row */
+  float* early;              /* (C, n) early reverberation, or NULL */
+  const int32_t* delay_dev;  /* device int32 (clamped to [0, k)), or NULL: `delay` below */
+  int64_t n;
+  int32_t k;
+  int32_t delay;             /* argmax of the source's channel-0 RIR: every row of the source uses it */
+} pk2_sim_rir_job;
+/* One launch for all (source, channel) rows.  early = the same convolution over the taps [0, min(k, early_taps + delay))
+ * (early_taps = int(0.04 fs)), bit-equal to out computed with the RIR cut there. */
+int pk2_sim_apply_rir_mc(const pk2_sim_rir_job* jobs, int32_t njobs, int32_t channels, int32_t early_taps, void* stream);
+
+typedef struct {
+  float* x;
+  int64_t count;
+} pk2_sim_seg;
+/* stats (device f64 (nseg, 2), zeroed by the caller): pk2_sim_power of every segment in one launch. */
+int pk2_sim_power_seg(const pk2_sim_seg* segs, int32_t nseg, double* stats, void* stream);
+/* every segment *= 0.5 / stats[1]; gain (device f64[1], or NULL) receives that factor. */
+int pk2_sim_gain_norm_seg(const pk2_sim_seg* segs, int32_t nseg, const double* stats, double* gain, void* stream);
+
+typedef struct {
+  const float* sig;    /* (C, n) reverberant source */
+  const float* sig2;   /* (C, n) second signal (early reverberation) or NULL */
+  float* pos;          /* (C, T) out or NULL: sig placed at `start`, unscaled */
+  float* pos2;         /* (C, T) out or NULL: scale * sig2 placed at `start` */
+  int64_t n;
+  int64_t start;
+  double spr_db;       /* 0 for source 0 */
+} pk2_sim_mix_src;
+/* Mixer.mix_signals: scale[i] = sqrt(P_0 / P_i * 10^(spr_i / 10)), P_i = stats[i][0] / (C n_i) (pk2_sim_power_seg);
+ * mixed (C, T) = sum_i scale[i] * sig_i placed at start_i (sum in source order); scales: device f64[nsrc] out. */
+int pk2_sim_mix(const pk2_sim_mix_src* srcs, int32_t nsrc, int32_t channels, int64_t T, const double* stats, float* mixed,
+                double* scales, void* stream);
+/* pk2_sim_add_noise over C rows, powers = means over all channels.  repeat = 0: 'sample_noise' placement; repeat = 1:
+ * 'repeat_noise' (_NoiseSampler.repeat_noise): the noise tiled ceil(n / m) times when shorter, read at (start + i) mod m;
+ * start in [0, tiled length - n]. */
+int pk2_sim_add_noise_mc(float* mixed, int64_t n, const float* noise, int64_t m, int32_t channels, int64_t start,
+                         float snr_db, int32_t repeat, const double* sig_stats, const double* noise_stats, void* stream);
+
+/* ------------------------------------------------------------------ *
+ * Isotropic (diffuse) noise field for a microphone array (reference simulation/_iso_noise_simulator.py
+ * `generate_isotropic_noise`, Habets & Gannot 2007).
+ *   X[m][f] = (1 / sqrt(P)) sum_i g[f] Z_i[f] exp(-j tau[m][i] w_f),  w_f = 2 pi f / fft_size, fft_size = 2 (bins - 1),
+ * then DC and Nyquist -> sqrt(fft_size) Re, the other bins * sqrt(fft_size / 2).  tau: device f64 (C, P) in samples;
+ * g: device f64 (bins) or NULL (white); draws: device f32 (P, bins, 2) standard normals, or NULL: the counter-based
+ * generator of pk2_iso_gauss(seed).  X: device f32 (C, bins, 2).  The sum over i runs in order in one thread:
+ * bit-reproducible.
+ * ------------------------------------------------------------------ */
+int pk2_iso_spectra(const double* tau, const double* g, const float* draws, uint64_t seed, int32_t channels, int32_t points,
+                    int32_t bins, float* X, void* stream);
+/* out (P, bins, 2): the generator's draws, a pure function of (seed, i, f): splitmix64 finaliser of
+ * seed * 0xD1342543DE82EF95 + i * bins + f, u1 / u2 = (k + 0.5) 2^-24 from bits 63..40 / 39..16, Box-Muller. */
+int pk2_iso_gauss(uint64_t seed, int32_t points, int32_t bins, float* out, void* stream);
+
+/* Inverse real FFT, numpy.fft.irfft normalisation: X (rows, n / 2 + 1) interleaved complex -> out (rows, n) real,
+ * n = 2^5 .. 2^20.  The imaginary parts of DC and Nyquist are ignored.  out must not alias X. */
+int pk2_irfft_pow2_f32(const float* X, int32_t rows, int32_t n, float* out, void* stream);
+
+/* ------------------------------------------------------------------ *
  * Room impulse responses by the image method (reference simulation/_rirgen.py `xp_rirgen`, method 1), a batch of
  * items per call; the host checks the arguments and forms the descriptors (pykaldi2_amd/rirgen.py).  All arrays are
  * device memory.  Lengths are in samples (metres / (c / fs)).

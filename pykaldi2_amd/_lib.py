@@ -32,6 +32,25 @@ class DecoderOpts(C.Structure):
                 ("tokens_per_frame", C.c_int32), ("links_per_frame", C.c_int32)]
 
 
+class SimRirJob(C.Structure):
+    """pk2_sim_rir_job"""
+    _fields_ = [("wav", C.c_void_p), ("rir", C.c_void_p), ("out", C.c_void_p), ("early", C.c_void_p),
+                ("delay_dev", C.c_void_p), ("n", C.c_int64), ("k", C.c_int32), ("delay", C.c_int32)]
+
+
+class SimSeg(C.Structure):
+    """pk2_sim_seg"""
+    _fields_ = [("x", C.c_void_p), ("count", C.c_int64)]
+
+
+class SimMixSrc(C.Structure):
+    """pk2_sim_mix_src"""
+    _fields_ = [("sig", C.c_void_p), ("sig2", C.c_void_p), ("pos", C.c_void_p), ("pos2", C.c_void_p),
+                ("n", C.c_int64), ("start", C.c_int64), ("spr_db", C.c_double)]
+
+
+SIM_MAX_SEGS = 16        # PK2_SIM_MAX_SEGS
+
 _vp, _i32, _i64, _f32, _sz = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_size_t
 
 # name -> (restype, argtypes); mirrors include/pk2hip.h one to one
@@ -125,6 +144,14 @@ SIGNATURES = {
     "pk2_rirgen": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _vp, _i32, _i64, _vp, _vp, _vp, _vp]),
     "pk2_sim_add_noise": (C.c_int, [_vp, _i64, _vp, _i64, _i64, _f32, _vp, _vp, _vp]),
     "pk2_sim_gain_norm": (C.c_int, [_vp, _i64, _vp, _vp]),
+    "pk2_sim_apply_rir_mc": (C.c_int, [C.POINTER(SimRirJob), _i32, _i32, _i32, _vp]),
+    "pk2_sim_power_seg": (C.c_int, [C.POINTER(SimSeg), _i32, _vp, _vp]),
+    "pk2_sim_gain_norm_seg": (C.c_int, [C.POINTER(SimSeg), _i32, _vp, _vp, _vp]),
+    "pk2_sim_mix": (C.c_int, [C.POINTER(SimMixSrc), _i32, _i32, _i64, _vp, _vp, _vp, _vp]),
+    "pk2_sim_add_noise_mc": (C.c_int, [_vp, _i64, _vp, _i64, _i32, _i64, _f32, _i32, _vp, _vp, _vp]),
+    "pk2_iso_spectra": (C.c_int, [_vp, _vp, _vp, C.c_uint64, _i32, _i32, _i32, _vp, _vp]),
+    "pk2_iso_gauss": (C.c_int, [C.c_uint64, _i32, _i32, _vp, _vp]),
+    "pk2_irfft_pow2_f32": (C.c_int, [_vp, _i32, _i32, _vp, _vp]),
     "pk2_fbank_create": (C.c_int, [_vp, C.POINTER(_vp)]),
     "pk2_fbank_destroy": (C.c_int, [_vp]),
     "pk2_fbank_num_frames": (_i32, [_i64]),

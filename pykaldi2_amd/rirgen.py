@@ -205,6 +205,17 @@ def sample_array_center(room):
     return ctr.reshape(3, 1) * room.reshape(3, 1)
 
 
+def sample_array(room, mic_positions):
+    """sample_array_position(ArrayPositionConfig(mic_positions)) of the reference (simulation/_sampling.py:206-237,
+    use_gaussian False): the array centre as sample_array_center draws it, and the microphones at centre + mic_positions
+    (3, C) (the offsets of the array geometry from its centre).  Returns (array_ctr (3, 1), mic_position (3, C))."""
+    mic_positions = np.asarray(mic_positions, dtype=np.float64)
+    if mic_positions.ndim != 2 or mic_positions.shape[0] != 3:
+        raise ValueError("mic_positions must be a (3, C) matrix")
+    ctr = sample_array_center(np.asarray(room, dtype=np.float64))
+    return ctr, ctr + mic_positions
+
+
 def sample_sources(n_spk, room, array_center):
     """sample_source_position_by_random_coordinate(SoundSourceConfig().config, n_spk, room, array_center): x, y at least
     0.5 m from the walls, height ~ U[1, 2] m, at least 0.3 m from the array centre in the horizontal plane and 0.5 m from
@@ -229,15 +240,19 @@ def sample_sources(n_spk, room, array_center):
     return source_position
 
 
-def sample_online_room(t60_range=(0.1, 0.5), n_src=2):
+def sample_online_room(t60_range=(0.1, 0.5), n_src=2, mic_positions=None):
     """One room for an on-the-fly RIR, drawn in this order: the room; the T60 ~ U[t60_range], raised to
     min_t60_of_room(room) when below it (the reference would raise 't60 value too small' there instead); one mic at the
     array centre; `n_src` sources (speech first, then the directional noise).  Returns (room (3,), t60, mic (3, 1),
-    sources (3, n_src))."""
+    sources (3, n_src)).  With `mic_positions` (3, C), the offsets of an array from its centre, the microphones are
+    sample_array's (3, C) instead; the draws are the same."""
     room = sample_room()
     lo, hi = float(t60_range[0]), float(t60_range[1])
     t60 = float(np.random.uniform(low=lo, high=hi, size=1)[0])
     t60 = max(t60, float(min_t60_of_room(room)))
-    mic = sample_array_center(room)
-    src = sample_sources(n_src, room, mic[:, 0])
+    if mic_positions is None:
+        ctr = mic = sample_array_center(room)
+    else:
+        ctr, mic = sample_array(room, mic_positions)
+    src = sample_sources(n_src, room, ctr[:, 0])
     return room, t60, mic, src
