@@ -560,7 +560,22 @@ int pk2_lstm_layer_bwd_bias(const float* dy, const float* whh, const float* gate
                             int32_t B, int32_t T, int32_t H, int32_t num_dirs, float* dgx, float* scratch,
                             float* dbias_ih, float* dbias_hh, int32_t* bias_done, void* stream);
 /* The W_hh gradient dwhh[d] = sum_t dgates[d][t]^T h[d][t-1] (t+1 for the reverse direction)
- * is one pk2_gemm_f32 by the caller over row-shifted slices of dgx and y. */
+ * is one pk2_gemm_f32 by the caller over row-shifted slices of dgx and y -- unless the recurrence has produced it on the
+ * way: pk2_lstm_layer_bwd_wgrad is pk2_lstm_layer_bwd_bias plus y (device f32 [T][B][D*H], the forward pass's output,
+ * before any dropout), dwhh (device f32 [D][4H][H], ACCUMULATED into, +=) and wgrad_ws (device f32, at least
+ * pk2_lstm_bwd_wgrad_workspace_floats(B,H,D); may be NULL when that is 0).  *whh_done = 1 when dwhh has received the sum
+ * (lstm_bwd_seq2_wgrad: each (sequence, direction) pair keeps its slice in MFMA accumulators, the sequences' slices are
+ * added in ascending order, so repeated calls give the same bits; T = 1: nothing to add), 0 when the path taken left dwhh
+ * and wgrad_ws untouched (every path but SEQ, a device on which the kernel's workgroups do not all fit, y not 16-byte
+ * aligned, PK2_LSTM_SEQ_WGRAD=0 -- read per call).  A launch that gave up leaves NaNs in dwhh as in dgx -- and so does
+ * every later *whh_done = 1 call on that stream, although its dgx is valid: the verdict read is the stream's sticky word
+ * (what pk2_lstm_persist_status reports), which nothing clears, pk2_persist_guard_clear included.  A process that lowers
+ * the guard and carries on sets PK2_LSTM_SEQ_WGRAD=0. */
+size_t pk2_lstm_bwd_wgrad_workspace_floats(int32_t B, int32_t H, int32_t num_dirs);
+int pk2_lstm_layer_bwd_wgrad(const float* dy, const float* whh, const float* gates, const float* cells, const float* y,
+                             int32_t B, int32_t T, int32_t H, int32_t num_dirs, float* dgx, float* scratch,
+                             float* dbias_ih, float* dbias_hh, float* dwhh, float* wgrad_ws, int32_t* bias_done,
+                             int32_t* whh_done, void* stream);
 
 /* ------------------------------------------------------------------ *
  * Row-wise pieces of TransformerAM (reference models/transformer.py:52-94: nn.TransformerEncoderLayer

@@ -571,7 +571,7 @@ extern "C" size_t pk2_lstm_bwd_scratch_floats(int32_t B, int32_t H, int32_t D) {
 
 static int lstm_layer_bwd_impl(const float* dy, const float* whh, const float* gates, const float* cells, int32_t B, int32_t T,
                                int32_t H, int32_t D, float* dgx, float* scratch, float* dbias_ih, float* dbias_hh,
-                               int32_t* bias_done, void* stream_);
+                               int32_t* bias_done, void* stream_, SeqWgradCall* wgrad = nullptr);
 
 extern "C" int pk2_lstm_layer_bwd(const float* dy, const float* whh, const float* gates, const float* cells,
                                   int32_t B, int32_t T, int32_t H, int32_t D, float* dgx, float* scratch,
@@ -590,9 +590,29 @@ extern "C" int pk2_lstm_layer_bwd_bias(const float* dy, const float* whh, const 
   return lstm_layer_bwd_impl(dy, whh, gates, cells, B, T, H, D, dgx, scratch, dbias_ih, dbias_hh, bias_done, stream_);
 }
 
+// The same, with the recurrent weight gradient where the kernel can produce it on the way (the one-launch recurrence of a
+// (sequence, direction) pair per XCD keeps its slice of dW_hh in MFMA accumulators, lstm_bwd_seq2_wgrad): dwhh [D][4H][H]
+// is ACCUMULATED into (+=); *whh_done = 0 when the path taken left dwhh and wgrad_ws untouched -- the caller then
+// multiplies the row-shifted slices of dgx and y itself.  T = 1 has no partner frame: done, nothing added.
+extern "C" size_t pk2_lstm_bwd_wgrad_workspace_floats(int32_t B, int32_t H, int32_t D) {
+  return lstm_seq_wgrad_workspace_floats(B, H, D);
+}
+
+extern "C" int pk2_lstm_layer_bwd_wgrad(const float* dy, const float* whh, const float* gates, const float* cells, const float* y,
+                                        int32_t B, int32_t T, int32_t H, int32_t D, float* dgx, float* scratch,
+                                        float* dbias_ih, float* dbias_hh, float* dwhh, float* wgrad_ws, int32_t* bias_done,
+                                        int32_t* whh_done, void* stream_) {
+  PK2_REQUIRE(bias_done && whh_done, "lstm_bwd_wgrad: null bias_done / whh_done");
+  *whh_done = 0;
+  SeqWgradCall wg{y, dwhh, wgrad_ws, false};
+  int rc = lstm_layer_bwd_impl(dy, whh, gates, cells, B, T, H, D, dgx, scratch, dbias_ih, dbias_hh, bias_done, stream_, &wg);
+  if (!rc) *whh_done = wg.done ? 1 : 0;
+  return rc;
+}
+
 static int lstm_layer_bwd_impl(const float* dy, const float* whh, const float* gates, const float* cells, int32_t B, int32_t T,
                                int32_t H, int32_t D, float* dgx, float* scratch, float* dbias_ih, float* dbias_hh,
-                               int32_t* bias_done, void* stream_) {
+                               int32_t* bias_done, void* stream_, SeqWgradCall* wgrad) {
   PK2_REQUIRE(dy && whh && gates && cells && dgx && scratch && B > 0 && T > 0 && (D == 1 || D == 2),
               "lstm_bwd: bad args");
   PK2_REQUIRE(lstm_h_ok(H), "lstm_bwd: hidden size %d unsupported (64,128,256,512,1024)", H);
@@ -600,7 +620,7 @@ static int lstm_layer_bwd_impl(const float* dy, const float* whh, const float* g
   if (bias_done) *bias_done = 0;
   if (lstm_seq_wanted(B, H, D)) {           // one launch, a (sequence, direction) pair per XCD (lstm_persist_seq.hip)
     bool ran = false, bdone = false;
-    int prc = lstm_bwd_seq_launch(dy, whh, gates, cells, B, T, H, D, dgx, stream, &ran, dbias_ih, dbias_hh, &bdone);
+    int prc = lstm_bwd_seq_launch(dy, whh, gates, cells, B, T, H, D, dgx, stream, &ran, dbias_ih, dbias_hh, &bdone, wgrad);
     if (prc) return prc;
     if (ran) { if (bias_done) *bias_done = bdone ? 1 : 0; g_last_bwd_path = PK2_LSTM_PATH_SEQ; return PK2_OK; }
   }

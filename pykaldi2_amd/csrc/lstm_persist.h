@@ -12,9 +12,14 @@ int lstm_fwd_seq_launch(const float* gx, const float* whh, const float* bhh, int
                         float* gates, float* cells, hipStream_t stream, bool* ran);
 // dbias_ih / dbias_hh (may be null): [D][4H] accumulators (+=) of the bias gradient, filled by the kernel inside its
 // launch; *bias_done says whether it was.
+// wgrad (may be null): the recurrent weight gradient from inside the recurrence -- y [T][B][D*H] the forward pass's
+// output, dwhh [D][4H][H] accumulated into (+=), ws at least lstm_seq_wgrad_workspace_floats(B, H, D) floats; done says
+// whether dwhh has received it (false: dwhh and ws untouched).
+struct SeqWgradCall { const float* y; float* dwhh; float* ws; bool done; };
+size_t lstm_seq_wgrad_workspace_floats(int B, int H, int D);
 int lstm_bwd_seq_launch(const float* dy, const float* whh, const float* gates, const float* cells, int B, int T, int H,
                         int D, float* dgx, hipStream_t stream, bool* ran, float* dbias_ih = nullptr, float* dbias_hh = nullptr,
-                        bool* bias_done = nullptr);
+                        bool* bias_done = nullptr, SeqWgradCall* wgrad = nullptr);
 int lstm_seq_status(unsigned* abort_flag);
 
 // Large batches (B >= 32, H = 512; lstm_persist_big.hip): a (direction, 64-row batch tile) task per XCD team, the rank's

@@ -12,6 +12,7 @@
 // the backward pass), so the two implementations are interchangeable behind pk2_lstm_layer_fwd / _bwd.
 // Replaces the same cuDNN RNN (reference models/lstm.py:49-58).
 #include <algorithm>
+#include <cstdint>
 #include <cstdlib>
 #include <map>
 
@@ -183,6 +184,13 @@ struct SeqBwdParams {
   int B, T, D;
   float* dbias_ih;     // [D][4H] += sum over frames and sequences of d gx (null: not wanted), likewise dbias_hh
   float* dbias_hh;
+};
+
+// The recurrent weight gradient from inside the backward recurrence (lstm_bwd_seq2_wgrad).  Kept out of
+// SeqBwdParams so that the kernel arguments -- and with them the code -- of lstm_bwd_seq2 stay what they were.
+struct SeqWgradParams {
+  const float* y;      // [T][B][D*H], the forward pass's output (complete, read-only)
+  float* ws;           // [B*D][4H][H]: the slice of dW_hh[d] every (sequence, direction) pair has summed over its frames
 };
 
 // ---- The kernels (round 4: lstm_fwd_seq2 / lstm_bwd_seq2), the step's critical path cut down ---------------------------
@@ -424,10 +432,29 @@ __device__ __forceinline__ void lstm_fwd_seq2_body(const SeqFwdParams& p, SeqCtl
   }
 }
 
-__device__ __forceinline__ void lstm_bwd_seq2_body(const SeqBwdParams& p, SeqCtl* ctl) {
+// WGRAD (lstm_bwd_seq2_wgrad): on top of the recurrence the workgroup keeps its 64 x 512 slice of
+//   dW_hh[d] = sum_t dg_d[t]^T h_d[t -+ 1]        (the partner frame is the one the NEXT backward step visits)
+// of its pair as MFMA accumulators: a step adds the rank-1 update dgl[64] x y[t_next][b][d*H ..][512] with 16
+// v_mfma_f32_32x32x1_2b_f32 (the two 32-row blocks of the instruction = the two halves of dgl, A operand = dgl[lane] = the
+// dg_own every wave reads anyway; an instruction per 32 columns, B operand = y[32 c + lane % 32] in both lane halves), four
+// per wave: wave w owns columns 128 w .. 128 w + 127, 4 x 32 accumulator registers per lane.  Wave 1 brings the row of y
+// in with its other prefetches (two 16-byte loads per lane, a step in flight, two steps ahead in an LDS ring of three).
+// The MFMAs of a step are issued behind the step's mailbox stores (and wave 0's slot reset): nothing the chain waits on
+// lies behind them.  At the end of the pair the slice goes to ws[task] with plain stores (one accumulator register = 32
+// consecutive columns of two rows) and lstm_seq_wgrad_reduce adds the slices of the sequences in ascending order.
+typedef float f32x32 __attribute__((ext_vector_type(32)));
+struct SeqNoWgrad {};
+__device__ __forceinline__ float (*seq_yring())[kSH] {     // (a function of its own: lstm_bwd_seq2 does not get the array)
+  __shared__ __attribute__((aligned(16))) float ring[3][kSH];
+  return ring;
+}
+template <bool WGRAD, typename WG>
+__device__ __forceinline__ void lstm_bwd_seq2_body(const SeqBwdParams& p, SeqCtl* ctl, const WG& g) {
   constexpr int H = kSH, G4 = 4 * kSH;
   __shared__ __attribute__((aligned(16))) float dgl[64];               // this workgroup's dgates [gate * 16 + unit]
   __shared__ __attribute__((aligned(16))) float cst[3][16][8];         // [step % 3][unit]{dy, A, F, Ci, Cf, Cg, Co, -}: written two steps ahead
+  float (*yring)[kSH] = nullptr;                                       // WGRAD: [step % 3] the partner frame's h, written two steps ahead
+  if constexpr (WGRAD) yring = seq_yring();
   __shared__ int s_i[8];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   SeqRole role;
@@ -479,8 +506,22 @@ __device__ __forceinline__ void lstm_bwd_seq2_body(const SeqBwdParams& p, SeqCtl
     // repeat the addresses of lanes 0..15.
     const float* cellsp_in = cells_in + (T > 1 ? cells_stride : 0);    // the cell of the time step before (forward order)
     float n_dy = 0.f, n_i = 0.f, n_f = 0.f, n_g = 0.f, n_o = 0.f, n_c = 0.f, n_cp = 0.f;
+    // WGRAD: the partner frame of step s is t0 + (s + 1) tdir (none for the last step: the pointer stops at step T - 2's)
+    const float* y_in = nullptr;
+    f32x4 n_y0 = {0.f, 0.f, 0.f, 0.f}, n_y1 = n_y0;
+    f32x32 acc0, acc1, acc2, acc3;
+    if constexpr (WGRAD) {
+      y_in = g.y + ((size_t)((ptrdiff_t)t0 + (T > 1 ? tdir : 0)) * B + b) * ((size_t)D * H) + (size_t)d * H + 4 * lane;
+#pragma unroll
+      for (int i = 0; i < 32; ++i) { acc0[i] = 0.f; acc1[i] = 0.f; acc2[i] = 0.f; acc3[i] = 0.f; }
+    }
     auto load_pw = [&](int step_) {                      // (called for step_ = 0, 1, 2, ...: the pointers walk along)
       const bool more = step_ + 1 < T, more2 = step_ + 2 < T;
+      if constexpr (WGRAD) {
+        n_y0 = *reinterpret_cast<const f32x4*>(y_in);
+        n_y1 = *reinterpret_cast<const f32x4*>(y_in + 256);
+        y_in += more2 ? dy_stride : 0;                   // (y and dy have the same frame stride)
+      }
       n_dy = *dy_in;
       n_i = gates_in[0]; n_f = gates_in[H]; n_g = gates_in[2 * H]; n_o = gates_in[3 * H];
       n_c = *cells_in;
@@ -490,6 +531,10 @@ __device__ __forceinline__ void lstm_bwd_seq2_body(const SeqBwdParams& p, SeqCtl
     };
     auto put_factors = [&](int step_, int slot) {        // from the values in flight (step step_) into cst[slot]
       const float cp = step_ == T - 1 ? 0.f : n_cp;      // the last step of the backward pass has no previous cell
+      if constexpr (WGRAD) {
+        *reinterpret_cast<f32x4*>(&yring[slot][4 * lane]) = n_y0;
+        *reinterpret_cast<f32x4*>(&yring[slot][256 + 4 * lane]) = n_y1;
+      }
       if (io16) {
         const float tc = seq_tanh(n_c);
         float* o = &cst[slot][lane][0];
@@ -565,6 +610,14 @@ __device__ __forceinline__ void lstm_bwd_seq2_body(const SeqBwdParams& p, SeqCtl
         if (tid == 0) p.dgx[(size_t)d * G4 + 16 * rank] = __int_as_float(0x7fc00000);
         return;
       }
+      // WGRAD: the wave's 4 x 32 columns of the partner frame.  Requested in front of dg_own, whose wait they share (a wait
+      // of their own in front of the product would put an LDS round trip on the chain); the mailbox stores' memory
+      // clobber keeps the reads above them.
+      float yb0 = 0.f, yb1 = 0.f, yb2 = 0.f, yb3 = 0.f;
+      if constexpr (WGRAD) {
+        const float* yq = &yring[s3][128 * w + (lane & 31)];
+        yb0 = yq[0]; yb1 = yq[32]; yb2 = yq[64]; yb3 = yq[96];
+      }
       float dg_own = dgl[lane];                // (wave 1 writes it out behind the product; wave 0 may be a step ahead by then:
       asm volatile("" : "+v"(dg_own));         // the read must not sink below the mailbox stores)
       if (step < T - 1) {
@@ -605,6 +658,15 @@ __device__ __forceinline__ void lstm_bwd_seq2_body(const SeqBwdParams& p, SeqCtl
         seq_store16(mail_rd + m8 * kBox + 256, sent);
       }
       SQ_T(3);
+      if constexpr (WGRAD) {
+        if (step < T - 1) {      // behind the hand-over: the step's rank-1 update of the pair's dW_hh slice
+          acc0 = __builtin_amdgcn_mfma_f32_32x32x1f32(dg_own, yb0, acc0, 0, 0, 0);
+          acc1 = __builtin_amdgcn_mfma_f32_32x32x1f32(dg_own, yb1, acc1, 0, 0, 0);
+          acc2 = __builtin_amdgcn_mfma_f32_32x32x1f32(dg_own, yb2, acc2, 0, 0, 0);
+          acc3 = __builtin_amdgcn_mfma_f32_32x32x1f32(dg_own, yb3, acc3, 0, 0, 0);
+        }
+        SQ_T(7);
+      }
       if (io) {                  // behind the hand-over: d gx of the step to HBM, the factors two steps ahead, the prefetch
         *dgx_out = dg_own;
         dgx_out += dgx_stride;
@@ -620,7 +682,19 @@ __device__ __forceinline__ void lstm_bwd_seq2_body(const SeqBwdParams& p, SeqCtl
       atomicAdd(p.dbias_ih + at, bias_sum);
       if (p.dbias_hh) atomicAdd(p.dbias_hh + at, bias_sum);
     }
-    SQ_PRINT("lstm_bwd_seq2", "(wave 0: mailbox poll + row sums | gate derivatives | lds barrier | product + mailbox stores || inside the poll: own stores acknowledged | first poll round trip | poll loop)", T);
+    if constexpr (WGRAD) {
+      // The pair's slice: accumulator register v of column group c holds, in lane l, row 32 (v / 16) + 8 ((v % 16) / 4) +
+      // 4 (l / 32) + v % 4 of dgl's 64 and column 128 w + 32 c + l % 32; dgl's row i is row (i / 16) H + 16 rank + i % 16
+      // of dW_hh[d].
+      float* wsp = g.ws + (size_t)task * G4 * H + 128 * w + (lane & 31);
+#pragma unroll
+      for (int v = 0; v < 32; ++v) {
+        const int i = 32 * (v >> 4) + 8 * ((v & 15) >> 2) + 4 * (lane >> 5) + (v & 3);
+        float* o = wsp + ((size_t)(i >> 4) * H + 16 * rank + (i & 15)) * H;
+        o[0] = acc0[v]; o[32] = acc1[v]; o[64] = acc2[v]; o[96] = acc3[v];
+      }
+    }
+    SQ_PRINT(WGRAD ? "lstm_bwd_seq2_wgrad" : "lstm_bwd_seq2", "(wave 0: mailbox poll + row sums | gate derivatives | lds barrier | product + mailbox stores || inside the poll: own stores acknowledged | first poll round trip | poll loop | wgrad: the MFMAs' issue)", T);
     if (tid == 0 && rank == 0) __hip_atomic_fetch_add(&ctl->done, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (!seq_team_barrier(ctl, role, &nbar, s_i)) return;     // nobody writes a mailbox of the next pair before everybody has read the last of this one
   }
@@ -670,8 +744,32 @@ __global__ void __launch_bounds__(256) lstm_fwd_seq2(SeqFwdParams p, SeqCtl* ctl
   seq_exit_check(ctl, x);
 }
 __global__ void __launch_bounds__(256) lstm_bwd_seq2(SeqBwdParams p, SeqCtl* ctl, SeqExit x) {
-  lstm_bwd_seq2_body(p, ctl);
+  lstm_bwd_seq2_body<false>(p, ctl, SeqNoWgrad());
   seq_exit_check(ctl, x);
+}
+__global__ void __launch_bounds__(256) lstm_bwd_seq2_wgrad(SeqBwdParams p, SeqCtl* ctl, SeqExit x, SeqWgradParams g) {
+  lstm_bwd_seq2_body<true>(p, ctl, g);
+  seq_exit_check(ctl, x);
+}
+
+// dwhh[d][r][k] += sum over the sequences b = 0 .. B - 1, in this order, of ws[b D + d][r][k]: the result is fixed by
+// construction (no float atomics).  A launch that gave up has left slices unwritten and the sticky word of its stream set
+// (seq_exit_check, which runs before this kernel starts): then dwhh turns NaN like dgx.  The word is the one
+// pk2_lstm_persist_status reports and is never cleared, not by pk2_persist_guard_clear either: once a recurrence launch on
+// this stream, forward or backward, has given up, EVERY later fused call writes NaN into dwhh although its dgx is valid -- a
+// process that lowers the guard and carries on sets PK2_LSTM_SEQ_WGRAD=0 (the caller's product, from the valid dgx).
+__global__ void __launch_bounds__(256) lstm_seq_wgrad_reduce(const float* __restrict__ ws, float* __restrict__ dwhh, int B, int D,
+                                                             const unsigned* __restrict__ sticky) {
+  constexpr size_t kSlice = (size_t)4 * kSH * kSH;
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;    // element of dwhh: the grid covers the D slices exactly
+  if (*sticky != 0u) {
+    dwhh[i] = __uint_as_float(0x7fc00000u);
+    return;
+  }
+  const float* in = ws + i;                                   // (task = b D + d: sequence b's slices lie D slices further on)
+  float sum = in[0];
+  for (int b = 1; b < B; ++b) sum += in[(size_t)b * D * kSlice];
+  dwhh[i] += sum;
 }
 
 // ---- host -------------------------------------------------------------------------------------------------------------
@@ -737,10 +835,46 @@ int lstm_fwd_seq_launch(const float* gx, const float* whh, const float* bhh, int
   return PK2_OK;
 }
 
+// The team protocol needs every launched workgroup resident: lstm_bwd_seq2_wgrad is used only when the runtime says that
+// `teams` of its workgroups fit a CU (asked once per device; nothing rests on a register count read off a listing).
+static bool seq_wgrad_resident(int teams) {
+  static std::map<int, int> fit;
+  const int dev = current_device();
+  auto it = fit.find(dev);
+  if (it == fit.end()) {
+    int n = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, lstm_bwd_seq2_wgrad, 256, 0) != hipSuccess) { (void)hipGetLastError(); n = 0; }
+    it = fit.emplace(dev, n).first;
+  }
+  return it->second >= teams;
+}
+
+// PK2_LSTM_SEQ_WGRAD, read per call: 0 = the caller multiplies as before; 2 = where the two teams per XCD that more than 8
+// pairs ask for are not resident, the fused kernel with ONE team per XCD (the pairs queue up behind 8 teams instead of 16:
+// for measuring that trade, and for the tests -- it is what makes a team flush and clear its accumulators between pairs).
+static int seq_wgrad_mode() {
+  const char* we = getenv("PK2_LSTM_SEQ_WGRAD");
+  return we ? atoi(we) : 1;
+}
+// Teams per XCD of a fused launch; 0: the launch is not fused.
+static int seq_wgrad_teams(int pairs) {
+  const int mode = seq_wgrad_mode();
+  if (mode == 0) return 0;
+  if (seq_wgrad_resident(seq_teams(pairs))) return seq_teams(pairs);
+  return (mode == 2 && seq_wgrad_resident(1)) ? 1 : 0;
+}
+
+// (0 where no launch of this shape would be fused: the caller then allocates nothing)
+size_t lstm_seq_wgrad_workspace_floats(int B, int H, int D) {
+  return (lstm_seq_wanted(B, H, D) && seq_wgrad_teams(B * D) > 0) ? (size_t)B * D * 4 * H * H : 0;
+}
+
 int lstm_bwd_seq_launch(const float* dy, const float* whh, const float* gates, const float* cells, int B, int T, int H,
-                        int D, float* dgx, hipStream_t stream, bool* ran, float* dbias_ih, float* dbias_hh, bool* bias_done) {
+                        int D, float* dgx, hipStream_t stream, bool* ran, float* dbias_ih, float* dbias_hh, bool* bias_done,
+                        SeqWgradCall* wgrad) {
   *ran = false;
   if (bias_done) *bias_done = false;
+  if (wgrad) wgrad->done = false;
   if (!g_seq.verified()) return PK2_OK;           // the forward pass verifies the device first
   SeqScratch* sc = nullptr;
   int rc = seq_scratch(stream, &sc);
@@ -750,16 +884,37 @@ int lstm_bwd_seq_launch(const float* dy, const float* whh, const float* gates, c
   // Every reader resets the slots it has read, so a launch that completes leaves the mailboxes as it found them: all
   // sentinels.  They are filled once (and again when a launch needs more teams than have been filled); a launch that
   // gave up raises the guard, which stops training anyway (persist_guard.h).
-  if (sc->mail_clean_teams < seq_teams(B * D)) {
-    PK2_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(sc->mail), (int)kSeqSentinel, (size_t)8 * seq_teams(B * D) * kSeqMailFloats, stream));
-    sc->mail_clean_teams = seq_teams(B * D);
+  // The recurrent weight gradient from inside the recurrence.  T = 1 has no partner frame: nothing to add, and nothing is
+  // launched for it (done all the same, unless switched off).
+  int teams = seq_teams(B * D);
+  bool fused = false, wgrad_trivial = false;
+  if (wgrad && wgrad->y && wgrad->dwhh && reinterpret_cast<uintptr_t>(wgrad->y) % 16 == 0) {
+    if (T == 1) {
+      wgrad_trivial = seq_wgrad_mode() != 0;
+    } else if (wgrad->ws) {
+      const int wt = seq_wgrad_teams(B * D);
+      if (wt > 0) { fused = true; teams = wt; }
+    }
+  }
+  if (sc->mail_clean_teams < teams) {
+    PK2_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(sc->mail), (int)kSeqSentinel, (size_t)8 * teams * kSeqMailFloats, stream));
+    sc->mail_clean_teams = teams;
   }
   SeqBwdParams p{dy, whh, gates, cells, dgx, sc->mail, B, T, D, dbias_ih, dbias_hh};
   if (bias_done) *bias_done = dbias_ih != nullptr;
   const SeqExit ex{(unsigned)(B * D), 1, dgx, (size_t)T * B * D * 4 * H, sc->sticky, sc->guard.dev, sc->guard.host_dev, sc->mail,
                    (size_t)8 * kSeqTeams * kSeqMailFloats};
-  hipLaunchKernelGGL(lstm_bwd_seq2, dim3(8 * kSWgs * seq_teams(B * D)), dim3(256), 0, stream, p, sc->ctl, ex);
+  if (fused) {
+    const SeqWgradParams g{wgrad->y, wgrad->ws};
+    hipLaunchKernelGGL(lstm_bwd_seq2_wgrad, dim3(8 * kSWgs * teams), dim3(256), 0, stream, p, sc->ctl, ex, g);
+    PK2_LAUNCH_CHECK();
+    hipLaunchKernelGGL(lstm_seq_wgrad_reduce, dim3((unsigned)((size_t)D * 4 * H * H / 256)), dim3(256), 0, stream, wgrad->ws,
+                       wgrad->dwhh, B, D, sc->sticky);
+  } else {
+    hipLaunchKernelGGL(lstm_bwd_seq2, dim3(8 * kSWgs * teams), dim3(256), 0, stream, p, sc->ctl, ex);
+  }
   PK2_LAUNCH_CHECK();
+  if (wgrad) wgrad->done = fused || wgrad_trivial;
   sc->ctl_clean = true;
   *ran = true;
   return PK2_OK;

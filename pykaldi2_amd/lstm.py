@@ -175,12 +175,17 @@ class _LstmAmFunction(torch.autograd.Function):
             gw_ih, gw_hh, gb_ih, gb_hh = m._layer_views(l, gflat)
             dgx = torch.empty(T, B, D * 4 * H, device=dev, dtype=torch.float32)
             bias_done = ctypes.c_int32(0)       # (the one-launch recurrence sums its d gates over the frames on the way)
-            _lib.check(L.pk2_lstm_layer_bwd_bias(_p(dy), _p(w_hh), _p(gates), _p(cells), B, T, H, D, _p(dgx), _p(scratch),
-                                                 _p(gb_ih), _p(gb_hh), ctypes.byref(bias_done), sp))
+            # ... and keeps its slices of dW_hh in MFMA accumulators (lstm_bwd_seq2_wgrad): the recurrence reads the undropped y
+            whh_done = ctypes.c_int32(0)
+            nws = L.pk2_lstm_bwd_wgrad_workspace_floats(B, H, D)
+            wgrad_ws = torch.empty(nws, device=dev, dtype=torch.float32) if nws else None
+            _lib.check(L.pk2_lstm_layer_bwd_wgrad(_p(dy), _p(w_hh), _p(gates), _p(cells), _p(y), B, T, H, D, _p(dgx), _p(scratch),
+                                                  _p(gb_ih), _p(gb_hh), _p(gw_hh), _p(wgrad_ws) if nws else None,
+                                                  ctypes.byref(bias_done), ctypes.byref(whh_done), sp))
             G = D * 4 * H
 
             def layer_grads(dgx=dgx, inp=inp, y=y, in_size=in_size, gw_ih=gw_ih, gw_hh=gw_hh, gb_ih=gb_ih,
-                            gb_hh=gb_hh, l=l, bias_done=bool(bias_done.value)):
+                            gb_hh=gb_hh, l=l, bias_done=bool(bias_done.value), whh_done=bool(whh_done.value)):
                 # dW_ih (both directions at once) = dgx^T inp; the bias gradients (b_ih and b_hh receive the same sum) with it
                 # unless the one-launch recurrence has summed them already
                 if not bias_done:
@@ -190,7 +195,8 @@ class _LstmAmFunction(torch.autograd.Function):
                 else:
                     _gemm(1, 0, G, in_size, rows, _p(dgx), G, _p(inp), in_size, _p(gw_ih), in_size, beta=1.0)
                 # dW_hh[d] = sum_t dg_d[t]^T h_d[t-1] (reverse direction: h_d[t+1]); time-major => row shift by B
-                if T > 1:
+                # (unless the recurrence has added it on the way)
+                if T > 1 and not whh_done:
                     k = (T - 1) * B
                     if D == 2:
                         # both directions in one batched launch (matrix 1 = matrix 0 + these strides: the reverse
