@@ -358,6 +358,44 @@ int pk2_iso_gauss(uint64_t seed, int32_t points, int32_t bins, float* out, void*
 int pk2_irfft_pow2_f32(const float* X, int32_t rows, int32_t n, float* out, void* stream);
 
 /* ------------------------------------------------------------------ *
+ * Short-time Fourier transform, its inverse and ideal time-frequency masks (reference simulation/freq_analysis.py
+ * `stft` / `istft` with center=False, simulation/mask.py `MaskEstimator`).  fft_size = 2^5 .. 2^12,
+ * 1 <= frame_len <= fft_size, 1 <= frame_shift <= frame_len; window: device f32 (frame_len).  Spectra are FRAME-MAJOR:
+ * (rows, N, F, 2) interleaved complex, F = fft_size / 2 + 1 (the reference's analyze returns (F, N)).
+ * ------------------------------------------------------------------ */
+/* N = ceil((n + frame_shift - frame_len) / frame_shift), the frames of _enframe(end='pad'); -1 when n < frame_len. */
+int64_t pk2_stft_num_frames(int64_t n, int32_t frame_len, int32_t frame_shift);
+/* rows: HOST array of R device pointers to signals of n samples each (n >= frame_len).  Frame = (x + dither) * window,
+ * zero-extended to fft_size; the signal is zero-padded at its end to N whole frames.  dither: device f32 (R, n) that is
+ * added, or NULL; with NULL and use_seed != 0 the generator of pk2_iso_gauss: the pair of (row r, sample pair p) is
+ * draw r * ceil(n / 2) + p of `seed`, sample 2p takes its real and 2p + 1 its imaginary part, added as
+ * x + fl(1e-5f * z) -- bit-equal to dither = 1e-5f * pk2_iso_gauss(seed, R, ceil(n / 2)).  out: (R, N, F, 2). */
+int pk2_stft_f32(const float* const* rows, int32_t R, int64_t n, int32_t fft_size, int32_t frame_len, int32_t frame_shift,
+                 const float* window, const float* dither, int32_t use_seed, uint64_t seed, float* out, void* stream);
+/* X (R, N, F, 2) -> out (R, fft_size + frame_shift (N - 1)): per frame the inverse real transform, overlap-add (a gather
+ * in frame order: bit-reproducible), divided by the summed analysis window (its frame_len taps) where that sum > 1e-10.
+ * No synthesis window.  work: device f32 (R, N, fft_size). */
+int pk2_istft_f32(const float* X, int32_t R, int32_t N, int32_t fft_size, int32_t frame_len, int32_t frame_shift,
+                  const float* window, float* work, float* out, void* stream);
+/* power[i] = |spec[i]|^2 over `count` complex values (the array pk2_mask_count_threshold reads). */
+int pk2_mask_power(const float* spec, int64_t count, float* power, void* stream);
+/* The cutoff of the 'count' clean mask for S arrays of m non-negative powers each (device f32 (S, m), m <= 2^27):
+ * with the values sorted ascending and summed cumulatively in float64, v* = the last value whose inclusive sum is
+ * < (1 - energy_threshold) * total, and the mask is power > v*.  out: device f32 (S, 3) = (v, strict, v*): keep
+ * power > v when strict != 0, power >= v otherwise (v* is then v's predecessor).  No element satisfying the inequality
+ * gives (min, 0, 0): everything is kept.  A radix descent over the bit pattern, no sort, independent of the order of
+ * its atomics; nothing is read back.  work: device memory of pk2_mask_count_workspace_bytes(S) bytes. */
+size_t pk2_mask_count_workspace_bytes(int32_t S);
+int pk2_mask_count_threshold(const float* power, int32_t S, int64_t m, double energy_threshold, void* work, size_t work_bytes,
+                             float* out, void* stream);
+/* mask (S, N, F) of S clean spectra (S, N, F, 2) against one distorted spectrum (N, F, 2): with P_c = |C|^2,
+ * soft == 0: P_c > snr_factor * max(|D - C|^2, FLT_EPSILON) (snr_factor = 10^(threshold_db / 10)); soft != 0:
+ * min(1, P_c / |D|^2).  Times the clean-mask decision of thr (S, 3) = pk2_mask_count_threshold's output (NULL: all
+ * ones) and of vad (N) > 0.5 per frame (NULL: all ones). */
+int pk2_mask_ibm(const float* clean, const float* distorted, int32_t S, int32_t N, int32_t F, float snr_factor, int32_t soft,
+                 const float* thr, const float* vad, float* mask, void* stream);
+
+/* ------------------------------------------------------------------ *
  * Room impulse responses by the image method (reference simulation/_rirgen.py `xp_rirgen`, method 1), a batch of
  * items per call; the host checks the arguments and forms the descriptors (pykaldi2_amd/rirgen.py).  All arrays are
  * device memory.  Lengths are in samples (metres / (c / fs)).

@@ -152,6 +152,13 @@ SIGNATURES = {
     "pk2_iso_spectra": (C.c_int, [_vp, _vp, _vp, C.c_uint64, _i32, _i32, _i32, _vp, _vp]),
     "pk2_iso_gauss": (C.c_int, [C.c_uint64, _i32, _i32, _vp, _vp]),
     "pk2_irfft_pow2_f32": (C.c_int, [_vp, _i32, _i32, _vp, _vp]),
+    "pk2_stft_num_frames": (_i64, [_i64, _i32, _i32]),
+    "pk2_stft_f32": (C.c_int, [C.POINTER(_vp), _i32, _i64, _i32, _i32, _i32, _vp, _vp, _i32, C.c_uint64, _vp, _vp]),
+    "pk2_istft_f32": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "pk2_mask_power": (C.c_int, [_vp, _i64, _vp, _vp]),
+    "pk2_mask_count_workspace_bytes": (_sz, [_i32]),
+    "pk2_mask_count_threshold": (C.c_int, [_vp, _i32, _i64, C.c_double, _vp, _sz, _vp, _vp]),
+    "pk2_mask_ibm": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _f32, _i32, _vp, _vp, _vp, _vp]),
     "pk2_fbank_create": (C.c_int, [_vp, C.POINTER(_vp)]),
     "pk2_fbank_destroy": (C.c_int, [_vp]),
     "pk2_fbank_num_frames": (_i32, [_i64]),

@@ -4,7 +4,7 @@
 // irfft of length n = one complex inverse transform of length h = n / 2 plus the Hermitian untangling at its input:
 //   Z[k] = (X[k] + conj X[h-k]) + j (X[k] - conj X[h-k]) e^{2 pi j k / n},   z = IDFT_h(Z),   x[2m] + j x[2m+1] = z[m] / n,
 // so the output rows are written as float2.  The complex transform is radix-2 decimation in time in LDS (bit-reversed
-// load, one barrier per stage).  h <= kFftLds: one workgroup per row.  Beyond that the four-step form h = h1 * h2:
+// load, one barrier per stage; fft_lds.h).  h <= kFftLds: one workgroup per row.  Beyond that the four-step form h = h1 * h2:
 //   pass 1: for every k1 the length-h2 transform over k2 of Z[k1 + h1 k2], times e^{2 pi j k1 m2 / h} -> tmp[k1][m2]
 //   pass 2: for every m2 the length-h1 transform over k1 of tmp[k1][m2] -> z[h2 m1 + m2]
 // with several columns per workgroup so that global accesses are runs of consecutive elements.  Pass 2 reads and
@@ -17,32 +17,9 @@
 #include <vector>
 
 #include "common.h"
+#include "fft_lds.h"
 
 namespace pk2 {
-
-constexpr int kFftLds = 4096;        // complex points in LDS (32 KB)
-constexpr int kFftThreads = 256;
-
-// In-LDS radix-2 DIT on `nb` independent transforms of `len` = 1 << lg points each, s[b * len + bitrev(index)] loaded
-// by the caller.  W[q * wstride] = e^{2 pi j q / len}.  Ends with a barrier.
-__device__ __forceinline__ void lds_fft(float2* s, int nb, int lg, const float2* __restrict__ W, int wstride) {
-  const int len = 1 << lg, half = (nb << lg) >> 1;
-  for (int st = 0; st < lg; ++st) {
-    const int m = 1 << st;
-    __syncthreads();
-    for (int t = threadIdx.x; t < half; t += kFftThreads) {
-      const int b = t >> (lg - 1), u = t & ((len >> 1) - 1);
-      const int j = u & (m - 1);
-      const int i0 = (b << lg) + ((u - j) << 1) + j, i1 = i0 + m;
-      const float2 w = W[(int64_t)j * (len >> (st + 1)) * wstride];
-      const float2 a = s[i0], c = s[i1];
-      const float2 p = make_float2(c.x * w.x - c.y * w.y, c.x * w.y + c.y * w.x);
-      s[i0] = make_float2(a.x + p.x, a.y + p.y);
-      s[i1] = make_float2(a.x - p.x, a.y - p.y);
-    }
-  }
-  __syncthreads();
-}
 
 // Z[k] of the untangling, k in [0, h); X is one row of h + 1 complex bins
 __device__ __forceinline__ float2 untangle(const float2* __restrict__ X, int k, int h, const float2* __restrict__ W) {
@@ -53,8 +30,6 @@ __device__ __forceinline__ float2 untangle(const float2* __restrict__ X, int k, 
   const float2 o = make_float2(d.x * w.x - d.y * w.y, d.x * w.y + d.y * w.x);
   return make_float2(e.x - o.y, e.y + o.x);
 }
-
-__device__ __forceinline__ int bitrev(int x, int lg) { return (int)(__brev((unsigned)x) >> (32 - lg)); }
 
 // h <= kFftLds: one workgroup per row
 __global__ void __launch_bounds__(kFftThreads) irfft_lds_kernel(const float2* __restrict__ X, int lgh, const float2* __restrict__ W,
@@ -123,7 +98,7 @@ static std::mutex g_tw_mutex;
 static std::map<TwiddleKey, float2*> g_tw;
 
 // W[k] = e^{2 pi j k / n}, k < n / 2: float64 on the host, one blocking upload the first time a length is used
-static int twiddles(int n, const float2** out) {
+int fft_twiddles(int n, const float2** out) {
   std::lock_guard<std::mutex> lock(g_tw_mutex);
   const TwiddleKey key{current_device(), n};
   auto it = g_tw.find(key);
@@ -152,7 +127,7 @@ extern "C" int pk2_irfft_pow2_f32(const float* X, int32_t rows, int32_t n, float
   PK2_REQUIRE(n >= 32 && n <= (1 << 20) && (n & (n - 1)) == 0, "irfft_pow2_f32: n = %d is not a power of two in [2^5, 2^20]", n);
   PK2_REQUIRE(X != out, "irfft_pow2_f32: in-place operation is not supported");
   const float2* W = nullptr;
-  if (int rc = twiddles(n, &W)) return rc;
+  if (int rc = fft_twiddles(n, &W)) return rc;
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   const int h = n / 2;
   int lgh = 0;

@@ -4,40 +4,18 @@
 // reference's configs fall back to a noise corpus.
 //
 //   pk2_iso_spectra   X[m][f] = (1/sqrt(P)) sum_i g[f] Z_i[f] exp(-j tau[m][i] w_f) with the reference's bin scaling
-//   pk2_iso_gauss     the draws Z of the built-in generator (tests and tools)
+//   pk2_iso_gauss     the draws Z of the built-in generator (sim_rng.h; tests and tools)
 // One thread owns one frequency bin of up to kIsoMics microphones and walks the directions in order: no atomics, the
 // result is bit-reproducible.  tau[m][i] is uniform over the workgroup (scalar loads); the phase tau * f / fft_size is
 // reduced to [-1/2, 1/2] turns in float64 (it reaches hundreds of radians for a large array) before the float32 sincospi.
 #include <algorithm>
 
 #include "common.h"
+#include "sim_rng.h"
 
 namespace pk2 {
 
 constexpr int kIsoMics = 4;          // microphones per thread: the draw (hash, log, sqrt, sincospi) is shared by them
-
-// splitmix64 finaliser (the one of dropout.hip), all 64 bits
-__device__ __forceinline__ uint64_t iso_mix64(uint64_t z) {
-  z += 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  z ^= z >> 31;
-  return z;
-}
-
-// One complex standard normal, a pure function of (seed, counter): u1, u2 = (k + 0.5) 2^-24 from bits 63..40 and 39..16,
-// Box-Muller.  k + 0.5 has 25 significant bits; for k >= 2^23 float32 would round u1 (to 1.0 for the last k), so the
-// logarithm of the upper half is taken as log1p(-(2^24 - k - 0.5) 2^-24), whose argument is exact.
-__device__ __forceinline__ float2 iso_gauss(uint64_t seed, uint64_t counter) {
-  const uint64_t z = iso_mix64(seed * 0xD1342543DE82EF95ull + counter);
-  const uint32_t k1 = (uint32_t)(z >> 40), k2 = (uint32_t)(z >> 16) & 0xFFFFFFu;
-  const float lg = k1 < (1u << 23) ? logf(((float)k1 + 0.5f) * 0x1p-24f)
-                                   : log1pf(-((float)((1u << 24) - 1u - k1) + 0.5f) * 0x1p-24f);
-  const float r = sqrtf(-2.f * lg);
-  float s, c;
-  sincospif(((float)k2 + 0.5f) * 0x1p-23f, &s, &c);       // angle 2 pi u2; (k2 + 0.5) 2^-23 is rounded harmlessly
-  return make_float2(r * c, r * s);
-}
 
 template <bool kDraws>
 __global__ void __launch_bounds__(256) iso_spectra_kernel(const double* __restrict__ tau, const double* __restrict__ g,

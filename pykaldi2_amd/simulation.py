@@ -102,15 +102,29 @@ class SimpleSimulator:
     """Single speech source simulator (reference simulation/simulation.py:181-234):
     ``SimpleSimulator(use_rir, use_noise, snr_range)(source_wav, dir_noise_wavs, source_rir, dir_noise_rirs,
     normalize_gain=...)`` -> (simulated waveform, sentence config).  A 2-D `source_rir` (C, k) (and (C, k') noise
-    RIRs) takes the multi-channel path and returns the (C, T) mixture."""
+    RIRs) takes the multi-channel path and returns the (C, T) mixture.  gen_mask=True returns the reference's 4-tuple
+    (mixed, [early reverberation], [mask (N, F)], sentence config), computed by the `mask_estimator` the simulator was
+    built with (see MultiSourceSimulator); `mask_seed` seeds the analyzer's dither."""
 
-    def __init__(self, array_geometry=None, use_rir=True, use_noise=True, snr_range=(0, 30)):
+    def __init__(self, array_geometry=None, use_rir=True, use_noise=True, snr_range=(0, 30), mask_estimator=None):
         self.array_geometry = array_geometry        # not read: the channels come from the RIRs (as in the reference)
         self.use_rir, self.use_noise = use_rir, use_noise
         self.snr_range = tuple(snr_range)      # sets `global_snr` in the reference, which its simulate() never reads
+        self.mask_estimator = mask_estimator   # what gen_mask=True computes the masks with
 
     def __call__(self, source_wav, dir_noise_wavs=None, source_rir=None, dir_noise_rirs=None, normalize_gain=True,
-                 rir_delays=None):
+                 rir_delays=None, gen_mask=False, mask_seed=None):
+        if gen_mask:
+            _require_mask_estimator(self.mask_estimator)
+            # the reference's 4-tuple (mixed, [early reverberation], [mask], sent_cfg); 1-D inputs come back 1-D
+            one_d = source_wav.dim() == 1 and (source_rir is None or source_rir.dim() == 1)
+            mixed, early, cfg = _simulate([source_wav], dir_noise_wavs, [source_rir] if source_rir is not None else None,
+                                          dir_noise_rirs, None, normalize_gain, True, rir_delays, None,
+                                          mask_estimator=self.mask_estimator, mask_seed=mask_seed)
+            mask = cfg.pop('mask')
+            if one_d:
+                mixed, early = mixed.view(-1), [e.view(-1) for e in early]
+            return mixed, early, mask, cfg
         if source_rir is not None and source_rir.dim() == 2:
             mixed, _, cfg = _simulate([source_wav], dir_noise_wavs, [source_rir], dir_noise_rirs, None, normalize_gain, False,
                                       rir_delays, None)
@@ -301,12 +315,21 @@ def _as_mc(x):
     return x.view(1, -1) if x.dim() == 1 else x
 
 
+def _require_mask_estimator(est):
+    if est is None:
+        raise NotImplementedError("gen_mask: this simulator was built without a mask estimator; pass "
+                                  "mask_estimator=MaskEstimator(SpectrumAnalyzer(...)) to its constructor")
+
+
 def _simulate(source_wavs, dir_noise_wavs, source_rirs, dir_noise_rirs, iso_noise_wav, normalize_gain, get_early_reverb,
-              rir_delays, mixer, fs=16000):
+              rir_delays, mixer, fs=16000, mask_estimator=None, mask_seed=None):
     """_Simulator.simulate (reference simulation/simulation.py:55-178) as its text means it (the reference itself stops at
     the undefined `simu_cfg` with more than one source or an isotropic noise).  Draws, in its textual order: spr, the
     mixer's starts, dir_snr, each noise's start, iso_snr, the repeat-noise start.  `mixed_noisy` aliases `mixed` there, so
-    every noise -- the isotropic one included -- is scaled against a power that contains the noises added before it."""
+    every noise -- the isotropic one included -- is scaled against a power that contains the noises added before it.
+    With a mask_estimator: the reference's step 5, cfg['mask'] = the list of the sources'
+    masks -- channel 0 of every positioned early-reverberation signal against channel 0 of the noisy mixture, before the
+    gain normalisation and after every other draw."""
     sources = list(source_wavs)
     noises = list(dir_noise_wavs) if dir_noise_wavs is not None else []
     n_source, n_noise = len(sources), len(noises)
@@ -343,6 +366,8 @@ def _simulate(source_wavs, dir_noise_wavs, source_rirs, dir_noise_rirs, iso_nois
     if iso_noise_wav is not None:
         cfg['iso_snr'] = np.random.uniform(low=10.0, high=30.0, size=1)               # ISONoiseConfig 'snr'
         cfg['iso_start'] = _add_noise_mc(mixed, _check_mc(_as_mc(iso_noise_wav), "iso_noise_wav"), cfg['iso_snr'][0], None, True)
+    if mask_estimator is not None:
+        cfg['mask'] = list(mask_estimator.get_mask_from_parallel_data([e[0] for e in pos_early], mixed[0], seed=mask_seed).unbind(0))
     if normalize_gain:
         bufs = [mixed] + (list(pos_early) if pos_early is not None else [])
         peak = _power_seg([mixed])
@@ -360,24 +385,32 @@ class MultiSourceSimulator:
     """Multiple speech source simulator, used to generate overlapping, multi-channel, noisy speech (reference
     simulation/simulation.py:237-296).  Channel-major device layout: sources and noises are 1-D CUDA float32 waveforms,
     their RIRs (C, k) tensors, `iso_noise_wav` a (C, m) tensor (generate_isotropic_noise); without RIRs the sources
-    themselves are (C, n).  Returns (mixed_noisy (C, T), positioned_source_early_reverb | None, None, sent_cfg);
+    themselves are (C, n).  Returns (mixed_noisy (C, T), positioned_source_early_reverb | None, mask | None, sent_cfg);
+    gen_mask=True forces the early reverberation and fills the third slot with the list of the sources' ideal binary masks,
+    (N, F) CUDA float32 each (frame-major; MaskEstimator on channel 0, before the gain normalisation; `mask_seed` seeds the
+    analyzer's dither, None draws one np.random.randint after every other draw).  The masks are computed by the
+    `mask_estimator` given to the constructor, MaskEstimator(SpectrumAnalyzer(...)): the analysis (FFT size, window, dither)
+    is the caller's choice, as the reference's config['analysis'] is; a simulator built without one keeps raising
+    NotImplementedError for gen_mask=True;
     sent_cfg holds the draws (spr, start_sample_idx, dir_snr, dir_start, iso_snr, iso_start) and, as CUDA tensors, the
     mixer's `scale` and `gain_norm_scale`.  `snr_range` sets `global_snr` in the reference, which nothing reads: the
     directional SNR is uniform[0, 20] dB and the isotropic one uniform[10, 30] dB."""
 
     def __init__(self, array_geometry=None, use_rir=True, use_noise=True, snr_range=(0, 30), n_source_range=(2, 2),
-                 spr_range=(-2.5, 2.5)):
+                 spr_range=(-2.5, 2.5), mask_estimator=None):
         self.array_geometry, self.use_rir, self.use_noise = array_geometry, use_rir, use_noise
         self.snr_range, self.n_source_range = tuple(snr_range), tuple(n_source_range)
         self.mixer = Mixer(MixerConfig(spr_range))
+        self.mask_estimator = mask_estimator   # what gen_mask=True computes the masks with
 
     def __call__(self, source_wavs, dir_noise_wavs=None, source_rirs=None, dir_noise_rirs=None, iso_noise_wav=None,
-                 gen_mask=False, normalize_gain=True, get_early_reverb=False, rir_delays=None, fs=16000):
+                 gen_mask=False, normalize_gain=True, get_early_reverb=False, rir_delays=None, fs=16000, mask_seed=None):
         if gen_mask:
-            raise NotImplementedError("gen_mask: the ideal-binary-mask estimator (MaskEstimator / SpectrumAnalyzer) is not built")
+            _require_mask_estimator(self.mask_estimator)
         mixed, early, cfg = _simulate(source_wavs, dir_noise_wavs, source_rirs, dir_noise_rirs, iso_noise_wav, normalize_gain,
-                                      get_early_reverb, rir_delays, self.mixer, fs)
-        return mixed, early, None, cfg
+                                      get_early_reverb or gen_mask, rir_delays, self.mixer, fs,
+                                      mask_estimator=self.mask_estimator if gen_mask else None, mask_seed=mask_seed)
+        return mixed, early, cfg.pop('mask', None), cfg
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -543,3 +576,215 @@ def generate_isotropic_noise(mic_xyz, N, samp_rate, type='sph', spectrum='hoth',
     X = iso_noise_spectra(mic_xyz, N, samp_rate, type, spectrum, seed, draws, device)
     n = irfft_pow2(X)
     return n[:, :int(N)].contiguous() if n.shape[1] != int(N) else n
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# STFT, inverse STFT and ideal time-frequency masks (reference simulation/freq_analysis.py, simulation/mask.py)
+# ---------------------------------------------------------------------------------------------------------------------
+def _get_window(window, wlen):
+    """The analysis window as host float64 (freq_analysis.py:9-38): a name, a callable or a vector."""
+    if isinstance(window, str):
+        if window == 'hamming':
+            w = np.hamming(wlen)
+        elif window == 'bartlett':
+            w = np.bartlett(wlen)
+        elif window in ('hann', 'hanning'):
+            w = np.hanning(wlen)
+        else:
+            raise ValueError('cannot obtain window type {}'.format(window))
+    elif callable(window):
+        w = window(wlen)
+    else:
+        w = window.detach().cpu().numpy() if isinstance(window, torch.Tensor) else np.asarray(window)
+    w = np.asarray(w, dtype=np.float64).reshape(-1)
+    if w.shape[0] != wlen:
+        raise ValueError("the window has %d taps, frame_len is %d" % (w.shape[0], wlen))
+    return w
+
+
+def stft_num_frames(n, frame_len, frame_shift):
+    """N = ceil((n + shift - len) / shift): the frames of the reference's _enframe(end='pad'), the signal zero-padded at
+    its end.  A signal shorter than one frame is an error."""
+    n, frame_len, frame_shift = int(n), int(frame_len), int(frame_shift)
+    if frame_len < 1 or frame_shift < 1:
+        raise ValueError("frame_len and frame_shift must be positive")
+    if n < frame_len:
+        raise ValueError("the signal (%d samples) is shorter than one frame (%d)" % (n, frame_len))
+    return (n - frame_len + 2 * frame_shift - 1) // frame_shift
+
+
+def _stft_rows(rows, fft_size, frame_len, frame_shift, window, seed=None, dither=None):
+    """One launch (per 16 rows) for a list of 1-D CUDA float32 signals of one length -> float32 (R, N, F, 2), frame-major."""
+    n, dev = rows[0].numel(), rows[0].device
+    for x in rows:
+        _check(x)
+        if x.numel() != n or x.device != dev:
+            raise ValueError("the signals of one STFT call differ in length or device")
+    N = stft_num_frames(n, frame_len, frame_shift)
+    R, F = len(rows), fft_size // 2 + 1
+    if dither is not None:
+        if not (isinstance(dither, torch.Tensor) and dither.is_cuda and dither.dtype == torch.float32 and dither.is_contiguous()
+                and tuple(dither.shape) == (R, n)):
+            raise ValueError("dither must be a contiguous CUDA float32 tensor of shape (%d, %d)" % (R, n))
+    out = torch.empty(R, N, F, 2, dtype=torch.float32, device=dev)
+    tab = (_lib.C.c_void_p * R)(*[x.data_ptr() for x in rows])
+    with torch.cuda.device(dev):
+        _lib.check(_lib.lib().pk2_stft_f32(tab, R, n, int(fft_size), int(frame_len), int(frame_shift), _lib.ptr(window),
+                                           _lib.ptr(dither), int(seed is not None), (int(seed) if seed is not None else 0) & (2 ** 64 - 1),
+                                           _lib.ptr(out), _lib.stream_ptr(dev)))
+    return out
+
+
+class SpectrumAnalyzer:
+    """Short-time Fourier analysis and synthesis on the device (reference simulation/freq_analysis.py:231-266).  `config`
+    overrides the attributes like the reference's; `dc_removal` is kept and unused, as there.  window: 'hamming',
+    'hann' / 'hanning', 'bartlett', a callable or a vector (numpy float64 on the host, uploaded once per device).
+
+    SPECTRA ARE FRAME-MAJOR: analyze returns (N, F) where the reference returns (F, N); `.transpose(-1, -2)` gives the
+    reference's orientation.  N = ceil((n + frame_shift - frame_len) / frame_shift), the signal zero-padded at its end."""
+
+    def __init__(self, config=None, fs=16000, fft_size=512, frame_len=400, frame_shift=160, window='hamming', do_dither=True,
+                 dc_removal=False):
+        self.fs, self.fft_size, self.frame_len, self.frame_shift = fs, fft_size, frame_len, frame_shift
+        self.window, self.do_dither, self.dc_removal = window, do_dither, dc_removal
+        if config is not None:
+            for attr in config:
+                setattr(self, attr, config[attr])
+        self.n_bin = self.fft_size // 2 + 1
+        self.frame_overlap = self.frame_len - self.frame_shift
+        self._win = {}
+
+    def window_taps(self):
+        """the window as host float64"""
+        return _get_window(self.window, int(self.frame_len))
+
+    def _window(self, device):
+        key = (torch.device(device), int(self.frame_len))
+        if key not in self._win:
+            self._win[key] = _lib.h2d(self.window_taps().astype(np.float32), device)
+        return self._win[key]
+
+    def num_frames(self, n):
+        return stft_num_frames(n, self.frame_len, self.frame_shift)
+
+    def _dither_args(self, seed, dither):
+        if dither is not None or not self.do_dither:
+            return None, dither
+        return (int(np.random.randint(0, 2 ** 31 - 1)) if seed is None else int(seed)), None
+
+    def _analyze_rows(self, rows, seed=None, dither=None):
+        seed, dither = self._dither_args(seed, dither)
+        return _stft_rows(rows, self.fft_size, self.frame_len, self.frame_shift, self._window(rows[0].device), seed, dither)
+
+    def analyze(self, signal, seed=None, dither=None):
+        """signal: (n,) or (R, n) CUDA float32 -> complex64 (N, F) or (R, N, F).
+
+        With do_dither the reference adds np.random.normal(0, 1e-5) to every sample.  Here the normals come from the
+        counter-based generator inside the kernel (simulation.iso_gauss(seed, R, ceil(n / 2)).view(R, -1)[:, :n] is the
+        draw array, added as x + 1e-5 * z); `seed=None` draws one np.random.randint(0, 2**31 - 1) per call.  A seeded run is
+        reproducible (bit for bit), but it is NOT the reference's dither for that numpy seed: the reference consumes n
+        normals of the global stream.  For parity pass them as `dither`, a CUDA float32 tensor of the signal's shape
+        that is added as it stands (and replaces the generator whatever do_dither is)."""
+        _lib.require_gpu()
+        one_d = signal.dim() == 1
+        sig = _check_mc(signal.view(1, -1) if one_d else signal, "signal")
+        if dither is not None:
+            dither = dither.view(1, -1) if dither.dim() == 1 else dither
+        spec = torch.view_as_complex(self._analyze_rows(list(sig.unbind(0)), seed, dither))
+        return spec[0] if one_d else spec
+
+    def log_spec(self, signal, seed=None, dither=None):
+        return torch.log(torch.abs(self.analyze(signal, seed, dither)))
+
+    def synthesize(self, stft_matrix):
+        """The reference's istft(center=False): complex64 (N, F) or (R, N, F) -> float32 (fft_size + frame_shift (N - 1),)
+        or (R, ...): overlap-add of the frames' inverse transforms divided by the summed analysis window where that sum
+        exceeds 1e-10 (no synthesis window)."""
+        _lib.require_gpu()
+        X = stft_matrix
+        if not (isinstance(X, torch.Tensor) and X.is_cuda and X.dtype == torch.complex64 and X.dim() in (2, 3)):
+            raise ValueError("synthesize: expected a CUDA complex64 (N, F) or (R, N, F) tensor")
+        one_d = X.dim() == 2
+        X = (X.unsqueeze(0) if one_d else X).contiguous()
+        R, N, F = X.shape
+        if F != self.fft_size // 2 + 1:
+            raise ValueError("synthesize: %d bins, fft_size / 2 + 1 = %d" % (F, self.fft_size // 2 + 1))
+        work = torch.empty(R, N, self.fft_size, dtype=torch.float32, device=X.device)
+        out = torch.empty(R, self.fft_size + self.frame_shift * (N - 1), dtype=torch.float32, device=X.device)
+        with torch.cuda.device(X.device):
+            _lib.check(_lib.lib().pk2_istft_f32(_lib.ptr(torch.view_as_real(X)), R, N, int(self.fft_size), int(self.frame_len),
+                                                int(self.frame_shift), _lib.ptr(self._window(X.device)), _lib.ptr(work),
+                                                _lib.ptr(out), _lib.stream_ptr(X.device)))
+        return out[0] if one_d else out
+
+
+def mask_count_threshold(power, energy_threshold=0.997):
+    """The cutoff of the 'count' clean mask (reference simulation/mask.py:75-79) for a CUDA float32 array of non-negative
+    powers, (m,) or (S, m): with the values sorted ascending and summed cumulatively (float64), v* = the last value whose
+    inclusive sum is < (1 - energy_threshold) * total; the clean mask is power > v*.  Returns a CUDA float32 (3,) or
+    (S, 3) tensor (v, strict, v*): keep power > v when strict is 1, power >= v when it is 0 (v* is then the largest value
+    below v).  Where the reference raises IndexError (no value satisfies the inequality) the result is (min, 0, 0):
+    everything is kept."""
+    _lib.require_gpu()
+    one_d = power.dim() == 1
+    p = _check_mc(power.view(1, -1) if one_d else power, "power")
+    S, m = p.shape
+    L = _lib.lib()
+    nbytes = L.pk2_mask_count_workspace_bytes(S)
+    work = torch.empty(nbytes, dtype=torch.uint8, device=p.device)
+    out = torch.empty(S, 3, dtype=torch.float32, device=p.device)
+    with torch.cuda.device(p.device):
+        _lib.check(L.pk2_mask_count_threshold(_lib.ptr(p), S, m, float(energy_threshold), _lib.ptr(work), nbytes, _lib.ptr(out),
+                                              _lib.stream_ptr(p.device)))
+    return out[0] if one_d else out
+
+
+class MaskEstimator:
+    """Ideal time-frequency masks from parallel clean / distorted waveforms (reference simulation/mask.py): 1 where a bin
+    is dominated by the clean signal.  Binary: 10 log10(P_c / max(P_n, eps)) > snr_threshold with P_c = |C|^2 and
+    P_n = |D - C|^2; soft: min(1, P_c / |D|^2).  Times the clean mask ('count': the loudest bins that hold 99.7 % of the
+    clean energy; 'floor' is unfinished in the reference -> NotImplementedError; anything else: all ones) and the
+    per-frame `vad > 0.5` (the reference's smoothing of it cannot run and its result is never used).  Masks are
+    FRAME-MAJOR (N, F) like the analyzer's spectra.  `last_threshold` keeps the 'count' cutoffs of the last call, a CUDA
+    float32 (S, 3) tensor (v, strict, v*) (see mask_count_threshold)."""
+
+    def __init__(self, analyzer, snr_threshold=0.5, clean_mask_type='count', clean_mask_energy_threshold=0.997):
+        self._analyzer = analyzer
+        self._snr_threshold = snr_threshold
+        self._clean_mask_type = clean_mask_type
+        self._clean_mask_energy_threshold = clean_mask_energy_threshold
+        self.last_threshold = None
+
+    def get_mask_from_parallel_data(self, clean, distorted, vad=None, use_soft_mask=False, seed=None, dither=None):
+        """clean: (n,) CUDA float32, or a list / an (S, n) batch of them; distorted: (n,).  Returns float32 (N, F), or
+        (S, N, F) for a list or a batch.  All S + 1 signals go through one STFT launch; with the analyzer's dither they
+        are its rows 0 .. S (the clean ones first), so clean and distorted get different dither: `seed` / `dither` as in
+        SpectrumAnalyzer.analyze, `dither` of shape (S + 1, n).  vad: (N,) per frame, CUDA or host."""
+        if self._clean_mask_type == 'floor':
+            raise NotImplementedError("clean_mask_type='floor' is not implemented (nor is it in the reference)")
+        _lib.require_gpu()
+        single = isinstance(clean, torch.Tensor) and clean.dim() == 1
+        rows = [clean] if single else list(clean.unbind(0) if isinstance(clean, torch.Tensor) else clean)
+        S = len(rows)
+        if S < 1:
+            raise ValueError("no clean signal")
+        spec = self._analyzer._analyze_rows(rows + [distorted], seed, dither)           # (S + 1, N, F, 2)
+        N, F, dev = spec.shape[1], spec.shape[2], spec.device
+        L, stream = _lib.lib(), _lib.stream_ptr(dev)
+        thr = None
+        with torch.cuda.device(dev):
+            if self._clean_mask_type == 'count':
+                power = torch.empty(S, N * F, dtype=torch.float32, device=dev)
+                _lib.check(L.pk2_mask_power(_lib.ptr(spec), S * N * F, _lib.ptr(power), stream))
+                thr = mask_count_threshold(power, self._clean_mask_energy_threshold)
+            self.last_threshold = thr
+            if vad is not None:
+                vad = torch.as_tensor(vad)
+                vad = _lib.h2d(vad.to(torch.float32).reshape(-1), dev).contiguous()
+                if vad.numel() != N:
+                    raise ValueError("vad has %d entries for %d frames" % (vad.numel(), N))
+            mask = torch.empty(S, N, F, dtype=torch.float32, device=dev)
+            factor = float(np.float32(10.0 ** (float(self._snr_threshold) / 10.0)))
+            _lib.check(L.pk2_mask_ibm(_lib.ptr(spec), _lib.ptr(spec[S]), S, N, F, factor, int(bool(use_soft_mask)), _lib.ptr(thr),
+                                      _lib.ptr(vad), _lib.ptr(mask), stream))
+        return mask[0] if single else mask
