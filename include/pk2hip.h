@@ -65,6 +65,11 @@ int32_t pk2_den_graph_path(const pk2_den_graph* g, int32_t num_seqs);
  * (graphs up to ~1.05 M arc slots / ~36 k states), 2 = chunked LDS table whose copy overlaps the arcs, two resident passes
  * and streamed overflow (any graph with < 65536 states); 0 = none (paths 0 / 1).  PK2_DEN_PERSIST = 0 | 1 | 2 forces one. */
 int32_t pk2_den_graph_persist_form(const pk2_den_graph* g, int32_t num_seqs);
+/* The route of a call on num_seqs sequences of at most max_frames frames, as the library decides it once per call
+ * ("How a call is routed"): out = {family (0 = per-arc-pdf, 1 = state-x), persistent form, sequences per
+ * group, buffers filled with zeros first, x gathered by pdf, launches in front of the recursions merged, launches behind
+ * them mergeable, occupancy kernel (1 = row staged in LDS, 0 = gather)}.  Reporting only. */
+int pk2_den_graph_plan(const pk2_den_graph* g, int32_t num_seqs, int32_t max_frames, int32_t out[8]);
 
 /* ------------------------------------------------------------------ *
  * LF-MMI objective and derivative for a minibatch of N sequences.

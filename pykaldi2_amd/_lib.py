@@ -65,6 +65,7 @@ SIGNATURES = {
     "pk2_den_graph_arcs_per_lane": (_i32, []),
     "pk2_den_graph_path": (_i32, [_vp, _i32]),
     "pk2_den_graph_persist_form": (_i32, [_vp, _i32]),
+    "pk2_den_graph_plan": (C.c_int, [_vp, _i32, _i32, _vp]),
     "pk2_den_graph_debug_ordering": (C.c_int, [_vp, C.c_int, C.POINTER(_i64), C.POINTER(_i32), _vp, _vp,
                                                _vp, _vp, _vp, _vp]),
     "pk2_den_graph_debug_virtual": (C.c_int, [_vp, C.c_int, C.POINTER(_i32), _vp, _vp, _vp, _vp, _vp,

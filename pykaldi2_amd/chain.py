@@ -85,6 +85,16 @@ class DenominatorGraph:
         overflow (csrc/chain_den_persist2.hip); 0 = none."""
         return int(_lib.lib().pk2_den_graph_persist_form(self._h, int(num_seqs)))
 
+    PLAN_FIELDS = ("family", "form", "NG", "need_fill", "xgather", "prep_merged", "tail_mergeable", "gamma_kernel")
+
+    def plan(self, num_seqs, max_frames):
+        """The route of a call on `num_seqs` sequences of at most `max_frames` frames (csrc/chain_internal.h: DenPlan), as a
+        dict over PLAN_FIELDS: family 0 = per-arc-pdf / 1 = state-x kernels, form as persist_form(), gamma_kernel 1 = LDS
+        row / 0 = gather; the rest are flags."""
+        out = np.zeros(8, dtype=np.int32)
+        _lib.check(_lib.lib().pk2_den_graph_plan(self._h, int(num_seqs), int(max_frames), _lib.ptr(out)))
+        return dict(zip(self.PLAN_FIELDS, (int(v) for v in out)))
+
     def debug_persist2(self, which):
         """Second persistent layout of an ordering (test hook; csrc/chain_internal.h: HostPersist2); None if absent."""
         L = _lib.lib()

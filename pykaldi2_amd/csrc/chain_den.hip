@@ -1457,35 +1457,97 @@ static size_t den_lds_bytes(int P, int NG) {
   return ((size_t)P * NG + (size_t)2 * kMaxRows * NG + (size_t)2 * kDenWaves * NG) * sizeof(float);
 }
 
+// The run-time switches of this path, read per call (the tests flip them inside one process).
+static DenEnv den_env() {
+  auto num = [](const char* name, int unset) { const char* e = getenv(name); return e ? atoi(e) : unset; };
+  DenEnv e;
+  const char* mode = getenv("PK2_DEN_MODE");
+  e.mode = mode && strcmp(mode, "general") == 0 ? 0 : (mode && strcmp(mode, "sx") == 0 ? 1 : -1);
+  e.persist = num("PK2_DEN_PERSIST", -1);
+  e.merge = num("PK2_DEN_MERGE", 1) != 0;
+  e.xgather = num("PK2_DEN_XGATHER", 1) != 0;
+  e.num_ride = num("PK2_DEN_NUM_RIDE", 1) != 0;
+  e.exp_gather = getenv("PK2_DEN_EXP_GATHER") != nullptr; e.gamma_gather = getenv("PK2_DEN_GAMMA_GATHER") != nullptr;
+  e.test_fail = num("PK2_DEN_TEST_FAIL", 0) == 1;
+  e.debug = num("PK2_DEN_DEBUG", 0);
+  if (const char* seed = getenv("PK2_DEN_DEBUG_BETA_SEED")) { const float v = (float)atof(seed); if (v > 0.f) e.beta_seed = v; }
+  return e;
+}
+
+// Which recursion kernel a state-x call of N sequences takes: 0 = the launch-per-frame kernels, 1 = den_persist_kernel
+// (everything resident: graphs up to ~1.05 M arc slots and ~36 k states), 2 = den_persist2_kernel.  The forced one
+// (PK2_DEN_PERSIST) if it fits, else the frame kernels; unforced, the second form whenever the whole graph is resident in it
+// (it takes every graph the first form takes and is a little faster); when it has to stream pieces or rotate table chunks,
+// whichever of it and the frame kernels the measured cost model (profiles/r03_den_sweep.txt) predicts to be faster.
+static int den_plan_form(const pk2_den_graph* g, int want, int N) {
+  if (want == 0 || N < 1 || 2 * N > kMaxTasks || device_cu_count() != 8 * kPR) return 0;
+  const bool ok1 = den_persist_usable(g), ok2 = den_persist2_usable(g);
+  if (want == 1) return ok1 ? 1 : 0;
+  if (want == 2) return ok2 ? 2 : 0;
+  if (!ok2) return ok1 ? 1 : 0;
+  const HostPersist2& f = g->h_p2fwd; const HostPersist2& b = g->h_p2bwd;
+  const int pieces = std::max(f.max_pieces, b.max_pieces), K = std::max(f.K, b.K);
+  if (pieces == 0 && K == 2) return 2;
+  // microseconds per frame, fitted to the sweep: the streaming frame grows with the vector (table copy, row epilogues,
+  // the row-indexed sums of the segments) and by ~0.9 per streamed piece of 4096 slots; the frame kernels stream both arc
+  // lists once per frame for up to 4 sequences at a time
+  const double S = (double)g->S * 1e-3, A = (double)g->A * 1e-6;
+  const double us2 = 5.2 + 0.30 * S + 0.9 * pieces;
+  const double usf = 6.0 + 0.12 * S + 10.5 * A;
+  // 2 N recursions on 8 XCDs (each sequence's two recursions side by side) against ceil(N / 4) groups of frame launches
+  const double t2 = us2 * std::max(1.0, 2.0 * N / 8.0), tf = usf * ((N + 3) / 4);
+  return t2 <= tf ? 2 : (ok1 ? 1 : 0);
+}
+
+// Everything that follows from (family, form, NG).  Also the plan of the fallback after a failed first-use verification:
+// the frame kernels (form 0) on the one-sequence groups the buffers were carved for.
+static void den_plan_route(const pk2_den_graph* g, DenPlan& pl, int form, int NG) {
+  pl.form = form; pl.NG = NG;
+  pl.G = (pl.N + NG - 1) / NG;
+  const HostOrdering& hf = pl.sx ? g->h_fwdv : g->h_fwd;
+  const HostOrdering& hb = pl.sx ? g->h_bwdv : g->h_bwd;
+  // (on the state-x path every alpha / beta' row and every occupancy is written by a plain store unless a row is
+  // split over several chunks, and values of frames beyond a sequence's end are only ever selected away, never used
+  // in arithmetic: the 0.9 GB of fills per call are skipped then)
+  auto any_atomic = [](const HostOrdering& h) { for (int32_t a : h.atomic) if (a) return true; return false; };
+  pl.need_fill = !pl.sx || any_atomic(hf) || any_atomic(hb);
+  // (the second persistent kernel gathers x by pdf from plain exp(logits) rows, which fit the xv buffer when V >= P)
+  pl.xgather = pl.env.xgather && form == 2 && NG == 1 && g->P <= 32767 && g->V >= g->P && g->p2_rowarrays == kP2RowArrays;
+  pl.prep_merged = pl.env.merge && form == 2 && !pl.need_fill && pl.xgather;
+  pl.tail_mergeable = pl.env.merge && NG == 1 && (size_t)(pl.Tmax + 1) * 2 * sizeof(float) <= 60 * 1024;
+  const size_t row_lds = (size_t)g->P * NG * sizeof(float);
+  pl.gamma_lds = row_lds <= kGammaMaxLds && !pl.env.gamma_gather;
+  if (!pl.sx) pl.exp_kernel = kExpTranspose;
+  else if (pl.xgather) pl.exp_kernel = pl.prep_merged ? kExpPrep1 : kExpRows;
+  else pl.exp_kernel = (form != 0 || (row_lds <= kGammaMaxLds && !pl.env.exp_gather)) ? kExpStatesLds : kExpStates;
+  pl.ncf = form != 0 ? kPR : hf.n_chunks;     // (a persistent kernel leaves one partial sum per workgroup of a team)
+  pl.ncb = form != 0 ? kPR : hb.n_chunks;
+}
+
 // The state-x kernels serve every graph; the general (per-arc pdf, LDS-staged exp(logits)) family remains for graphs
 // whose virtual-state count explodes (more than 4 distinct entering pdfs per state on average) and for A/B runs:
 // PK2_DEN_MODE=general | sx overrides the choice.
-bool den_use_sx(const pk2_den_graph* g) {
-  const char* mode = getenv("PK2_DEN_MODE");
-  if (mode && strcmp(mode, "general") == 0) return false;
-  if (mode && strcmp(mode, "sx") == 0) return true;
-  return (int64_t)g->V <= 4 * (int64_t)g->S;
+DenPlan den_plan(const pk2_den_graph* g, int N, int Tmax) {
+  DenPlan pl;
+  pl.env = den_env();
+  pl.N = N; pl.Tmax = Tmax;
+  pl.sx = pl.env.mode >= 0 ? pl.env.mode == 1 : (int64_t)g->V <= 4 * (int64_t)g->S;
+  const int form = pl.sx ? den_plan_form(g, pl.env.persist, N) : 0;
+  int ng = 0;      // the largest group whose LDS need is at most 160 KB
+  for (int n : {1, 2, 4}) if (den_lds_bytes(g->P, n) <= 160 * 1024) ng = n;
+  if (ng == 0) { pl.rc = PK2_ERR_LIMIT; ng = 1; }      // (den_compute reports it; sizing and the hooks go on with NG = 1)
+  pl.NG_frames = ng;
+  den_plan_route(g, pl, form, form != 0 ? 1 : ng);
+  return pl;
 }
 
-int den_choose_ng(const pk2_den_graph* g) {
-  const size_t limit = 160 * 1024;
-  for (int ng : {4, 2, 1})
-    if (den_lds_bytes(g->P, ng) <= limit) return ng;
-  return 0;
-}
-
-static size_t den_workspace_as(const pk2_den_graph* g, int N, int Tmax, bool persist, DenGeom* geom, DenBuffers* buf,
-                               void* base) {
-  DenGeom ge;
-  ge.NG = persist ? 1 : den_choose_ng(g);
-  if (ge.NG == 0) ge.NG = 1;
-  ge.N = N; ge.Tmax = Tmax;
-  ge.G = (N + ge.NG - 1) / ge.NG;
-  ge.persist = persist;
+// (sized for NG-sequence groups of the plan's family; `persist`: with the persistent kernels' xv and kPR partial sums)
+static size_t den_carve(const pk2_den_graph* g, const DenPlan& pl, int NG, bool persist, DenBuffers* buf, void* base) {
+  const int Tmax = pl.Tmax;
+  const bool sx = pl.sx;
   Carver c(base);
   DenBuffers b;
-  const size_t GN = (size_t)ge.G * ge.NG;
-  const bool sx = den_use_sx(g);
+  const size_t GN = (size_t)((pl.N + NG - 1) / NG) * NG;
   const size_t V = sx ? (size_t)g->V : (size_t)g->S, Vo = sx ? (size_t)g->Vo : (size_t)g->S;
   b.alpha = c.take<float>(GN * (Tmax + 1) * (size_t)g->S);
   b.alphav = (Vo == (size_t)g->S) ? b.alpha : c.take<float>(GN * (Tmax + 1) * Vo);
@@ -1506,21 +1568,16 @@ static size_t den_workspace_as(const pk2_den_graph* g, int N, int Tmax, bool per
   b.csum = c.take<float>(GN * (Tmax + 1) * 2);   // {cu, sum pi*btilde' / cu}
   b.kscale = c.take<float>(GN * (Tmax + 1));
   b.xv = persist ? c.take<float>(GN * (size_t)Tmax * V + 64) : nullptr;   // (read in whole 64-entry rows: up to 63 floats past the end)
-  if (geom) *geom = ge;
   if (buf) *buf = b;
   return c.bytes();
 }
 
-// The persistent kernel works on one-sequence groups (NG = 1).  A sizing call (no base) answers for both geometries:
-// the choice can still change before the compute call (the first launch on a device is verified).
-size_t den_workspace(const pk2_den_graph* g, int N, int Tmax, DenGeom* geom, DenBuffers* buf,
-                     void* base) {
-  const bool persist = den_persist_version(g, N) != 0;
-  if (base) return den_workspace_as(g, N, Tmax, persist, geom, buf, base);
-  const size_t a = den_workspace_as(g, N, Tmax, false, nullptr, nullptr, nullptr);
-  const size_t b = den_workspace_as(g, N, Tmax, true, nullptr, nullptr, nullptr);
-  den_workspace_as(g, N, Tmax, persist, geom, buf, nullptr);
-  return std::max(a, b);
+size_t den_workspace(const pk2_den_graph* g, int N, int Tmax, DenPlan* plan, DenBuffers* buf, void* base) {
+  const DenPlan pl = den_plan(g, N, Tmax);
+  if (plan) *plan = pl;
+  const size_t own = den_carve(g, pl, pl.NG, pl.form != 0, buf, base);
+  if (base) return own;
+  return std::max(den_carve(g, pl, pl.NG_frames, false, nullptr, nullptr), den_carve(g, pl, 1, true, nullptr, nullptr));
 }
 
 static StepGraphs g_den_graphs;
@@ -1541,52 +1598,18 @@ int get_side_stream(hipStream_t main, SideStream** out) {
   return PK2_OK;
 }
 
-template <int NG>
-static int den_compute_t(pk2_den_graph* g, const float* logits, int64_t seq_stride,
-                         int64_t frame_stride, const int32_t* lengths_host, const DenGeom& ge,
-                         const DenBuffers& b, float leaky, hipStream_t stream, const NumDeferred* tail, const DenZeroRows* zr) {
-  const int Tmax = ge.Tmax, G = ge.G;
-  const size_t GN = (size_t)G * NG;
-  // Round 6: on the bench path (NG = 1, state-x kernels, second persistent form with the x gather) the passes in front of the
-  // recursions are ONE launch (den_prep1) and the ones behind them one more (den_tail1); PK2_DEN_MERGE=0 keeps the round-5
-  // launches.  The caller's gradient rows (zr) are zeroed by that launch, or by one of their own on every other path.
-  static const bool merge_env = [] { const char* e = getenv("PK2_DEN_MERGE"); return !(e && atoi(e) == 0); }();
-  bool zero_pending = zr != nullptr && zr->grad != nullptr;
-  // lengths travel as kernel arguments (no dependence on the lifetime of the caller's host array);
-  // padding sequences get 0 frames
-  for (size_t base = 0; base < GN; base += IntPack::kN) {
-    IntPack pack;
-    for (int i = 0; i < IntPack::kN; ++i) {
-      size_t n = base + i;
-      pack.v[i] = (n < (size_t)ge.N) ? lengths_host[n] : 0;
-    }
-    int cnt = (int)std::min<size_t>(IntPack::kN, GN - base);
-    hipLaunchKernelGGL(store_ints, dim3(1), dim3(64), 0, stream, pack, cnt, b.lengths + base);
-  }
-  // alpha / beta / gamma rows of split ("atomic") chunks accumulate with atomics -> start at zero
-  // (on the state-x path every alpha / beta' row and every occupancy is written by a plain store unless a row is
-  // split over several chunks, and values of frames beyond a sequence's end are only ever selected away, never used
-  // in arithmetic: the 0.9 GB of fills per call are skipped then)
-  const bool sx = den_use_sx(g);
-  const HostOrdering& hf = sx ? g->h_fwdv : g->h_fwd;
-  const HostOrdering& hb = sx ? g->h_bwdv : g->h_bwd;
-  auto any_atomic = [](const HostOrdering& h) { for (int32_t a : h.atomic) if (a) return true; return false; };
-  const bool need_fill = !sx || any_atomic(hf) || any_atomic(hb);
-  if (need_fill) {
-    PK2_HIP(hipMemsetAsync(b.alpha, 0, GN * (Tmax + 1) * (size_t)g->S * sizeof(float), stream));
-    if (b.alphav != b.alpha) PK2_HIP(hipMemsetAsync(b.alphav, 0, GN * (Tmax + 1) * (size_t)g->Vo * sizeof(float), stream));
-    PK2_HIP(hipMemsetAsync(b.beta, 0, GN * (Tmax + 1) * (size_t)(sx ? g->V : g->S) * 2 * sizeof(float), stream));
-    PK2_HIP(hipMemsetAsync(b.gamma, 0, GN * (size_t)Tmax * g->P * sizeof(float), stream));
-  }
-  const bool persist = ge.persist && NG == 1 && sx;
-  const size_t bpart_floats = GN * (Tmax + 1) * std::max<size_t>(hb.n_chunks, persist ? kPR : 0) * (sx ? 2 : 1);
-  bool use_prep = false;
-  if (merge_env && persist && NG == 1 && den_persist_version(g, ge.N) == 2 && !need_fill) {
-    const char* xg_e0 = getenv("PK2_DEN_XGATHER");
-    use_prep = !(xg_e0 && atoi(xg_e0) == 0) && g->P <= 32767 && g->V >= g->P && g->p2_rowarrays == kP2RowArrays;
-  }
-  if (!use_prep) PK2_HIP(hipMemsetAsync(b.bpart, 0, bpart_floats * sizeof(float), stream));
+// The arguments of one den_compute call, as its three phases need them.
+struct DenCall {
+  pk2_den_graph* g; const float* logits; int64_t seq_stride, frame_stride; const int32_t* lengths_host;
+  const DenBuffers& b; float leaky; hipStream_t stream; const NumDeferred* tail;
+};
 
+// The kernels' parameter block for a plan.  brec = 2: what the launches in front of the recursions and the frame kernels'
+// copy receive on every route (the caller lowers it for the second persistent form and what follows it).
+static DenParams den_params(const DenCall& c, const DenPlan& pl) {
+  const pk2_den_graph* g = c.g;
+  const DenBuffers& b = c.b;
+  const bool sx = pl.sx;
   DenParams p;
   p.fwd = sx ? g->fwdv : g->fwd; p.bwd = sx ? g->bwdv : g->bwd; p.gam = g->gam;
   p.pi = g->d_pi;
@@ -1597,193 +1620,224 @@ static int den_compute_t(pk2_den_graph* g, const float* logits, int64_t seq_stri
   p.voff = g->d_voff; p.ooff = g->d_ooff; p.opdf = g->d_opdf; p.ovirt = g->d_ovirt; p.loop_prob = g->d_loop_prob;
   p.alphav = b.alphav; p.xl = b.xl; p.V = sx ? g->V : g->S; p.Vo = sx ? g->Vo : g->S;
   p.brec = 2;
-  p.S = g->S; p.P = g->P; p.Tmax = Tmax;
-  p.leaky = leaky; p.pi_sum = (float)g->pi_sum; p.wu = (float)(kBetaFloor * g->pi_sum / g->S);
-  p.debug = getenv("PK2_DEN_DEBUG") ? atoi(getenv("PK2_DEN_DEBUG")) : 0;
-  p.beta_seed = 1.0f;
-  if (const char* env = getenv("PK2_DEN_DEBUG_BETA_SEED")) { const float v = (float)atof(env); if (v > 0.f) p.beta_seed = v; }
-  if (persist) { p.fwd.n_chunks = kPR; p.bwd.n_chunks = kPR; }     // partial sums per frame: one per workgroup of a team
+  p.S = g->S; p.P = g->P; p.Tmax = pl.Tmax;
+  p.leaky = c.leaky; p.pi_sum = (float)g->pi_sum; p.wu = (float)(kBetaFloor * g->pi_sum / g->S);
+  p.debug = pl.env.debug;
+  p.beta_seed = pl.env.beta_seed;
+  p.fwd.n_chunks = pl.ncf; p.bwd.n_chunks = pl.ncb;
+  return p;
+}
 
-  const size_t lds = den_lds_bytes(g->P, NG);
+// Phase 1: everything in front of the recursions -- lengths, fills, the frame kernels' parameter block, the caller's
+// gradient rows (`zr`, may be null), the initial vectors and the exp(logits) copies the plan's recursions read.
+// Round 6: on the bench path (plan.prep_merged) all of it but the lengths is ONE launch, den_prep1.
+template <int NG>
+static int den_prologue(const DenCall& c, const DenPlan& pl, const DenParams& p, const DenZeroRows* zr, ParamSlot<DenParams>** slot) {
+  const pk2_den_graph* g = c.g;
+  const DenBuffers& b = c.b;
+  hipStream_t stream = c.stream;
+  const int Tmax = pl.Tmax, G = pl.G;
+  const size_t GN = (size_t)G * NG;
+  const bool sx = pl.sx, persist = pl.form != 0;
+  // lengths travel as kernel arguments (no dependence on the lifetime of the caller's host array);
+  // padding sequences get 0 frames
+  for (size_t base = 0; base < GN; base += IntPack::kN) {
+    IntPack pack;
+    for (int i = 0; i < IntPack::kN; ++i) {
+      size_t n = base + i;
+      pack.v[i] = (n < (size_t)pl.N) ? c.lengths_host[n] : 0;
+    }
+    int cnt = (int)std::min<size_t>(IntPack::kN, GN - base);
+    hipLaunchKernelGGL(store_ints, dim3(1), dim3(64), 0, stream, pack, cnt, b.lengths + base);
+  }
+  // alpha / beta / gamma rows of split ("atomic") chunks accumulate with atomics -> start at zero
+  if (pl.need_fill) {
+    PK2_HIP(hipMemsetAsync(b.alpha, 0, GN * (Tmax + 1) * (size_t)g->S * sizeof(float), stream));
+    if (b.alphav != b.alpha) PK2_HIP(hipMemsetAsync(b.alphav, 0, GN * (Tmax + 1) * (size_t)g->Vo * sizeof(float), stream));
+    PK2_HIP(hipMemsetAsync(b.beta, 0, GN * (Tmax + 1) * (size_t)(sx ? g->V : g->S) * 2 * sizeof(float), stream));
+    PK2_HIP(hipMemsetAsync(b.gamma, 0, GN * (size_t)Tmax * g->P * sizeof(float), stream));
+  }
+  // (as carved: the fallback's chunk counts where they exceed the persistent kernel's kPR)
+  const size_t bpart_floats = GN * (Tmax + 1) * std::max<size_t>((sx ? g->h_bwdv : g->h_bwd).n_chunks, pl.ncb) * (sx ? 2 : 1);
+  if (!pl.prep_merged) PK2_HIP(hipMemsetAsync(b.bpart, 0, bpart_floats * sizeof(float), stream));
   PK2_DYN_LDS_ONCE(den_fwd_step<NG>, 160 * 1024);
   PK2_DYN_LDS_ONCE(den_bwd_step<NG>, 160 * 1024);
-  ParamSlot<DenParams>* slot;
-  int rc = get_param_slot(g_den_slots, NG, stream, &slot);
+  int rc = get_param_slot(g_den_slots, NG, stream, slot);
   if (rc) return rc;
   // (the frame kernels read their parameters from this block; the persistent kernels carry their own)
-  if (!(merge_env && persist)) hipLaunchKernelGGL(param_block_store<DenParams>, dim3(1), dim3(1), 0, stream, p, slot->params);
-  const DenParams* pb = slot->params;
-  const StepCounter* cnt = slot->counter;
+  if (!(pl.env.merge && persist)) hipLaunchKernelGGL(param_block_store<DenParams>, dim3(1), dim3(1), 0, stream, p, (*slot)->params);
 
-  // Two kernel families: the "state-x" path (exp(logit) as a per-virtual-state factor; den_use_sx), else LDS-staged
-  // exp(logits) + arc-based occupancies.
-  char key[96];
+  const bool zero = zr != nullptr && zr->grad != nullptr;
   const int init_bx = std::min(256, (g->S + 255) / 256);
-  if constexpr (NG == 1) {
-    if (use_prep) {
-      DenPrepJobs j{Tmax * G, init_bx * G, init_bx, 64, zero_pending ? Tmax * zr->N : 0, bpart_floats, logits, seq_stride, frame_stride,
-                    b.xv, zero_pending ? zr->grad : nullptr, zero_pending ? zr->gss : 0, zero_pending ? zr->gfs : 0, zero_pending ? zr->N : 0};
-      hipLaunchKernelGGL(den_prep1, dim3(j.exp_blocks + j.init_blocks + j.bpart_blocks + j.zero_blocks), dim3(256), 0, stream, p, j);
-      zero_pending = false;
-    } else if (zero_pending) {        // the gradient rows alone (same kernel, one job)
-      DenPrepJobs j{0, 0, 1, 0, Tmax * zr->N, 0, logits, seq_stride, frame_stride, nullptr, zr->grad, zr->gss, zr->gfs, zr->N};
-      hipLaunchKernelGGL(den_prep1, dim3(j.zero_blocks), dim3(256), 0, stream, p, j);
-      zero_pending = false;
-    }
-  }
-  if (zero_pending) {
-    DenParams pz = p;
-    DenPrepJobs j{0, 0, 1, 0, Tmax * zr->N, 0, logits, seq_stride, frame_stride, nullptr, zr->grad, zr->gss, zr->gfs, zr->N};
-    hipLaunchKernelGGL(den_prep1, dim3(j.zero_blocks), dim3(256), 0, stream, pz, j);
-    zero_pending = false;
-  }
-  if (!use_prep) hipLaunchKernelGGL(den_init<NG>, dim3(init_bx, G), dim3(256), 0, stream, p);
-  if (sx) {
-    // a frame's entries are cut into slices on grid.z so that short minibatches still fill the chip
-    auto slices = [&](int n) { return std::max(1, std::min((n + 1023) / 1024, (4096 + Tmax * G - 1) / (Tmax * G))); };
-    const size_t exp_lds = (size_t)g->P * NG * sizeof(float);
-    const int form = persist ? den_persist_version(g, ge.N) : 0;
-    // (the second persistent kernel gathers x by pdf from plain exp(logits) rows, which fit the xv buffer when V >= P;
-    // PK2_DEN_XGATHER=0 keeps the expanded copies)
-    const char* xg_e = getenv("PK2_DEN_XGATHER");      // (read per call: the tests switch it inside one process)
-    const bool xg_env = !(xg_e && atoi(xg_e) == 0);
-    const bool xgather = xg_env && form == 2 && NG == 1 && g->P <= 32767 && g->V >= g->P && g->p2_rowarrays == kP2RowArrays;
-    if (form == 2 && NG == 1) p.brec = 1;       // (dense btilde' records: den_kernels.h; the frame kernels' copy of p keeps 2)
-    if (xgather && use_prep) {
-      // (den_prep1 has written the rows)
-    } else if (xgather) {
-      hipLaunchKernelGGL(den_exp_rows, dim3(Tmax, G), dim3(256), 0, stream, logits, seq_stride, frame_stride, b.lengths, b.xv,
+  // den_prep1's jobs: the gradient rows alone, or with the exp rows, the initial vectors and the bpart fill in front
+  DenPrepJobs j{0, 0, 1, 0, zero ? Tmax * zr->N : 0, 0, c.logits, c.seq_stride, c.frame_stride, nullptr,
+                zero ? zr->grad : nullptr, zero ? zr->gss : 0, zero ? zr->gfs : 0, zero ? zr->N : 0};
+  if (pl.prep_merged) { j.exp_blocks = Tmax * G; j.init_blocks = init_bx * G; j.init_bx = init_bx; j.bpart_blocks = 64; j.bpart_floats = bpart_floats; j.xp = b.xv; }
+  const int prep_blocks = j.exp_blocks + j.init_blocks + j.bpart_blocks + j.zero_blocks;
+  if (pl.prep_merged || zero) hipLaunchKernelGGL(den_prep1, dim3(prep_blocks), dim3(256), 0, stream, p, j);
+  if (!pl.prep_merged) hipLaunchKernelGGL(den_init<NG>, dim3(init_bx, G), dim3(256), 0, stream, p);
+
+  // a frame's entries are cut into slices on grid.z so that short minibatches still fill the chip
+  auto slices = [&](int n) { return std::max(1, std::min((n + 1023) / 1024, (4096 + Tmax * G - 1) / (Tmax * G))); };
+  switch (pl.exp_kernel) {
+    case kExpPrep1: break;      // (den_prep1 has written the rows)
+    case kExpRows:
+      hipLaunchKernelGGL(den_exp_rows, dim3(Tmax, G), dim3(256), 0, stream, c.logits, c.seq_stride, c.frame_stride, b.lengths, b.xv,
                          g->P, Tmax);
-    } else if (persist || (exp_lds <= kGammaMaxLds && !getenv("PK2_DEN_EXP_GATHER"))) {
+      break;
+    case kExpStatesLds: {
       PK2_DYN_LDS_ONCE(den_exp_states_lds<NG>, 160 * 1024);
       const int z = std::max(1, std::min((g->V + kExpThreads - 1) / kExpThreads, (2048 + Tmax * G - 1) / (Tmax * G)));
-      hipLaunchKernelGGL(den_exp_states_lds<NG>, dim3(Tmax, G, z), dim3(kExpThreads), exp_lds, stream, logits, seq_stride,
-                         frame_stride, b.lengths, g->d_vpdf, b.beta, g->V, g->d_loop_pdf, b.xl, g->S, g->P, Tmax,
-                         persist ? b.xv : nullptr);
-    } else {
+      hipLaunchKernelGGL(den_exp_states_lds<NG>, dim3(Tmax, G, z), dim3(kExpThreads), (size_t)g->P * NG * sizeof(float), stream,
+                         c.logits, c.seq_stride, c.frame_stride, b.lengths, g->d_vpdf, b.beta, g->V, g->d_loop_pdf, b.xl, g->S, g->P,
+                         Tmax, persist ? b.xv : nullptr);
+      break;
+    }
+    case kExpStates: {
       const int zv = slices(g->V), zl = slices(g->S);
-      hipLaunchKernelGGL(den_exp_states<NG>, dim3(Tmax, G, zv + zl), dim3(256), 0, stream, logits, seq_stride, frame_stride,
+      hipLaunchKernelGGL(den_exp_states<NG>, dim3(Tmax, G, zv + zl), dim3(256), 0, stream, c.logits, c.seq_stride, c.frame_stride,
                          b.lengths, g->d_vpdf, b.beta, g->V, g->d_loop_pdf, b.xl, g->S, Tmax, zv);
+      break;
     }
-    PK2_LAUNCH_CHECK();
-    bool ran = false, num_rode = false;
-    int persist_form = 0;
-    if (persist) {      // both recursions of every sequence in one launch (chain_den_persist.hip / chain_den_persist2.hip)
-      rc = form == 2 ? den_persist2_launch(g, p, b.xv, lengths_host, ge.N, stream, &ran, tail, &num_rode, xgather)
-                     : den_persist_launch(g, p, b.xv, lengths_host, ge.N, stream, &ran);
-      if (rc) return rc;
-      persist_form = ran ? form : 0;
-      if (!ran) {       // the device failed the first-use verification: the frame kernels, with their own chunk counts
-        DenGeom ge2 = ge;
-        ge2.persist = false;
-        DenZeroRows none{};       // (the gradient rows have been zeroed above)
-        return den_compute_t<NG>(g, logits, seq_stride, frame_stride, lengths_host, ge2, b, leaky, stream, tail, zr ? &none : nullptr);
-      }
-    } else {
-      // the backward chain needs only exp(logits): forward frame `step` and backward frame Tmax-1-step
-      // share one launch
-      const dim3 gridS(g->fwdv.n_chunks + g->bwdv.n_chunks, G);
-      snprintf(key, sizeof(key), "den_sx_%d_%u_%d_%p", NG, gridS.x, G, (void*)stream);
-      rc = g_den_graphs.run(key, Tmax, slot->counter, stream, [&](hipStream_t s, int j) {
-        hipLaunchKernelGGL(den_step_sx<NG>, gridS, dim3(kDenThreads), 0, s, pb, cnt, j);
-      });
-      if (rc) return rc;
-    }
-#ifdef PK2_DEN_PROFILE
-    hipLaunchKernelGGL(den_prof_print, dim3(1), dim3(1), 0, stream, Tmax);
-#endif
-    bool tail_merged = false;
-    if constexpr (NG == 1) {
-      if (merge_env && (!ran || persist_form == 2) && (size_t)(Tmax + 1) * 2 * sizeof(float) <= 60 * 1024) {
-        DenTailCheck ck{};
-        if (ran && !den_persist2_tail_check(stream, &ck)) ck = DenTailCheck{};
-        // (test hook, read per call: PK2_DEN_TEST_FAIL=1 makes the folded check behave as if the persistent launch had given up)
-        if (ck.ctl) { const char* tf_e = getenv("PK2_DEN_TEST_FAIL"); if (tf_e && atoi(tf_e) == 1) ck.ntasks = -1; }
-        hipLaunchKernelGGL(den_tail1, dim3(G), dim3(256), (size_t)(Tmax + 1) * 2 * sizeof(float), stream, p, b.csum, b.den_lp, b.kscale,
-                           b.check, ck);
-        tail_merged = true;
-      }
-    }
-    if (!tail_merged) {
-      hipLaunchKernelGGL(den_csum<NG>, dim3(Tmax + 1, G), dim3(256), 0, stream, p, b.csum);
-      hipLaunchKernelGGL(den_finalize<NG>, dim3(G, NG), dim3(256), 0, stream, p, b.den_lp);
-      if (ran && persist_form == 2) den_persist2_check_launch(b.den_lp, ge.N, stream);
-      else if (ran) den_persist_check_launch(b.den_lp, ge.N, stream);
-      hipLaunchKernelGGL(den_scales<NG>, dim3(G, NG), dim3(256), 0, stream, p, b.csum, b.kscale, b.check);
-    }
-    const size_t row_lds = (size_t)g->P * NG * sizeof(float);
-    const bool lds_row = row_lds <= kGammaMaxLds && !getenv("PK2_DEN_GAMMA_GATHER");
-    PK2_DYN_LDS_ONCE((den_gamma_states_num<NG, false>), 160 * 1024);
-    PK2_DYN_LDS_ONCE((den_gamma_states_num<NG, true>), 160 * 1024);
-    PK2_DYN_LDS_ONCE(den_gamma_states_lds<NG>, 160 * 1024);
-    if (tail && tail->valid && !num_rode) {
-      if (lds_row && std::max(row_lds, (size_t)tail->lds) <= kGammaMaxLds)
-        hipLaunchKernelGGL((den_gamma_states_num<NG, true>), dim3(Tmax + tail->N, G), dim3(kGammaThreads),
-                           std::max(row_lds, (size_t)tail->lds), stream, p, b.csum, b.kscale, tail->p, tail->N, tail->stage ? 1 : 0);
-      else
-        hipLaunchKernelGGL((den_gamma_states_num<NG, false>), dim3(Tmax + tail->N, G), dim3(256), tail->lds, stream, p, b.csum,
-                           b.kscale, tail->p, tail->N, tail->stage ? 1 : 0);
-    } else if (lds_row) {
-      hipLaunchKernelGGL(den_gamma_states_lds<NG>, dim3(Tmax, G), dim3(kGammaThreads), row_lds, stream, p, b.csum, b.kscale);
-    } else {
-      hipLaunchKernelGGL(den_gamma_states<NG>, dim3(Tmax, G), dim3(256), 0, stream, p, b.csum, b.kscale);
-    }
-    PK2_LAUNCH_CHECK();
-    return PK2_OK;
-  } else {
-    hipLaunchKernelGGL(den_exp_transpose<NG>, dim3(Tmax, G), dim3(256), 0, stream, logits, seq_stride,
-                       frame_stride, b.lengths, b.xs, g->P, Tmax);
-    PK2_LAUNCH_CHECK();
-    const dim3 gridF(g->fwd.n_chunks, G);
-    snprintf(key, sizeof(key), "den_fwd_%d_%u_%d_%zu_%p", NG, gridF.x, G, lds, (void*)stream);
-    rc = g_den_graphs.run(key, Tmax, slot->counter, stream, [&](hipStream_t s, int j) {
-      hipLaunchKernelGGL(den_fwd_step<NG>, gridF, dim3(kDenThreads), lds, s, pb, cnt, j);
-    });
-    if (rc) return rc;
-    hipLaunchKernelGGL(den_finalize<NG>, dim3(G, NG), dim3(256), 0, stream, p, b.den_lp);
-    const dim3 gridB(std::max(g->bwd.n_chunks, g->gam.n_chunks), G);
-    snprintf(key, sizeof(key), "den_bwd_%d_%u_%d_%zu_%p", NG, gridB.x, G, lds, (void*)stream);
-    rc = g_den_graphs.run(key, Tmax, slot->counter, stream, [&](hipStream_t s, int j) {
-      hipLaunchKernelGGL(den_bwd_step<NG>, gridB, dim3(kDenBwdThreads), lds, s, pb, cnt, j);
-    });
-    if (rc) return rc;
+    case kExpTranspose:
+      hipLaunchKernelGGL(den_exp_transpose<NG>, dim3(Tmax, G), dim3(256), 0, stream, c.logits, c.seq_stride, c.frame_stride,
+                         b.lengths, b.xs, g->P, Tmax);
+      break;
   }
-  hipLaunchKernelGGL(den_check<NG>, dim3(G), dim3(kDenThreads), 0, stream, p, b.check);
   PK2_LAUNCH_CHECK();
-  if (tail && tail->valid) return num_launch_deferred(*tail, stream);
   return PK2_OK;
 }
 
-int den_compute(pk2_den_graph* g, const float* logits, int64_t seq_stride, int64_t frame_stride,
-                const int32_t* lengths_host, const DenGeom& ge, const DenBuffers& b, float leaky,
-                hipStream_t stream, const NumDeferred* tail, const DenZeroRows* zr) {
-  int rc = den_upload(g);
+// Phase 2: the alpha / beta recursions of the plan.  *ran = false: a persistent form failed the first-use verification
+// of its device (the caller falls back to the frame kernels); *num_rode: the deferred numerator ran inside the launch.
+template <int NG>
+static int den_recursions(const DenCall& c, const DenPlan& pl, const DenParams& p, const ParamSlot<DenParams>& slot, bool* ran,
+                          bool* num_rode) {
+  pk2_den_graph* g = c.g;
+  hipStream_t stream = c.stream;
+  const int Tmax = pl.Tmax, G = pl.G;
+  // both recursions of every sequence in one launch (chain_den_persist2.hip / chain_den_persist.hip)
+  if (pl.form == 2)
+    return den_persist2_launch(g, p, c.b.xv, c.lengths_host, pl.N, stream, ran, c.tail, pl.env.num_ride ? num_rode : nullptr, pl.xgather);
+  if (pl.form == 1) return den_persist_launch(g, p, c.b.xv, c.lengths_host, pl.N, stream, ran);
+  *ran = true;
+  const DenParams* pb = slot.params;
+  const StepCounter* cnt = slot.counter;
+  char key[96];
+  if (pl.sx) {
+    // the backward chain needs only exp(logits): forward frame `step` and backward frame Tmax-1-step
+    // share one launch
+    const dim3 gridS(g->fwdv.n_chunks + g->bwdv.n_chunks, G);
+    snprintf(key, sizeof(key), "den_sx_%d_%u_%d_%p", NG, gridS.x, G, (void*)stream);
+    return g_den_graphs.run(key, Tmax, slot.counter, stream, [&](hipStream_t s, int j) {
+      hipLaunchKernelGGL(den_step_sx<NG>, gridS, dim3(kDenThreads), 0, s, pb, cnt, j);
+    });
+  }
+  const size_t lds = den_lds_bytes(g->P, NG);
+  const dim3 gridF(g->fwd.n_chunks, G);
+  snprintf(key, sizeof(key), "den_fwd_%d_%u_%d_%zu_%p", NG, gridF.x, G, lds, (void*)stream);
+  int rc = g_den_graphs.run(key, Tmax, slot.counter, stream, [&](hipStream_t s, int j) {
+    hipLaunchKernelGGL(den_fwd_step<NG>, gridF, dim3(kDenThreads), lds, s, pb, cnt, j);
+  });
   if (rc) return rc;
-  if (den_choose_ng(g) == 0) {
-    set_error("den graph: num_pdfs %d too large for the LDS-staged kernel", g->P);
-    return PK2_ERR_LIMIT;
+  hipLaunchKernelGGL(den_finalize<NG>, dim3(G, NG), dim3(256), 0, stream, p, c.b.den_lp);
+  const dim3 gridB(std::max(g->bwd.n_chunks, g->gam.n_chunks), G);
+  snprintf(key, sizeof(key), "den_bwd_%d_%u_%d_%zu_%p", NG, gridB.x, G, lds, (void*)stream);
+  return g_den_graphs.run(key, Tmax, slot.counter, stream, [&](hipStream_t s, int j) {
+    hipLaunchKernelGGL(den_bwd_step<NG>, gridB, dim3(kDenBwdThreads), lds, s, pb, cnt, j);
+  });
+}
+
+// Phase 3: log-probability, consistency check, scales and occupancies from what the recursions of `pl` left (state-x: one
+// launch, den_tail1, unless the plan or the first persistent form rules it out), and the deferred numerator -- in the
+// occupancy kernel's launch on the state-x family, after den_check on the general one -- unless it rode already.
+template <int NG>
+static int den_epilogue(const DenCall& c, const DenPlan& pl, const DenParams& p, bool num_rode) {
+  const pk2_den_graph* g = c.g;
+  const DenBuffers& b = c.b;
+  hipStream_t stream = c.stream;
+  const NumDeferred* tail = c.tail;
+  const int Tmax = pl.Tmax, G = pl.G;
+  if (!pl.sx) {     // (den_bwd_step has left the occupancies)
+    hipLaunchKernelGGL(den_check<NG>, dim3(G), dim3(kDenThreads), 0, stream, p, b.check);
+    PK2_LAUNCH_CHECK();
+    return tail && tail->valid ? num_launch_deferred(*tail, stream) : PK2_OK;
   }
-  switch (ge.NG) {
-    case 4: return den_compute_t<4>(g, logits, seq_stride, frame_stride, lengths_host, ge, b, leaky, stream, tail, zr);
-    case 2: return den_compute_t<2>(g, logits, seq_stride, frame_stride, lengths_host, ge, b, leaky, stream, tail, zr);
-    default: return den_compute_t<1>(g, logits, seq_stride, frame_stride, lengths_host, ge, b, leaky, stream, tail, zr);
+#ifdef PK2_DEN_PROFILE
+  hipLaunchKernelGGL(den_prof_print, dim3(1), dim3(1), 0, stream, Tmax);
+#endif
+  if (pl.tail_mergeable && pl.form != 1) {
+    DenTailCheck ck{};      // (the persistent launch's check as a phase of the kernel)
+    if (pl.form == 2 && !den_persist2_tail_check(stream, &ck)) ck = DenTailCheck{};
+    if (ck.ctl && pl.env.test_fail) ck.ntasks = -1;      // (test hook: as if the persistent launch had given up)
+    hipLaunchKernelGGL(den_tail1, dim3(G), dim3(256), (size_t)(Tmax + 1) * 2 * sizeof(float), stream, p, b.csum, b.den_lp, b.kscale,
+                       b.check, ck);
+  } else {
+    hipLaunchKernelGGL(den_csum<NG>, dim3(Tmax + 1, G), dim3(256), 0, stream, p, b.csum);
+    hipLaunchKernelGGL(den_finalize<NG>, dim3(G, NG), dim3(256), 0, stream, p, b.den_lp);
+    if (pl.form == 2) den_persist2_check_launch(b.den_lp, pl.N, stream);
+    else if (pl.form == 1) den_persist_check_launch(b.den_lp, pl.N, stream);
+    hipLaunchKernelGGL(den_scales<NG>, dim3(G, NG), dim3(256), 0, stream, p, b.csum, b.kscale, b.check);
   }
+  const size_t row_lds = (size_t)g->P * NG * sizeof(float);
+  PK2_DYN_LDS_ONCE((den_gamma_states_num<NG, false>), 160 * 1024);
+  PK2_DYN_LDS_ONCE((den_gamma_states_num<NG, true>), 160 * 1024);
+  PK2_DYN_LDS_ONCE(den_gamma_states_lds<NG>, 160 * 1024);
+  if (tail && tail->valid && !num_rode) {
+    if (pl.gamma_lds && std::max(row_lds, (size_t)tail->lds) <= kGammaMaxLds)
+      hipLaunchKernelGGL((den_gamma_states_num<NG, true>), dim3(Tmax + tail->N, G), dim3(kGammaThreads),
+                         std::max(row_lds, (size_t)tail->lds), stream, p, b.csum, b.kscale, tail->p, tail->N, tail->stage ? 1 : 0);
+    else
+      hipLaunchKernelGGL((den_gamma_states_num<NG, false>), dim3(Tmax + tail->N, G), dim3(256), tail->lds, stream, p, b.csum,
+                         b.kscale, tail->p, tail->N, tail->stage ? 1 : 0);
+  } else if (pl.gamma_lds) {
+    hipLaunchKernelGGL(den_gamma_states_lds<NG>, dim3(Tmax, G), dim3(kGammaThreads), row_lds, stream, p, b.csum, b.kscale);
+  } else {
+    hipLaunchKernelGGL(den_gamma_states<NG>, dim3(Tmax, G), dim3(256), 0, stream, p, b.csum, b.kscale);
+  }
+  PK2_LAUNCH_CHECK();
+  return PK2_OK;
 }
 
 template <int NG>
-static void launch_gamma_out(const DenGeom& ge, const DenBuffers& b, int P, float scale, float* out,
-                             int64_t ss, int64_t fs, hipStream_t stream) {
-  hipLaunchKernelGGL(den_gamma_out<NG>, dim3(ge.Tmax, ge.G), dim3(256), 0, stream, b.gamma, b.lengths,
-                     ge.N, P, ge.Tmax, scale, out, ss, fs);
+static int den_compute_t(const DenCall& c, DenPlan pl, const DenZeroRows* zr) {
+  for (;;) {
+    ParamSlot<DenParams>* slot;
+    bool ran = false, num_rode = false;
+    DenParams p = den_params(c, pl);
+    int rc = den_prologue<NG>(c, pl, p, zr, &slot);
+    if (rc) return rc;
+    if (pl.form == 2) p.brec = 1;       // (dense btilde' records: den_kernels.h)
+    rc = den_recursions<NG>(c, pl, p, *slot, &ran, &num_rode);
+    if (rc) return rc;
+    if (ran) return den_epilogue<NG>(c, pl, p, num_rode);
+    // The device failed the first-use verification of the persistent form: once more with the frame kernels' plan (their
+    // own chunk counts) on the same buffers.  They get their prologue in full -- the fills and initial vectors again,
+    // their own exp copies and parameter block -- but for the gradient rows, which are zero already.
+    den_plan_route(c.g, pl, 0, NG);
+    zr = nullptr;
+  }
 }
 
-void den_gamma_out_launch(const DenGeom& ge, const DenBuffers& b, int P, float scale, float* out,
-                          int64_t ss, int64_t fs, hipStream_t stream) {
-  switch (ge.NG) {
-    case 4: launch_gamma_out<4>(ge, b, P, scale, out, ss, fs, stream); break;
-    case 2: launch_gamma_out<2>(ge, b, P, scale, out, ss, fs, stream); break;
-    default: launch_gamma_out<1>(ge, b, P, scale, out, ss, fs, stream); break;
+int den_compute(pk2_den_graph* g, const float* logits, int64_t seq_stride, int64_t frame_stride,
+                const int32_t* lengths_host, const DenPlan& pl, const DenBuffers& b, float leaky,
+                hipStream_t stream, const NumDeferred* tail, const DenZeroRows* zr) {
+  int rc = den_upload(g);
+  if (rc) return rc;
+  if (pl.rc) {
+    set_error("den graph: num_pdfs %d too large for the LDS-staged kernel", g->P);
+    return pl.rc;
   }
+  const DenCall c{g, logits, seq_stride, frame_stride, lengths_host, b, leaky, stream, tail};
+  return dispatch_ng(pl.NG, [&](auto ng) { return den_compute_t<decltype(ng)::value>(c, pl, zr); });
+}
+
+void den_gamma_out_launch(const DenPlan& pl, const DenBuffers& b, int P, float scale, float* out,
+                          int64_t ss, int64_t fs, hipStream_t stream) {
+  dispatch_ng(pl.NG, [&](auto ng) {
+    hipLaunchKernelGGL(den_gamma_out<decltype(ng)::value>, dim3(pl.Tmax, pl.G), dim3(256), 0, stream, b.gamma, b.lengths,
+                       pl.N, P, pl.Tmax, scale, out, ss, fs);
+  });
 }
 
 }  // namespace pk2
@@ -1803,30 +1857,36 @@ extern "C" int pk2_chain_den_fwd_bwd(const pk2_den_graph* gc, const float* logit
     PK2_REQUIRE(lengths[n] > 0, "den_fwd_bwd: sequence %d has no frames", n);
     Tmax = std::max(Tmax, lengths[n]);
   }
-  DenGeom ge; DenBuffers b;
-  size_t need = den_workspace(g, num_seqs, Tmax, &ge, &b, workspace);
+  DenPlan pl; DenBuffers b;
+  size_t need = den_workspace(g, num_seqs, Tmax, &pl, &b, workspace);
   PK2_REQUIRE(workspace_bytes >= need, "den_fwd_bwd: workspace %zu < %zu", workspace_bytes, need);
-  int rc = den_compute(g, logits, seq_stride, frame_stride, lengths, ge, b, leaky, stream);
+  int rc = den_compute(g, logits, seq_stride, frame_stride, lengths, pl, b, leaky, stream);
   if (rc) return rc;
-  if (gamma) den_gamma_out_launch(ge, b, g->P, 1.0f, gamma, gamma_seq_stride, gamma_frame_stride, stream);
+  if (gamma) den_gamma_out_launch(pl, b, g->P, 1.0f, gamma, gamma_seq_stride, gamma_frame_stride, stream);
   if (den_logprob)
     PK2_HIP(hipMemcpyAsync(den_logprob, b.den_lp, num_seqs * sizeof(float), hipMemcpyDeviceToDevice, stream));
   PK2_LAUNCH_CHECK();
   return PK2_OK;
 }
 
-// Which kernels a denominator call on `num_seqs` sequences takes: 0 = general (per-arc pdf), 1 = state-x, a launch per
-// frame, 2 = state-x, persistent recursion kernel (chain_den_persist.hip).  Reporting hook (bench.py).
+// Reporting hooks (bench.py, the tests): fields of the plan a call on `num_seqs` sequences gets.
+// Kernels: 0 = general (per-arc pdf), 1 = state-x, a launch per frame, 2 = state-x, persistent recursion kernel.
 extern "C" int32_t pk2_den_graph_path(const pk2_den_graph* g, int32_t num_seqs) {
   if (!g) return -1;
-  if (!pk2::den_use_sx(g)) return 0;
-  return pk2::den_persist_version(g, num_seqs) != 0 ? 2 : 1;
+  const DenPlan pl = den_plan(g, num_seqs, 1);
+  return !pl.sx ? 0 : (pl.form != 0 ? 2 : 1);
 }
 
-// Which form of the persistent recursion kernel such a call takes: 0 = none (frame kernels), 1 = den_persist_kernel
-// (everything resident), 2 = den_persist2_kernel (chunked table, two resident passes, streamed overflow).
+// Form of the persistent recursion kernel: 0 = none (frame kernels), 1 = den_persist_kernel (everything resident),
+// 2 = den_persist2_kernel (chunked table, two resident passes, streamed overflow).
 extern "C" int32_t pk2_den_graph_persist_form(const pk2_den_graph* g, int32_t num_seqs) {
-  if (!g) return -1;
-  if (!pk2::den_use_sx(g)) return 0;
-  return pk2::den_persist_version(g, num_seqs);
+  return g ? den_plan(g, num_seqs, 1).form : -1;
+}
+
+extern "C" int pk2_den_graph_plan(const pk2_den_graph* g, int32_t num_seqs, int32_t max_frames, int32_t out[8]) {
+  PK2_REQUIRE(g && out && num_seqs > 0 && max_frames > 0, "den_graph_plan: bad args");
+  const DenPlan pl = den_plan(g, num_seqs, max_frames);
+  const int32_t v[8] = {pl.sx, pl.form, pl.NG, pl.need_fill, pl.xgather, pl.prep_merged, pl.tail_mergeable, pl.gamma_lds};
+  std::copy(v, v + 8, out);
+  return PK2_OK;
 }

@@ -528,8 +528,6 @@ __global__ void den_persist_check(const DenPersistCtl* ctl, int ntasks, float* d
 // host
 // ----------------------------------------------------------------------------------------
 static PersistFamily g_den_persist("den_persist");      // (no sticky word: nothing asks this form for its status)
-struct DenPersistParams;
-struct DenPersistScratch { DenPersistParams* params = nullptr; DenPersistCtl* ctl = nullptr; float* ring = nullptr; float* pring = nullptr; int rpad = 0; int ntasks = 0; };
 static std::map<DevStream, DenPersistScratch> g_den_scratch;
 
 static int den_rpad(const pk2_den_graph* g) { return (std::max(g->S, g->V) + 63) / 64 * 64; }
@@ -544,12 +542,33 @@ bool den_persist_fits(const pk2_den_graph* g) {
   return g->h_pfwd.ok && g->h_pbwd.ok && den_persist_lds_bytes(g) <= kDenPersistMaxLds;
 }
 
-bool den_persist_wanted(const pk2_den_graph* g, int N) {
-  const char* env = getenv("PK2_DEN_PERSIST");
-  if (env && atoi(env) == 0) return false;
-  if (!g_den_persist.usable() || !den_persist_fits(g) || !den_use_sx(g)) return false;
-  if (N < 1 || 2 * N > kMaxTasks) return false;
-  return device_cu_count() == 8 * kPR;
+bool den_persist_usable(const pk2_den_graph* g) { return g_den_persist.usable() && den_persist_fits(g); }
+
+int den_persist_scratch_alloc(DenPersistScratch& sc, size_t params_bytes, int rpad, size_t* ring_bytes) {
+  *ring_bytes = 0;
+  if (!sc.ctl) PK2_HIP(hipMalloc(reinterpret_cast<void**>(&sc.ctl), sizeof(DenPersistCtl)));
+  if (!sc.params) PK2_HIP(hipMalloc(&sc.params, params_bytes));
+  if (!sc.pring) PK2_HIP(hipMalloc(reinterpret_cast<void**>(&sc.pring), (size_t)8 * kMaxTeams * 3 * kPR * kPWords * sizeof(float)));
+  if (sc.rpad < rpad) {
+    if (sc.ring) PK2_HIP(hipFree(sc.ring));
+    sc.ring = nullptr; sc.rpad = 0;
+    const size_t bytes = (size_t)8 * kMaxTeams * 2 * rpad * sizeof(float);
+    PK2_HIP(hipMalloc(reinterpret_cast<void**>(&sc.ring), bytes));
+    sc.rpad = rpad;
+    *ring_bytes = bytes;
+  }
+  return PK2_OK;
+}
+
+int den_persist_tasks(const int32_t* lengths_host, int N, short (&task_seq)[kMaxTasks], unsigned char (&task_dir)[kMaxTasks]) {
+  std::vector<std::pair<int, int>> order;    // (-T, task id = 2 n + dir)
+  for (int n = 0; n < N; ++n)
+    if (lengths_host[n] > 0) { order.push_back({-lengths_host[n], 2 * n}); order.push_back({-lengths_host[n], 2 * n + 1}); }
+  std::sort(order.begin(), order.end());
+  const int ntasks = (int)order.size();
+  for (int k = 0; k < kMaxTasks; ++k) { task_seq[k] = 0; task_dir[k] = 0; }
+  for (int k = 0; k < ntasks; ++k) { task_seq[k] = (short)(order[k].second >> 1); task_dir[k] = (unsigned char)(order[k].second & 1); }
+  return ntasks;
 }
 
 int den_persist_launch(pk2_den_graph* g, const DenParams& dp, const float* xv, const int32_t* lengths_host, int N,
@@ -557,42 +576,30 @@ int den_persist_launch(pk2_den_graph* g, const DenParams& dp, const float* xv, c
   *ran = false;
   DenPersistScratch& sc = g_den_scratch[dev_stream(stream)];
   const int rpad = den_rpad(g);
-  if (!sc.ctl) PK2_HIP(hipMalloc(reinterpret_cast<void**>(&sc.ctl), sizeof(DenPersistCtl)));
-  if (!sc.params) PK2_HIP(hipMalloc(reinterpret_cast<void**>(&sc.params), sizeof(DenPersistParams)));
-  if (!sc.pring) PK2_HIP(hipMalloc(reinterpret_cast<void**>(&sc.pring), (size_t)8 * kMaxTeams * 3 * kPR * kPWords * sizeof(float)));
-  if (sc.rpad < rpad) {
-    if (sc.ring) PK2_HIP(hipFree(sc.ring));
-    sc.ring = nullptr; sc.rpad = 0;
-    PK2_HIP(hipMalloc(reinterpret_cast<void**>(&sc.ring), (size_t)8 * kMaxTeams * 2 * rpad * sizeof(float)));
-    sc.rpad = rpad;
-  }
+  size_t ring_bytes;
+  int rc = den_persist_scratch_alloc(sc, sizeof(DenPersistParams), rpad, &ring_bytes);
+  if (rc) return rc;
   DenPersistParams p;
   p.d = dp;
   p.fwd = g->pfwd; p.bwd = g->pbwd;
   p.xv = xv; p.ring = sc.ring; p.pring = sc.pring;
   p.rpad = rpad; p.cap = den_cap(g);
-  // recursions, longest first
-  std::vector<std::pair<int, int>> order;    // (-T, task id = 2 n + dir)
-  for (int n = 0; n < N; ++n)
-    if (lengths_host[n] > 0) { order.push_back({-lengths_host[n], 2 * n}); order.push_back({-lengths_host[n], 2 * n + 1}); }
-  std::sort(order.begin(), order.end());
-  p.ntasks = (int)order.size();
-  for (int k = 0; k < kMaxTasks; ++k) { p.task_seq[k] = 0; p.task_dir[k] = 0; }
-  for (int k = 0; k < p.ntasks; ++k) { p.task_seq[k] = (short)(order[k].second >> 1); p.task_dir[k] = (unsigned char)(order[k].second & 1); }
+  p.ntasks = den_persist_tasks(lengths_host, N, p.task_seq, p.task_dir);
   sc.ntasks = 0;
   if (p.ntasks == 0) { *ran = true; return PK2_OK; }
   const size_t lds = den_persist_lds_bytes(g);
   PK2_DYN_LDS_ONCE(den_persist_kernel, 160 * 1024);
   PK2_HIP(hipMemsetAsync(sc.ctl, 0, sizeof(DenPersistCtl), stream));
-  hipLaunchKernelGGL(param_block_store<DenPersistParams>, dim3(1), dim3(1), 0, stream, p, sc.params);
-  hipLaunchKernelGGL(den_persist_kernel, dim3(8 * kPR), dim3(kPT), lds, stream, sc.params, sc.ctl);
+  DenPersistParams* params = static_cast<DenPersistParams*>(sc.params);
+  hipLaunchKernelGGL(param_block_store<DenPersistParams>, dim3(1), dim3(1), 0, stream, p, params);
+  hipLaunchKernelGGL(den_persist_kernel, dim3(8 * kPR), dim3(kPT), lds, stream, params, sc.ctl);
 #ifdef PK2_DP_PROFILE
   { int tot = 0; for (int n = 0; n < N; ++n) tot += lengths_host[n];
     hipLaunchKernelGGL(dp_prof_print, dim3(1), dim3(1), 0, stream, std::max(1, tot / 4), 1); }   // (rank 0 of every team adds up)
 #endif
   PK2_LAUNCH_CHECK();
   bool ok = false;                            // first use on this device: every recursion done, nobody timed out?
-  int rc = g_den_persist.verify_first_use(&sc.ctl->abort, &sc.ctl->done, (unsigned)p.ntasks, stream, &ok);
+  rc = g_den_persist.verify_first_use(&sc.ctl->abort, &sc.ctl->done, (unsigned)p.ntasks, stream, &ok);
   if (rc || !ok) return rc;
   sc.ntasks = p.ntasks;
   *ran = true;

@@ -1293,10 +1293,7 @@ __global__ void den_persist2_check(DenPersistCtl* ctl, int ntasks, float* den_lp
 // host
 // ----------------------------------------------------------------------------------------
 static PersistFamily g_den_persist2("den_persist2");    // (no sticky word: nothing asks this form for its status)
-struct DenPersist2Scratch { DenPersist2Params* params = nullptr; DenPersistCtl* ctl = nullptr; float* ring = nullptr; float* pring = nullptr; int rpad = 0; int ntasks = 0;
-                            bool ctl_clean = false;         // the last launch's check kernel has zeroed the control block
-                            std::vector<unsigned char> params_host; };      // what `params` holds (a call with the same block skips the store)
-static std::map<DevStream, DenPersist2Scratch> g_den2_scratch;
+static std::map<DevStream, DenPersistScratch> g_den2_scratch;
 
 static int den2_rpad(const pk2_den_graph* g) { return (std::max(g->S, g->V) + 255) / 256 * 256 + 256; }
 static int den2_tfloats(const pk2_den_graph* g) { return std::max(g->h_p2fwd.tfloats, g->h_p2bwd.tfloats); }
@@ -1305,49 +1302,19 @@ bool den_persist2_fits(const pk2_den_graph* g) {
   return g->h_p2fwd.ok && g->h_p2bwd.ok && g->p2_cap > 0 && den_persist2_lds_bytes(den2_tfloats(g), g->p2_cap, g->p2_rowarrays) <= kDenPersistMaxLds;
 }
 
-// Which form runs: the forced one if it fits; else the second form whenever the whole graph is resident in it (it takes
-// every graph the first form takes and is a little faster); when it has to stream pieces or rotate table chunks, whichever of
-// it and the launch-per-frame kernels the measured cost model (profiles/r03_den_sweep.txt) predicts to be faster.
-int den_persist_version(const pk2_den_graph* g, int N) {
-  const char* env = getenv("PK2_DEN_PERSIST");
-  const int want = env ? atoi(env) : -1;
-  if (want == 0 || !den_use_sx(g) || N < 1 || 2 * N > kMaxTasks || device_cu_count() != 8 * kPR) return 0;
-  const bool ok1 = den_persist_wanted(g, N);
-  const bool ok2 = g_den_persist2.usable() && den_persist2_fits(g);
-  if (want == 1) return ok1 ? 1 : 0;
-  if (want == 2) return ok2 ? 2 : 0;
-  if (!ok2) return ok1 ? 1 : 0;
-  const HostPersist2& f = g->h_p2fwd; const HostPersist2& b = g->h_p2bwd;
-  const int pieces = std::max(f.max_pieces, b.max_pieces), K = std::max(f.K, b.K);
-  if (pieces == 0 && K == 2) return 2;
-  // microseconds per frame, fitted to the sweep: the streaming frame grows with the vector (table copy, row epilogues,
-  // the row-indexed sums of the segments) and by ~0.9 per streamed piece of 4096 slots; the frame kernels stream both arc
-  // lists once per frame for up to 4 sequences at a time
-  const double S = (double)g->S * 1e-3, A = (double)g->A * 1e-6;
-  const double us2 = 5.2 + 0.30 * S + 0.9 * pieces;
-  const double usf = 6.0 + 0.12 * S + 10.5 * A;
-  // 2 N recursions on 8 XCDs (each sequence's two recursions side by side) against ceil(N / 4) groups of frame launches
-  const double t2 = us2 * std::max(1.0, 2.0 * N / 8.0), tf = usf * ((N + 3) / 4);
-  return t2 <= tf ? 2 : (ok1 ? 1 : 0);
-}
+bool den_persist2_usable(const pk2_den_graph* g) { return g_den_persist2.usable() && den_persist2_fits(g); }
 
 int den_persist2_launch(pk2_den_graph* g, const DenParams& dp, const float* xv, const int32_t* lengths_host, int N,
                         hipStream_t stream, bool* ran, const NumDeferred* tail, bool* num_ran, bool xgather) {
   *ran = false;
   if (num_ran) *num_ran = false;
-  DenPersist2Scratch& sc = g_den2_scratch[dev_stream(stream)];
+  DenPersistScratch& sc = g_den2_scratch[dev_stream(stream)];
   const int rpad = den2_rpad(g);
-  if (!sc.ctl) PK2_HIP(hipMalloc(reinterpret_cast<void**>(&sc.ctl), sizeof(DenPersistCtl)));
-  if (!sc.params) PK2_HIP(hipMalloc(reinterpret_cast<void**>(&sc.params), sizeof(DenPersist2Params)));
-  if (!sc.pring) PK2_HIP(hipMalloc(reinterpret_cast<void**>(&sc.pring), (size_t)8 * kMaxTeams * 3 * kPR * kPWords * sizeof(float)));
-  if (sc.rpad < rpad) {
-    if (sc.ring) PK2_HIP(hipFree(sc.ring));
-    sc.ring = nullptr; sc.rpad = 0;
-    PK2_HIP(hipMalloc(reinterpret_cast<void**>(&sc.ring), (size_t)8 * kMaxTeams * 2 * rpad * sizeof(float)));
-    // (entries past a vector's end are copied into LDS with the last 16-byte granule but never gathered: keep them finite)
-    PK2_HIP(hipMemsetAsync(sc.ring, 0, (size_t)8 * kMaxTeams * 2 * rpad * sizeof(float), stream));
-    sc.rpad = rpad;
-  }
+  size_t ring_bytes;
+  int rc = den_persist_scratch_alloc(sc, sizeof(DenPersist2Params), rpad, &ring_bytes);
+  if (rc) return rc;
+  // (entries past a vector's end are copied into LDS with the last 16-byte granule but never gathered: keep them finite)
+  if (ring_bytes) PK2_HIP(hipMemsetAsync(sc.ring, 0, ring_bytes, stream));
   DenPersist2Params p;
   memset(static_cast<void*>(&p), 0, sizeof(p));      // (padding too: the block is compared with the last one stored)
   p.d = dp;
@@ -1358,21 +1325,14 @@ int den_persist2_launch(pk2_den_graph* g, const DenParams& dp, const float* xv, 
   p.pspt = g->p2_cap <= 2 * kPT ? 2 : (g->p2_cap <= 3 * kPT ? 3 : kPSPT);
   p.fwd_stream = (!g->h_p2fwd.sends.empty() || g->h_p2fwd.K > 2) ? 1 : 0;
   p.bwd_stream = (!g->h_p2bwd.sends.empty() || g->h_p2bwd.K > 2) ? 1 : 0;
-  std::vector<std::pair<int, int>> order;    // (-T, task id = 2 n + dir), longest first
-  for (int n = 0; n < N; ++n)
-    if (lengths_host[n] > 0) { order.push_back({-lengths_host[n], 2 * n}); order.push_back({-lengths_host[n], 2 * n + 1}); }
-  std::sort(order.begin(), order.end());
-  p.ntasks = (int)order.size();
-  for (int k = 0; k < kMaxTasks; ++k) { p.task_seq[k] = 0; p.task_dir[k] = 0; }
-  for (int k = 0; k < p.ntasks; ++k) { p.task_seq[k] = (short)(order[k].second >> 1); p.task_dir[k] = (unsigned char)(order[k].second & 1); }
+  p.ntasks = den_persist_tasks(lengths_host, N, p.task_seq, p.task_dir);
   sc.ntasks = 0;
   if (p.ntasks == 0) { *ran = true; return PK2_OK; }
   // The numerator forward-backward of the minibatch (two waves per sequence, LDS-staged) as further tasks behind the
   // recursions: the teams of the short sequences run them while the longest recursion is still going.  Not during the
   // first, verified launch of a process (a fallback would have to undo the posteriors already added to the gradient).
   const bool with_num = tail && tail->valid && tail->stage && num_ran && g_den_persist2.verified() && tail->N == N &&
-                        tail->lds <= (size_t)den2_tfloats(g) * sizeof(float) && p.ntasks + N <= kMaxTasks &&
-                        !(getenv("PK2_DEN_NUM_RIDE") && atoi(getenv("PK2_DEN_NUM_RIDE")) == 0);
+                        tail->lds <= (size_t)den2_tfloats(g) * sizeof(float) && p.ntasks + N <= kMaxTasks;
   if (with_num) {
     p.np = tail->p;
     for (int n = 0; n < N; ++n) { p.task_seq[p.ntasks] = (short)n; p.task_dir[p.ntasks] = 2; ++p.ntasks; }
@@ -1381,21 +1341,22 @@ int den_persist2_launch(pk2_den_graph* g, const DenParams& dp, const float* xv, 
   PK2_DYN_LDS_ONCE(den_persist2_kernel, 160 * 1024);
   if (!sc.ctl_clean) PK2_HIP(hipMemsetAsync(sc.ctl, 0, sizeof(DenPersistCtl), stream));
   sc.ctl_clean = false;
+  DenPersist2Params* params = static_cast<DenPersist2Params*>(sc.params);
   {
     const unsigned char* pb = reinterpret_cast<const unsigned char*>(&p);
     if (sc.params_host.size() != sizeof(p) || memcmp(sc.params_host.data(), pb, sizeof(p)) != 0) {
-      hipLaunchKernelGGL(param_block_store<DenPersist2Params>, dim3(1), dim3(1), 0, stream, p, sc.params);
+      hipLaunchKernelGGL(param_block_store<DenPersist2Params>, dim3(1), dim3(1), 0, stream, p, params);
       sc.params_host.assign(pb, pb + sizeof(p));
     }
   }
-  hipLaunchKernelGGL(den_persist2_kernel, dim3(8 * kPR), dim3(kPT), lds, stream, sc.params, sc.ctl);
+  hipLaunchKernelGGL(den_persist2_kernel, dim3(8 * kPR), dim3(kPT), lds, stream, params, sc.ctl);
 #ifdef PK2_DP_PROFILE
   { int tot = 0; for (int n = 0; n < N; ++n) tot += lengths_host[n];
     hipLaunchKernelGGL(dp_prof_print, dim3(1), dim3(1), 0, stream, std::max(1, tot / 4), 2); }
 #endif
   PK2_LAUNCH_CHECK();
   bool ok = false;                             // first use on this device: every recursion done, nobody timed out?
-  int rc = g_den_persist2.verify_first_use(&sc.ctl->abort, &sc.ctl->done, (unsigned)p.ntasks, stream, &ok);
+  rc = g_den_persist2.verify_first_use(&sc.ctl->abort, &sc.ctl->done, (unsigned)p.ntasks, stream, &ok);
   if (rc || !ok) return rc;
   sc.ntasks = p.ntasks;
   *ran = true;
@@ -1404,7 +1365,7 @@ int den_persist2_launch(pk2_den_graph* g, const DenParams& dp, const float* xv, 
 }
 
 void den_persist2_check_launch(float* den_lp, int N, hipStream_t stream) {
-  DenPersist2Scratch& sc = g_den2_scratch[dev_stream(stream)];
+  DenPersistScratch& sc = g_den2_scratch[dev_stream(stream)];
   const PersistGuard guard = persist_guard_or_null();
   if (sc.ctl && sc.ntasks > 0) {
     hipLaunchKernelGGL(den_persist2_check, dim3(1), dim3(256), 0, stream, sc.ctl, sc.ntasks, den_lp, N, guard.dev, guard.host_dev);
@@ -1413,7 +1374,7 @@ void den_persist2_check_launch(float* den_lp, int N, hipStream_t stream) {
 }
 
 bool den_persist2_tail_check(hipStream_t stream, DenTailCheck* ck) {
-  DenPersist2Scratch& sc = g_den2_scratch[dev_stream(stream)];
+  DenPersistScratch& sc = g_den2_scratch[dev_stream(stream)];
   const PersistGuard guard = persist_guard_or_null();
   if (!sc.ctl || sc.ntasks <= 0) return false;
   ck->ctl = reinterpret_cast<unsigned*>(sc.ctl);

@@ -1,5 +1,6 @@
 // Internal declarations shared by chain_den.hip / chain_num.hip / chain_objf.hip.
 #pragma once
+#include <type_traits>
 #include <vector>
 
 #include "common.h"
@@ -216,14 +217,41 @@ struct pk2_den_graph {
 
 namespace pk2 {
 
-// Per-call geometry of the denominator computation.
-struct DenGeom {
-  int NG;      // sequences interleaved per group (4, 2 or 1)
-  int G;       // number of groups
-  int N;       // sequences
-  int Tmax;
-  bool persist = false;   // NG = 1, one group per sequence, recursions by the persistent kernel (chain_den_persist.hip)
+// Run-time switches of the denominator (the PK2_DEN_* variables of INTEGRATION.md), read once per call by den_plan.
+struct DenEnv {
+  int mode = -1;          // PK2_DEN_MODE: 0 = general, 1 = sx, -1 = by the graph
+  int persist = -1;       // PK2_DEN_PERSIST: 0 | 1 | 2, -1 = by the cost model
+  bool merge = true;      // PK2_DEN_MERGE=0: the round-5 launches in front of and behind the recursions
+  bool xgather = true;    // PK2_DEN_XGATHER=0: x from the copies expanded per virtual state
+  bool num_ride = true;   // PK2_DEN_NUM_RIDE=0: the numerator never rides in the persistent launch
+  bool exp_gather = false, gamma_gather = false;   // PK2_DEN_EXP_GATHER / PK2_DEN_GAMMA_GATHER set: the gather kernels
+  bool test_fail = false; // PK2_DEN_TEST_FAIL=1 (test hook): the folded check sees a launch that gave up
+  int debug = 0;          // PK2_DEN_DEBUG ablation bits (DenParams::debug)
+  float beta_seed = 1.0f; // PK2_DEN_DEBUG_BETA_SEED (DenParams::beta_seed)
 };
+
+enum DenExpKernel { kExpPrep1, kExpRows, kExpStatesLds, kExpStates, kExpTranspose };
+
+// What one denominator call runs ("How a call is routed"): decided once, by den_plan, and read by the
+// workspace carve, the driver and the reporting hooks.
+struct DenPlan {
+  int rc = 0;     // PK2_ERR_LIMIT: no group size fits the LDS-staged kernels (the other fields then hold NG = 1)
+  int N, Tmax;
+  int NG;         // sequences interleaved per group: 1 with a persistent form, else NG_frames
+  int NG_frames;  // the frame kernels' group size: the largest of 4, 2, 1 whose LDS need is at most 160 KB
+  int G;          // number of groups
+  bool sx;        // family: the state-x kernels (else the general, per-arc-pdf ones)
+  int form;       // recursions: 0 = a launch per frame, 1 = den_persist_kernel, 2 = den_persist2_kernel (state-x only)
+  bool need_fill;       // some alpha / beta / gamma rows accumulate with atomics: the buffers start at zero
+  bool xgather;         // form 2 gathers x by pdf from plain exp(logits) rows in the xv buffer
+  bool prep_merged;     // the passes in front of the recursions are one launch (den_prep1)
+  bool tail_mergeable;  // the passes behind them may be one (den_tail1): taken unless form 1 ran
+  bool gamma_lds;       // occupancy kernel: the frame's row staged in LDS (else gathered)
+  DenExpKernel exp_kernel;
+  int ncf, ncb;   // partial sums per frame the recursions leave: kPR with a persistent form, else the chunk counts
+  DenEnv env;
+};
+DenPlan den_plan(const pk2_den_graph* g, int N, int Tmax);
 
 struct DenBuffers {
   float* alpha;   // [G][Tmax+1][S][NG]  alpha (before the leaky term)
@@ -244,9 +272,10 @@ struct DenBuffers {
   float* xv;      // [G][Tmax][V]     exp(logit) per virtual state, compact (persistent kernel only)
 };
 
-int den_choose_ng(const pk2_den_graph* g);
-bool den_use_sx(const pk2_den_graph* g);
-size_t den_workspace(const pk2_den_graph* g, int N, int Tmax, DenGeom* geom, DenBuffers* buf,
+// Carves the buffers of den_plan(g, N, Tmax) from `base` and returns their bytes.  A sizing call (no base) answers for the
+// persistent and the frame-kernel geometry alike: the choice can change before the compute call (the first launch on a
+// device is verified).
+size_t den_workspace(const pk2_den_graph* g, int N, int Tmax, DenPlan* plan, DenBuffers* buf,
                      void* base);
 struct NumDeferred;
 int den_upload(pk2_den_graph* g);
@@ -256,13 +285,25 @@ int den_upload(pk2_den_graph* g);
 // zeroed by the launch that prepares the recursions (round 6: one launch less per step) or by one of their own.
 struct DenZeroRows { float* grad = nullptr; int64_t gss = 0, gfs = 0; int N = 0; };
 int den_compute(pk2_den_graph* g, const float* logits, int64_t seq_stride, int64_t frame_stride,
-                const int32_t* lengths_host, const DenGeom& geom, const DenBuffers& buf,
+                const int32_t* lengths_host, const DenPlan& plan, const DenBuffers& buf,
                 float leaky, hipStream_t stream, const NumDeferred* tail = nullptr, const DenZeroRows* zero = nullptr);
 
 // Internal side stream (+ fork/join events) paired with a caller stream: the numerator runs there while
 // the denominator occupies the caller's stream.
 struct SideStream { hipStream_t stream = nullptr; hipEvent_t fork = nullptr, join = nullptr; };
 int get_side_stream(hipStream_t main, SideStream** out);
+void den_gamma_out_launch(const DenPlan& plan, const DenBuffers& b, int P, float scale, float* out,
+                          int64_t ss, int64_t fs, hipStream_t stream);
+
+// Calls fn(std::integral_constant<int, NG>) for the group size of a plan.
+template <typename F>
+auto dispatch_ng(int ng, F&& fn) {
+  switch (ng) {
+    case 4: return fn(std::integral_constant<int, 4>{});
+    case 2: return fn(std::integral_constant<int, 2>{});
+    default: return fn(std::integral_constant<int, 1>{});
+  }
+}
 
 // Numerator.
 // seqinfo[n] = {frame_off base index, length, state count, final lo, final hi, -, -, -}

@@ -9,9 +9,6 @@
 
 namespace pk2 {
 
-void den_gamma_out_launch(const DenGeom& ge, const DenBuffers& b, int P, float scale, float* out,
-                          int64_t ss, int64_t fs, hipStream_t stream);
-
 __global__ void __launch_bounds__(256) zero_rows(float* out, int64_t seq_stride, int64_t frame_stride,
                                                  int P, int Tmax) {
   float* row = out + (int64_t)blockIdx.y * seq_stride + (int64_t)blockIdx.x * frame_stride;
@@ -90,9 +87,9 @@ __global__ void __launch_bounds__(256) chain_combine(const float* __restrict__ g
 using namespace pk2;
 
 static size_t chain_carve(const pk2_den_graph* g, int N, int Tmax, int64_t total_arcs,
-                          int64_t total_frames, void* base, DenGeom* ge, DenBuffers* db,
+                          int64_t total_frames, void* base, DenPlan* plan, DenBuffers* db,
                           NumBuffers* nb, int32_t** flags, int32_t** lengths_dev) {
-  size_t den_bytes = den_workspace(g, N, Tmax, ge, db, base);
+  size_t den_bytes = den_workspace(g, N, Tmax, plan, db, base);
   char* b2 = base ? static_cast<char*>(base) + den_bytes : nullptr;
   size_t num_bytes = num_workspace(N, total_arcs, total_frames, nb, b2);
   Carver c(base ? b2 + num_bytes : nullptr);
@@ -133,8 +130,8 @@ static int chain_objf_impl(const pk2_den_graph* gc, const float* logits,
   }
   int64_t bound = std::max<int64_t>(std::max<int64_t>(num->total_arcs, total_frames + N),
                                     (int64_t)N * (Tmax + 1));
-  DenGeom ge; DenBuffers db; NumBuffers nbuf; int32_t* flags; int32_t* ldev;
-  size_t need = chain_carve(g, N, Tmax, bound, bound, workspace, &ge, &db, &nbuf, &flags, &ldev);
+  DenPlan plan; DenBuffers db; NumBuffers nbuf; int32_t* flags; int32_t* ldev;
+  size_t need = chain_carve(g, N, Tmax, bound, bound, workspace, &plan, &db, &nbuf, &flags, &ldev);
   PK2_REQUIRE(workspace_bytes >= need, "chain_objf_and_deriv: workspace %zu < %zu", workspace_bytes, need);
 
   // 1. gradient buffer starts at zero; the numerator adds (1 + xent_regularize) * w * posterior.
@@ -166,29 +163,18 @@ static int chain_objf_impl(const pk2_den_graph* gc, const float* logits,
   if (use_side) PK2_HIP(hipEventRecord(side->join, side->stream));
   // 2. denominator
   DenZeroRows zr; zr.grad = grad; zr.gss = gss; zr.gfs = gfs; zr.N = N;
-  rc = den_compute(g, logits, seq_stride, frame_stride, lengths, ge, db, leaky, stream, use_side ? nullptr : &deferred,
+  rc = den_compute(g, logits, seq_stride, frame_stride, lengths, plan, db, leaky, stream, use_side ? nullptr : &deferred,
                    use_side ? nullptr : &zr);
   if (rc) return rc;
   if (use_side) PK2_HIP(hipStreamWaitEvent(stream, side->join, 0));
   // 3. objective, guards, gradient = numerator - denominator occupancies
   hipLaunchKernelGGL(chain_flags, dim3(1), dim3(256), 0, stream, nbuf.num_lp, db.den_lp,
                      db.check, db.lengths, N, weight, out, flags, objf_sum);
-  switch (ge.NG) {
-    case 4:
-      hipLaunchKernelGGL(chain_combine<4>, dim3(Tmax, ge.G), dim3(256), 0, stream, db.gamma, db.lengths,
-                         flags, N, g->P, Tmax, weight, l2_regularize, logits, seq_stride, frame_stride,
-                         grad, gss, gfs, gscale);
-      break;
-    case 2:
-      hipLaunchKernelGGL(chain_combine<2>, dim3(Tmax, ge.G), dim3(256), 0, stream, db.gamma, db.lengths,
-                         flags, N, g->P, Tmax, weight, l2_regularize, logits, seq_stride, frame_stride,
-                         grad, gss, gfs, gscale);
-      break;
-    default:
-      hipLaunchKernelGGL(chain_combine<1>, dim3(Tmax, ge.G), dim3(256), 0, stream, db.gamma, db.lengths,
-                         flags, N, g->P, Tmax, weight, l2_regularize, logits, seq_stride, frame_stride,
-                         grad, gss, gfs, gscale);
-  }
+  dispatch_ng(plan.NG, [&](auto ng) {
+    hipLaunchKernelGGL(chain_combine<decltype(ng)::value>, dim3(Tmax, plan.G), dim3(256), 0, stream, db.gamma, db.lengths,
+                       flags, N, g->P, Tmax, weight, l2_regularize, logits, seq_stride, frame_stride,
+                       grad, gss, gfs, gscale);
+  });
   PK2_LAUNCH_CHECK();
   return PK2_OK;
 }

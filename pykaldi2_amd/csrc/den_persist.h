@@ -1,13 +1,17 @@
 // Persistent denominator recursion (chain_den_persist.hip): internal interface used by chain_den.hip.
 #pragma once
+#include <vector>
+
 #include "den_kernels.h"
 
 namespace pk2 {
 
-// True when the alpha / beta recursions of this graph can run as one launch: the persistent layouts exist, a state
-// vector fits the LDS of a CU next to the row buffers, the device is an 8 x 32-CU part, PK2_DEN_PERSIST != 0 and an
-// earlier launch has not failed its verification.
-bool den_persist_wanted(const pk2_den_graph* g, int N);
+constexpr int kMaxTeams = 8;                         // teams per XCD the control block has room for
+constexpr int kMaxTasks = 64;
+
+// The first form can take this graph (den_persist_fits) and no earlier launch of it has failed its verification on this
+// device.  Whether a call uses it is den_plan's decision (chain_den.hip).
+bool den_persist_usable(const pk2_den_graph* g);
 size_t den_persist_lds_bytes(const pk2_den_graph* g);
 // The layouts exist and a state vector fits the LDS table and a thread's registers (a property of the graph alone).
 bool den_persist_fits(const pk2_den_graph* g);
@@ -38,8 +42,9 @@ inline size_t den_persist2_lds_bytes(int tfloats, int cap, int arrays = kP2RowAr
   return ((size_t)tfloats + arrays * (size_t)cap + kP2FixedFloats) * sizeof(float);
 }
 bool den_persist2_fits(const pk2_den_graph* g);
+bool den_persist2_usable(const pk2_den_graph* g);      // (as den_persist_usable, for the second form)
 // `tail`: the minibatch's deferred numerator forward-backward (may be null); *num_ran = true when it rode in this launch
-// (as tasks behind the recursions) and must not be launched again.
+// (as tasks behind the recursions) and must not be launched again; num_ran = null: it may not ride.
 struct NumDeferred;
 int den_persist2_launch(pk2_den_graph* g, const DenParams& p, const float* xv, const int32_t* lengths_host, int N,
                         hipStream_t stream, bool* ran, const NumDeferred* tail = nullptr, bool* num_ran = nullptr,
@@ -50,9 +55,21 @@ void den_persist2_check_launch(float* den_lp, int N, hipStream_t stream);
 struct DenTailCheck { unsigned* ctl; int ctl_words; int ntasks; unsigned* abort_word; unsigned* done_word; unsigned* count_word;
                       unsigned* guard_dev; unsigned* guard_host; };
 bool den_persist2_tail_check(hipStream_t stream, DenTailCheck* ck);
-// Which recursion kernel a call of N sequences takes: 0 = the launch-per-frame kernels, 1 = den_persist_kernel (everything
-// resident: graphs up to ~1.05 M arc slots and ~36 k states), 2 = den_persist2_kernel.  PK2_DEN_PERSIST = 0 | 1 | 2 forces one
-// (a forced form that does not fit the graph falls back to the frame kernels).
-int den_persist_version(const pk2_den_graph* g, int N);
+
+// ---- host half shared by the two launchers ----
+// Scratch of a form's launches on one (device, stream): the control block, the parameter block, the exchange words and
+// the ring of state vectors, which grows with the graphs it has served.
+struct DenPersistCtl;
+struct DenPersistScratch {
+  void* params = nullptr; DenPersistCtl* ctl = nullptr; float* ring = nullptr; float* pring = nullptr; int rpad = 0;
+  int ntasks = 0;                             // recursions of the last launch that passed (what its check kernel expects)
+  bool ctl_clean = false;                     // form 2: the last launch's check has zeroed the control block
+  std::vector<unsigned char> params_host;     // form 2: what `params` holds (a call with the same block skips the store)
+};
+// Allocates what is missing; *ring_bytes = size of a ring (re)allocated by this call for `rpad` floats per slot, else 0.
+int den_persist_scratch_alloc(DenPersistScratch& sc, size_t params_bytes, int rpad, size_t* ring_bytes);
+// The recursions of a minibatch, longest first: task k is direction task_dir[k] (0 forward, 1 backward) of sequence
+// task_seq[k]; sequences without frames have none.  Returns their number, the rest of the arrays is zeroed.
+int den_persist_tasks(const int32_t* lengths_host, int N, short (&task_seq)[kMaxTasks], unsigned char (&task_dir)[kMaxTasks]);
 
 }  // namespace pk2

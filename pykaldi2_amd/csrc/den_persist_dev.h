@@ -8,8 +8,6 @@
 namespace pk2 {
 
 constexpr unsigned kRingSentinel = 0x7fc0dead;       // a NaN payload no arithmetic produces
-constexpr int kMaxTeams = 8;                         // teams per XCD the control block has room for
-constexpr int kMaxTasks = 64;
 constexpr long long kDenSpinTicks = 1000LL * 1000 * 100;   // 1 s of the 100 MHz wall clock
 
 #ifdef PK2_DP_PROFILE

@@ -90,8 +90,36 @@ def test_denominator_matches_oracle(S, A, P, lens, leaky, path, monkeypatch):
                 assert ("stream" not in variant or A < 60000 or lay["pieces"] > 0) and ("chunk" not in variant or S < 1024 or lay["K"] > 2)
                 if "shared" in variant and 1024 < S <= 2048:      # the forward table (S entries) exceeds the 1024 of the LDS table
                     assert lay["K"] == 2 and lay["lds_off"][:2] == [0, 0] and 0 < lay["cbeg"][1] < lay["cbeg"][2]
+    # the plan the call below is routed by (csrc/chain_internal.h: DenPlan) agrees with the two older hooks ...
+    n, T = len(lens), max(lens)
+    pl = G.plan(n, T)
+    assert pl["family"] == int(G.kernel_path(n) != 0) and pl["form"] == G.persist_form(n), pl
+    assert pl["form"] == 0 or pl["NG"] == 1, pl
+    # ... fills the buffers where rows are split over chunks (the 20000-arc graph) and on the general family ...
+    if A == 20000 or pl["family"] == 0:
+        assert pl["need_fill"] == 1 and pl["prep_merged"] == 0, pl
+    # ... and gathers x by pdf exactly where the second form can: the rows fit the xv buffer (V >= P), the pdfs are 16-bit,
+    # the LDS layout has the pdf arrays, and the variable does not switch it off
+    V = len(G.debug_ordering(3)["vpdf"])
+    if pl["form"] == 2 and P <= 32767 and V >= P:
+        if form and variant in ("p2expanded", "p2rows7"):
+            want_xg = 0
+        elif not form and path in ("state_x", "chain_topology", "multi_entry"):
+            want_xg = 1
+        else:               # (the other layout variants: the builder may have left the pdf arrays out)
+            want_xg = int(G.debug_persist2(0)["row_arrays"] == 8)
+        assert pl["xgather"] == want_xg and pl["prep_merged"] == (want_xg and not pl["need_fill"]), pl
+    else:
+        assert pl["xgather"] == 0 and pl["prep_merged"] == 0, pl
+    if S == 8 and path == "state_x" and not form:      # the environment is read per call
+        monkeypatch.setenv("PK2_DEN_GAMMA_GATHER", "1")
+        assert pl["gamma_kernel"] == 1 and G.plan(n, T)["gamma_kernel"] == 0
+        monkeypatch.delenv("PK2_DEN_GAMMA_GATHER")
+        monkeypatch.setenv("PK2_DEN_PERSIST", "0")
+        assert pl["form"] == 2 and G.plan(n, T)["form"] == 0
+        monkeypatch.delenv("PK2_DEN_PERSIST")
+        assert G.plan(n, T) == pl
     rng = np.random.default_rng(1)
-    T = max(lens)
     lg = rng.normal(0, 3, size=(len(lens), T, P)).astype(np.float32)
     lg[0, 0, 0] = 45.0   # exercises the +-30 clamp
     x = torch.from_numpy(lg).cuda()
