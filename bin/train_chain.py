@@ -12,6 +12,13 @@ transition-id alignment (`label`) by the library's SplitToPhones / AlignmentToPr
 ProtoSupervisionToSupervision (pykaldi2_amd.chain, csrc/chain_sup.hip), with the reference's options
 (frame_subsampling_factor 3, tolerances 5, convert_to_pdfs).  -synthetic trains on the seeded
 LibriSpeech-shaped generator with a synthetic denominator graph, tree and transition model.
+
+-e2e (no counterpart in the reference) trains alignment-free: no -ali_dir and no transition-id labels.  The label files'
+`aux_label` holds each utterance's word ids (as for train_se2.py), -lang_dir supplies L.fst and phones/disambig.int, the
+chain directory's tree and 0.trans_mdl build the training graphs, and the numerator is the full sum over the graph of the
+transcript at the subsampled frame count (chain.graph_supervisions).  An utterance whose transcript has no
+path of its length is left out of the step and counted in the progress line.  With -synthetic the transcripts are seeded
+(synth.word_transcript) over the synthetic lexicon and monophone model of train_se2.py, in the same label space.
 """
 import argparse
 import json
@@ -61,6 +68,11 @@ def parse_config(argv=None):
     parser.add_argument('-synthetic', action='store_true', help='seeded synthetic utterances and denominator graph')
     parser.add_argument('-den_states', default=30000, type=int, help='(synthetic) denominator graph states')
     parser.add_argument('-den_arcs', default=1000000, type=int, help='(synthetic) denominator graph arcs')
+    parser.add_argument('-e2e', action='store_true', help='alignment-free LF-MMI: the numerator sums over the training graph '
+                        'of the word transcript (aux_label); needs -lang_dir and -chain_dir, no -ali_dir')
+    parser.add_argument('-transition_scale', default=0.0, type=float, help='(-e2e) transition scale of the training graphs')
+    parser.add_argument('-self_loop_scale', default=0.0, type=float, help='(-e2e) self-loop scale of the training graphs')
+    parser.add_argument('-graph_words', default=200, type=int, help='(-e2e -synthetic) words of the synthetic lexicon')
     args = parser.parse_args(argv)
 
     with open(args.config) as f:
@@ -104,8 +116,26 @@ def main():
 
     if args.synthetic:
         den = chain.DenominatorGraph(synth.den_graph_arcs(args.den_states, args.den_arcs, P, seed=0, loop_pdf_differs=True), P)
-        chain_tree, chain_trans_model = synth.chain_model(P, seed=0)
-        aligner = chain.MappedAligner(chain_trans_model)
+        if args.e2e:     # monophone 3-state model and the lexicon of its word loop, pdfs in the same label space
+            chain_tree, chain_trans_model = synth.alignment_model(P)
+            aligner = chain.MappedAligner.from_models(chain_trans_model, chain_tree, synth.lexicon_arcs(args.graph_words, P, seed=0))
+        else:
+            chain_tree, chain_trans_model = synth.chain_model(P, seed=0)
+            aligner = chain.MappedAligner(chain_trans_model)
+    elif args.e2e:
+        paths = {"chain denominator graph": os.path.join(args.chain_dir or "", "den.fst"),
+                 "trans_model": os.path.join(args.chain_dir or "", "0.trans_mdl"),
+                 "chain tree": os.path.join(args.chain_dir or "", "tree"),
+                 "lexicon": os.path.join(args.lang_dir or "", "L.fst")}
+        for what, path in paths.items():
+            if not os.path.isfile(path):
+                sys.stderr.write('ERROR: The {} {} does not exist!\n'.format(what, path))
+                sys.exit(0)
+        den = chain.DenominatorGraph(paths["chain denominator graph"], P)
+        chain_trans_model = TransitionModel.read(paths["trans_model"])
+        chain_tree = ContextDependency.read(paths["chain tree"])
+        aligner = chain.MappedAligner.from_files(paths["trans_model"], paths["chain tree"], paths["lexicon"], None,
+                                                 os.path.join(args.lang_dir or "", "phones/disambig.int"))
     else:
         den_path = os.path.join(args.chain_dir or "", "den.fst")
         chain_model_path = os.path.join(args.chain_dir or "", "0.trans_mdl")
@@ -123,7 +153,7 @@ def main():
                                                  os.path.join(args.lang_dir or "", "phones/disambig.int"))
     supervision_opts = chain.SupervisionOptions()
     chain_opts = chain.ChainTrainingOptions(leaky_hmm_coefficient=1e-4, xent_regularize=args.xent_regularize)
-    source = data.make_source(config, P, hvd.rank(), hvd.size(), ali_model=aligner.transition_model)
+    source = data.make_source(config, P, hvd.rank(), hvd.size(), ali_model=None if args.e2e else aligner.transition_model)
     transform = None
     if args.transform is not None and os.path.isfile(args.transform):
         transform = fbank.GlobalMeanVarianceNormalization.load(args.transform)
@@ -145,8 +175,11 @@ def run_train_epoch(model, optimizer, source, fb, epoch, supervision_opts, den, 
     losses = utils.AverageMeter('Loss', ':.4e')
     grad_norm = utils.AverageMeter('grad_norm', ':.4e')
     n_batches = max(1, int(args.sweep_size * 3600 / (12.3 * args.batch_size)))
-    progress = utils.ProgressMeter(n_batches, batch_time, losses, grad_norm, prefix="Epoch: [{}]".format(epoch))
+    no_path = utils.AverageMeter('no_path', ':d')      # (-e2e) utterances left out: no path of their length
+    meters = (batch_time, losses, grad_norm) + ((no_path,) if args.e2e else ())
+    progress = utils.ProgressMeter(n_batches, *meters, prefix="Epoch: [{}]".format(epoch))
     sub = supervision_opts.frame_subsampling_factor
+    text_rng = np.random.default_rng(4321 + epoch + hvd.rank())
     end = time.time()
     for i, batch in enumerate(data.sequence_batches(source, args.batch_size, args.sweep_size, dev, epoch=epoch,
                                                          length_bucketed=args.length_bucketed)):
@@ -156,8 +189,21 @@ def run_train_epoch(model, optimizer, source, fb, epoch, supervision_opts, den, 
             feats = transform(feats)
         x = fb.pad_roll_subsample(feats, row_off, frames, shift=frame_shift, subsample=sub, time_major=True)
         aligner, tree, trans_model = sup_model
-        sups = [chain.supervision_from_alignment(aligner, tree, trans_model, supervision_opts, np.asarray(y)[:T])
-                for y, T in zip(batch["y"], frames)]    # reference bin/train_chain.py:262-272
+        if args.e2e:
+            sub_frames = [-(-int(T) // sub) for T in frames]
+            if args.synthetic:
+                texts = [synth.word_transcript(text_rng, T, args.graph_words) for T in sub_frames]
+            else:
+                texts = [np.asarray(a).reshape(-1).astype(int).tolist() for a in batch["aux"]]
+            sups = chain.graph_supervisions(aligner, texts, sub_frames, args.transition_scale, args.self_loop_scale)
+            skipped = [j for j, st in enumerate(sups.status) if st != chain.ALIGN_OK]
+            for j in skipped:
+                print("Warning: no path of {} frames for utterance {}, skip the utterance".format(sub_frames[j], batch["utt_ids"][j]))
+            no_path.sum += len(skipped)
+            no_path.val, no_path.avg = len(skipped), no_path.sum
+        else:
+            sups = [chain.supervision_from_alignment(aligner, tree, trans_model, supervision_opts, np.asarray(y)[:T])
+                    for y, T in zip(batch["y"], frames)]    # reference bin/train_chain.py:262-272
         prediction = model.forward_time_major(x).transpose(0, 1)
         loss = ops.ChainObjtiveBatch.apply(prediction, den, sups, chain_opts)
         optimizer.zero_grad()

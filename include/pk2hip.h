@@ -270,6 +270,40 @@ int pk2_align_viterbi(const pk2_align_graphs* graphs, const int32_t* packed_dev,
                       void* stream);
 
 /* ------------------------------------------------------------------ *
+ * Alignment-free LF-MMI ("flat-start" / e2e chain): the numerator is the full sum over every path of exactly frames[n]
+ * frames through the training graph of utterance n (pk2_align_compile; csrc/chain_num_graph.hip):
+ *   alpha_0(d) = sum_{a: dst=d, src=-1} exp(-w_a + x[0, pdf_a]),  alpha_t(d) = sum_{a: dst=d, src>=0} alpha_{t-1}(src_a) exp(-w_a + x[t, pdf_a]),
+ *   log p_num  = log sum_s alpha_{T-1}(s) exp(-final[s]),         posterior[t, p] = d log p_num / d x[t, p].
+ * No beam, logits unscaled.  An utterance without a graph (status 2: no path of that length; 3: not compiled) takes no part:
+ * log p_num = 0 and its rows are not touched.
+ * ------------------------------------------------------------------ */
+size_t pk2_num_graph_workspace_bytes(const pk2_align_graphs* graphs);
+/* 1 when the next call keeps the working vectors and the arcs in LDS (they fit and PK2_NUM_GRAPH_LDS is not 0). */
+int pk2_num_graph_use_lds(const pk2_align_graphs* graphs);
+/* The numerator alone (tests, tools).  logits / grad: device f32 addressed as in pk2_chain_objf_and_deriv, num_pdfs columns;
+ * scale * posterior is ADDED into grad rows t < frames[n].  logprob f32[N], status i32[N] (0, or 2 / 3 as compiled): device.
+ * workspace: device, 256-byte aligned, pk2_num_graph_workspace_bytes().  The result is bit-reproducible. */
+int pk2_num_graph_fwd_bwd(const pk2_align_graphs* graphs, const int32_t* packed_dev, const float* logits, int64_t seq_stride,
+                          int64_t frame_stride, int32_t num_pdfs, int32_t Tmax, float scale, float* grad, int64_t grad_seq_stride,
+                          int64_t grad_frame_stride, float* logprob, int32_t* status, void* workspace, size_t workspace_bytes,
+                          void* stream);
+/* pk2_chain_objf_and_deriv[_op] with the graphs in place of pk2_num_batch: lengths are the graphs' frame counts, the
+ * denominator, the regularisers and the non-finite-objective rule are those of the alignment-based entry.  An utterance
+ * without a graph is left out of the denominator too: its three outputs and its gradient rows are 0.  Rows t < max_n frames[n]
+ * of grad are written.  workspace: device, 256-byte aligned, pk2_chain_graph_workspace_bytes(). */
+size_t pk2_chain_graph_workspace_bytes(const pk2_den_graph* g, const pk2_align_graphs* graphs);
+int pk2_chain_objf_and_deriv_graph(const pk2_den_graph* g, const float* logits, int64_t seq_stride, int64_t frame_stride,
+                                   const pk2_align_graphs* graphs, const int32_t* packed_dev, float leaky_hmm_coefficient,
+                                   float xent_regularize, float l2_regularize, float weight, float* grad,
+                                   int64_t grad_seq_stride, int64_t grad_frame_stride, float* out, void* workspace,
+                                   size_t workspace_bytes, void* stream);
+int pk2_chain_objf_and_deriv_graph_op(const pk2_den_graph* g, const float* logits, int64_t seq_stride, int64_t frame_stride,
+                                      const pk2_align_graphs* graphs, const int32_t* packed_dev, float leaky_hmm_coefficient,
+                                      float xent_regularize, float l2_regularize, float weight, float* grad,
+                                      int64_t grad_seq_stride, int64_t grad_frame_stride, float* out, void* workspace,
+                                      size_t workspace_bytes, float grad_scale, float* objf_sum, void* stream);
+
+/* ------------------------------------------------------------------ *
  * Reverberation + additive noise of one utterance (single channel), device arrays throughout.
  * Replaces the numpy arithmetic of the reference's dynamic data simulation: Distorter.apply_rir /
  * Distorter.add_noise (reference simulation/_distorter.py:86-154) as _Simulator.simulate uses them for one

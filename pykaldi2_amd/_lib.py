@@ -105,6 +105,14 @@ SIGNATURES = {
     "pk2_align_workspace_bytes": (_sz, [_vp]),
     "pk2_align_use_lds": (C.c_int, [_vp]),
     "pk2_align_viterbi": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i32, _i32, _f32, _f32, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "pk2_num_graph_workspace_bytes": (_sz, [_vp]),
+    "pk2_num_graph_use_lds": (C.c_int, [_vp]),
+    "pk2_num_graph_fwd_bwd": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i32, _i32, _f32, _vp, _i64, _i64, _vp, _vp, _vp, _sz, _vp]),
+    "pk2_chain_graph_workspace_bytes": (_sz, [_vp, _vp]),
+    "pk2_chain_objf_and_deriv_graph": (C.c_int, [_vp, _vp, _i64, _i64, _vp, _vp, _f32, _f32, _f32, _f32, _vp, _i64, _i64, _vp,
+                                                 _vp, _sz, _vp]),
+    "pk2_chain_objf_and_deriv_graph_op": (C.c_int, [_vp, _vp, _i64, _i64, _vp, _vp, _f32, _f32, _f32, _f32, _vp, _i64, _i64,
+                                                    _vp, _vp, _sz, _f32, _vp, _vp]),
     "pk2_decode_graph_create": (C.c_int, [_i32, _i32, _i64, _vp, _vp, _vp, _vp, _vp, C.POINTER(_vp)]),
     "pk2_decode_graph_create_words": (C.c_int, [_i32, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_vp)]),
     "pk2_decode_graph_link_words": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp]),

@@ -10,6 +10,8 @@
   alignment_to_proto_supervision             bin/train_chain.py:271
   proto_supervision_to_supervision           bin/train_chain.py:272
   compute_chain_objf_and_deriv(...)          ops/ops.py:265
+  GraphSupervision / graph_supervisions      alignment-free LF-MMI (no counterpart in the reference): the numerator is
+                                             the full sum over the training graph of the transcript
 
 ``den_fst`` may be a path to an OpenFst binary ``den.fst`` or a dict of arc
 arrays (``num_states, start, src, dst, pdf, prob`` as produced by
@@ -498,7 +500,7 @@ class MappedAligner:
     compiled on the host (csrc/align_graph.hip), the Viterbi pass aligns a whole minibatch in one launch
     (csrc/align_viterbi.hip).  The tree and L.fst of from_files are read at the first align."""
 
-    _tree = _lexicon = _model = _symbols = None
+    _tree = _lexicon = _model = _symbols = _scaled_models = None
     _tree_path = _lexicon_path = _disambig_path = _symbols_path = None
     beam, retry_beam, transition_scale, self_loop_scale, acoustic_scale = 200.0, None, 1.0, 1.0, 0.1
 
@@ -550,6 +552,16 @@ class MappedAligner:
                     self._symbols = read_symbols(self._symbols_path)
             self._model = AlignModel(self._tree, self.transition_model, self.transition_scale, self.self_loop_scale)
         return self._model, self._lexicon
+
+    def _graph_model_scaled(self, transition_scale, self_loop_scale):
+        """(AlignModel, Lexicon) with other graph scales than the aligner's own (graph_supervisions); built once per pair."""
+        _, lexicon = self._graph_model()
+        if self._scaled_models is None:
+            self._scaled_models = {}
+        key = (float(transition_scale), float(self_loop_scale))
+        if key not in self._scaled_models:
+            self._scaled_models[key] = AlignModel(self._tree, self.transition_model, *key)
+        return self._scaled_models[key], lexicon
 
     def _words(self, text):
         if isinstance(text, str):
@@ -617,6 +629,53 @@ class MappedAligner:
         return [self._result(ali[n], costs[n], lengths[n]) if status[n] == ALIGN_OK else None for n in range(len(lengths))]
 
 
+class GraphSupervision:
+    """Alignment-free ("flat-start" / e2e) chain supervision of a MINIBATCH: the training graphs of its transcripts
+    (AlignmentGraphs), over which the numerator sums every path of exactly frames_per_sequence[n] frames
+    (csrc/chain_num_graph.hip).  status[n]: 0 compiled, 2 no path of that many frames -- the utterance then takes no part
+    in the objective (outputs and gradient rows 0) -- and errors[n] says why."""
+
+    def __init__(self, graphs, weight=1.0, label_dim=None):
+        self.graphs = graphs
+        self.weight = float(weight)
+        self.label_dim = label_dim
+        self.num_sequences = graphs.n
+        self.frames_per_sequence = [int(t) for t in graphs.frames]
+        self.status = list(graphs.status)
+        self.errors = list(graphs.errors)
+
+    def __len__(self):
+        return self.num_sequences
+
+
+def graph_supervisions(aligner, texts, frames, transition_scale=0.0, self_loop_scale=0.0, weight=1.0):
+    """GraphSupervision of a minibatch of transcripts in one compile call.  aligner: a MappedAligner with tree and lexicon
+    (from_files / from_models); frames[n]: network-rate frames of utterance n.  With both scales 0 (the default) only the
+    lexicon's costs remain in the graph, like the unweighted alignment-based supervisions.  Raises when a transcript does
+    not compile (status 3: a word outside the lexicon, a phone without a model)."""
+    model, lexicon = aligner._graph_model_scaled(transition_scale, self_loop_scale)
+    graphs = AlignmentGraphs(model, lexicon, [aligner._words(t) for t in texts], frames)
+    for n, st in enumerate(graphs.status):
+        if st == ALIGN_ERROR:
+            raise _lib.Pk2Error("graph_supervisions: utterance %d: %s" % (n, graphs.errors[n]))
+    return GraphSupervision(graphs, weight, aligner.transition_model.num_pdfs())
+
+
+def _as_graph_supervision(supervisions):
+    """The GraphSupervision behind the `supervisions` argument of the chain entry points, or None for Supervision lists."""
+    if isinstance(supervisions, GraphSupervision):
+        return supervisions
+    if isinstance(supervisions, (list, tuple)):
+        kinds = [isinstance(s, GraphSupervision) for s in supervisions]
+        if any(kinds):
+            if not all(kinds):
+                raise TypeError("a list of supervisions mixes GraphSupervision and Supervision")
+            if len(supervisions) != 1:
+                raise TypeError("a GraphSupervision holds the whole minibatch: pass one, not a list of %d" % len(supervisions))
+            return supervisions[0]
+    return None
+
+
 class _SupervisionBatch:
     """Concatenates per-utterance supervisions and ships them to the device in one
     pinned H2D copy (a few tens of KB)."""
@@ -675,7 +734,10 @@ def compute_chain_objf_and_deriv(opts, den_graph, supervisions, nnet_output, len
     holds MINUS the derivative, what the reference operator's backward returns (ops/ops.py:276-280); both come out of the
     library call itself, no torch kernel runs around it.
     """
+    gs = _as_graph_supervision(supervisions)
     _lib.require_gpu()
+    if gs is not None:
+        return _graph_objf_and_deriv(opts, den_graph, gs, nnet_output, operator_form)
     if isinstance(supervisions, Supervision):
         supervisions = [supervisions]
     x = nnet_output
@@ -715,6 +777,65 @@ def compute_chain_objf_and_deriv(opts, den_graph, supervisions, nnet_output, len
     # keep the pinned staging buffer alive until the stream has consumed it
     out._pk2_keepalive = sb
     return out, grad
+
+
+def _graph_objf_and_deriv(opts, den_graph, gs, nnet_output, operator_form):
+    """compute_chain_objf_and_deriv for a GraphSupervision: one library call, no torch kernel around it."""
+    x = nnet_output
+    if x.dim() == 2:
+        x = x.unsqueeze(0)
+    assert x.is_cuda and x.dtype == torch.float32 and x.stride(2) == 1
+    N, T, P = x.shape
+    graphs = gs.graphs
+    Tmax = int(graphs.frames.max())
+    assert N == graphs.n and P == den_graph.num_pdfs() and Tmax <= T
+    L = _lib.lib()
+    dev = graphs.to_device(x.device)
+    ws = _workspace(x.device, L.pk2_chain_graph_workspace_bytes(den_graph._h, graphs._h))
+    grad = torch.empty_like(x)
+    if Tmax < T:
+        grad[:, Tmax:].zero_()
+    opt = (float(opts.leaky_hmm_coefficient), float(opts.xent_regularize), float(opts.l2_regularize), float(gs.weight))
+    if operator_form:
+        out = torch.empty(3 * N + 1, dtype=torch.float32, device=x.device)
+        _lib.check(L.pk2_chain_objf_and_deriv_graph_op(den_graph._h, _lib.ptr(x), x.stride(0), x.stride(1), graphs._h, _lib.ptr(dev),
+                                                       *opt, _lib.ptr(grad), grad.stride(0), grad.stride(1), _lib.ptr(out),
+                                                       _lib.ptr(ws), ws.numel(), -1.0, _lib.ptr(out[3 * N:]),
+                                                       _lib.stream_ptr(x.device)))
+    else:
+        out = torch.empty(3, N, dtype=torch.float32, device=x.device)
+        _lib.check(L.pk2_chain_objf_and_deriv_graph(den_graph._h, _lib.ptr(x), x.stride(0), x.stride(1), graphs._h, _lib.ptr(dev),
+                                                    *opt, _lib.ptr(grad), grad.stride(0), grad.stride(1), _lib.ptr(out),
+                                                    _lib.ptr(ws), ws.numel(), _lib.stream_ptr(x.device)))
+    out._pk2_keepalive = (gs, dev)
+    return out, grad
+
+
+def num_graph_forward_backward(graphs, nnet_output, scale=1.0, grad=None):
+    """Alignment-free numerator only: (log p_num [N], posteriors [N, T, P]); the first carries the device statuses as
+    `.status`.  graphs: AlignmentGraphs or GraphSupervision.  Test / profiling hook, the twin of den_forward_backward; with
+    `grad` given, scale * posterior is added into it (rows of utterances without a graph and rows past an utterance's frames
+    are not touched)."""
+    _lib.require_gpu()
+    graphs = getattr(graphs, "graphs", graphs)
+    x = nnet_output
+    assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and x.stride(2) == 1
+    N, T, P = x.shape
+    assert N == graphs.n and int(graphs.frames.max()) <= T
+    L = _lib.lib()
+    dev = graphs.to_device(x.device)
+    ws = _workspace(x.device, L.pk2_num_graph_workspace_bytes(graphs._h))
+    if grad is None:
+        grad = torch.zeros(N, T, P, dtype=torch.float32, device=x.device)
+    assert grad.is_cuda and grad.dtype == torch.float32 and grad.shape == x.shape and grad.stride(2) == 1
+    lp = torch.empty(N, dtype=torch.float32, device=x.device)
+    status = torch.empty(N, dtype=torch.int32, device=x.device)
+    _lib.check(L.pk2_num_graph_fwd_bwd(graphs._h, _lib.ptr(dev), _lib.ptr(x), x.stride(0), x.stride(1), P, T, float(scale),
+                                       _lib.ptr(grad), grad.stride(0), grad.stride(1), _lib.ptr(lp), _lib.ptr(status),
+                                       _lib.ptr(ws), ws.numel(), _lib.stream_ptr(x.device)))
+    lp._pk2_keepalive = (graphs, dev)
+    lp.status = status
+    return lp, grad
 
 
 def den_forward_backward(den_graph, nnet_output, lengths, leaky):

@@ -5,9 +5,13 @@
 #include <algorithm>
 #include <cstdlib>
 
+#include "align_internal.h"
 #include "chain_internal.h"
+#include "chain_num_graph.h"
 
 namespace pk2 {
+void align_graphs_limits(const pk2_align_graphs* G, int32_t* num_utts, int32_t* max_states, int32_t* max_pdf, int32_t* max_arcs,
+                         size_t* ws_bytes, const int32_t** packed);
 
 __global__ void __launch_bounds__(256) zero_rows(float* out, int64_t seq_stride, int64_t frame_stride,
                                                  int P, int Tmax) {
@@ -21,10 +25,11 @@ __global__ void __launch_bounds__(256) zero_rows(float* out, int64_t seq_stride,
 // (a product that is merely not ApproxEqual to it -- relative 1e-3 -- only draws a warning there and is trained on); here
 // the check is per sequence, so num_sequences = 1.  (Rounds 1-3 abandoned at 0.05: VERDICT r3, weak #1b.)
 constexpr float kAlphaBetaAbandon = 2.0f;
-// One workgroup of 256; *objf_sum (optional) = sum_n out[n], added in a fixed order.
+// One workgroup of 256; *objf_sum (optional) = sum_n out[n], added in a fixed order.  The three output rows are `ostride`
+// apart (N for a whole batch; the graph entry hands in a run of a longer batch and adds the run's sum to *objf_sum).
 __global__ void __launch_bounds__(256) chain_flags(const float* num_lp, const float* den_lp, const float* check,
                                                    const int32_t* lengths, int N, float weight, float* out, int32_t* flags,
-                                                   float* objf_sum) {
+                                                   float* objf_sum, int ostride, int add_sum) {
   __shared__ float red[4];
   float acc = 0.f;
   for (int n = threadIdx.x; n < N; n += 256) {
@@ -34,15 +39,24 @@ __global__ void __launch_bounds__(256) chain_flags(const float* num_lp, const fl
     flags[n] = ok ? 1 : 0;
     const float o = ok ? objf : -10.0f * weight * (float)lengths[n];
     out[n] = o;
-    out[N + n] = nl;
-    out[2 * N + n] = dl;
+    out[ostride + n] = nl;
+    out[2 * ostride + n] = dl;
     acc += o;
   }
   if (objf_sum == nullptr) return;
   acc = wave_sum(acc);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
   __syncthreads();
-  if (threadIdx.x == 0) *objf_sum = (red[0] + red[1]) + (red[2] + red[3]);
+  if (threadIdx.x == 0) {
+    const float sum = (red[0] + red[1]) + (red[2] + red[3]);
+    *objf_sum = add_sum ? *objf_sum + sum : sum;
+  }
+}
+
+// The graph entry's outputs before its runs fill them in: an utterance without a graph keeps (0, 0, 0).
+__global__ void __launch_bounds__(256) chain_out_clear(float* out, int count, float* objf_sum) {
+  for (int i = threadIdx.x; i < count; i += 256) out[i] = 0.f;
+  if (threadIdx.x == 0 && objf_sum != nullptr) *objf_sum = 0.f;
 }
 
 // grad[n][t][p] = ok ? gscale * (grad - weight*gamma - weight*l2*logit) : 0     (grad holds the numerator part)
@@ -169,7 +183,7 @@ static int chain_objf_impl(const pk2_den_graph* gc, const float* logits,
   if (use_side) PK2_HIP(hipStreamWaitEvent(stream, side->join, 0));
   // 3. objective, guards, gradient = numerator - denominator occupancies
   hipLaunchKernelGGL(chain_flags, dim3(1), dim3(256), 0, stream, nbuf.num_lp, db.den_lp,
-                     db.check, db.lengths, N, weight, out, flags, objf_sum);
+                     db.check, db.lengths, N, weight, out, flags, objf_sum, N, 0);
   dispatch_ng(plan.NG, [&](auto ng) {
     hipLaunchKernelGGL(chain_combine<decltype(ng)::value>, dim3(Tmax, plan.G), dim3(256), 0, stream, db.gamma, db.lengths,
                        flags, N, g->P, Tmax, weight, l2_regularize, logits, seq_stride, frame_stride,
@@ -196,6 +210,117 @@ extern "C" int pk2_chain_objf_and_deriv_op(const pk2_den_graph* gc, const float*
                          gss, gfs, out, workspace, workspace_bytes, grad_scale, objf_sum, stream_);
 }
 
+// ---- the same objective with the alignment-free numerator (csrc/chain_num_graph.hip) ----
+// An utterance whose graph has no path of its length (or did not compile) takes no part: the batch is cut into the runs of
+// consecutive utterances that have a graph, and the denominator -- one DenPlan per run -- sees only those.
+namespace {
+struct GraphBatch {
+  int32_t N = 0, max_pdf = -1, Tmax = 0;
+  const AlignDesc* desc = nullptr;
+  std::vector<std::pair<int, int>> runs;     // [first, one past last)
+};
+GraphBatch graph_batch(const pk2_align_graphs* G) {
+  GraphBatch b;
+  int32_t S, A;
+  size_t wsb;
+  const int32_t* packed;
+  align_graphs_limits(G, &b.N, &S, &b.max_pdf, &A, &wsb, &packed);
+  b.desc = reinterpret_cast<const AlignDesc*>(packed);
+  for (int n = 0; n < b.N; ++n) {
+    b.Tmax = std::max(b.Tmax, b.desc[n].T);
+    if (b.desc[n].S == 0) continue;
+    if (!b.runs.empty() && b.runs.back().second == n) b.runs.back().second = n + 1;
+    else b.runs.push_back({n, n + 1});
+  }
+  return b;
+}
+struct GraphCarve { char* num_ws; size_t num_bytes; float* num_lp; int32_t* status; int32_t* flags; void* den; size_t den_bytes; };
+size_t graph_carve(const pk2_den_graph* g, const pk2_align_graphs* G, const GraphBatch& b, void* base, GraphCarve* out) {
+  Carver c(base);
+  GraphCarve k;
+  k.num_bytes = num_graph_workspace(G);
+  k.num_ws = c.take<char>(k.num_bytes);
+  k.num_lp = c.take<float>((size_t)b.N);
+  k.status = c.take<int32_t>((size_t)b.N);
+  k.flags = c.take<int32_t>((size_t)b.N);
+  k.den_bytes = 0;
+  for (auto& r : b.runs) {
+    int T = 0;
+    for (int n = r.first; n < r.second; ++n) T = std::max(T, b.desc[n].T);
+    k.den_bytes = std::max(k.den_bytes, den_workspace(g, r.second - r.first, T, nullptr, nullptr, nullptr));
+  }
+  k.den = c.take<char>(k.den_bytes);
+  if (out) *out = k;
+  return c.bytes();
+}
+}  // namespace
+
+extern "C" size_t pk2_chain_graph_workspace_bytes(const pk2_den_graph* g, const pk2_align_graphs* G) {
+  if (!g || !G) return 0;
+  return graph_carve(g, G, graph_batch(G), nullptr, nullptr);
+}
+
+static int chain_objf_graph_impl(const pk2_den_graph* gc, const float* logits, int64_t seq_stride, int64_t frame_stride,
+                                 const pk2_align_graphs* G, const int32_t* packed_dev, float leaky, float xent_regularize,
+                                 float l2_regularize, float weight, float* grad, int64_t gss, int64_t gfs, float* out,
+                                 void* workspace, size_t workspace_bytes, float gscale, float* objf_sum, void* stream_) {
+  PK2_REQUIRE(gc && logits && G && packed_dev && grad && out && workspace, "chain_objf_and_deriv_graph: null argument");
+  pk2_den_graph* g = const_cast<pk2_den_graph*>(gc);
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  const GraphBatch b = graph_batch(G);
+  PK2_REQUIRE(b.max_pdf < g->P, "chain_objf_and_deriv_graph: the graphs use pdf %d, the denominator graph has %d pdfs", b.max_pdf, g->P);
+  PK2_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255) == 0, "chain_objf_and_deriv_graph: the workspace must be 256-byte aligned");
+  GraphCarve k;
+  const size_t need = graph_carve(g, G, b, workspace, &k);
+  PK2_REQUIRE(workspace_bytes >= need, "chain_objf_and_deriv_graph: workspace %zu < %zu", workspace_bytes, need);
+  // 1. every row of the batch starts at zero (an utterance without a graph keeps that), the outputs too; the numerator
+  //    of all runs adds (1 + xent_regularize) * w * posterior in one call
+  hipLaunchKernelGGL(zero_rows, dim3(b.Tmax, b.N), dim3(256), 0, stream, grad, gss, gfs, g->P, b.Tmax);
+  hipLaunchKernelGGL(chain_out_clear, dim3(1), dim3(256), 0, stream, out, 3 * b.N, objf_sum);
+  int rc = num_graph_compute(G, packed_dev, logits, seq_stride, frame_stride, g->P, weight * (1.0f + xent_regularize), grad, gss,
+                             gfs, k.num_lp, k.status, k.num_ws, k.num_bytes, stream);
+  if (rc) return rc;
+  // 2. per run: denominator, then objective, guards and gradient as in the alignment-based entry
+  std::vector<int32_t> lengths;
+  for (auto& r : b.runs) {
+    const int n0 = r.first, Nr = r.second - r.first;
+    lengths.clear();
+    int Tr = 0;
+    for (int n = n0; n < r.second; ++n) { lengths.push_back(b.desc[n].T); Tr = std::max(Tr, b.desc[n].T); }
+    DenPlan plan; DenBuffers db;
+    den_workspace(g, Nr, Tr, &plan, &db, k.den);
+    const float* x = logits + (int64_t)n0 * seq_stride;
+    float* gr = grad + (int64_t)n0 * gss;
+    rc = den_compute(g, x, seq_stride, frame_stride, lengths.data(), plan, db, leaky, stream);
+    if (rc) return rc;
+    hipLaunchKernelGGL(chain_flags, dim3(1), dim3(256), 0, stream, k.num_lp + n0, db.den_lp, db.check, db.lengths, Nr, weight,
+                       out + n0, k.flags, objf_sum, b.N, 1);
+    dispatch_ng(plan.NG, [&](auto ng) {
+      hipLaunchKernelGGL(chain_combine<decltype(ng)::value>, dim3(Tr, plan.G), dim3(256), 0, stream, db.gamma, db.lengths,
+                         k.flags, Nr, g->P, Tr, weight, l2_regularize, x, seq_stride, frame_stride, gr, gss, gfs, gscale);
+    });
+  }
+  PK2_LAUNCH_CHECK();
+  return PK2_OK;
+}
+
+extern "C" int pk2_chain_objf_and_deriv_graph(const pk2_den_graph* gc, const float* logits, int64_t seq_stride, int64_t frame_stride,
+                                              const pk2_align_graphs* graphs, const int32_t* packed_dev, float leaky,
+                                              float xent_regularize, float l2_regularize, float weight, float* grad, int64_t gss,
+                                              int64_t gfs, float* out, void* workspace, size_t workspace_bytes, void* stream_) {
+  return chain_objf_graph_impl(gc, logits, seq_stride, frame_stride, graphs, packed_dev, leaky, xent_regularize, l2_regularize, weight,
+                               grad, gss, gfs, out, workspace, workspace_bytes, 1.0f, nullptr, stream_);
+}
+
+extern "C" int pk2_chain_objf_and_deriv_graph_op(const pk2_den_graph* gc, const float* logits, int64_t seq_stride,
+                                                 int64_t frame_stride, const pk2_align_graphs* graphs, const int32_t* packed_dev,
+                                                 float leaky, float xent_regularize, float l2_regularize, float weight, float* grad,
+                                                 int64_t gss, int64_t gfs, float* out, void* workspace, size_t workspace_bytes,
+                                                 float grad_scale, float* objf_sum, void* stream_) {
+  return chain_objf_graph_impl(gc, logits, seq_stride, frame_stride, graphs, packed_dev, leaky, xent_regularize, l2_regularize, weight,
+                               grad, gss, gfs, out, workspace, workspace_bytes, grad_scale, objf_sum, stream_);
+}
+
 // Test hook: the objective / guard rule of ComputeChainObjfAndDeriv on given per-sequence quantities (device arrays of N):
 // out[3N] = {objf, num_lp, den_lp}, flags[N] = 1 where the sequence is trained on.  The alpha-beta product of a healthy
 // sequence is 1 to rounding, so the band between Kaldi's warning and its "abandon" threshold can only be reached by
@@ -204,7 +329,7 @@ extern "C" int pk2_chain_debug_flags(const float* num_lp, const float* den_lp, c
                                      int32_t N, float weight, float* out, int32_t* flags, void* stream_) {
   PK2_REQUIRE(num_lp && den_lp && check && lengths && out && flags && N > 0, "chain_debug_flags: bad args");
   hipLaunchKernelGGL(chain_flags, dim3(1), dim3(256), 0, static_cast<hipStream_t>(stream_), num_lp, den_lp, check,
-                     lengths, N, weight, out, flags, static_cast<float*>(nullptr));
+                     lengths, N, weight, out, flags, static_cast<float*>(nullptr), N, 0);
   PK2_LAUNCH_CHECK();
   return PK2_OK;
 }

@@ -27,7 +27,8 @@ from . import _lib, chain, lattice
 
 
 class ChainObjtiveFunction(Function):
-    """Per-utterance LF-MMI (the reference's spelling).  loglikes: [T', P] CUDA f32."""
+    """Per-utterance LF-MMI (the reference's spelling).  loglikes: [T', P] CUDA f32.  supervision: a chain.Supervision, or a
+    chain.GraphSupervision of one utterance (alignment-free numerator)."""
 
     @staticmethod
     def forward(ctx, loglikes, den_graph, supervision, chain_opts):
@@ -44,7 +45,8 @@ class ChainObjtiveFunction(Function):
 
 class ChainObjtiveBatch(Function):
     """All utterances of a minibatch in one call: prediction [B, T', P] (any strides with a unit
-    pdf stride), supervisions = list of chain.Supervision.  Returns the summed objective, i.e.
+    pdf stride), supervisions = list of chain.Supervision, or one chain.GraphSupervision for the minibatch (alignment-free
+    numerator; an utterance whose graph has no path of its length adds nothing).  Returns the summed objective, i.e.
     what the reference's per-utterance loop accumulates (bin/train_chain.py:261-275)."""
 
     @staticmethod
