@@ -603,6 +603,17 @@ size_t pk2_lstm_fwd_workspace_floats(int32_t B, int32_t H, int32_t num_dirs);
 int pk2_lstm_layer_fwd(const float* gx, const float* whh, const float* bhh, int32_t B, int32_t T,
                        int32_t H, int32_t num_dirs, float* y, float* gates, float* cells,
                        void* workspace, void* stream);
+/* The same with the input projections computed inside the recurrence where the kernel can: inp (device f32
+ * [T][B][in_size], the layer's input), w_ih (device f32 [D][4H][in_size]) and b_ih (device f32 [D][4H] or NULL) in place of
+ * gx.  *gx_done = 1: the one-launch recurrence lstm_fwd_seq2_xproj multiplied on its idle MFMA pipe (H = 512, up to 8
+ * (sequence, direction) pairs, in_size 80 or 1024, 16-byte aligned operands, a device whose first forward launch has been
+ * verified); y, gates and cells are written and gx was not read (may be NULL).  *gx_done = 0: nothing was launched or
+ * written; the caller computes gx with pk2_gemm_f32 and calls pk2_lstm_layer_fwd.  PK2_LSTM_SEQ_XPROJ (read per call):
+ * 0 = never fused, 1 = the default, 2 = also 9 .. 32 pairs, queued behind one team per XCD. */
+int pk2_lstm_layer_fwd_xproj(const float* gx, const float* whh, const float* bhh, int32_t B, int32_t T,
+                             int32_t H, int32_t num_dirs, float* y, float* gates, float* cells, void* workspace,
+                             const float* inp, int32_t in_size, const float* w_ih, const float* b_ih,
+                             int32_t* gx_done, void* stream);
 /* dy: device f32 [T][B][D*H] gradient wrt y.  dgx: device f32 [T][B][D*4H]
  * receives the gradient wrt the pre-activations (= gradient wrt gx).
  * scratch: device f32, at least pk2_lstm_bwd_scratch_floats(B,H,D). */

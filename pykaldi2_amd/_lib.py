@@ -205,6 +205,8 @@ SIGNATURES = {
     "pk2_colsum_f32": (C.c_int, [_vp, _i64, _i32, _i32, _f32, _vp, _vp]),
     "pk2_lstm_fwd_workspace_floats": (_sz, [_i32, _i32, _i32]),
     "pk2_lstm_layer_fwd": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "pk2_lstm_layer_fwd_xproj": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp,
+                                           C.POINTER(_i32), _vp]),
     "pk2_lstm_persist_status": (C.c_int, [C.POINTER(C.c_uint32)]),
     "pk2_lstm_last_path": (C.c_int, [C.POINTER(_i32), C.POINTER(_i32)]),
     "pk2_lattice_determinize": (C.c_int, [_i32, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_double, _i64, C.POINTER(_vp)]),

@@ -553,6 +553,26 @@ extern "C" int pk2_lstm_layer_fwd(const float* gx, const float* whh, const float
   return PK2_OK;
 }
 
+// The same, with the input projections gx = inp W_ih^T + b_ih computed inside the recurrence where the kernel can
+// (lstm_fwd_seq2_xproj: the one-launch recurrence of up to 8 (sequence, direction) pairs at H = 512, in_size 80 or 1024).
+// *gx_done = 1: y, gates and cells are written, gx was not read (may be NULL); *gx_done = 0: nothing was launched or
+// written -- the caller runs the product and pk2_lstm_layer_fwd as before.
+extern "C" int pk2_lstm_layer_fwd_xproj(const float* gx, const float* whh, const float* bhh, int32_t B, int32_t T, int32_t H,
+                                        int32_t D, float* y, float* gates, float* cells, void* workspace, const float* inp,
+                                        int32_t in_size, const float* w_ih, const float* b_ih, int32_t* gx_done, void* stream_) {
+  PK2_REQUIRE(gx_done, "lstm_fwd_xproj: null gx_done");
+  *gx_done = 0;
+  PK2_REQUIRE(whh && y && gates && cells && inp && w_ih && B > 0 && T > 0 && in_size > 0 && (D == 1 || D == 2), "lstm_fwd_xproj: bad args");
+  PK2_REQUIRE(lstm_h_ok(H), "lstm_fwd_xproj: hidden size %d unsupported (64,128,256,512,1024)", H);
+  (void)gx; (void)workspace;
+  if (!lstm_seq_wanted(B, H, D)) return PK2_OK;
+  bool ran = false;
+  int prc = lstm_fwd_seq_xproj_launch(inp, in_size, w_ih, b_ih, whh, bhh, B, T, H, D, y, gates, cells, static_cast<hipStream_t>(stream_), &ran);
+  if (prc) return prc;
+  if (ran) { g_last_fwd_path = PK2_LSTM_PATH_SEQ; *gx_done = 1; }
+  return PK2_OK;
+}
+
 // Test / monitoring hook: 1 in *abort_flag when a poll of a persistent recurrence (lstm_persist_seq.hip,
 // lstm_persist_big.hip) has timed out (synchronises the device).
 extern "C" int pk2_lstm_persist_status(uint32_t* abort_flag) {

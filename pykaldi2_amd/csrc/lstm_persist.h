@@ -10,6 +10,12 @@ namespace pk2 {
 bool lstm_seq_wanted(int B, int H, int D);
 int lstm_fwd_seq_launch(const float* gx, const float* whh, const float* bhh, int B, int T, int H, int D, float* y,
                         float* gates, float* cells, hipStream_t stream, bool* ran);
+// The same launch computing its own input projections gx = inp W_ih^T + b_ih (lstm_fwd_seq2_xproj): inp [T][B][in_size],
+// wih [D][4H][in_size], bih [D][4H] or null.  *ran = false: not fused (PK2_LSTM_SEQ_XPROJ, more than 8 pairs, in_size,
+// alignment, residency, a device not verified yet) -- nothing was launched or written, the caller multiplies and calls
+// lstm_fwd_seq_launch.
+int lstm_fwd_seq_xproj_launch(const float* inp, int in_size, const float* wih, const float* bih, const float* whh, const float* bhh,
+                              int B, int T, int H, int D, float* y, float* gates, float* cells, hipStream_t stream, bool* ran);
 // dbias_ih / dbias_hh (may be null): [D][4H] accumulators (+=) of the bias gradient, filled by the kernel inside its
 // launch; *bias_done says whether it was.
 // wgrad (may be null): the recurrent weight gradient from inside the recurrence -- y [T][B][D*H] the forward pass's

@@ -432,6 +432,295 @@ __device__ __forceinline__ void lstm_fwd_seq2_body(const SeqFwdParams& p, SeqCtl
   }
 }
 
+// XPROJ (lstm_fwd_seq2_xproj): the recurrence computes its own input projections gx = inp W_ih^T + b_ih on the MFMA pipe,
+// which lstm_fwd_seq2 leaves idle for the whole launch.  The workgroup has eight waves: waves 0..3 run the recurrence of
+// lstm_fwd_seq2 (minus wave 2's prefetch of gx), waves 4..7 -- one more per SIMD -- are projection waves and run a block of
+// 32 time steps ahead of them:
+//  * projection wave g owns gate g's 16 rows of the workgroup's 64 (all of K: no partial sums to add, the k order of a
+//    result is fixed) and both 16-step halves of a block: G[16 rows][2 x 16 steps] in accumulators of
+//    v_mfma_f32_16x16x4_f32 (the f32 fmaf chain), two per half -- the k's with the same k % 2 form one chain of K / 2
+//    products, the two are added at the end of the block (four per half do not fit 256 registers) -- which take turns (40 clocks of dependent latency, 32 of issue);
+//  * a loop iteration = one step of the recurrence = one chunk of 32 k's: 16 MFMAs per wave (512 clocks of a ~2100-clock
+//    step), so a block of 32 steps covers K = 1024 (in_size 80: three chunks, the rest of the block idles);
+//  * its rows of W_ih (16 x K): the first 16 chunks in registers (128 per lane), the other 16 in LDS (4 x 32 KB, lane-major
+//    16-byte granules: conflict-free), read once per block;
+//  * the chunk of inp (32 steps x 32 k's = 4 KB, a 16-byte granule per projection thread, clamped to the last step) is
+//    loaded two iterations ahead and staged in LDS a barrier ahead, so the 32 CUs of a team read inp once from their L2;
+//  * the projection waves take part in the step's one s_barrier and in nothing else of the recurrence; the finished
+//    block (+ b_ih) goes into an LDS ring of two blocks, from which the recurrence waves read their step's 64 values as
+//    they read gxs in lstm_fwd_seq2 -- behind the step's barrier, not in front of it: block n is written in the iteration
+//    of step 32 n - 1, so that barrier lies between the write and step 32 n's read, and 32 barriers between the last read
+//    of block n - 2 and the write;
+//  * before step 0 the recurrence waves sit out 32 barriers while block 0 is computed;
+//  * the f32 MFMA runs at the vector rate on the SIMD a projection wave shares with a recurrence wave, so the chunk is
+//    issued while that wave polls, not while it multiplies: the projection waves rest behind the barrier (kXSleep) and
+//    the recurrence waves run at a higher priority (the measurements).
+struct SeqXprojParams {
+  const float* inp;   // [T][B][K]
+  const float* wih;   // [D][4H][K]
+  const float* bih;   // [D][4H] or null
+  int K;              // in_size: 80 or 1024, the kernel's template argument
+};
+constexpr int kXBlock = 32;                 // time steps per block = k's per chunk = iterations the projection waves run ahead
+constexpr int kXPitch = 36;                 // (as kSlicePitch)
+#ifndef PK2_SEQ_XSLEEP
+#define PK2_SEQ_XSLEEP 17
+#endif
+constexpr int kXSleep = PK2_SEQ_XSLEEP;     // x 64 clocks: the projection waves' rest behind a step's barrier (experiment builds: -DPK2_SEQ_XSLEEP=n)
+
+template <int K>
+__device__ __forceinline__ void lstm_fwd_seq2_xproj_body(const SeqFwdParams& p, const SeqXprojParams& xp, SeqCtl* ctl) {
+  constexpr int H = kSH;
+  constexpr int kSlicePitch = 36;
+  constexpr int NCH = (K + 31) / 32;                                    // chunks of 32 k's (the last one may be short)
+  constexpr int NREG = NCH < 16 ? NCH : 16, NLDS = NCH - NREG;          // chunks of W_ih in registers / in LDS
+  static_assert(K % 4 == 0 && NCH >= 1 && NCH <= kXBlock, "a block of 32 iterations holds at most 32 chunks of 16-byte granules");
+  __shared__ __attribute__((aligned(16))) float hs[2][16 * kSlicePitch];
+  __shared__ __attribute__((aligned(16))) float xring[2][kXBlock][64];  // input projections [block & 1][step % 32][gate * 16 + unit]
+  __shared__ __attribute__((aligned(16))) float xs[2][kXBlock][kXPitch];  // the chunk of inp [iteration & 1][step % 32][k % 32]
+  __shared__ __attribute__((aligned(16))) float wl[NLDS > 0 ? NLDS : 1][2][256][4];  // W_ih [chunk - NREG][half][projection thread]
+  __shared__ float outs[2][80];
+  __shared__ int s_i[8];
+  const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  SeqRole role;
+  if (!seq_register(ctl, s_i, &role)) return;
+  const int rank = role.rank, B = p.B, T = p.T, D = p.D;
+  const int ul = lane >> 4, l16 = lane & 15;
+  const int uw = 4 * (w & 3) + ul;
+  const int gu = 16 * rank + uw;
+  const bool unit_lane = l16 == 0, gate_lane = l16 < 4;
+  const bool poller = w < 2;
+  const int gran = (w & 1) * 64 + lane;
+  const float act_s = l16 == 2 ? -2.8853900817779268f : -1.4426950408889634f;
+  const float act_a = l16 == 2 ? 2.0f : 1.0f, act_b = l16 == 2 ? -1.0f : 0.0f;
+  const int pre_idx = 16 * (l16 & 3) + uw, out_idx = gate_lane ? 16 * l16 + uw : 0;
+  const size_t yrow = (size_t)D * H;
+  unsigned nbar = 0;
+  for (int iter = 0; iter <= kSeqMaxTasks; ++iter) {
+    const int task = seq_next_task(ctl, role, iter, B * D, s_i);
+    if (task < 0) return;
+    const int b = task / D, d = task % D;
+    if (w >= 4) {
+      // ---- projection waves ------------------------------------------------------------------------------------------------
+      // MFMA operands: lane = (m = lane % 16, kq = lane / 16); instruction e of a chunk multiplies the k's 32 c + 8 kq + e:
+      // A = W_ih[row m][k], B = inp[step n = m][k]; D: lane holds rows 4 kq .. 4 kq + 3 of column (step) m.
+      const int q = tid - 256, pw = w - 4, m = l16, kq = ul;
+      const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
+      f32x4 wreg[NREG][2];
+      {
+        const float* wrow = xp.wih + ((size_t)d * 4 * H + (size_t)pw * H + 16 * rank + m) * K;
+        auto wload = [&](int c, int h) -> f32x4 {          // (K is a multiple of 4: a granule lies inside the row or outside)
+          const int k = 32 * c + 8 * kq + 4 * h;
+          const f32x4 v = *reinterpret_cast<const f32x4*>(wrow + (k < K ? k : 0));
+          return k < K ? v : zero4;
+        };
+#pragma unroll 2
+        for (int c = NREG; c < NCH; ++c) {                 // (first, a few at a time: the registers are for the chunks that stay)
+          *reinterpret_cast<f32x4*>(&wl[c - NREG][0][q][0]) = wload(c, 0);
+          *reinterpret_cast<f32x4*>(&wl[c - NREG][1][q][0]) = wload(c, 1);
+        }
+#pragma unroll
+        for (int c = 0; c < NREG; ++c) { wreg[c][0] = wload(c, 0); wreg[c][1] = wload(c, 1); }
+      }
+      f32x4 bi = zero4;
+      if (xp.bih) bi = *reinterpret_cast<const f32x4*>(xp.bih + (size_t)d * 4 * H + (size_t)pw * H + 16 * rank + 4 * kq);
+      // the thread's 16-byte granule of chunk c of a block: step 32 block + tq (clamped: the last block), k's 32 c + 4 k4 ..;
+      // loads are unconditional (see lstm_fwd_seq2), granules past K read the row's start and count 0
+      const int tq = q >> 3, k4 = q & 7;
+      auto xrow = [&](int block) -> const float* {
+        const int s = min(kXBlock * block + tq, T - 1);
+        const size_t t = d == 0 ? (size_t)s : (size_t)(T - 1 - s);
+        return xp.inp + (t * B + b) * (size_t)K;
+      };
+      auto xload = [&](const float* row, int c) -> f32x4 {
+        const int k = 32 * c + 4 * k4;
+        const f32x4 v = *reinterpret_cast<const f32x4*>(row + (k < K ? k : 0));
+        return k < K ? v : zero4;
+      };
+      const float* xrow_cur = xrow(0);
+      const float* xrow_next = xrow(1);
+      f32x4 xnext = xload(xrow_cur, 0);
+      *reinterpret_cast<f32x4*>(&xs[0][tq][4 * k4]) = xnext;
+      xnext = NCH > 1 ? xload(xrow_cur, 1) : zero4;
+      f32x4 acc0[2] = {zero4, zero4}, acc1[2] = {zero4, zero4};     // [k % 2]: chains of K / 2 products
+      __builtin_amdgcn_s_waitcnt(0x0F70);      // vmcnt(0): as below
+      __syncthreads();
+#ifdef PK2_SEQ_PROFILE
+      long long xq_bar = 0, xq_work = 0;
+#endif
+      const int iters = T + kXBlock;
+      for (int i0 = 0; i0 < iters; i0 += kXBlock) {
+        if (i0 > 0) { xrow_cur = xrow_next; xrow_next = xrow((i0 >> 5) + 1); }
+#pragma unroll
+        for (int c = 0; c < kXBlock; ++c) {
+          const int i = i0 + c;
+          if (i >= iters) break;
+#ifdef PK2_SEQ_PROFILE
+          const long long xq0 = clock64();
+#endif
+          seq_lds_barrier();
+          if (s_i[3]) return;
+#ifdef PK2_SEQ_PROFILE
+          const long long xq1 = clock64();
+          xq_bar += xq1 - xq0;
+#endif
+          // The f32 MFMAs run at the VALU's rate on the SIMD they share with a recurrence wave: issued right behind the
+          // barrier they delay that wave's product by their whole length (measured: product + row sums 806 -> 1331 clocks).
+          // So the chunk waits until the recurrence waves have stored h and only poll (~930 clocks behind the barrier;
+          // not while block 0 is computed, when they only sit at the barrier).
+          if (i0 > 0) __builtin_amdgcn_s_sleep(kXSleep);
+          // the next iteration's chunk of inp into LDS (loaded an iteration ago), the one after it requested
+          if ((c + 1) % kXBlock < NCH) *reinterpret_cast<f32x4*>(&xs[(c + 1) & 1][tq][4 * k4]) = xnext;
+          if ((c + 2) % kXBlock < NCH) xnext = xload(c + 2 < kXBlock ? xrow_cur : xrow_next, (c + 2) % kXBlock);
+          if (c < NCH) {
+            f32x4 a0, a1;
+            if (c < NREG) { a0 = wreg[c < NREG ? c : 0][0]; a1 = wreg[c < NREG ? c : 0][1]; }
+            else {
+              a0 = *reinterpret_cast<const f32x4*>(&wl[c < NREG ? 0 : c - NREG][0][q][0]);
+              a1 = *reinterpret_cast<const f32x4*>(&wl[c < NREG ? 0 : c - NREG][1][q][0]);
+            }
+            const float* x0 = &xs[c & 1][m][8 * kq];
+            const float* x1 = &xs[c & 1][16 + m][8 * kq];
+            const f32x4 b00 = *reinterpret_cast<const f32x4*>(x0), b01 = *reinterpret_cast<const f32x4*>(x0 + 4);
+            const f32x4 b10 = *reinterpret_cast<const f32x4*>(x1), b11 = *reinterpret_cast<const f32x4*>(x1 + 4);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+              acc0[e & 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[e], b00[e], acc0[e & 1], 0, 0, 0);
+              acc1[e & 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0[e], b10[e], acc1[e & 1], 0, 0, 0);
+            }
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+              acc0[e & 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[e], b01[e], acc0[e & 1], 0, 0, 0);
+              acc1[e & 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1[e], b11[e], acc1[e & 1], 0, 0, 0);
+            }
+          }
+          if (c == kXBlock - 1) {          // the block is complete: into the ring, a barrier ahead of its first reader
+            float (*ring)[64] = xring[(i >> 5) & 1];
+            *reinterpret_cast<f32x4*>(&ring[m][16 * pw + 4 * kq]) = (acc0[0] + acc0[1]) + bi;
+            *reinterpret_cast<f32x4*>(&ring[16 + m][16 * pw + 4 * kq]) = (acc1[0] + acc1[1]) + bi;
+#pragma unroll
+            for (int e = 0; e < 2; ++e) { acc0[e] = zero4; acc1[e] = zero4; }
+          }
+#ifdef PK2_SEQ_PROFILE
+          xq_work += clock64() - xq1;
+#endif
+        }
+      }
+#ifdef PK2_SEQ_PROFILE
+      if (q == 0 && rank == 0 && iter == 0)
+        printf("lstm_fwd_seq2_xproj<%d> projection wave 4, %d iterations: %lld clocks per iteration at the barrier | %lld on its chunk\n", K, iters,
+               xq_bar / iters, xq_work / iters);
+#endif
+      __syncthreads();
+    } else {
+      // ---- recurrence waves: lstm_fwd_seq2 with the input projections from the ring ------------------------------------------
+      // (they win the issue arbitration of their SIMD against its projection wave: a poll's compare does not queue behind MFMAs)
+      __builtin_amdgcn_s_setprio(3);
+      f32x2 wa[4][16];                                     // W_hh[d][g*H + gu][32 l16 + 2 i, + 1]
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const float* wrow = p.whh + ((size_t)d * 4 * H + (size_t)g * H + gu) * H + 32 * l16;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+          const f32x4 v = *reinterpret_cast<const f32x4*>(wrow + i * 4);
+          wa[g][2 * i] = f32x2{v[0], v[1]};
+          wa[g][2 * i + 1] = f32x2{v[2], v[3]};
+        }
+      }
+      const float bias = (gate_lane && p.bhh) ? p.bhh[(size_t)d * 4 * H + (size_t)l16 * H + gu] : 0.f;
+      const ptrdiff_t tdir = d == 0 ? 1 : -1;
+      const size_t t0 = d == 0 ? 0 : (size_t)(T - 1);
+      const ptrdiff_t y_stride = tdir * (ptrdiff_t)((size_t)B * yrow);
+      float* y_out = p.y + (t0 * B + b) * yrow + (size_t)d * H + gu;
+      const float* y_poll = p.y + (t0 * B + b) * yrow + (size_t)d * H + 4 * gran - y_stride;
+      const ptrdiff_t gates_stride = tdir * (ptrdiff_t)((size_t)B * 4 * H), cells_stride = tdir * (ptrdiff_t)((size_t)B * H);
+      float* gates_out = p.gates + (((size_t)d * T + t0) * B + b) * 4 * H + (size_t)(lane >> 4) * H + 16 * rank + (lane & 15);
+      float* cells_out = p.cells + (((size_t)d * T + t0) * B + b) * H + 16 * rank + (lane & 15);
+      __builtin_amdgcn_s_waitcnt(0x0F70);      // vmcnt(0): W_hh is there before the loop (see lstm_fwd_seq2)
+      __syncthreads();
+      for (int i = 0; i < kXBlock; ++i) {      // block 0 of the projections
+        seq_lds_barrier();
+        if (s_i[3]) return;
+      }
+      float cstate = 0.f;
+      bool timed_out = false;
+      SeqSpin spin(ctl);
+      spin.limit = 10 * kSeqSpinTicks;
+      SQ_T0();
+      for (int step = 0; step < T; ++step) {
+        if (step == 2) { spin.limit = kSeqSpinTicks; spin.t0 = 0; }
+        const int buf = step & 1;
+        if (step > 0 && poller) {
+          u32x4 v = seq_load16(y_poll);
+          while (seq_has_sentinel(v)) {
+            if (spin.expired()) { timed_out = true; break; }
+            v = seq_load16(y_poll);
+          }
+          *reinterpret_cast<u32x4*>(&hs[buf][(gran >> 3) * kSlicePitch + 4 * (gran & 7)]) = v;
+        }
+        y_poll += y_stride;
+        SQ_T(0);
+        if (timed_out) s_i[3] = 1;
+        seq_lds_barrier();
+        SQ_T(1);
+        if (s_i[3]) return;
+        const float pre = xring[(step >> 5) & 1][step & 31][pre_idx] + bias;
+        float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+        if (step > 0) {
+          const float* hq = &hs[buf][l16 * kSlicePitch];
+          f32x2 a0 = {0.f, 0.f}, a1 = a0, a2 = a0, a3 = a0, c0 = a0, c1 = a0, c2 = a0, c3 = a0;
+          f32x4 hva[8];
+#pragma unroll
+          for (int i = 0; i < 8; ++i) hva[i] = *reinterpret_cast<const f32x4*>(hq + 4 * i);
+          __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+          for (int i = 0; i < 8; ++i) {
+            const f32x4 hv = hva[i];
+            const f32x2 h01 = {hv[0], hv[1]}, h23 = {hv[2], hv[3]};
+            a0 = __builtin_elementwise_fma(wa[0][2 * i], h01, a0); c0 = __builtin_elementwise_fma(wa[0][2 * i + 1], h23, c0);
+            a1 = __builtin_elementwise_fma(wa[1][2 * i], h01, a1); c1 = __builtin_elementwise_fma(wa[1][2 * i + 1], h23, c1);
+            a2 = __builtin_elementwise_fma(wa[2][2 * i], h01, a2); c2 = __builtin_elementwise_fma(wa[2][2 * i + 1], h23, c2);
+            a3 = __builtin_elementwise_fma(wa[3][2 * i], h01, a3); c3 = __builtin_elementwise_fma(wa[3][2 * i + 1], h23, c3);
+          }
+          s0 = (a0[0] + a0[1]) + (c0[0] + c0[1]);
+          s1 = (a1[0] + a1[1]) + (c1[0] + c1[1]);
+          s2 = (a2[0] + a2[1]) + (c2[0] + c2[1]);
+          s3 = (a3[0] + a3[1]) + (c3[0] + c3[1]);
+          seq_row_sum4(s0, s1, s2, s3);
+        }
+#ifdef PK2_SEQ_PROFILE
+        asm volatile("" : "+v"(s0), "+v"(s1), "+v"(s2), "+v"(s3));
+#endif
+        SQ_T(2);
+        const float x = pre + (l16 == 0 ? s0 : l16 == 1 ? s1 : l16 == 2 ? s2 : s3);
+        const float act = fmaf(act_a, __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(act_s * x)), act_b);
+        const float fg = seq_dpp<0x101>(act), gg = seq_dpp<0x102>(act), og = seq_dpp<0x103>(act);
+        cstate = fg * cstate + act * gg;
+        const float h = og * seq_tanh(cstate);
+        if (unit_lane) seq_store(y_out, h);
+        y_out += y_stride;
+        SQ_T(3);
+        if (gate_lane) outs[buf][out_idx] = act;
+        if (unit_lane) outs[buf][64 + uw] = cstate;
+        if (w == 3 && step > 0) {
+          *gates_out = outs[buf ^ 1][lane];
+          if (lane < 16) *cells_out = outs[buf ^ 1][64 + lane];
+          gates_out += gates_stride; cells_out += cells_stride;
+        }
+        SQ_T(4);
+      }
+      __syncthreads();
+      if (w == 3) {
+        *gates_out = outs[(T - 1) & 1][lane];
+        if (lane < 16) *cells_out = outs[(T - 1) & 1][64 + lane];
+      }
+      SQ_PRINT("lstm_fwd_seq2_xproj", "(poll | lds + barrier | product + row sums | gates + h store | lds hand-over, wave 3 traffic)", T);
+      if (tid == 0 && rank == 0) __hip_atomic_fetch_add(&ctl->done, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    if (!seq_team_barrier(ctl, role, &nbar, s_i)) return;
+  }
+}
+
 // WGRAD (lstm_bwd_seq2_wgrad): on top of the recurrence the workgroup keeps its 64 x 512 slice of
 //   dW_hh[d] = sum_t dg_d[t]^T h_d[t -+ 1]        (the partner frame is the one the NEXT backward step visits)
 // of its pair as MFMA accumulators: a step adds the rank-1 update dgl[64] x y[t_next][b][d*H ..][512] with 16
@@ -752,6 +1041,13 @@ __global__ void __launch_bounds__(256) lstm_bwd_seq2_wgrad(SeqBwdParams p, SeqCt
   seq_exit_check(ctl, x);
 }
 
+// (512 threads: two waves per SIMD, at most 256 registers per lane; one workgroup per CU by its LDS)
+template <int K>
+__global__ void __launch_bounds__(512) lstm_fwd_seq2_xproj(SeqFwdParams p, SeqXprojParams xp, SeqCtl* ctl, SeqExit x) {
+  lstm_fwd_seq2_xproj_body<K>(p, xp, ctl);
+  seq_exit_check(ctl, x);
+}
+
 // dwhh[d][r][k] += sum over the sequences b = 0 .. B - 1, in this order, of ws[b D + d][r][k]: the result is fixed by
 // construction (no float atomics).  A launch that gave up has left slices unwritten and the sticky word of its stream set
 // (seq_exit_check, which runs before this kernel starts): then dwhh turns NaN like dgx.  The word is the one
@@ -807,23 +1103,31 @@ bool lstm_seq_wanted(int B, int H, int D) {
   return device_cu_count() == 8 * kSWgs;
 }
 
-int lstm_fwd_seq_launch(const float* gx, const float* whh, const float* bhh, int B, int T, int H, int D, float* y,
-                        float* gates, float* cells, hipStream_t stream, bool* ran) {
+// The forward launch protocol, shared by lstm_fwd_seq2 and lstm_fwd_seq2_xproj (xp != null: `teams` teams per XCD of its
+// 512-thread workgroups): control block, y pre-filled with the sentinel, the folded exit check (or, on first use of a device,
+// the host's verdict and the separate check kernel).
+static int seq_fwd_launch(const SeqFwdParams& p, const SeqXprojParams* xp, int teams, int H, hipStream_t stream, bool* ran) {
   *ran = false;
+  const int B = p.B, T = p.T, D = p.D;
+  float* y = p.y;
   SeqScratch* sc = nullptr;
   int rc = seq_scratch(stream, &sc);
   if (rc) return rc;
   if (!sc->ctl_clean) PK2_HIP(hipMemsetAsync(sc->ctl, 0, sizeof(SeqCtl), stream));
   sc->ctl_clean = false;
   PK2_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(y), (int)kSeqSentinel, (size_t)T * B * D * H, stream));
-  SeqFwdParams p{gx, whh, bhh, y, gates, cells, B, T, D};
   // (the first launch on a device is checked by the host below and by the separate check kernel: no folded check)
   const bool fold = g_seq.verified();
   // (test hook, read per call: PK2_LSTM_SEQ_TEST_FAIL=1 makes the folded check of a forward launch behave as if a poll had timed out)
   const char* tf_e = getenv("PK2_LSTM_SEQ_TEST_FAIL");
   const int fold_mode = fold ? ((tf_e && atoi(tf_e) == 1) ? 2 : 1) : 0;
   const SeqExit ex{(unsigned)(B * D), fold_mode, y, (size_t)T * B * D * H, sc->sticky, sc->guard.dev, sc->guard.host_dev, nullptr, (size_t)0};
-  hipLaunchKernelGGL(lstm_fwd_seq2, dim3(8 * kSWgs * seq_teams(B * D)), dim3(256), 0, stream, p, sc->ctl, ex);
+  if (!xp)
+    hipLaunchKernelGGL(lstm_fwd_seq2, dim3(8 * kSWgs * teams), dim3(256), 0, stream, p, sc->ctl, ex);
+  else if (xp->K == 80)
+    hipLaunchKernelGGL(lstm_fwd_seq2_xproj<80>, dim3(8 * kSWgs * teams), dim3(512), 0, stream, p, *xp, sc->ctl, ex);
+  else
+    hipLaunchKernelGGL(lstm_fwd_seq2_xproj<1024>, dim3(8 * kSWgs * teams), dim3(512), 0, stream, p, *xp, sc->ctl, ex);
   PK2_LAUNCH_CHECK();
   bool ok = false;                                // first use on this device: every pair done, nobody timed out?
   rc = g_seq.verify_first_use(&sc->ctl->abort, &sc->ctl->done, (unsigned)(B * D), stream, &ok);
@@ -833,6 +1137,46 @@ int lstm_fwd_seq_launch(const float* gx, const float* whh, const float* bhh, int
   sc->ctl_clean = true;
   *ran = true;
   return PK2_OK;
+}
+
+int lstm_fwd_seq_launch(const float* gx, const float* whh, const float* bhh, int B, int T, int H, int D, float* y,
+                        float* gates, float* cells, hipStream_t stream, bool* ran) {
+  const SeqFwdParams p{gx, whh, bhh, y, gates, cells, B, T, D};
+  return seq_fwd_launch(p, nullptr, seq_teams(B * D), H, stream, ran);
+}
+
+// lstm_fwd_seq2_xproj keeps 156 KB of LDS and eight waves: it is used only where the runtime says that a workgroup of
+// either instantiation fits a CU (asked once per device, as for lstm_bwd_seq2_wgrad).
+static bool seq_xproj_resident() {
+  static std::map<int, bool> fit;
+  const int dev = current_device();
+  auto it = fit.find(dev);
+  if (it == fit.end()) {
+    int n80 = 0, n1024 = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n80, lstm_fwd_seq2_xproj<80>, 512, 0) != hipSuccess) { (void)hipGetLastError(); n80 = 0; }
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n1024, lstm_fwd_seq2_xproj<1024>, 512, 0) != hipSuccess) { (void)hipGetLastError(); n1024 = 0; }
+    it = fit.emplace(dev, n80 >= 1 && n1024 >= 1).first;
+  }
+  return it->second;
+}
+
+// PK2_LSTM_SEQ_XPROJ, read per call: 0 = the caller multiplies as before; 1 = fused for up to 8 pairs (one team per XCD, a
+// workgroup per CU); 2 = also for 9 .. 32 pairs, which then queue up behind 8 teams instead of 16 (for the tests: it is
+// what makes a team compute a second pair's projections over the ring of the first).
+// Not fused (*ran = false, nothing launched or written): a device whose first forward launch has not been verified yet,
+// in_size other than 80 and 1024, operands that are not 16-byte aligned.
+int lstm_fwd_seq_xproj_launch(const float* inp, int in_size, const float* wih, const float* bih, const float* whh, const float* bhh,
+                              int B, int T, int H, int D, float* y, float* gates, float* cells, hipStream_t stream, bool* ran) {
+  *ran = false;
+  const char* xe = getenv("PK2_LSTM_SEQ_XPROJ");
+  const int mode = xe ? atoi(xe) : 1;
+  if (mode == 0 || !g_seq.verified() || (in_size != 80 && in_size != 1024)) return PK2_OK;
+  if (B * D > 8 && mode != 2) return PK2_OK;
+  if ((reinterpret_cast<uintptr_t>(inp) | reinterpret_cast<uintptr_t>(wih) | reinterpret_cast<uintptr_t>(bih)) % 16 != 0) return PK2_OK;
+  if (!seq_xproj_resident()) return PK2_OK;
+  const SeqFwdParams p{nullptr, whh, bhh, y, gates, cells, B, T, D};
+  const SeqXprojParams xp{inp, wih, bih, in_size};
+  return seq_fwd_launch(p, &xp, 1, H, stream, ran);
 }
 
 // The team protocol needs every launched workgroup resident: lstm_bwd_seq2_wgrad is used only when the runtime says that

@@ -89,16 +89,23 @@ class _LstmAmFunction(torch.autograd.Function):
         for l in range(Lr):
             w_ih, w_hh, b_ih, b_hh = m._layer_views(l)
             in_size = inp.shape[-1]
-            gx = torch.empty(T, B, D * 4 * H, device=dev, dtype=torch.float32)
-            _gemm(0, 1, rows, D * 4 * H, in_size, _p(inp), in_size, _p(w_ih), in_size, _p(gx), D * 4 * H,
-                  bias=_p(b_ih))
             y = torch.empty(T, B, D * H, device=dev, dtype=torch.float32)
             gates = torch.empty(D, T, B, 4 * H, device=dev, dtype=torch.float32)
             cells = torch.empty(D, T, B, H, device=dev, dtype=torch.float32)
             nws = L.pk2_lstm_fwd_workspace_floats(B, H, D)
             ws = torch.empty(nws, device=dev, dtype=torch.float32) if nws else None
-            _lib.check(L.pk2_lstm_layer_fwd(_p(gx), _p(w_hh), _p(b_hh), B, T, H, D, _p(y), _p(gates), _p(cells),
-                                            _p(ws) if ws is not None else None, sp))
+            # the one-launch recurrence of a few sequences multiplies inp by W_ih itself (lstm_fwd_seq2_xproj); where it does
+            # not, the product is a GEMM in front of the recurrence as before
+            gx_done = ctypes.c_int32(0)
+            _lib.check(L.pk2_lstm_layer_fwd_xproj(None, _p(w_hh), _p(b_hh), B, T, H, D, _p(y), _p(gates), _p(cells),
+                                                  _p(ws) if ws is not None else None, _p(inp), in_size, _p(w_ih), _p(b_ih),
+                                                  ctypes.byref(gx_done), sp))
+            if not gx_done.value:
+                gx = torch.empty(T, B, D * 4 * H, device=dev, dtype=torch.float32)
+                _gemm(0, 1, rows, D * 4 * H, in_size, _p(inp), in_size, _p(w_ih), in_size, _p(gx), D * 4 * H,
+                      bias=_p(b_ih))
+                _lib.check(L.pk2_lstm_layer_fwd(_p(gx), _p(w_hh), _p(b_hh), B, T, H, D, _p(y), _p(gates), _p(cells),
+                                                _p(ws) if ws is not None else None, sp))
             saved.append((inp, y, gates, cells))
             inp = y
             if m.dropout > 0 and m.training and l + 1 < Lr:
