@@ -500,8 +500,13 @@ int pk2_mvn_apply(const float* x, const float* mean, const float* stdv, int64_t 
  * (ignore_index=-100; reduction mean: reference bin/train_ce.py:134,189;
  * reduction sum: bin/train_se.py:214,235).
  * loss_sum, count: device f32[1] / int32[1] accumulators (zeroed inside);
- * grad receives d(sum loss)/d logits * grad_scale (rows with ignore_index get
- * zeros); the caller divides by count for the mean reduction.
+ * grad (optional) receives d(sum loss)/d logits, rows at grad_row_stride (rows
+ * with ignore_index get zeros); the caller divides by count for the mean
+ * reduction, or calls pk2_softmax_ce_fwd_bwd_mean.  A target outside
+ * [0, num_classes) that is not ignore_index makes *loss_sum NaN, gets a zero
+ * gradient row and is not counted.
+ * logprob_out (optional, dense [rows][num_classes]) receives log softmax of
+ * EVERY row, rows with an ignored or out-of-range target included.
  * ------------------------------------------------------------------ */
 int pk2_softmax_ce_fwd_bwd(const float* logits, int64_t row_stride, const int64_t* targets,
                            int64_t ignore_index, int64_t rows, int32_t num_classes,
@@ -728,7 +733,11 @@ int pk2_grad_norm(const float* grad, int64_t n, float* norm_out, void* workspace
 size_t pk2_grad_norm_workspace_bytes(int64_t n);
 /* clip coefficient = min(1, max_norm / (*norm + 1e-6)) read on the device;
  * max_norm <= 0 disables clipping.  step is 1-based.  grad_scale multiplies the
- * gradient first (1/world_size for the averaged all-reduce). */
+ * gradient first (1/world_size for the averaged all-reduce).
+ * beta1 / beta2 are float32 and the update is Adam with THOSE betas: 1 - beta and the bias corrections are formed
+ * from them.  torch's float32 kernels use float32(0.999) for the decay but float32(1 - 0.999) for the new term;
+ * 1 - float32(0.999) is 1.3e-5 below it, so exp_avg_sq (checkpointed state) is 1.3e-5 relative below torch's while
+ * exp_avg_sq / (1 - beta2^t), and with it the parameters, agree. */
 int pk2_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq,
                   float* max_exp_avg_sq /* NULL = no amsgrad */, int64_t n, float lr, float beta1,
                   float beta2, float eps, float weight_decay, int64_t step, float max_norm,

@@ -39,6 +39,35 @@ def logfbank(wav, mel):
     return np.log(power.dot(normalised_mel(mel) * 32768 ** 2) + 1)
 
 
+def logfbank64(wav, mel, pad_short=False):
+    """logfbank with the float32 pre-emphasis of the reference (it is part of the operator's definition) and everything
+    behind it in float64: window, FFT, power and mel sums, with no complex64 cast.  The mel matrix is the reference's float32
+    normalised table, taken as data.  pad_short: an utterance whose pre-emphasised signal is shorter than one window
+    (2...241 samples), for which enframe_pad gives NO frame, is zero-padded to one frame -- what pk2_fbank_num_frames does."""
+    wav = np.asarray(wav, dtype=np.float32)
+    y = (wav[1:] - np.float32(0.96) * wav[:-1]).astype(np.float64)
+    if pad_short and 0 < y.shape[0] < 400:
+        y = np.concatenate([y, np.zeros(400 - y.shape[0])])
+    frames = enframe_pad(y)
+    spec = np.fft.fft(np.hamming(400)[None, :] * frames, n=512, axis=1)[:, :257]
+    power = spec.real ** 2 + spec.imag ** 2
+    return np.log(power.dot(normalised_mel(mel).astype(np.float64) * 32768.0 ** 2) + 1)
+
+
+def logfbank_model(wav, mel, pad_short=False):
+    """A CPU model of a correct kernel in the arithmetic csrc/fbank.hip uses: float32 pre-emphasis in two roundings, window
+    and FFT in double, then float32 power, float32 mel sums and a float32 logarithm.  What it loses against logfbank64
+    (about half an ulp of the log-mel, 1e-6) calibrates the tight bound of tests/edge_cases.py."""
+    wav = np.asarray(wav, dtype=np.float32)
+    y = (wav[1:] - np.float32(0.96) * wav[:-1]).astype(np.float64)
+    if pad_short and 0 < y.shape[0] < 400:
+        y = np.concatenate([y, np.zeros(400 - y.shape[0])])
+    spec = np.fft.fft(np.hamming(400)[None, :] * enframe_pad(y), n=512, axis=1)[:, :257]
+    power = (spec.real ** 2 + spec.imag ** 2).astype(np.float32)
+    acc = power.dot((normalised_mel(mel) * np.float32(32768.0 ** 2)).astype(np.float32))
+    return np.log(acc + np.float32(1))
+
+
 def cmn(feats):
     return feats - np.mean(feats, axis=0, keepdims=True)
 

@@ -6,12 +6,14 @@
 //   preprocess.cmn(axis=0)                    reference reader/preprocess.py:34-41 (sr_dataset.py:365-366)
 //   roll + unfold subsampling                 reference bin/train_chain.py:251-255
 // Semantics restated from those lines: y = wav[1:] - 0.96*wav[:-1] (float32); frames of 400
-// samples every 160, the tail zero padded so T = ceil((N-1-400)/160)+1; symmetric Hamming(400);
+// samples every 160, the tail zero padded so T = max(1, ceil((N-1-400)/160)+1) from N = 242 samples up (the reference's
+// _enframe gives an utterance of 2...241 samples NO frame; pk2_fbank_num_frames answers 1 there, the samples zero padded
+// to one window -- pinned by tests/test_gpu_ce_optim_frontend.py, noted in DESIGN.md); symmetric Hamming(400);
 // 512-point FFT -> 257 bins; power; mel matrix = rows of mel80_window.txt with every FFT-bin
 // column normalised to sum 1 over the filters (all-zero columns stay zero); * 32768^2, + 1, ln.
 //
 // One 256-thread workgroup per frame: the frame is windowed into LDS, transformed with a
-// radix-2 FFT that never leaves LDS (9 stages, one butterfly per thread per stage), and the 80
+// radix-2 FFT in double that never leaves LDS (9 stages, one butterfly per thread per stage), and the 80
 // mel sums read the power spectrum from LDS; HBM traffic is the 4 B/sample wav read (frames
 // overlap 2.5x but hit L2) and the 320 B/frame output.
 #include <algorithm>
@@ -22,9 +24,10 @@
 
 struct pk2_fbank {
   std::vector<float> melT;      // [257][80], column-normalised, times 32768^2
-  std::vector<float> window;    // [400]
-  std::vector<float> tw_re, tw_im;  // [256] exp(-2 pi i k / 512)
-  float *d_melT = nullptr, *d_window = nullptr, *d_tw_re = nullptr, *d_tw_im = nullptr;
+  std::vector<double> window;   // [400]
+  std::vector<double> tw_re, tw_im;  // [256] exp(-2 pi i k / 512)
+  float* d_melT = nullptr;
+  double *d_window = nullptr, *d_tw_re = nullptr, *d_tw_im = nullptr;
   bool uploaded = false;
 };
 
@@ -41,12 +44,16 @@ constexpr int kFbankBatch = 32;
 struct FbankBatch { int64_t wav_off[kFbankBatch + 1]; int32_t row_off[kFbankBatch + 1]; int32_t n; };
 
 __global__ void __launch_bounds__(256) fbank_frame_kernel(FbankBatch b, const float* __restrict__ wav_all,
-                                                          const float* __restrict__ window,
-                                                          const float* __restrict__ tw_re,
-                                                          const float* __restrict__ tw_im,
+                                                          const double* __restrict__ window,
+                                                          const double* __restrict__ tw_re,
+                                                          const double* __restrict__ tw_im,
                                                           const float* __restrict__ melT,
                                                           float* __restrict__ feats_all) {
-  __shared__ float re[kNfft], im[kNfft];
+  // Window, FFT and power in double (the reference transforms in double and rounds the spectrum to complex64): a float32
+  // transform leaves every bin with an error of 2e-7 of the FRAME's amplitude, and a mel filter that is one FFT bin wide
+  // (the lowest filters) over a bin that happens to hold a millionth of the frame's power is 1e-4 off in a float32 CPU
+  // model of the transform (2.3e-4 was measured on the device, with the contracted pre-emphasis below on top of it).
+  __shared__ double re[kNfft], im[kNfft];
   __shared__ float pw[kBins + 3];
   int u = 0;
   while (u + 1 < b.n && (int)blockIdx.x >= b.row_off[u + 1]) ++u;
@@ -59,15 +66,20 @@ __global__ void __launch_bounds__(256) fbank_frame_kernel(FbankBatch b, const fl
 #pragma unroll
   for (int h = 0; h < 2; ++h) {
     const int i = tid + h * 256;
-    float v = 0.f;
+    double v = 0.0;
     if (i < kWin && s0 + i < m) {
-      // float32 like numpy: round the product, then the difference (no FMA contraction)
-      const float pe = __fmul_rn(0.96f, wav[s0 + i]);
-      v = __fsub_rn(wav[s0 + i + 1], pe) * window[i];
+      // float32 like numpy: round the product, then the difference.  __fmul_rn / __fsub_rn are plain operators here and
+      // this file is built with hipcc's default -ffp-contract=fast, which turned the pair into ONE fma (one rounding,
+      // 3e-8 of the sample: up to 7e-5 of a log-mel in bins that hold 1e-8 of the frame's power).  The empty asm makes the
+      // rounded product a value the compiler cannot look through, so the subtraction stays a separate instruction; the
+      // butterflies and mel sums below keep their fused multiply-adds.
+      float pe = 0.96f * wav[s0 + i];
+      asm volatile("" : "+v"(pe));
+      v = (double)(wav[s0 + i + 1] - pe) * window[i];
     }
     const unsigned r = rev9((unsigned)i);
     re[r] = v;
-    im[r] = 0.f;
+    im[r] = 0.0;
   }
   __syncthreads();
 #pragma unroll
@@ -76,15 +88,15 @@ __global__ void __launch_bounds__(256) fbank_frame_kernel(FbankBatch b, const fl
     const int grp = tid >> (s - 1), pos = tid & (half - 1);
     const int i0 = (grp << s) + pos, i1 = i0 + half;
     const int tw = pos << (9 - s);
-    const float wr = tw_re[tw], wi = tw_im[tw];
-    const float xr = re[i1], xi = im[i1];
-    const float tr = wr * xr - wi * xi, ti = wr * xi + wi * xr;
-    const float ar = re[i0], ai = im[i0];
+    const double wr = tw_re[tw], wi = tw_im[tw];
+    const double xr = re[i1], xi = im[i1];
+    const double tr = wr * xr - wi * xi, ti = wr * xi + wi * xr;
+    const double ar = re[i0], ai = im[i0];
     re[i1] = ar - tr; im[i1] = ai - ti;
     re[i0] = ar + tr; im[i0] = ai + ti;
     __syncthreads();
   }
-  for (int b = tid; b < kBins; b += 256) pw[b] = re[b] * re[b] + im[b] * im[b];
+  for (int b = tid; b < kBins; b += 256) pw[b] = (float)(re[b] * re[b] + im[b] * im[b]);
   __syncthreads();
   if (tid < kMel) {
     float acc = 0.f;
@@ -155,9 +167,9 @@ __global__ void __launch_bounds__(256) mvn_apply_kernel(const float* __restrict_
 
 static int fbank_upload(pk2_fbank* fb) {
   if (fb->uploaded) return PK2_OK;
-  auto up = [&](const std::vector<float>& h, float** d) -> int {
-    PK2_HIP(hipMalloc(reinterpret_cast<void**>(d), h.size() * sizeof(float)));
-    PK2_HIP(hipMemcpy(*d, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice));
+  auto up = [&](const auto& h, auto** d) -> int {
+    PK2_HIP(hipMalloc(reinterpret_cast<void**>(d), h.size() * sizeof(h[0])));
+    PK2_HIP(hipMemcpy(*d, h.data(), h.size() * sizeof(h[0]), hipMemcpyHostToDevice));
     return PK2_OK;
   };
   int rc;
@@ -188,11 +200,11 @@ extern "C" int pk2_fbank_create(const float* mel, pk2_fbank** out) {
   }
   fb->window.resize(kWin);
   for (int i = 0; i < kWin; ++i)  // np.hamming(400): 0.54 - 0.46 cos(2 pi i / (M-1))
-    fb->window[i] = (float)(0.54 - 0.46 * cos(2.0 * M_PI * i / (kWin - 1)));
+    fb->window[i] = 0.54 - 0.46 * cos(2.0 * M_PI * i / (kWin - 1));
   fb->tw_re.resize(kNfft / 2); fb->tw_im.resize(kNfft / 2);
   for (int k = 0; k < kNfft / 2; ++k) {
-    fb->tw_re[k] = (float)cos(-2.0 * M_PI * k / kNfft);
-    fb->tw_im[k] = (float)sin(-2.0 * M_PI * k / kNfft);
+    fb->tw_re[k] = cos(-2.0 * M_PI * k / kNfft);
+    fb->tw_im[k] = sin(-2.0 * M_PI * k / kNfft);
   }
   *out = fb;
   return PK2_OK;

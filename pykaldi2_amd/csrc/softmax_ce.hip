@@ -81,10 +81,12 @@ __global__ void __launch_bounds__(kCeThreads) softmax_ce_kernel(
     for (int p = tid; p < P; p += kCeThreads) s += expf(x[p] - m);
   }
   s = ce_block_sum(s, red);
-  const float lse = m + logf(s);
+  // The maximum is subtracted FIRST, as torch does: (x - m) is exact or rounded at the size of the difference, where
+  // x - (m + log s) rounds at the size of the logits -- with logits around 3000 that costs 1e-4 of every log-prob and row loss.
+  const float ls = logf(s);
   const float inv = 1.0f / s;
   if (!ignored && tid == 0) {
-    loss_local += lse - x[tgt];
+    loss_local += ls - (x[tgt] - m);
     ++count_local;
   }
   if (IN_REGS) {
@@ -93,13 +95,12 @@ __global__ void __launch_bounds__(kCeThreads) softmax_ce_kernel(
       const int p = tid + k * kCeThreads;
       if (p < P) {
         const float sm = v[k] * inv;
-        if (g) g[p] = ignored ? 0.f : (sm - (p == tgt ? 1.f : 0.f)) * gs;
-        if (logprob) logprob[row * (int64_t)P + p] = logf(fmaxf(sm, 1e-45f)) ;
+        if (g) g[p] = ignored ? 0.f : (sm - (p == tgt ? 1.f : 0.f)) * gs;       // (logprob_out takes the streaming variant)
       }
     }
   } else {
     for (int p = tid; p < P; p += kCeThreads) {
-      const float lp = x[p] - lse;
+      const float lp = (x[p] - m) - ls;
       if (g) g[p] = ignored ? 0.f : (expf(lp) - (p == tgt ? 1.f : 0.f)) * gs;
       if (logprob) logprob[row * (int64_t)P + p] = lp;
     }
