@@ -845,7 +845,21 @@ int pk2_lattice_summary(const pk2_lattice_batch* b, const void* workspace, int32
  * first, as fst::ScaleLattice does: float weights multiplied in double and stored back as float; 1.0 / 0.2
  * at reference ops/ops.py:58); frames whose reference transition-id is not in the lattice
  * are dropped when drop_frames != 0.  ref_tids: device i32, utterance n at n*ref_stride.  post rows must
- * be zero on entry.  lat_like: device f64[num_seq] = total log-likelihood of each lattice. */
+ * be zero on entry.  lat_like: device f64[num_seq] = total log-likelihood of each lattice.
+ * Any scale is allowed (so is any rescoring): the recursions (of mmi, mpe, posteriors and ts alike) keep a frame's values in
+ * linear form, exp(value - the frame's log scale) in a double.  With the neighbouring frame's maximum scaled to 1 it holds a
+ * token of a kept link down to 1e-280 (~645 nats) and a link whose scaled log-likelihood lies in [-708, 34.5].  A recursion
+ * that meets anything beyond that -- a finished token value outside [1e-280, 1e200], a link weight outside [2.2e-308, 1e15] --
+ * marks itself in the utterance's frame state and is run again in the log domain by the launch behind it (no host
+ * synchronisation; utterances inside the range cost that launch a flag test): the results are those of a float64 log-domain
+ * forward-backward over the whole range of the scores.  PK2_FB_LINEAR=0 (read once per process) runs everything in the log domain.
+ * An utterance that failed to decode, or whose lattice has no path of non-zero weight (total likelihood not finite), gives
+ * NaN here (and in pk2_lattice_mpe / pk2_lattice_posteriors) and nothing is added to its post rows. */
+/* Which recursions of the last forward-backward call on the batch (mmi, mpe, posteriors; ts: its second one) left the linear
+ * form's range and were run again in the log domain: rerun: device i32 [num_seq][2], [n][0] alpha, [n][1] beta; 1 = run again,
+ * 0 = the linear kernel's values stood, -1 = no linear kernel ran (failed utterance, PK2_FB_LINEAR=0).  For tests and
+ * diagnosis; the results do not depend on it.  Enqueued on `stream`. */
+int pk2_lattice_fb_rerun(const pk2_lattice_batch* b, void* workspace, int32_t* rerun, void* stream);
 int pk2_lattice_mmi(const pk2_lattice_batch* b, void* workspace, const int32_t* ref_tids,
                     int64_t ref_stride, const int32_t* tid2pdf, double lm_scale, double acoustic_scale,
                     int32_t drop_frames, float* post, int64_t post_seq_stride,
@@ -896,8 +910,8 @@ int pk2_lattice_rescore(const pk2_lattice_batch* b, void* workspace, const float
                         float old_acoustic_scale, void* stream);
 /* Kaldi's LatticeForwardBackward + Posterior.to_pdf_matrix with no reference alignment: post[n][t][pdf] += post_sign *
  * (sum of the posteriors of the frame's links with that pdf) on the lattice scaled by lm_scale / acoustic_scale as in
- * pk2_lattice_mmi; lat_like: device f64[num_seq] = total log-likelihood (NaN for a failed utterance; a lattice without a
- * path of non-zero weight adds nothing to post). */
+ * pk2_lattice_mmi; lat_like: device f64[num_seq] = total log-likelihood (NaN for a failed utterance and for a lattice without
+ * a path of non-zero weight, which adds nothing to post). */
 int pk2_lattice_posteriors(const pk2_lattice_batch* b, void* workspace, const int32_t* tid2pdf, double lm_scale,
                            double acoustic_scale, float post_sign, float* post, int64_t post_seq_stride,
                            int64_t post_frame_stride, double* lat_like, void* stream);

@@ -134,6 +134,7 @@ SIGNATURES = {
     "pk2_lattice_mwe": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _vp, _i32, C.c_double, C.c_double, _i32, _i32,
                                   _vp, _i64, _vp, _vp, _i32, _vp, _i64, _i64, _vp, _vp]),
     "pk2_lattice_rescore": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i32, _vp, _i32, _f32, _vp]),
+    "pk2_lattice_fb_rerun": (C.c_int, [_vp, _vp, _vp, _vp]),
     "pk2_lattice_posteriors": (C.c_int, [_vp, _vp, _vp, C.c_double, C.c_double, _f32, _vp, _i64, _i64, _vp, _vp]),
     "pk2_lattice_ts": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i32, _vp, _i32, _f32, C.c_double, C.c_double, _vp, _i64, _i64,
                                  _vp, _vp, _vp, _vp]),

@@ -82,7 +82,8 @@ __device__ __forceinline__ double fb_log_of(double x, double r) { return (r == r
 // Host side (lattice_fb.hip).  fb_recursions: alpha / beta of every utterance under p's scales and the total
 // log-likelihood in the utterance's frame state (failed utterances: p.out[n] = NaN); with_acc also clears the accuracy
 // accumulators of sMBR / MPFE.  *linear: the values lie in memory as the linear-domain kernel leaves them (fb_log_of with
-// fb_scale reads them).  fb_plain_posteriors: post += post_sign * gamma per (frame, pdf), p.out[n] = the total.
+// fb_scale reads them; a recursion that left the linear form's range has been run again in the log domain, its frame scales say
+// "logs").  fb_plain_posteriors: post += post_sign * gamma per (frame, pdf), p.out[n] = the total (NaN when it is not finite).
 int fb_recursions(const pk2_lattice_batch* b, const FbParams& p, int with_acc, hipStream_t stream, bool* linear);
 int fb_plain_posteriors(const pk2_lattice_batch* b, const FbParams& p, bool linear, hipStream_t stream);
 

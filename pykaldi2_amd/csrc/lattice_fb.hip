@@ -107,16 +107,22 @@ struct FbSc { int base, cnt, m0, m1, e0, e1, nlev; };
 struct FbEmit { int m0, m1; int src[kFbEmit], dst[kFbEmit]; double like[kFbEmit]; };
 struct FbEpsR { int e0, e1, nlev; int src[kFbEps], dst[kFbEps], lev[kFbEps]; double like[kFbEps]; };
 
-__global__ void __launch_bounds__(kFbThreads) lat_fb_alpha_beta(FbParams p, int cap) {
+// redo != 0: the launch behind the linear-domain kernel below.  A workgroup returns at once unless that kernel left its
+// recursion (alpha: x = 0, beta: x = 1) of the utterance marked "out of the linear range" in the frame state; for a marked one it
+// runs the recursion again, here, and sets the frame scales of its values to NaN: every later pass reads them as logs.
+__global__ void __launch_bounds__(kFbThreads) lat_fb_alpha_beta(FbParams p, int cap, int redo) {
   __shared__ double red[kFbWaves];
   const int n = blockIdx.y, tid = threadIdx.x;
   const LatUtt U = p.L.utt[n];
   if (U.status != kLatOk) { if (tid == 0 && blockIdx.x == 0) p.out[n] = NAN; return; }
+  if (redo && p.L.frame[n].fb_range[blockIdx.x] == 0) return;
   const FbView v = fb_view(p, n, U);
   const int T = v.T;
   const int fT0 = v.ftok[T], fT1 = v.ftok[T + 1];
   const bool fwd = blockIdx.x == 0;
   double* val = fwd ? v.alpha : v.beta;          // the recursion's values in global memory
+  if (redo)
+    for (int t = tid; t <= T; t += kFbThreads) (fwd ? v.sca : v.scb)[t] = __longlong_as_double(0x7ff8000000000000LL);
   double* A = lat_fb_smem;                       // the frame being accumulated / finished
   double* P = lat_fb_smem + cap;                 // its neighbour: the frame before it (alpha), the one being built (beta)
   for (int i = tid; i < v.nt; i += kFbThreads) { val[i] = -INFINITY; (fwd ? v.af : v.ab)[i] = 0.0; }
@@ -314,6 +320,18 @@ __global__ void __launch_bounds__(kFbThreads) lat_fb_alpha_beta(FbParams p, int 
 // across a frame -- into scratch, whose reloads are round trips to L2; 256 registers hold four emitting and two epsilon links per
 // thread, a frame of the bench lattices has ~1100)
 constexpr int kLinThreads = 512, kLinWaves = kLinThreads / 64, kLinEmit = 4, kLinEps = 2;
+// The range of the linear form (include/pk2hip.h): a double holds exp(x) as a normal number for x in [-708, 709].
+// The chain of adds is not slowed by tests.  Instead every LIVE token of a finished frame -- an end of a kept link: in a pruned
+// lattice each of them lies on a complete path, so its alpha and its beta are not 0 -- must hold a value in [kLinSmall, kLinBig]
+// (lin_in_range, in the pass that takes the frame's maximum or writes it back).  Anything else marks the recursion, and lat_fb_alpha_beta(redo)
+// behind this kernel runs it again in the log domain: a 0 (every product into the token underflowed -- or, after a rescoring
+// with -inf scores, nothing reaches it indeed: the log domain gives the same answer), a value below 1e-280 where the neighbouring
+// frame's maximum is scaled to 1 (~645 nats; its sum may hold subnormal terms of a few bits), a sum on its way to inf, a NaN (what lat_fb_prep stores for a link weight outside [kLinTiny, kLinBigW]).
+// The window is absolute, on values that are sums of (a value of the neighbouring frame / that frame's maximum, so <= 1) x weight:
+// with weights <= kLinBigW a frame's maximum stays below 1e15 x a token's fan-in, a live token at kLinSmall divided by it is
+// still a normal number (> 1e-305), and a product that vanishes beside a sum in the window was below 1e-43 of it.
+constexpr double kLinTiny = 2.2250738585072014e-308, kLinSmall = 1e-280, kLinBig = 1e200, kLinBigW = 1e15;
+__device__ __forceinline__ bool lin_in_range(double v) { return v >= kLinSmall && v <= kLinBig; }
 __device__ __forceinline__ double lin_block_max(double v, double* red) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
@@ -355,13 +373,19 @@ __device__ __forceinline__ double fb_block_max(double v, double* red) {     // r
 // recognisable), the accumulators of the posterior passes.  (The recursion kernel's own workgroup used to fill the utterance's
 // 13.5 M token slots by itself: ~2 ms at the head of the longest chain of the step.)
 __global__ void __launch_bounds__(256) lat_fb_prep(FbParams p, int with_acc) {
+  const double kNaN = __longlong_as_double(0x7ff8000000000000LL);
   const int n = blockIdx.y;
   const LatUtt U = p.L.utt[n];
   if (U.status != kLatOk) return;
   const FbView v = fb_view(p, n, U);
   for (int sgm = blockIdx.x; sgm < 2 * (v.T + 1); sgm += gridDim.x) {
     const int l0 = v.seg[sgm], l1 = l0 + v.kept[sgm];
-    for (int l = l0 + threadIdx.x; l < l1; l += 256) v.lw[l] = exp(link_like(p, v, v.lrec[l], l));
+    for (int l = l0 + threadIdx.x; l < l1; l += 256) {
+      const double like = link_like(p, v, v.lrec[l], l), w = exp(like);
+      // (like = -inf, a link no path takes, is 0 as it should be; any other weight outside [kLinTiny, kLinBigW] -- exp() gave
+      // 0, a subnormal, or something whose sums could reach inf -- is stored as NaN: the recursion that meets it gives up)
+      v.lw[l] = (like == -INFINITY || (w >= kLinTiny && w <= kLinBigW)) ? w : kNaN;
+    }
   }
   const int64_t i0 = (int64_t)blockIdx.x * 256 + threadIdx.x, step = (int64_t)gridDim.x * 256;
   for (int64_t i = i0; i < v.nt; i += step) {
@@ -399,6 +423,7 @@ __global__ void __launch_bounds__(kLinThreads) lat_fb_alpha_beta_lin(FbParams p,
   const LatUtt U = p.L.utt[n];
   if (U.status != kLatOk) { if (tid == 0 && blockIdx.x == 0) p.out[n] = NAN; return; }
   const FbView v = fb_view(p, n, U);
+  bool oor = false;                   // this thread saw the recursion leave the linear range (frame state, when the kernel ends)
   const int T = v.T;
   const int fT0 = v.ftok[T], fT1 = v.ftok[T + 1];
   const bool fwd = blockIdx.x == 0;
@@ -489,7 +514,11 @@ __global__ void __launch_bounds__(kLinThreads) lat_fb_alpha_beta_lin(FbParams p,
     for (int i = tid; i < cnt; i += kLinThreads) mx = fmax(mx, A[i]);
     mx = fb_block_max(mx, redm[nmax++ & 1]);
     if (mx == -INFINITY) mx = 0.0;
-    for (int i = tid; i < cnt; i += kLinThreads) A[i] = exp(A[i] - mx);
+    for (int i = tid; i < cnt; i += kLinThreads) {
+      const double a = A[i], x = exp(a - mx);
+      if (a != -INFINITY && !(x >= kLinTiny)) oor = true;
+      A[i] = x;
+    }
     return mx;
   };
   FbEmitW cm, nm; FbEpsW ce, ne;
@@ -554,8 +583,12 @@ __global__ void __launch_bounds__(kLinThreads) lat_fb_alpha_beta_lin(FbParams p,
       if (lin) {
         // finished: written back as it is, with its scale; its maximum becomes a factor of the next frame's gathers
         double mx = 0.0;
-        if (whole) { for (int i = tid; i < cnt; i += kLinThreads) mx = fmax(mx, A[i]); }
-        else touch(cm, ce, [&](int tok) { mx = fmax(mx, A[tok - base]); });
+        if (whole) {      // (frame 0, every slot: the live ones are tested on their own)
+          for (int i = tid; i < cnt; i += kLinThreads) mx = fmax(mx, A[i]);
+          touch(cm, ce, [&](int tok) { oor |= !lin_in_range(A[tok - base]); });
+        } else {
+          touch(cm, ce, [&](int tok) { const double a = A[tok - base]; oor |= !lin_in_range(a); mx = fmax(mx, a); });
+        }
         mx = fb_block_max(mx, redm[nmax++ & 1]);
         FBL_T(4);
         if (whole) { for (int i = tid; i < cnt; i += kLinThreads) val[base + i] = A[i]; }
@@ -596,7 +629,8 @@ __global__ void __launch_bounds__(kLinThreads) lat_fb_alpha_beta_lin(FbParams p,
     for (int i = fT0 + tid; i < fT1; i += kLinThreads)
       if (v.tf[i] < INFINITY) sm += exp(fb_log_of(ldc(&v.alpha[i]), rT) + final_like(p, v, i) - mx);
     sm = lin_block_sum(sm, red);
-    if (tid == 0) v.F->fb_tot = mx + log(sm);
+    const int any = __syncthreads_or(oor);
+    if (tid == 0) { v.F->fb_tot = mx + log(sm); v.F->fb_range[0] = any; }
   } else {
     int base = fT0, cnt = fT1 - fT0;
     bool lds = cnt <= cap, alin = false, whole = true;     // whole: every slot of A is meaningful (the last frame; a converted frame)
@@ -622,8 +656,13 @@ __global__ void __launch_bounds__(kLinThreads) lat_fb_alpha_beta_lin(FbParams p,
       load_eps_levels(ne);
       const bool all = whole || t == 0;
       if (lin) {
-        if (all) { for (int i = tid; i < cnt; i += kLinThreads) { const double a = A[i]; val[base + i] = a == 0.0 ? -INFINITY : a; } }
-        else touch(cm, ce, [&](int tok) { val[tok] = A[tok - base]; });
+        // (the range test rides on the write-back: the maximum below is not taken of a frame in front of a global-memory one)
+        if (all) {
+          for (int i = tid; i < cnt; i += kLinThreads) { const double a = A[i]; val[base + i] = a == 0.0 ? -INFINITY : a; }
+          touch(cm, ce, [&](int tok) { oor |= !lin_in_range(A[tok - base]); });
+        } else {
+          touch(cm, ce, [&](int tok) { const double a = A[tok - base]; oor |= !lin_in_range(a); val[tok] = a; });
+        }
       } else if (lds) {
         for (int i = tid; i < cnt; i += kLinThreads) val[base + i] = A[i];
       }
@@ -668,6 +707,8 @@ __global__ void __launch_bounds__(kLinThreads) lat_fb_alpha_beta_lin(FbParams p,
         cm = nm; ce = ne; s0 = s1; s1 = s2;
       }
     }
+    const int any = __syncthreads_or(oor);
+    if (tid == 0) v.F->fb_range[1] = any;
 #ifdef PK2_FB_PROFILE
     if (tid == 0 && n == 1) printf("lat_fb_lin beta utt %d, %d frames, 10 ns ticks per frame: prefetch issue %lld | eps levels %lld | level loads + write-back %lld | zeroes + maximum %lld | emitting + barrier %lld\n", n, T,
                                 lph[0] / (T + 1), lph[1] / (T + 1), lph[2] / (T + 1), lph[3] / (T + 1), lph[4] / (T + 1));
@@ -742,8 +783,7 @@ __global__ void __launch_bounds__(kFbThreads) lat_fb_accuracy(FbParams p) {
 
 // Posteriors, frame by frame in parallel (frames dealt round-robin to the workgroups of an utterance).
 // MODE 0: MMI (numerator - denominator with MergePosteriors' drop_frames test), MODE 1: sMBR / MPFE, MODE 2: the plain
-// link posteriors of Kaldi's LatticeForwardBackward, post += post_sign * gamma (no reference alignment; a lattice without a
-// path of non-zero weight adds nothing).
+// link posteriors of Kaldi's LatticeForwardBackward, post += post_sign * gamma (no reference alignment).
 template <int MODE>
 __global__ void __launch_bounds__(kFbThreads) lat_fb_posteriors(FbParams p, int lin) {
   const double kNaN = __longlong_as_double(0x7ff8000000000000LL);
@@ -753,8 +793,10 @@ __global__ void __launch_bounds__(kFbThreads) lat_fb_posteriors(FbParams p, int 
   const FbView v = fb_view(p, n, U);
   const double tot = v.F->fb_tot, tot_score = v.F->fb_score;
   float* post = p.post + (int64_t)n * p.post_seq_stride;
-  if (blockIdx.x == 0 && tid == 0) p.out[n] = MODE == 1 ? tot_score : tot;
-  if (MODE == 2 && !(fabs(tot) < INFINITY)) return;
+  // a lattice without a path of non-zero weight (a rescored frame nobody scores): NaN, and nothing is added to its post rows
+  const bool dead = !(fabs(tot) < INFINITY);
+  if (blockIdx.x == 0 && tid == 0) p.out[n] = dead ? (double)NAN : MODE == 1 ? tot_score : tot;
+  if (dead) return;
   for (int t = blockIdx.x; t < v.T; t += gridDim.x) {
     const int m0 = v.seg[2 * t + 1], m1 = m0 + v.kept[2 * t + 1];
     const int r = MODE == 2 ? 0 : v.ref[t];
@@ -804,6 +846,21 @@ using namespace pk2;
 
 namespace pk2 {
 
+static bool fb_linear() {
+  static const bool linear = [] { const char* e = getenv("PK2_FB_LINEAR"); return !(e && atoi(e) == 0); }();
+  return linear;
+}
+
+// out[n][x]: 1 = the last forward-backward ran utterance n's alpha (x = 0) / beta (x = 1) recursion again in the log domain,
+// 0 = the linear kernel's values stood, -1 = no linear kernel ran (failed utterance, PK2_FB_LINEAR=0)
+__global__ void lat_fb_range_read(LatPtrs L, int N, int linear, int32_t* out) {
+  const int n = blockIdx.x * blockDim.x + threadIdx.x;
+  if (n >= N) return;
+  const bool ran = linear && L.utt[n].status == kLatOk;
+  out[2 * n] = ran ? (L.frame[n].fb_range[0] != 0) : -1;
+  out[2 * n + 1] = ran ? (L.frame[n].fb_range[1] != 0) : -1;
+}
+
 int fb_recursions(const pk2_lattice_batch* b, const FbParams& p, int with_acc, hipStream_t stream, bool* linear_out) {
   const dim3 two(2, b->N), thr(kFbThreads);
   constexpr int kFbCap = 19456;                    // doubles of LDS (152 KB): two frames of kFbCap / 2 tokens each
@@ -811,14 +868,16 @@ int fb_recursions(const pk2_lattice_batch* b, const FbParams& p, int with_acc, h
   PK2_DYN_LDS_ONCE(lat_fb_alpha_beta_lin, kFbCap * (int)sizeof(double));
   const char* cap_env = getenv("PK2_LAT_FIN_CAP");       // (test hook, shared with the pruning pass of the decoder)
   const int cap = cap_env ? std::max(0, std::min(kFbCap / 2, atoi(cap_env))) : kFbCap / 2;
-  static const bool linear = [] { const char* e = getenv("PK2_FB_LINEAR"); return !(e && atoi(e) == 0); }();
+  const bool linear = fb_linear();
   const dim3 wide(256, b->N);
   if (linear) {
     hipLaunchKernelGGL(lat_fb_prep, wide, dim3(256), 0, stream, p, with_acc);
     hipLaunchKernelGGL(lat_fb_alpha_beta_lin, two, dim3(kLinThreads), kFbCap * sizeof(double), stream, p, cap);
+    // (no host synchronisation: workgroups of utterances inside the linear range return at once)
+    hipLaunchKernelGGL(lat_fb_alpha_beta, two, thr, kFbCap * sizeof(double), stream, p, cap, 1);
     if (with_acc) hipLaunchKernelGGL(lat_fb_logs, wide, dim3(256), 0, stream, p);     // (the other posterior passes take the logs of what they read)
   } else {
-    hipLaunchKernelGGL(lat_fb_alpha_beta, two, thr, kFbCap * sizeof(double), stream, p, cap);
+    hipLaunchKernelGGL(lat_fb_alpha_beta, two, thr, kFbCap * sizeof(double), stream, p, cap, 0);
   }
   PK2_LAUNCH_CHECK();
   *linear_out = linear;
@@ -848,6 +907,17 @@ static int fb_launch(int mode, const pk2_lattice_batch* b, void* workspace, FbPa
     hipLaunchKernelGGL(lat_fb_accuracy, two, thr, 0, stream, p);
     hipLaunchKernelGGL(lat_fb_posteriors<1>, many, thr, 0, stream, p, 0);
   }
+  PK2_LAUNCH_CHECK();
+  return PK2_OK;
+}
+
+extern "C" int pk2_lattice_fb_rerun(const pk2_lattice_batch* b, void* workspace, int32_t* rerun, void* stream_) {
+  PK2_REQUIRE(b && workspace && rerun, "lattice fb rerun: null pointer");
+  PK2_REQUIRE(b->decoded, "lattice fb rerun: pk2_lattice_decode has not run on this batch");
+  LatPtrs L;
+  lattice_carve(b, workspace, &L);
+  hipLaunchKernelGGL(lat_fb_range_read, dim3((b->N + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream_), L, b->N,
+                     fb_linear() ? 1 : 0, rerun);
   PK2_LAUNCH_CHECK();
   return PK2_OK;
 }

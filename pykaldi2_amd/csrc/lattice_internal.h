@@ -77,6 +77,7 @@ struct LatFrame {
   const float* ll_base;        // the utterance's log-likelihood rows (kept out of the graph-baked parameters)
   int64_t ll_stride;
   double fb_tot, fb_score;     // lattice forward-backward: total log-likelihood, expected accuracy
+  int32_t fb_range[2];         // the linear-domain alpha [0] / beta [1] recursion left its range: the log-domain kernel runs it again
 };
 
 // Arrays of the workspace (device pointers).

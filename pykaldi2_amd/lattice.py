@@ -493,6 +493,14 @@ class LatticeBatch:
                                                      _lib.ptr(out), _lib.stream_ptr(self.device)))
         return out, post
 
+    def fb_rerun(self):
+        """-> i32 [N, 2] (host): per utterance, whether the last forward-backward call ran its alpha / beta recursion again in
+        the log domain because it left the linear form's range (1), or not (0); -1: no linear kernel ran (failed utterance,
+        PK2_FB_LINEAR=0).  Reads back from the device: for tests and diagnosis."""
+        out = torch.empty(len(self.lengths), 2, dtype=torch.int32, device=self.device)
+        _lib.check(_lib.lib().pk2_lattice_fb_rerun(self._h, _lib.ptr(self.workspace), _lib.ptr(out), _lib.stream_ptr(self.device)))
+        return out.cpu().numpy()
+
     def teacher_student(self, loglikes_S, lm_scale=1.0, acoustic_scale=1.0, old_acoustic_scale=0.0):
         """Sequence-level distillation over this (the teacher's) lattice: forward-backward with the lattice's scores, rescore()
         with the student's log-likelihoods, forward-backward again, in one launch chain.
