@@ -153,6 +153,13 @@ int pk2_chain_den_fwd_bwd(const pk2_den_graph* g, const float* logits, int64_t s
 int pk2_chain_debug_flags(const float* num_lp, const float* den_lp, const float* alpha_beta_product,
                           const int32_t* lengths, int32_t N, float weight, float* out, int32_t* flags, void* stream);
 
+/* Reporting hook: where the forward-backward of the supervised numerator ran in the last pk2_chain_objf_and_deriv[_op] call
+ * of the process, as the host code decided it: out = {staged (frame table and arcs copied into LDS),
+ * carrier, threads of the routine (256, 128 or 64), its LDS bytes}; carrier: 0 = none yet (or the call failed first),
+ * 1 = stand-alone launch, 2 = inside the occupancy launch, LDS-row variant, 3 = the same, gather variant, 4 = tasks of the
+ * persistent denominator launch, 5 = stand-alone on the internal side stream.  It changes no decision and launches nothing. */
+int pk2_chain_debug_num_route(int32_t out[4]);
+
 /* ------------------------------------------------------------------ *
  * Chain supervision of one utterance from its alignment (host-side integer work, no device memory).
  * Replaces, for bin/train_chain.py:262-272 of the reference,

@@ -80,6 +80,7 @@ SIGNATURES = {
     "pk2_chain_den_fwd_bwd": (C.c_int, [_vp, _vp, _i64, _i64, _vp, _i32, _f32, _vp, _vp, _i64, _i64,
                                         _vp, _sz, _vp]),
     "pk2_chain_debug_flags": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _f32, _vp, _vp, _vp]),
+    "pk2_chain_debug_num_route": (C.c_int, [_vp]),
     "pk2_split_to_phones": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp, C.POINTER(_i32), C.POINTER(_i32)]),
     "pk2_sup_model_create": (_vp, [_i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _vp, _vp,
                                    _vp, _vp, _i32, _vp]),

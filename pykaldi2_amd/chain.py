@@ -779,6 +779,18 @@ def compute_chain_objf_and_deriv(opts, den_graph, supervisions, nnet_output, len
     return out, grad
 
 
+NUM_CARRIERS = ("none", "stand_alone", "occupancy_lds_row", "occupancy_gather", "persistent", "side_stream")
+
+
+def last_num_route():
+    """Where the supervised numerator's forward-backward ran in the last compute_chain_objf_and_deriv call of the process
+    (csrc/chain_internal.h: NumRoute), as a dict: staged (frame table and arcs copied into LDS), carrier (one of
+    NUM_CARRIERS), threads (of the routine: 256, 128 = the two-wave one, 64) and lds_bytes.  Reporting only."""
+    out = np.zeros(4, dtype=np.int32)
+    _lib.check(_lib.lib().pk2_chain_debug_num_route(_lib.ptr(out)))
+    return dict(staged=bool(out[0]), carrier=NUM_CARRIERS[int(out[1])], threads=int(out[2]), lds_bytes=int(out[3]))
+
+
 def _graph_objf_and_deriv(opts, den_graph, gs, nnet_output, operator_form):
     """compute_chain_objf_and_deriv for a GraphSupervision: one library call, no torch kernel around it."""
     x = nnet_output

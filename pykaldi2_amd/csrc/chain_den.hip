@@ -1784,12 +1784,15 @@ static int den_epilogue(const DenCall& c, const DenPlan& pl, const DenParams& p,
   PK2_DYN_LDS_ONCE((den_gamma_states_num<NG, true>), 160 * 1024);
   PK2_DYN_LDS_ONCE(den_gamma_states_lds<NG>, 160 * 1024);
   if (tail && tail->valid && !num_rode) {
-    if (pl.gamma_lds && std::max(row_lds, (size_t)tail->lds) <= kGammaMaxLds)
+    const bool lds_row = pl.gamma_lds && std::max(row_lds, (size_t)tail->lds) <= kGammaMaxLds;
+    if (lds_row)
       hipLaunchKernelGGL((den_gamma_states_num<NG, true>), dim3(Tmax + tail->N, G), dim3(kGammaThreads),
                          std::max(row_lds, (size_t)tail->lds), stream, p, b.csum, b.kscale, tail->p, tail->N, tail->stage ? 1 : 0);
     else
       hipLaunchKernelGGL((den_gamma_states_num<NG, false>), dim3(Tmax + tail->N, G), dim3(256), tail->lds, stream, p, b.csum,
                          b.kscale, tail->p, tail->N, tail->stage ? 1 : 0);
+    // (the numerator's workgroups keep two waves for the staged routine, one for the unstaged one)
+    num_route().carrier = lds_row ? kNumGammaLds : kNumGammaGather; num_route().threads = tail->stage ? 128 : 64;
   } else if (pl.gamma_lds) {
     hipLaunchKernelGGL(den_gamma_states_lds<NG>, dim3(Tmax, G), dim3(kGammaThreads), row_lds, stream, p, b.csum, b.kscale);
   } else {

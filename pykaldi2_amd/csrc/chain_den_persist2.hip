@@ -1360,7 +1360,10 @@ int den_persist2_launch(pk2_den_graph* g, const DenParams& dp, const float* xv, 
   if (rc || !ok) return rc;
   sc.ntasks = p.ntasks;
   *ran = true;
-  if (with_num) *num_ran = true;
+  if (with_num) {
+    *num_ran = true;
+    num_route().carrier = kNumPersist; num_route().threads = 128;      // (num_fwd_bwd_two_waves)
+  }
   return PK2_OK;
 }
 

@@ -317,6 +317,19 @@ struct NumParams {
   float scale;
 };
 
+// Where the forward-backward of the supervised numerator ran in the last objective call of the process, as the host code
+// decided it (pk2_chain_debug_num_route): written where the decisions are taken, read by nobody else.
+enum NumCarrier {
+  kNumCarrierNone = 0,    // no call yet, or the call failed before the launch
+  kNumStandAlone = 1,     // num_fwd_bwd on the caller's stream (general family)
+  kNumGammaLds = 2,       // den_gamma_states_num<NG, true>: inside the occupancy launch, LDS-row variant
+  kNumGammaGather = 3,    // den_gamma_states_num<NG, false>: inside the occupancy launch, gather variant
+  kNumPersist = 4,        // tasks of den_persist2_kernel
+  kNumSideStream = 5,     // num_fwd_bwd on the internal side stream (PK2_NUM_SIDE / PK2_SIDE_STREAM)
+};
+struct NumRoute { int32_t staged = 0, carrier = kNumCarrierNone, threads = 0, lds_bytes = 0; };
+NumRoute& num_route();
+
 // A numerator whose forward-backward launch has been handed to the denominator (see chain_num.h).
 struct NumDeferred { NumParams p; size_t lds = 0; int N = 0; bool valid = false; bool stage = false; };
 int num_launch_deferred(const NumDeferred& d, hipStream_t stream);

@@ -62,6 +62,11 @@ size_t num_workspace(int N, int64_t total_arcs, int64_t total_frames, NumBuffers
   return c.bytes();
 }
 
+NumRoute& num_route() {
+  static NumRoute r;
+  return r;
+}
+
 struct InfoPack { static constexpr int kSeqs = 8; int32_t v[kSeqs * 8]; };
 __global__ void store_info(InfoPack pack, int count, int32_t* out) {
   if ((int)threadIdx.x < count * 8) out[threadIdx.x] = pack.v[threadIdx.x];
@@ -74,6 +79,7 @@ int num_compute(const pk2_num_batch* nb, const float* logits, int64_t seq_stride
   PK2_REQUIRE(nb && nb->arc_src && nb->arc_dst && nb->arc_pdf && nb->arc_weight && nb->frame_off &&
                   nb->state_off && nb->final_state && nb->final_weight && nb->final_off,
               "numerator: null pointer in pk2_num_batch");
+  num_route() = NumRoute{};
   int max_states = 0, Tmax = 0;
   int64_t fbase = 0;
   for (int base = 0; base < N; base += InfoPack::kSeqs) {
@@ -117,6 +123,8 @@ int num_compute(const pk2_num_batch* nb, const float* logits, int64_t seq_stride
   PK2_DYN_LDS_ONCE(num_fwd_bwd, 160 * 1024);
   const int blocks_x = std::max(1, std::min(64, (Tmax + 3) / 4));
   hipLaunchKernelGGL(num_scores, dim3(blocks_x, N), dim3(kNumThreads), 0, stream, p, (int64_t)0);
+  num_route().staged = stage ? 1 : 0;
+  num_route().lds_bytes = (int32_t)lds;
   if (defer) {   // the caller launches the forward-backward together with the denominator's occupancy kernel
     defer->p = p; defer->lds = lds; defer->N = N; defer->valid = true; defer->stage = stage;
     PK2_LAUNCH_CHECK();
@@ -124,12 +132,14 @@ int num_compute(const pk2_num_batch* nb, const float* logits, int64_t seq_stride
   }
   hipLaunchKernelGGL(num_fwd_bwd, dim3(N), dim3(kNumThreads), lds, stream, p, stage ? 1 : 0);
   PK2_LAUNCH_CHECK();
+  num_route().carrier = kNumStandAlone; num_route().threads = kNumThreads;
   return PK2_OK;
 }
 
 int num_launch_deferred(const NumDeferred& d, hipStream_t stream) {
   hipLaunchKernelGGL(num_fwd_bwd, dim3(d.N), dim3(kNumThreads), d.lds, stream, d.p, d.stage ? 1 : 0);
   PK2_LAUNCH_CHECK();
+  num_route().carrier = kNumStandAlone; num_route().threads = kNumThreads;
   return PK2_OK;
 }
 

@@ -59,7 +59,7 @@ __global__ void __launch_bounds__(256) chain_out_clear(float* out, int count, fl
   if (threadIdx.x == 0 && objf_sum != nullptr) *objf_sum = 0.f;
 }
 
-// grad[n][t][p] = ok ? gscale * (grad - weight*gamma - weight*l2*logit) : 0     (grad holds the numerator part)
+// grad[n][t][p] = gscale * ((ok ? grad - weight*gamma : 0) - weight*l2*logit), 0 past the length   (grad holds the numerator part)
 template <int NG>
 __global__ void __launch_bounds__(256) chain_combine(const float* __restrict__ gamma,
                                                      const int32_t* __restrict__ lengths,
@@ -83,10 +83,11 @@ __global__ void __launch_bounds__(256) chain_combine(const float* __restrict__ g
       const int seq = g * NG + n;
       if (seq < N) {
         float* o = grad + (int64_t)seq * gss + (int64_t)t * gfs + p;
-        const bool live = t < lengths[seq] && flags[seq] != 0;
+        // (step 4 zeroes the derivative of an abandoned sequence, step 5 subtracts the l2 term afterwards)
+        const bool ok = flags[seq] != 0;
         float r = 0.f;
-        if (live) {
-          r = *o - weight * v[n];
+        if (t < lengths[seq] && (ok || l2 != 0.f)) {
+          if (ok) r = *o - weight * v[n];
           if (l2 != 0.f) r -= weight * l2 * logits[(int64_t)seq * lss + (int64_t)t * lfs + p];
           r *= gscale;
         }
@@ -174,6 +175,7 @@ static int chain_objf_impl(const pk2_den_graph* gc, const float* logits,
   rc = num_compute(num, logits, seq_stride, frame_stride, lengths, N,
                    weight * (1.0f + xent_regularize), grad, gss, gfs, nbuf, num_stream, use_side ? nullptr : &deferred);
   if (rc) return rc;
+  if (use_side) num_route().carrier = kNumSideStream;
   if (use_side) PK2_HIP(hipEventRecord(side->join, side->stream));
   // 2. denominator
   DenZeroRows zr; zr.grad = grad; zr.gss = gss; zr.gfs = gfs; zr.N = N;
@@ -319,6 +321,14 @@ extern "C" int pk2_chain_objf_and_deriv_graph_op(const pk2_den_graph* gc, const 
                                                  float grad_scale, float* objf_sum, void* stream_) {
   return chain_objf_graph_impl(gc, logits, seq_stride, frame_stride, graphs, packed_dev, leaky, xent_regularize, l2_regularize, weight,
                                grad, gss, gfs, out, workspace, workspace_bytes, grad_scale, objf_sum, stream_);
+}
+
+// Reporting hook: where the supervised numerator of the process's last objective call ran (chain_internal.h: NumRoute).
+extern "C" int pk2_chain_debug_num_route(int32_t out[4]) {
+  PK2_REQUIRE(out, "chain_debug_num_route: null pointer");
+  const NumRoute& r = num_route();
+  out[0] = r.staged; out[1] = r.carrier; out[2] = r.threads; out[3] = r.lds_bytes;
+  return PK2_OK;
 }
 
 // Test hook: the objective / guard rule of ComputeChainObjfAndDeriv on given per-sequence quantities (device arrays of N):

@@ -31,6 +31,17 @@ def test_library_exports_every_declared_symbol():
     assert _lib.lib().pk2_version() == 1
 
 
+def test_num_route_report_needs_no_gpu_and_starts_empty():
+    """pk2_chain_debug_num_route / chain.last_num_route(): host state only -- before any objective call of the process it
+    reports no carrier, and a null pointer fails loudly."""
+    out = np.full(4, -1, dtype=np.int32)
+    assert _lib.lib().pk2_chain_debug_num_route(_lib.ptr(out)) == 0 and (out == 0).all()
+    assert chain.last_num_route() == dict(staged=False, carrier="none", threads=0, lds_bytes=0)
+    assert len(chain.NUM_CARRIERS) == 6
+    rc = _lib.lib().pk2_chain_debug_num_route(None)
+    assert rc < 0 and b"null" in _lib.lib().pk2_last_error().lower()
+
+
 def test_bad_arguments_fail_loudly():
     h = C.c_void_p()
     rc = _lib.lib().pk2_den_graph_create(0, 5, 0, None, None, None, None, 0, C.byref(h))
