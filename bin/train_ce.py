@@ -18,7 +18,7 @@ import torch as th
 import yaml
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from pykaldi2_amd import _lib, data, fbank, hvd, lstm, ops, optim, utils  # noqa: E402
+from pykaldi2_amd import _lib, augment, data, fbank, hvd, lstm, ops, optim, utils  # noqa: E402
 
 
 class ChunkPool:
@@ -90,6 +90,7 @@ def parse_config(argv=None):
 
 def main():
     args, config = parse_config()
+    augment.refuse_speed_perturb(config, "train_ce.py")     # frame-level labels: exits before a model is built
 
     if args.hvd:
         hvd.init()

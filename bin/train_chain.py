@@ -19,6 +19,11 @@ chain directory's tree and 0.trans_mdl build the training graphs, and the numera
 transcript at the subsampled frame count (chain.graph_supervisions).  An utterance whose transcript has no
 path of its length is left out of the step and counted in the progress line.  With -synthetic the transcripts are seeded
 (synth.word_transcript) over the synthetic lexicon and monophone model of train_se2.py, in the same label space.
+
+data_config `speed_perturb: [0.9, 1.0, 1.1]` / `volume_perturb: [0.125, 2.0]` (pykaldi2_amd.augment) perturb
+every utterance on the device before the features are computed.  -e2e honours both: its frame counts come from the
+perturbed waveform.  Without -e2e the labels are per frame of the unperturbed audio, so a speed factor other than 1 is
+refused at start-up; the volume gain is honoured.
 """
 import argparse
 import json
@@ -31,7 +36,7 @@ import torch as th
 import yaml
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from pykaldi2_amd import chain, data, fbank, hvd, lstm, ops, optim, synth, utils  # noqa: E402
+from pykaldi2_amd import augment, chain, data, fbank, hvd, lstm, ops, optim, synth, utils  # noqa: E402
 from pykaldi2_amd.lattice import TransitionModel  # noqa: E402
 from pykaldi2_amd.tree import ContextDependency  # noqa: E402
 
@@ -95,6 +100,8 @@ def parse_config(argv=None):
 
 def main():
     args, config = parse_config()
+    if not args.e2e:      # the supervision is built from frame-level labels; -e2e takes its frame count from the waveform
+        augment.refuse_speed_perturb(config, "train_chain.py without -e2e")
 
     hvd.init()
     th.cuda.set_device(hvd.local_rank())

@@ -24,7 +24,7 @@ import torch as th
 import yaml
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from pykaldi2_amd import data, fbank, hvd, lattice, lstm, ops, optim, se, synth, transformer, utils  # noqa: E402
+from pykaldi2_amd import augment, data, fbank, hvd, lattice, lstm, ops, optim, se, synth, transformer, utils  # noqa: E402
 
 
 def parse_config(argv=None, arch="blstm"):
@@ -87,6 +87,8 @@ def parse_config(argv=None, arch="blstm"):
 
 def main(arch="blstm"):
     args, config = parse_config(None, arch)
+    # frame-level labels: exits before a model is built
+    augment.refuse_speed_perturb(config, "train_transformer_se.py" if arch == "transformer" else "train_se.py")
 
     hvd.init()
     th.cuda.set_device(hvd.local_rank())

@@ -39,7 +39,7 @@ import torch as th
 import yaml
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from pykaldi2_amd import chain, data, fbank, hvd, lattice, lstm, ops, optim, se, synth, utils  # noqa: E402
+from pykaldi2_amd import augment, chain, data, fbank, hvd, lattice, lstm, ops, optim, se, synth, utils  # noqa: E402
 
 
 def parse_config(argv=None):
@@ -91,6 +91,7 @@ def parse_config(argv=None):
 
 def main():
     args, config = parse_config()
+    augment.refuse_speed_perturb(config, "train_se2.py")     # frame-level labels: exits before a model is built
     hvd.init()
     th.cuda.set_device(hvd.local_rank())
     dev = th.device("cuda", hvd.local_rank())

@@ -20,7 +20,7 @@ import torch as th
 import yaml
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from pykaldi2_amd import _lib, data, fbank, hvd, ops, optim, transformer, utils  # noqa: E402
+from pykaldi2_amd import _lib, augment, data, fbank, hvd, ops, optim, transformer, utils  # noqa: E402
 
 
 def parse_config(argv=None):
@@ -71,6 +71,7 @@ def parse_config(argv=None):
 
 def main():
     args, config = parse_config()
+    augment.refuse_speed_perturb(config, "train_transformer_ce.py")     # frame-level labels: exits before a model is built
 
     if args.hvd:
         hvd.init()

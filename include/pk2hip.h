@@ -385,6 +385,59 @@ int pk2_sim_add_noise_mc(float* mixed, int64_t n, const float* noise, int64_t m,
                          float snr_db, int32_t repeat, const double* sig_stats, const double* noise_stats, void* stream);
 
 /* ------------------------------------------------------------------ *
+ * Sampling-rate conversion of a ragged minibatch: Kaldi's LinearResample / ResampleWaveform (polyphase windowed sinc),
+ * the arithmetic of speed perturbation (resample rate_in = round(fs * factor) -> rate_out = fs) with the volume gain
+ * folded in.  No counterpart in the reference; the contract is restated in DESIGN.md 7.7.
+ *   g = gcd(rate_in, rate_out), iu = rate_in / g, ou = rate_out / g, cutoff = 0.99 * 0.5 * min(rate_in, rate_out),
+ *   ww = num_zeros / (2 cutoff); phase p in [0, ou): t = p / rate_out, first[p] = ceil((t - ww) rate_in),
+ *   last[p] = floor((t + ww) rate_in), taps[p] = last - first + 1,
+ *   w[p][j] = f(dt) h(dt) / rate_in at dt = (first[p] + j) / rate_in - t   (Hann-windowed sinc, computed in double and
+ *   rounded to float32 once);  y[u ou + p] = gain * sum_j w[p][j] x[first[p] + u iu + j], x = 0 outside [0, n_in).
+ * rate_in == rate_out is the plan iu = ou = 1, first = 0, one weight 1: a copy (times the gain).
+ * A plan is a host object: creating, inspecting and exporting it needs no GPU.  Its tables go to a device on the first
+ * launch there (one allocation and one blocking copy per plan and device) and are freed by pk2_resample_plan_destroy.
+ * ------------------------------------------------------------------ */
+typedef struct pk2_resample_plan pk2_resample_plan;
+/* cutoff_hz = 0: the default above; otherwise 0 < cutoff_hz <= 0.5 min(rate_in, rate_out).  num_zeros >= 1.
+ * PK2_ERR_LIMIT when even the smallest output tile would read more input than the kernel stages (rate_in / rate_out
+ * beyond about 20) or a phase has more than PK2_RESAMPLE_MAX_TAPS taps. */
+#define PK2_RESAMPLE_MAX_TAPS 1024
+int pk2_resample_plan_create(int32_t rate_in, int32_t rate_out, double cutoff_hz, int32_t num_zeros,
+                             pk2_resample_plan** plan);
+int pk2_resample_plan_destroy(pk2_resample_plan* plan);
+/* tile: consecutive outputs one workgroup owns; table_bytes: what a device holds for the plan.  Any pointer may be NULL. */
+int pk2_resample_plan_info(const pk2_resample_plan* plan, int32_t* iu, int32_t* ou, int32_t* max_taps, int32_t* tile,
+                           int64_t* table_bytes);
+/* Host arrays: first (ou) int32, taps (ou) int32, weights (ou, max_taps) float32, zero beyond taps[p]. */
+int pk2_resample_plan_export(const pk2_resample_plan* plan, int32_t* first, int32_t* taps, float* weights);
+/* ceil(n_in * rate_out / rate_in) (Kaldi's flushed length); -1 on a bad argument. */
+int64_t pk2_resample_num_output(const pk2_resample_plan* plan, int64_t n_in);
+
+/* The job table is a HOST array of at most PK2_RESAMPLE_MAX_JOBS entries that travels as a kernel argument; `in` / `out`
+ * are device memory and must not overlap.  1 <= n_out <= pk2_resample_num_output(plan, n_in). */
+#define PK2_RESAMPLE_MAX_JOBS 32
+typedef struct {
+  const pk2_resample_plan* plan;
+  const float* in;
+  int64_t n_in;
+  float* out;
+  int64_t n_out;
+  float gain;     /* multiplies the finished float32 sum once */
+} pk2_resample_job;
+/* One launch for all jobs: a workgroup owns one tile of consecutive outputs of one job, stages the input span the tile
+ * reads in LDS (zeros outside [0, n_in)) and the plan's weight table too when ou * max_taps <= 4096 and ou <= 512 (else it
+ * reads the table from memory).  float32 accumulation in tap order, one writer per output, no atomics: a job's result is
+ * bit-reproducible and does not depend on the other jobs. */
+int pk2_resample_batch(const pk2_resample_job* jobs, int32_t njobs, void* stream);
+/* Where the jobs of the most recent pk2_resample_batch of this process read their weights (host-side bookkeeping):
+ * the OR of PK2_RESAMPLE_PATH_LDS / _MEM over the jobs.  PK2_RESAMPLE_WEIGHTS=mem in the environment sends every job to
+ * the memory path (measurements, tests). */
+#define PK2_RESAMPLE_PATH_NONE 0
+#define PK2_RESAMPLE_PATH_LDS 1
+#define PK2_RESAMPLE_PATH_MEM 2
+int pk2_resample_last_path(int32_t* path);
+
+/* ------------------------------------------------------------------ *
  * Isotropic (diffuse) noise field for a microphone array (reference simulation/_iso_noise_simulator.py
  * `generate_isotropic_noise`, Habets & Gannot 2007).
  *   X[m][f] = (1 / sqrt(P)) sum_i g[f] Z_i[f] exp(-j tau[m][i] w_f),  w_f = 2 pi f / fft_size, fft_size = 2 (bins - 1),

@@ -49,7 +49,14 @@ class SimMixSrc(C.Structure):
                 ("n", C.c_int64), ("start", C.c_int64), ("spr_db", C.c_double)]
 
 
+class ResampleJob(C.Structure):
+    """pk2_resample_job"""
+    _fields_ = [("plan", C.c_void_p), ("inp", C.c_void_p), ("n_in", C.c_int64), ("out", C.c_void_p), ("n_out", C.c_int64),
+                ("gain", C.c_float)]
+
+
 SIM_MAX_SEGS = 16        # PK2_SIM_MAX_SEGS
+RESAMPLE_MAX_JOBS = 32   # PK2_RESAMPLE_MAX_JOBS
 
 _vp, _i32, _i64, _f32, _sz = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_size_t
 
@@ -160,6 +167,14 @@ SIGNATURES = {
     "pk2_sim_gain_norm_seg": (C.c_int, [C.POINTER(SimSeg), _i32, _vp, _vp, _vp]),
     "pk2_sim_mix": (C.c_int, [C.POINTER(SimMixSrc), _i32, _i32, _i64, _vp, _vp, _vp, _vp]),
     "pk2_sim_add_noise_mc": (C.c_int, [_vp, _i64, _vp, _i64, _i32, _i64, _f32, _i32, _vp, _vp, _vp]),
+    "pk2_resample_plan_create": (C.c_int, [_i32, _i32, C.c_double, _i32, C.POINTER(_vp)]),
+    "pk2_resample_plan_destroy": (C.c_int, [_vp]),
+    "pk2_resample_plan_info": (C.c_int, [_vp, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32),
+                                         C.POINTER(_i64)]),
+    "pk2_resample_plan_export": (C.c_int, [_vp, _vp, _vp, _vp]),
+    "pk2_resample_num_output": (_i64, [_vp, _i64]),
+    "pk2_resample_batch": (C.c_int, [C.POINTER(ResampleJob), _i32, _vp]),
+    "pk2_resample_last_path": (C.c_int, [C.POINTER(_i32)]),
     "pk2_iso_spectra": (C.c_int, [_vp, _vp, _vp, C.c_uint64, _i32, _i32, _i32, _vp, _vp]),
     "pk2_iso_gauss": (C.c_int, [C.c_uint64, _i32, _i32, _vp, _vp]),
     "pk2_irfft_pow2_f32": (C.c_int, [_vp, _i32, _i32, _vp, _vp]),

@@ -13,7 +13,8 @@ padding run on the device (pykaldi2_amd.fbank).  Two sources share one interface
 
 Batch dict (cf. reference data/dataloader.py:128-134): ``wav`` (1-D CUDA f32, utterances back to
 back), ``lens`` (samples), ``y`` (list of int64 pdf alignments, one per utterance), ``aux`` (list),
-``utt_ids``, ``seconds``.
+``utt_ids``, ``seconds``.  With data_config ``speed_perturb`` / ``volume_perturb`` (pykaldi2_amd.augment) also ``speed``, the
+factor of each utterance; ``lens`` / ``seconds`` are then those of the perturbed audio.
 """
 import io
 import os
@@ -24,7 +25,7 @@ import zipfile
 import numpy as np
 import torch
 
-from . import _lib, synth
+from . import _lib, augment, synth
 
 
 def read_label_file(path):
@@ -214,6 +215,7 @@ def make_source(config, num_pdfs, rank=0, world=1, with_tids=False, ali_model=No
     else:
         source = ZipWavSource(config["source_paths"], config.get("data_path", ""), rank=rank, world=world)
     source.simulation = SimulationPool.from_config(config, seed=rank)     # None unless data_config switches it on
+    source.augment = augment.WaveAugment.from_config(config, seed=0)      # None without speed_perturb / volume_perturb
     return source
 
 
@@ -280,9 +282,10 @@ class SimulationPool:
         return self._dev[key]
 
     def maybe_simulate(self, wav, device):
-        """wav: host float32 -> device tensor, simulated with probability simulation_prob (the draws use numpy's
-        global generator like the reference: data/sr_dataset.py:321-336)."""
-        x = _lib.h2d(wav, device)
+        """wav: host float32 (or a tensor already on the device, e.g. a speed-perturbed row of the minibatch) -> device
+        tensor, simulated with probability simulation_prob (the draws use numpy's global generator like the reference:
+        data/sr_dataset.py:321-336)."""
+        x = wav if isinstance(wav, torch.Tensor) and wav.is_cuda else _lib.h2d(wav, device)
         if np.random.random() > self.prob:
             return x
         noise = noise_rir = src_rir = None
@@ -367,15 +370,37 @@ def sequence_batches(source, batch_size, hours, device, simulation=None, rank=No
                      length_bucketed=False):
     """Whole-utterance minibatches of one epoch: `hours` of audio per rank (the reference's sweep_size,
     data/sr_dataset.py:226) on the synthetic generator, one sharded pass over the utterance list on a finite source
-    (see epoch_plan: the number of steps is the same on every rank).  `simulation`: a SimulationPool, or None."""
+    (see epoch_plan: the number of steps is the same on every rank).  `simulation`: a SimulationPool, or None.
+
+    `source.augment` (a WaveAugment, set by make_source from data_config speed_perturb / volume_perturb) perturbs every
+    utterance in Kaldi's order: speed (the whole minibatch in one launch of the resampler), then the simulation, then the
+    volume gain -- folded into the resampling launch when there is no simulation in between, one more launch otherwise.
+    `lens` / `seconds` are those of the perturbed audio, `speed` lists the factors, and `y` of an utterance whose factor
+    is not 1 is None: its frame-level labels belong to another length."""
     rank = getattr(source, "rank", 0) if rank is None else rank
     world = getattr(source, "world", 1) if world is None else world
     if simulation is None:
         simulation = getattr(source, "simulation", None)
+    aug = getattr(source, "augment", None)
+    aug_gen = aug.generator(rank, epoch) if aug is not None else None
     finite = hasattr(source, "items")
     for step in epoch_plan(source, batch_size, hours, rank, world, epoch, length_bucketed):
         utts = [source.get(int(it)) if finite else source.draw(it) for it in step]
         lens = [u[0].shape[0] for u in utts]
+        if aug is not None:
+            factors, gains = aug.draw(aug_gen, len(utts))
+            ratios = aug.ratios(factors)
+            wav = _lib.h2d(np.concatenate([u[0] for u in utts]), device)
+            if simulation is None:
+                wav, lens = augment.resample_ragged(wav, lens, ratios, gains)
+            else:
+                wav, lens = augment.resample_ragged(wav, lens, ratios)
+                offs = np.concatenate([[0], np.cumsum(lens)])
+                wav = torch.cat([simulation.maybe_simulate(wav[offs[n]:offs[n + 1]], device) for n in range(len(lens))])
+                wav, lens = augment.resample_ragged(wav, lens, [(aug.fs, aug.fs)] * len(lens), gains)
+            yield dict(wav=wav, lens=lens, y=[u[1] if r[0] == r[1] else None for u, r in zip(utts, ratios)],
+                       aux=[u[2] for u in utts], utt_ids=[u[3] for u in utts], seconds=sum(lens) / 16000.0, speed=factors)
+            continue
         if simulation is not None:
             wav = torch.cat([simulation.maybe_simulate(u[0], device) for u in utts])
         else:
