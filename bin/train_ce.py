@@ -91,6 +91,8 @@ def parse_config(argv=None):
 def main():
     args, config = parse_config()
     augment.refuse_speed_perturb(config, "train_ce.py")     # frame-level labels: exits before a model is built
+    augment.refuse_time_warp(config, "train_ce.py")
+    args.spec = augment.SpecAugment.from_config(config)     # None without data_config spec_augment
 
     if args.hvd:
         hvd.init()
@@ -150,6 +152,7 @@ def run_train_epoch(model, optimizer, criterion, source, fb, epoch, config, args
     n_batches = max(1, int(args.sweep_size * 3600 / (seg_len * 0.01 * args.batch_size)))
     progress = utils.ProgressMeter(n_batches, batch_time, losses, grad_norm, prefix="Epoch: [{}]".format(epoch))
     pool = ChunkPool(capacity=max(4 * args.batch_size, 2048), seed=epoch + 17 * hvd.rank())
+    spec = args.spec.epoch(hvd.rank(), epoch) if args.spec is not None else None
     end = time.time()
     i = 0
 
@@ -182,6 +185,8 @@ def run_train_epoch(model, optimizer, criterion, source, fb, epoch, config, args
         feats, frames, row_off = fb(batch["wav"], batch["lens"], apply_cmn=dc.get("use_cmn", True))
         if transform is not None:
             feats = transform(feats)
+        if spec is not None:          # SpecAugment masks on whole utterances, before they are cut into chunks
+            feats = spec(feats, row_off, frames)
         off = np.concatenate([[0], np.cumsum(frames)])
         for n, y in enumerate(batch["y"]):
             f = feats[off[n]:off[n + 1]]

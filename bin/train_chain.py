@@ -23,7 +23,8 @@ path of its length is left out of the step and counted in the progress line.  Wi
 data_config `speed_perturb: [0.9, 1.0, 1.1]` / `volume_perturb: [0.125, 2.0]` (pykaldi2_amd.augment) perturb
 every utterance on the device before the features are computed.  -e2e honours both: its frame counts come from the
 perturbed waveform.  Without -e2e the labels are per frame of the unperturbed audio, so a speed factor other than 1 is
-refused at start-up; the volume gain is honoured.
+refused at start-up; the volume gain is honoured.  data_config `spec_augment: true` (or a mapping of its keys)
+masks the features of every training minibatch in one launch; its `time_warp` moves frames, so it too needs -e2e.
 """
 import argparse
 import json
@@ -102,6 +103,8 @@ def main():
     args, config = parse_config()
     if not args.e2e:      # the supervision is built from frame-level labels; -e2e takes its frame count from the waveform
         augment.refuse_speed_perturb(config, "train_chain.py without -e2e")
+        augment.refuse_time_warp(config, "train_chain.py without -e2e")
+    args.spec = augment.SpecAugment.from_config(config)      # None without data_config spec_augment
 
     hvd.init()
     th.cuda.set_device(hvd.local_rank())
@@ -187,6 +190,7 @@ def run_train_epoch(model, optimizer, source, fb, epoch, supervision_opts, den, 
     progress = utils.ProgressMeter(n_batches, *meters, prefix="Epoch: [{}]".format(epoch))
     sub = supervision_opts.frame_subsampling_factor
     text_rng = np.random.default_rng(4321 + epoch + hvd.rank())
+    spec = args.spec.epoch(hvd.rank(), epoch) if args.spec is not None else None
     end = time.time()
     for i, batch in enumerate(data.sequence_batches(source, args.batch_size, args.sweep_size, dev, epoch=epoch,
                                                          length_bucketed=args.length_bucketed)):
@@ -194,6 +198,8 @@ def run_train_epoch(model, optimizer, source, fb, epoch, supervision_opts, den, 
         feats, frames, row_off = fb(batch["wav"], batch["lens"])
         if transform is not None:     # dataset.transform of the reference (bin/train_chain.py:118-122)
             feats = transform(feats)
+        if spec is not None:          # SpecAugment: masks always, the time warp under -e2e only
+            feats = spec(feats, row_off, frames)
         x = fb.pad_roll_subsample(feats, row_off, frames, shift=frame_shift, subsample=sub, time_major=True)
         aligner, tree, trans_model = sup_model
         if args.e2e:

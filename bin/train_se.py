@@ -89,6 +89,8 @@ def main(arch="blstm"):
     args, config = parse_config(None, arch)
     # frame-level labels: exits before a model is built
     augment.refuse_speed_perturb(config, "train_transformer_se.py" if arch == "transformer" else "train_se.py")
+    augment.refuse_time_warp(config, "train_transformer_se.py" if arch == "transformer" else "train_se.py")
+    args.spec = augment.SpecAugment.from_config(config)      # None without data_config spec_augment
 
     hvd.init()
     th.cuda.set_device(hvd.local_rank())
@@ -174,11 +176,12 @@ def run_train_epoch(model, optimizer, log_prior, source, fb, epoch, asr_decoder,
     n_batches = max(1, int(args.sweep_size * 3600 / (12.3 * args.batch_size)))
     progress = utils.ProgressMeter(n_batches, batch_time, losses, grad_norm, prefix="Epoch: [{}]".format(epoch))
     ce_criterion = ops.CrossEntropyLoss(ignore_index=-100, reduction='sum')
+    spec = args.spec.epoch(hvd.rank(), epoch) if args.spec is not None else None
     end = time.time()
     for i, batch in enumerate(data.sequence_batches(source, args.batch_size, args.sweep_size, dev, epoch=epoch,
                                                          length_bucketed=args.length_bucketed)):
         loss, se_val, ce_loss, frames = se.sequence_loss(model, fb, batch, asr_decoder, trans_model, log_prior, args.criterion,
-                                                         silence_ids, args.ce_ratio, ce_criterion, forward, transform)
+                                                         silence_ids, args.ce_ratio, ce_criterion, forward, transform, spec)
         optimizer.zero_grad()
         loss.backward()
         norm = optim.clip_grad_norm_(optimizer, args.max_grad_norm)

@@ -92,6 +92,8 @@ def parse_config(argv=None):
 def main():
     args, config = parse_config()
     augment.refuse_speed_perturb(config, "train_se2.py")     # frame-level labels: exits before a model is built
+    augment.refuse_time_warp(config, "train_se2.py")
+    args.spec = augment.SpecAugment.from_config(config)      # None without data_config spec_augment
     hvd.init()
     th.cuda.set_device(hvd.local_rank())
     dev = th.device("cuda", hvd.local_rank())
@@ -210,6 +212,7 @@ def run_train_epoch(model, optimizer, log_prior, source, fb, epoch, asr_decoder,
     progress = utils.ProgressMeter(n_batches, batch_time, losses, grad_norm, prefix="Epoch: [{}]".format(epoch))
     ce_criterion = ops.CrossEntropyLoss(ignore_index=-100, reduction='sum')
     text_rng = np.random.default_rng(1000 + hvd.rank())
+    spec = args.spec.epoch(hvd.rank(), epoch) if args.spec is not None else None
     end = time.time()
     for i, batch in enumerate(data.sequence_batches(source, args.batch_size, args.sweep_size, dev, epoch=epoch)):
         if args.synthetic:     # word transcripts the utterances can hold (aux carries transition-ids there)
@@ -218,15 +221,17 @@ def run_train_epoch(model, optimizer, log_prior, source, fb, epoch, asr_decoder,
             texts = [np.asarray(a).reshape(-1).astype(int).tolist() for a in batch["aux"]]
         if args.criterion == "ts":
             loss, se_val, ce_loss, frames, failed = se.sequence_loss_ts(model, teacher, fb, batch, asr_decoder, log_prior, args.ts,
-                                                                        args.ce_ratio, ce_criterion, transform=transform)
+                                                                        args.ce_ratio, ce_criterion, transform=transform,
+                                                                        spec=spec)
         elif args.criterion == "mwe":
             loss, se_val, ce_loss, frames, failed = se.sequence_loss_mwe(model, fb, batch, texts, aligner, asr_decoder, trans_model,
                                                                          log_prior, args.mwe, args.ce_ratio, ce_criterion,
-                                                                         transform=transform)
+                                                                         transform=transform, spec=spec)
         else:
             loss, se_val, ce_loss, frames, failed = se.sequence_loss_aligned(model, fb, batch, texts, aligner, asr_decoder,
                                                                              trans_model, log_prior, args.criterion, silence_ids,
-                                                                             args.ce_ratio, ce_criterion, transform=transform)
+                                                                             args.ce_ratio, ce_criterion, transform=transform,
+                                                                             spec=spec)
         for j in failed:
             print("Warning: failed to align utterance {}, skip the utterance for SE loss".format(batch["utt_ids"][j]))
         optimizer.zero_grad()

@@ -72,6 +72,8 @@ def parse_config(argv=None):
 def main():
     args, config = parse_config()
     augment.refuse_speed_perturb(config, "train_transformer_ce.py")     # frame-level labels: exits before a model is built
+    augment.refuse_time_warp(config, "train_transformer_ce.py")
+    args.spec = augment.SpecAugment.from_config(config)                 # None without data_config spec_augment
 
     if args.hvd:
         hvd.init()
@@ -126,11 +128,14 @@ def run_train_epoch(model, optimizer, criterion, source, fb, epoch, config, args
     n_batches = max(1, int(args.sweep_size * 3600 / (12.3 * args.batch_size)))
     progress = utils.ProgressMeter(n_batches, batch_time, losses, grad_norm, prefix="Epoch: [{}]".format(epoch))
     use_cmn = config["data_config"].get("use_cmn", True)
+    spec = args.spec.epoch(hvd.rank(), epoch) if args.spec is not None else None
     end = time.time()
     for i, batch in enumerate(data.sequence_batches(source, args.batch_size, args.sweep_size, dev, epoch=epoch)):
         feats, frames, row_off = fb(batch["wav"], batch["lens"], apply_cmn=use_cmn)
         if transform is not None:
             feats = transform(feats)
+        if spec is not None:
+            feats = spec(feats, row_off, frames)
         x = fb.pad_roll_subsample(feats, row_off, frames, shift=0, subsample=1, time_major=True)     # [Tmax, N, 80]
         prediction = transformer.padded_forward(model, x, frames, args.look_ahead)                    # [N, Tmax, P]
         N, Tmax = prediction.shape[0], prediction.shape[1]

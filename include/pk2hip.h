@@ -556,6 +556,35 @@ int pk2_mvn_apply(const float* x, const float* mean, const float* stdv, int64_t 
                   float* y, void* stream);
 
 /* ------------------------------------------------------------------ *
+ * SpecAugment (Park et al. 2019) on the packed feature rows of a ragged minibatch: time warp, then frequency and time
+ * masks in output coordinates.  One launch on the caller's stream, no host synchronisation, no atomics.  No counterpart
+ * in the reference; Kaldi's spec-augment-layer differs (which restates this contract).
+ * in / out: device f32 [total_rows][80], the layout of pk2_fbank_compute; row_off: DEVICE int64 [n + 1] as there.
+ * plan: DEVICE int32 [n][PK2_SPEC_PLAN_STRIDE]; the row of an utterance of T frames is
+ *   c, d                                    the warp's centre and where it moves to (c == d: no warp)
+ *   PK2_SPEC_MAX_FREQ_MASKS pairs (a, b)    half-open bin intervals, 0 <= a <= b <= 80
+ *   PK2_SPEC_MAX_TIME_MASKS pairs (a, b)    half-open frame intervals, 0 <= a <= b <= T
+ * unused intervals are (0, 0); intervals may overlap or be empty.
+ * Warp (c != d; 1 <= c, d <= T - 2 keeps both denominators >= 1), output frame t, products in int64:
+ *   t <= d: base = 0, num = t c, den = d;   else: base = c, num = (t - d)(T - 1 - c), den = T - 1 - d;
+ *   i = base + num / den, r = num % den, a = in[i], b = in[min(i + 1, T - 1)];
+ *   out[t] = a when r == 0, else fmaf((float)r / (float)den, b - a, a).
+ * Frames 0 and T - 1 map to themselves; source indices are clamped into [0, T - 1], and a row whose den would not be
+ * positive is copied, so no plan reads another utterance's rows.
+ * Masks: out[t][f] = fill when t lies in any time interval or f in any frequency interval.
+ * Elements that are neither masked nor interpolated are bit-exact copies (-0.0, denormals, NaN payloads included).
+ * has_warp == 0: c and d are ignored; in == out is allowed, and then nothing is read and only masked elements are
+ * written.  has_warp != 0 with in == out, or in and out overlapping without being equal: PK2_ERR_INVALID.  n < 1,
+ * total_rows < n and null pointers: PK2_ERR_INVALID.
+ * ------------------------------------------------------------------ */
+#define PK2_SPEC_MAX_FREQ_MASKS 4
+#define PK2_SPEC_MAX_TIME_MASKS 16
+#define PK2_SPEC_PLAN_STRIDE (2 + 2 * PK2_SPEC_MAX_FREQ_MASKS + 2 * PK2_SPEC_MAX_TIME_MASKS)   /* int32 per utterance */
+int pk2_spec_augment(const float* in, float* out, const int64_t* row_off /* device [n+1] */, int32_t n,
+                     int64_t total_rows, const int32_t* plan /* device [n, STRIDE] */, int32_t has_warp,
+                     float fill, void* stream);
+
+/* ------------------------------------------------------------------ *
  * Fused log-softmax + NLL + gradient.  Replaces nn.CrossEntropyLoss
  * (ignore_index=-100; reduction mean: reference bin/train_ce.py:134,189;
  * reduction sum: bin/train_se.py:214,235).

@@ -10,6 +10,12 @@ ratio, length and gain, and nothing returns to the host.
   resample_ragged(wav, lens, ratios, gains) the 1-D concatenation data.sequence_batches yields
   speed_perturb(wav, lens, factors, fs)     factor s = resample round(fs s) -> fs
   WaveAugment                               the per-utterance draws of data_config `speed_perturb` / `volume_perturb`
+
+and feature augmentation, SpecAugment in interval form (csrc/spec_augment.hip): time warp, frequency and time
+masks on the packed rows FbankExtractor returns, one launch per minibatch, in place when nothing warps.
+
+  spec_augment(feats, row_off, frames, plan) a host plan (validated without a GPU) applied to the minibatch
+  SpecAugment                               the per-utterance draws of data_config `spec_augment`
 """
 import ctypes as C
 import math
@@ -187,4 +193,152 @@ def refuse_speed_perturb(config, prog):
     if aug is not None and aug.changes_length():
         sys.stderr.write("ERROR: %s reads frame-level labels and cannot train on speed-perturbed audio: remove data_config "
                          "speed_perturb %r (bin/train_chain.py -e2e honours it)\n" % (prog, sp))
+        sys.exit(2)
+
+
+NUM_BINS = 80
+SPEC_KEYS = ("freq_masks", "freq_width", "time_masks", "time_width", "time_ratio", "time_warp", "fill")
+_SPEC_FREQ0, _SPEC_TIME0 = 2, 2 + 2 * _lib.SPEC_MAX_FREQ_MASKS      # plan row: c, d, frequency pairs, time pairs
+
+
+def _check_plan(plan, frames):
+    """The host plan of pk2_spec_augment against the frame counts: ValueError, or whether any row warps.  Needs no GPU."""
+    if not (isinstance(plan, np.ndarray) and plan.dtype == np.int32 and plan.ndim == 2 and plan.flags.c_contiguous
+            and plan.shape == (len(frames), _lib.SPEC_PLAN_STRIDE) and len(frames) >= 1):
+        raise ValueError("spec_augment: the plan must be a host int32 array [%d, %d], one row per utterance"
+                         % (len(frames), _lib.SPEC_PLAN_STRIDE))
+    T = np.asarray(frames, dtype=np.int64).reshape(-1, 1)
+    if T.min() < 1:
+        raise ValueError("spec_augment: every utterance needs at least one frame")
+    p = plan.astype(np.int64)
+    for what, lo, hi, limit in (("frequency", _SPEC_FREQ0, _SPEC_TIME0, NUM_BINS), ("time", _SPEC_TIME0, plan.shape[1], T)):
+        a, b = p[:, lo:hi:2], p[:, lo + 1:hi:2]
+        bad = np.argwhere((a < 0) | (a > b) | (b > limit))
+        if len(bad):
+            n, k = (int(v) for v in bad[0])
+            raise ValueError("spec_augment: utterance %d (%d frames): %s interval [%d, %d) outside 0 <= a <= b <= %d"
+                             % (n, int(T[n, 0]), what, a[n, k], b[n, k], NUM_BINS if what == "frequency" else int(T[n, 0])))
+    c, d = p[:, 0:1], p[:, 1:2]
+    warps = c != d
+    bad = np.argwhere(warps & ((c < 1) | (d < 1) | (c > T - 2) | (d > T - 2)))
+    if len(bad):
+        n = int(bad[0][0])
+        raise ValueError("spec_augment: utterance %d (%d frames): warp (c, d) = (%d, %d) needs c == d or 1 <= c, d <= T - 2"
+                         % (n, int(T[n, 0]), c[n, 0], d[n, 0]))
+    return bool(warps.any())
+
+
+def spec_augment(feats, row_off, frames, plan, fill=0.0, out=None):
+    """pk2_spec_augment on feats [sum(frames), 80] (what FbankExtractor.__call__ returns, with its row_off): time warp, then
+    the frequency and time masks of the host `plan` (int32 [N, SPEC_PLAN_STRIDE], SpecAugment.draw), in one launch.  The plan
+    is validated against `frames` before anything touches the GPU.  out=None: in place when no row warps (only the masked
+    elements are written), else a new tensor; `out is feats` with a warping plan raises ValueError.  Returns the result."""
+    has_warp = _check_plan(plan, frames)
+    if not math.isfinite(float(fill)):
+        raise ValueError("spec_augment: fill must be finite, got %r" % (fill,))
+    if out is feats and out is not None and has_warp:
+        raise ValueError("spec_augment: a warping plan cannot run in place (out is feats)")
+    _check(feats, "spec_augment")
+    total = int(sum(int(t) for t in frames))
+    if feats.dim() != 2 or tuple(feats.shape) != (total, NUM_BINS):
+        raise ValueError("spec_augment: expected feats [%d, %d], got %r" % (total, NUM_BINS, tuple(feats.shape)))
+    if not (isinstance(row_off, torch.Tensor) and row_off.device == feats.device and row_off.dtype == torch.int64
+            and row_off.is_contiguous() and row_off.numel() == len(frames) + 1):
+        raise ValueError("spec_augment: row_off must be the int64 [N + 1] tensor of FbankExtractor.__call__ on the device of feats")
+    if out is None:
+        out = torch.empty_like(feats) if has_warp else feats
+    elif out is not feats:
+        _check(out, "spec_augment")
+        if out.shape != feats.shape or out.device != feats.device:
+            raise ValueError("spec_augment: out must have the shape and device of feats")
+    with torch.cuda.device(feats.device):
+        plan_dev = _lib.h2d(plan, feats.device)
+        _lib.check(_lib.lib().pk2_spec_augment(_lib.ptr(feats), _lib.ptr(out), _lib.ptr(row_off), len(frames), total,
+                                               _lib.ptr(plan_dev), 1 if has_warp else 0, float(fill),
+                                               _lib.stream_ptr(feats.device)))
+    return out
+
+
+class SpecAugment:
+    """SpecAugment (Park et al. 2019) in interval form, data_config `spec_augment`: per utterance of T frames an optional
+    time warp (`time_warp` = W > 0 and T >= 2 W + 3: centre c uniform in [W + 1, T - W - 2] moves to c + w, w uniform in
+    [-W, W]), `freq_masks` bin intervals of width uniform in [0, freq_width], and `time_masks` frame intervals of width
+    uniform in [0, min(time_width, floor(time_ratio T))]; masked elements become `fill` (0 is the utterance mean after CMN or
+    -transform).  The draws come from a generator of their own, np.random.default_rng([seed, rank, epoch, 611953]): numpy's
+    global stream and WaveAugment's draws are never touched."""
+
+    def __init__(self, freq_masks=2, freq_width=27, time_masks=2, time_width=40, time_ratio=0.2, time_warp=0, fill=0.0, seed=0):
+        def integer(name, v, lo, hi):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < lo or (hi is not None and v > hi):
+                raise ValueError("spec_augment: %s must be an integer %s, got %r"
+                                 % (name, ">= %d" % lo if hi is None else "in [%d, %d]" % (lo, hi), v))
+            return int(v)
+        self.freq_masks = integer("freq_masks", freq_masks, 0, _lib.SPEC_MAX_FREQ_MASKS)
+        self.freq_width = integer("freq_width", freq_width, 0, NUM_BINS)
+        self.time_masks = integer("time_masks", time_masks, 0, _lib.SPEC_MAX_TIME_MASKS)
+        self.time_width = integer("time_width", time_width, 0, None)
+        self.time_warp = integer("time_warp", time_warp, 0, None)
+        if isinstance(time_ratio, bool) or not isinstance(time_ratio, (int, float, np.integer, np.floating)) \
+                or not (0.0 <= float(time_ratio) <= 1.0):
+            raise ValueError("spec_augment: time_ratio must lie in [0, 1], got %r" % (time_ratio,))
+        if isinstance(fill, bool) or not isinstance(fill, (int, float, np.integer, np.floating)) or not math.isfinite(float(fill)):
+            raise ValueError("spec_augment: fill must be a finite number, got %r" % (fill,))
+        self.time_ratio, self.fill, self.seed = float(time_ratio), float(fill), int(seed)
+
+    @classmethod
+    def from_config(cls, config, seed=0):
+        """data_config `spec_augment`: true (the defaults) or a mapping over them (a key it does not know raises KeyError);
+        None when the key is absent or false."""
+        sa = (config.get("data_config") or {}).get("spec_augment")
+        if sa is None or sa is False:
+            return None
+        if sa is True:
+            return cls(seed=seed)
+        if not isinstance(sa, dict):
+            raise ValueError("spec_augment: expected true or a mapping, got %r" % (sa,))
+        for k in sa:
+            if k not in SPEC_KEYS:
+                raise KeyError("spec_augment: unknown key %r (known: %s)" % (k, ", ".join(SPEC_KEYS)))
+        return cls(seed=seed, **sa)
+
+    def generator(self, rank=0, epoch=0):
+        return np.random.default_rng([self.seed, int(rank), int(epoch), 611953])
+
+    def draw(self, gen, frames):
+        """The host plan (int32 [N, SPEC_PLAN_STRIDE]) of the next utterances from `gen` (self.generator(rank, epoch))."""
+        plan = np.zeros((len(frames), _lib.SPEC_PLAN_STRIDE), np.int32)
+        W = self.time_warp
+        for row, T in zip(plan, frames):
+            T = int(T)
+            if W > 0 and T >= 2 * W + 3:
+                c = int(gen.integers(W + 1, T - W - 1))          # uniform in [W + 1, T - W - 2]
+                row[0], row[1] = c, c + int(gen.integers(-W, W + 1))
+            for k in range(self.freq_masks):
+                width = int(gen.integers(0, self.freq_width + 1))
+                a = int(gen.integers(0, NUM_BINS - width + 1))
+                row[_SPEC_FREQ0 + 2 * k], row[_SPEC_FREQ0 + 2 * k + 1] = a, a + width
+            widest = min(self.time_width, int(math.floor(self.time_ratio * T)))
+            for k in range(self.time_masks):
+                width = int(gen.integers(0, widest + 1))
+                a = int(gen.integers(0, T - width + 1))
+                row[_SPEC_TIME0 + 2 * k], row[_SPEC_TIME0 + 2 * k + 1] = a, a + width
+        return plan
+
+    def __call__(self, feats, row_off, frames, gen, out=None):
+        return spec_augment(feats, row_off, frames, self.draw(gen, frames), self.fill, out)
+
+    def epoch(self, rank=0, epoch=0):
+        """The callable (feats, row_off, frames, out=None) -> feats of one training epoch: the `spec` argument of the
+        se.sequence_loss* functions and the call the trainers make after `transform(feats)`."""
+        gen = self.generator(rank, epoch)
+        return lambda feats, row_off, frames, out=None: self(feats, row_off, frames, gen, out)
+
+
+def refuse_time_warp(config, prog):
+    """For the trainers that read frame-level labels: a time warp moves frames under the labels, so exit with a one-line
+    message when data_config `spec_augment` has time_warp > 0.  The masks are honoured everywhere."""
+    aug = SpecAugment.from_config(config)
+    if aug is not None and aug.time_warp > 0:
+        sys.stderr.write("ERROR: %s reads frame-level labels and cannot train on time-warped features: set data_config "
+                         "spec_augment time_warp %r to 0 (bin/train_chain.py -e2e honours it)\n" % (prog, aug.time_warp))
         sys.exit(2)

@@ -45,13 +45,15 @@ def log_prior_from_counts(counts):
 
 
 def sequence_loss(model, fb, batch, asr_decoder, trans_model, log_prior, criterion, silence_ids, ce_ratio, ce_criterion,
-                  forward=None, transform=None):
+                  forward=None, transform=None, spec=None):
     """Forward of one minibatch: batch = dict(wav, lens, y = pdf alignments, aux = transition-id alignments)
     from pykaldi2_amd.data.  `forward(model, x[Tmax, N, 80], frames) -> [N, Tmax, P]` replaces the BLSTM call
     (TransformerAM with its masks: bin/train_transformer_se.py).  Returns (loss, se_value, ce_loss, frames)."""
     feats, frames, row_off = fb(batch["wav"], batch["lens"])
     if transform is not None:      # the `-transform` MVN statistics (reference bin/train_se.py:104-108)
         feats = transform(feats)
+    if spec is not None:
+        feats = spec(feats, row_off, frames)
     x = fb.pad_roll_subsample(feats, row_off, frames, shift=0, subsample=1, time_major=True)      # [Tmax, N, 80]
     if forward is not None:
         prediction = forward(model, x, frames)
@@ -69,7 +71,7 @@ def sequence_loss(model, fb, batch, asr_decoder, trans_model, log_prior, criteri
 
 
 def sequence_loss_aligned(model, fb, batch, texts, aligner, asr_decoder, trans_model, log_prior, criterion, silence_ids,
-                          ce_ratio, ce_criterion, forward=None, transform=None):
+                          ce_ratio, ce_criterion, forward=None, transform=None, spec=None):
     """The step of the reference's bin/train_se2.py:240-273: the numerator alignment of every utterance is made on the fly
     from its word transcript (`texts`) with the current model -- one MappedAligner.align_batch on prediction - log_prior
     for the whole minibatch -- instead of being read from the label files.  Utterances that fail to align are left out of
@@ -78,6 +80,8 @@ def sequence_loss_aligned(model, fb, batch, texts, aligner, asr_decoder, trans_m
     feats, frames, row_off = fb(batch["wav"], batch["lens"])
     if transform is not None:
         feats = transform(feats)
+    if spec is not None:
+        feats = spec(feats, row_off, frames)
     x = fb.pad_roll_subsample(feats, row_off, frames, shift=0, subsample=1, time_major=True)
     prediction = forward(model, x, frames) if forward is not None else model.forward_time_major(x).transpose(0, 1)
     N, Tmax = prediction.shape[0], prediction.shape[1]
@@ -113,7 +117,7 @@ def mwe_settings(config, acoustic_scale):
 
 
 def sequence_loss_mwe(model, fb, batch, texts, aligner, asr_decoder, trans_model, log_prior, mwe_cfg, ce_ratio, ce_criterion,
-                      forward=None, transform=None):
+                      forward=None, transform=None, spec=None):
     """The train_se2 step with the N-best minimum word error criterion (ops.MWEBatchFunction): the supervision is the word
     transcript (`texts`); with mwe_cfg['phone_level'] it is the transition-id alignment made on the fly as in
     sequence_loss_aligned (utterances that fail to align are left out).  loss = ce_ratio * ce_loss + sum of the MWE losses.
@@ -121,6 +125,8 @@ def sequence_loss_mwe(model, fb, batch, texts, aligner, asr_decoder, trans_model
     feats, frames, row_off = fb(batch["wav"], batch["lens"])
     if transform is not None:
         feats = transform(feats)
+    if spec is not None:
+        feats = spec(feats, row_off, frames)
     x = fb.pad_roll_subsample(feats, row_off, frames, shift=0, subsample=1, time_major=True)
     prediction = forward(model, x, frames) if forward is not None else model.forward_time_major(x).transpose(0, 1)
     N, Tmax = prediction.shape[0], prediction.shape[1]
@@ -161,22 +167,27 @@ def ts_settings(config, acoustic_scale):
 
 
 def sequence_loss_ts(model, teacher, fb, batch, asr_decoder, log_prior, ts_cfg, ce_ratio, ce_criterion, forward=None,
-                     transform=None):
+                     transform=None, spec=None):
     """The train_se2 step with the lattice teacher-student criterion (ops.TeacherStudentBatch): the frozen `teacher` runs
     under torch.no_grad() in eval mode on the same features, the lattices are decoded from its log-likelihoods and rescored
     with the student's; the log prior is subtracted from both, as the reference's docstring asks (ops/ops.py:81).
+    `spec` (feats, row_off, frames, out=) augments the student's features only, out of place.
     loss = ce_ratio * ce_loss + sum of the per-utterance divergences.  Returns (loss, ts_value, ce_loss, frames, [])."""
     feats, frames, row_off = fb(batch["wav"], batch["lens"])
     if transform is not None:
         feats = transform(feats)
     x = fb.pad_roll_subsample(feats, row_off, frames, shift=0, subsample=1, time_major=True)
-    run = (lambda m: forward(m, x, frames)) if forward is not None else (lambda m: m.forward_time_major(x).transpose(0, 1))
+    x_T = x          # the teacher decodes its lattices from the clean features; only the student sees the augmented ones
+    if spec is not None:
+        x = fb.pad_roll_subsample(spec(feats, row_off, frames, out=torch.empty_like(feats)), row_off, frames, shift=0,
+                                  subsample=1, time_major=True)
+    run = (lambda m, x: forward(m, x, frames)) if forward is not None else (lambda m, x: m.forward_time_major(x).transpose(0, 1))
     was_training = teacher.training
     teacher.eval()
     with torch.no_grad():
-        prediction_T = run(teacher)
+        prediction_T = run(teacher, x_T)
     teacher.train(was_training)
-    prediction = run(model)
+    prediction = run(model, x)
     N, Tmax = prediction.shape[0], prediction.shape[1]
     y = np.full((N, Tmax), -100, np.int64)
     for n, lab in enumerate(batch["y"]):
