@@ -29,7 +29,12 @@ FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-at
 # contract(off)`; the decoder's costs must round like the oracle's separate float32 operations.
 FILE_FLAGS = {"lattice_decode.hip": ["-ffp-contract=off"], "lattice_decode_frames.hip": ["-ffp-contract=off"],
               "align_viterbi.hip": ["-ffp-contract=off"], "rirgen.hip": ["-ffp-contract=off"],
-              "lattice_nbest.hip": ["-ffp-contract=off"], "lattice_rescore.hip": ["-ffp-contract=off"]}
+              "lattice_nbest.hip": ["-ffp-contract=off"], "lattice_rescore.hip": ["-ffp-contract=off"],
+              # ng_chains<true> (graph in LDS) and ng_chains<false> (global memory) are one source, but under =fast the
+              # backend fused `mysum += h` with the product that made h in one of them only: the beta rows of the two
+              # routes differed in the last bit, and so did a small utterance's posteriors with and without a large
+              # neighbour in its batch.  =on fuses inside a statement only, the same way in every instantiation.
+              "chain_num_graph.hip": ["-ffp-contract=on"]}
 # experiment builds: PK2_FILE_FLAGS="gemm_f32.hip:-mllvm,-align-loops=64;..." adds flags to single sources
 for _spec in os.environ.get("PK2_FILE_FLAGS", "").split(";"):
     if ":" in _spec:

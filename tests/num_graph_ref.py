@@ -43,14 +43,20 @@ def forward_backward(g, x, with_arcs=False):
     tot = la[T - 1] - fin
     m = tot.max()
     logp = m + np.log(np.exp(tot - m).sum()) if np.isfinite(m) else -np.inf
-    occ = np.zeros((T, A))
+    # the occupancies [T, A] are kept only when asked for (260 MB for 8000 states over 1700 frames): without them each
+    # frame's row is formed, added into gamma and dropped -- the same operations on the same numbers
+    occ = np.zeros((T, A)) if with_arcs else None
     gamma = np.zeros((T, P))
     if np.isfinite(logp):
-        occ[0, first] = np.exp(-w[first] + x[0, pdf[first]] + lb[0, dst[first]] - logp)
-        for t in range(1, T):
-            occ[t, rest] = np.exp(la[t - 1, src[rest]] - w[rest] + x[t, pdf[rest]] + lb[t, dst[rest]] - logp)
         for t in range(T):
-            np.add.at(gamma[t], pdf, occ[t])
+            row = np.zeros(A)
+            if t == 0:
+                row[first] = np.exp(-w[first] + x[0, pdf[first]] + lb[0, dst[first]] - logp)
+            else:
+                row[rest] = np.exp(la[t - 1, src[rest]] - w[rest] + x[t, pdf[rest]] + lb[t, dst[rest]] - logp)
+            np.add.at(gamma[t], pdf, row)
+            if with_arcs:
+                occ[t] = row
     return (logp, gamma, occ) if with_arcs else (logp, gamma)
 
 

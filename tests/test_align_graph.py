@@ -5,6 +5,7 @@ Also: <LogProbs> of text and binary transition models, and the error cases.  No 
 
 The helpers here (model builders, Viterbi references, the f32 emulation of the device kernel) are shared with
 tests/test_gpu_align.py and tests/test_gpu_cli_se2.py."""
+import re
 import struct
 
 import numpy as np
@@ -288,9 +289,14 @@ def brute_force(tree, tm, lex, words, ll, ascale, tscale, lscale, disambig=()):
 
 
 # ---------------------------------------------------------------- f32 emulation of csrc/align_viterbi.hip
-def emulate_viterbi(g, ll, ascale, beam):
-    """Bit-exact numpy model of the device kernel on an exported graph: -> (status, tids, total, graph, acoustic)."""
+def emulate_viterbi(g, ll, ascale, beam, trace=None):
+    """Bit-exact numpy model of the device kernel on an exported graph: -> (status, tids, total, graph, acoustic).
+    trace: a dict that receives what the run met -- arc_ties (frame/state pairs where a later in-arc equalled the finite
+    best so far, which strict < leaves to the earlier arc), pruned (source costs the beam turned into +inf), final_ties
+    (final states with the least finite total) and, when a path was found, margin (the largest amount by which a state
+    of the chosen path exceeded its frame's best cost: a smaller beam prunes that path)."""
     f = np.float32
+    arc_ties = pruned = 0
     S = g["final"].shape[0]
     T = ll.shape[0]
     off, src, w, pdf, tid = g["in_off"], g["src"], g["weight"].astype(f), g["pdf"], g["tid"]
@@ -310,25 +316,39 @@ def emulate_viterbi(g, ll, ascale, beam):
                 a = off[:-1][has] + k
                 sa = src[a]
                 v = np.where(sa < 0, f(0.0) if t == 0 else f(np.inf), cost[np.maximum(sa, 0)]).astype(f)
+                if trace is not None:
+                    pruned += int(((v > thr) & (v < np.inf)).sum())
                 v = np.where(v > thr, f(np.inf), v).astype(f)
                 cand = ((v + w[a]).astype(f) + ac[pdf[a]]).astype(f)
                 idx = np.flatnonzero(has)
+                if trace is not None:
+                    arc_ties += int(((cand == best[idx]) & (cand < np.inf)).sum())
                 better = cand < best[idx]
                 best[idx[better]] = cand[better]
                 arg[idx[better]] = a[better]
             cost = best
             bps[t] = arg
+            if trace is not None:
+                trace.setdefault("costs", []).append(cost)
             thr = f(np.fmin.reduce(cost) + f(beam))
         v = np.where(cost > thr, f(np.inf), cost).astype(f)
         tot = (v + g["final"].astype(f)).astype(f)
     s = int(np.argmin(tot))
+    if trace is not None:
+        costs = trace.pop("costs")
+        trace.update(arc_ties=arc_ties, pruned=pruned, final_ties=int((tot == tot[s]).sum()) if tot[s] < np.inf else 0)
     if not tot[s] < np.inf:
         return 1, None, np.inf, np.inf, np.inf
     path = np.zeros(T, np.int64)
+    excess = np.zeros(T)
     x = s
     for t in range(T - 1, -1, -1):
         path[t] = bps[t][x]
+        if trace is not None:
+            excess[t] = float(costs[t][x]) - float(np.fmin.reduce(costs[t]))
         x = int(src[path[t]])
+    if trace is not None:
+        trace.update(excess=excess, margin=float(excess.max()))
     gs, acs = f(0.0), f(0.0)
     for t in range(T):
         gs = f(gs + w[path[t]])
@@ -460,3 +480,29 @@ def test_synthetic_lexicon_matches_decoding_graph():
     tree, am = synth.alignment_model(P)
     g = chain.AlignmentGraphs(chain.AlignModel(tree, am), chain.Lexicon(lex), [[2, 3], [4]], [60, 30])
     assert g.status == [0, 0]
+
+
+def test_state_limit():
+    """kAlignMaxStates = 32 * 512 (align_internal.h): a transcript just under it compiles, a longer one is refused with
+    status 3 and a message that names both numbers, and the other utterances of the call are what they are alone."""
+    import graph_cases as GC
+    model, lexicon = GC.triphone()
+    under, over = GC.ladder_words(800), GC.ladder_words(810)
+    texts, frames = [[2, 4], over, under, [4]], [40, 4000, 4000, 30]
+    g = chain.AlignmentGraphs(model, lexicon, texts, frames)
+    assert g.status == [chain.ALIGN_OK, chain.ALIGN_ERROR, chain.ALIGN_OK, chain.ALIGN_OK], g.errors
+    S = g.num_states[2]
+    assert 16000 < S <= GC.MAX_STATES == 16384, S
+    assert GC.states_per_thread(S) == 32 and not g.uses_lds()
+    assert g.num_states[1] == 0 and g.num_arcs[1] == 0
+    m = re.search(r"has (\d+) states, more than (\d+)", g.errors[1])
+    assert m and int(m.group(1)) > 16384 and int(m.group(2)) == 16384, g.errors[1]
+    assert g.errors[0] == g.errors[2] == g.errors[3] == ""
+    for n in (0, 2, 3):
+        alone = chain.AlignmentGraphs(model, lexicon, [texts[n]], [frames[n]])
+        assert alone.status == [chain.ALIGN_OK]
+        a, b = alone.export(0), g.export(n)
+        assert a.keys() == b.keys() and all(np.array_equal(a[k], b[k]) for k in a)
+    # the refused transcript alone: the same status, nothing compiled, nothing to launch on
+    alone = chain.AlignmentGraphs(model, lexicon, [over], [4000])
+    assert alone.status == [chain.ALIGN_ERROR] and alone.num_states == [0] and alone.errors[0] == g.errors[1]

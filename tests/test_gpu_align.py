@@ -7,6 +7,8 @@ import torch
 
 from pykaldi2_amd import chain, synth
 
+import graph_cases as GC
+from graph_cases import planted as _planted
 from test_align_graph import PRONS, emulate_viterbi, exported_arcs, kaldi_like_lexicon, make_model, viterbi64
 
 pytestmark = pytest.mark.gpu
@@ -75,29 +77,6 @@ def test_batch_bit_exact_in_nan_buffer(monkeypatch, lds):
         assert np.array_equal(again[2], status)
 
 
-def _planted(rng, graph, T, pdfs, peak=8.0):
-    """A random path of exactly T frames through an exported graph, and log-likelihoods peaked along its pdfs."""
-    S = graph["final"].shape[0]
-    src, dst = graph["src"], graph["dst"]
-    reach = np.zeros((T, S), bool)
-    reach[0, dst[src < 0]] = True
-    for t in range(1, T):
-        ok = (src >= 0) & reach[t - 1, np.maximum(src, 0)]
-        reach[t, dst[ok]] = True
-    cand = np.flatnonzero(reach[T - 1] & np.isfinite(graph["final"]))
-    s = int(rng.choice(cand))
-    arcs = []
-    for t in range(T - 1, -1, -1):
-        ks = np.flatnonzero((dst == s) & ((src < 0) if t == 0 else ((src >= 0) & reach[t - 1, np.maximum(src, 0)])))
-        k = int(rng.choice(ks))
-        arcs.append(k)
-        s = int(src[k])
-    arcs = arcs[::-1]
-    ll = rng.uniform(-1.0, 0.0, (T, pdfs)).astype(np.float32) - peak
-    ll[np.arange(T), graph["pdf"][arcs]] = 0.0
-    return ll, graph["tid"][arcs]
-
-
 def _synthetic_aligner(beam=10.0, retry_beam=None):
     P = 60
     tree, tm = synth.alignment_model(P)
@@ -164,3 +143,126 @@ def test_beam_failure_and_retry():
     plain, _, _ = _synthetic_aligner(beam=1.0)
     with pytest.raises(RuntimeError, match="beam"):
         plain.align(x[0], text)
+
+
+# ---------------------------------------------------------------- graphs beyond 1024 states (tests/graph_cases.py)
+def _nan_buffer(ll_list):
+    """The utterances' log-likelihoods inside a NaN-filled buffer: row stride PDFS + 9, padded frames NaN."""
+    N, Tmax = len(ll_list), max(ll.shape[0] for ll in ll_list)
+    big = torch.full((N, Tmax + 3, PDFS + 9), float("nan"), dtype=torch.float32, device="cuda")
+    x = big[:, :Tmax, :PDFS]
+    for n, ll in enumerate(ll_list):
+        x[n, :ll.shape[0]] = torch.from_numpy(ll).cuda()
+    return x
+
+
+def _run(graphs, x, beam):
+    return [t.cpu().numpy() for t in chain.align_viterbi(graphs, x, GC.ASCALE, beam)]
+
+
+def _same_bits(a, b):
+    return np.array_equal(a[0], b[0]) and np.array_equal(a[1].view(np.int32), b[1].view(np.int32)) and np.array_equal(a[2], b[2])
+
+
+def _check_row(got, n, T, ref):
+    """Row n of a launch against an emulation result: status, transition-ids and the three costs bit for bit."""
+    ali, costs, status = got
+    st, tids, tot, gc, ac = ref
+    assert status[n] == st, (n, status[n], st)
+    assert (ali[n, T:] == 0).all()
+    if st == 0:
+        assert np.array_equal(ali[n, :T], tids), (n, int((ali[n, :T] != tids).sum()))
+        assert np.array_equal(costs[n].view(np.int32), np.asarray([tot, gc, ac], np.float32).view(np.int32)), (n, costs[n], tot, gc, ac)
+    else:
+        assert (ali[n] == 0).all() and np.isinf(costs[n]).all()
+
+
+def _ladder_references(k):
+    """Both emulations of rung k, with what the binding beam must have done on the CPU."""
+    wide, _ = GC.viterbi_reference(k, 1e30)
+    tight, trace = GC.viterbi_reference(k, GC.BINDING_BEAM[k])
+    assert wide[0] == 0 and tight[0] == 0 and trace["pruned"] > 0
+    assert GC.differs(wide, tight), "rung %d: the beam %g does not change the alignment" % (k, GC.BINDING_BEAM[k])
+    return {1e30: wide, GC.BINDING_BEAM[k]: tight}
+
+
+@pytest.mark.parametrize("k", [1, 2, 3])
+def test_ladder_bit_exact(monkeypatch, k):
+    """One utterance per rung, T = minimum + 50: 4, 8 and 16 states per thread; LDS below 64 KiB, above it (the opt-in
+    attribute), and global memory chosen by size.  Rungs 1 and 2 again with the graph forced out of LDS."""
+    monkeypatch.delenv("PK2_ALIGN_LDS", raising=False)
+    words, T = GC.rung(k)
+    model, lexicon = GC.triphone()
+    graphs = chain.AlignmentGraphs(model, lexicon, [words], [T])
+    assert graphs.status == [0], graphs.errors
+    S, A = graphs.num_states[0], graphs.num_arcs[0]
+    GC.assert_rung(k, S)
+    lds = GC.viterbi_lds(S, A)
+    if k == 1:
+        assert lds <= GC.LDS_OPT_IN and graphs.uses_lds()
+    elif k == 2:
+        assert GC.LDS_OPT_IN < lds <= GC.LDS_LIMIT and graphs.uses_lds()
+    else:
+        assert lds > GC.LDS_LIMIT and not graphs.uses_lds()
+    print("rung %d: S %d A %d T %d, %d states per thread, LDS %d bytes -> %s" % (
+        k, S, A, T, GC.states_per_thread(S), lds, "LDS" if graphs.uses_lds() else "global"))
+    x = _nan_buffer([GC.rung_loglikes(k)])
+    for beam, ref in _ladder_references(k).items():
+        got = _run(graphs, x, beam)
+        _check_row(got, 0, T, ref)
+        if k < 3:
+            monkeypatch.setenv("PK2_ALIGN_LDS", "0")
+            assert not graphs.uses_lds()
+            assert _same_bits(_run(graphs, x, beam), got)
+            monkeypatch.delenv("PK2_ALIGN_LDS")
+
+
+def test_widest_route_in_a_mixed_batch(monkeypatch):
+    """Rung 4 (32 states per thread, global memory by size) in one launch with a two-word utterance, a one-word utterance
+    at its minimum length and one without a path: everything runs on the route of the largest graph."""
+    monkeypatch.delenv("PK2_ALIGN_LDS", raising=False)
+    model, lexicon = GC.triphone()
+    words, T = GC.rung(4)
+    one = [4]
+    texts = [words, [2, 4], one, [5, 5, 5, 5]]
+    frames = [T, 40, GC.min_frames(one, hi=64), 14]
+    graphs = chain.AlignmentGraphs(model, lexicon, texts, frames)
+    assert graphs.status == [0, 0, 0, chain.ALIGN_NO_PATH], graphs.errors
+    S, A = graphs.num_states[0], graphs.num_arcs[0]
+    GC.assert_rung(4, S)
+    assert S > 8192 and GC.states_per_thread(max(graphs.num_states)) == 32
+    assert GC.viterbi_lds(S, A) > GC.LDS_LIMIT and not graphs.uses_lds()
+    print("rung 4: S %d A %d T %d, 32 states per thread, LDS %d bytes -> global; neighbours S %s T %s" % (
+        S, A, T, GC.viterbi_lds(S, A), graphs.num_states[1:], frames[1:]))
+    rng = np.random.default_rng(31)
+    lls = [GC.rung_loglikes(4)] + [(3.0 * rng.standard_normal((t, PDFS))).astype(np.float32) for t in frames[1:]]
+    x = _nan_buffer(lls)
+    small = chain.AlignmentGraphs(model, lexicon, texts[1:3], frames[1:3])
+    assert small.status == [0, 0] and GC.states_per_thread(max(small.num_states)) == 1 and small.uses_lds()
+    xs = _nan_buffer(lls[1:3])
+    for beam, ref in _ladder_references(4).items():
+        got = _run(graphs, x, beam)
+        _check_row(got, 0, T, ref)
+        for n in (1, 2):
+            _check_row(got, n, frames[n], emulate_viterbi(graphs.export(n), lls[n], GC.ASCALE, beam))
+        assert got[2][3] == chain.ALIGN_NO_PATH and (got[0][3] == 0).all() and (got[1][3] == np.inf).all()
+        assert (got[2][:3] == 0).all()
+        # the small utterances alone run with one state per thread in LDS: the arithmetic does not depend on the route
+        alone = _run(small, xs, beam)
+        for n in (1, 2):
+            assert np.array_equal(alone[0][n - 1, :frames[n]], got[0][n, :frames[n]])
+            assert np.array_equal(alone[1][n - 1].view(np.int32), got[1][n].view(np.int32)) and alone[2][n - 1] == got[2][n]
+
+
+def test_ties_bit_exact():
+    """Only the lexicon's costs and all-zero log-likelihoods on more than 1024 states: exact ties at almost every state,
+    and between two final states; strict < keeps the first arc in stored order, the lowest final state wins."""
+    graphs, T, beams = GC.ties_case()
+    S = graphs.num_states[0]
+    assert S > 1024 and graphs.status == [0]
+    ll = np.zeros((T, PDFS), np.float32)
+    x = _nan_buffer([ll])
+    for beam in beams:
+        ref, trace = GC.ties_reference(beam)
+        assert ref[0] == 0 and trace["arc_ties"] > 0 and trace["final_ties"] >= 2
+        _check_row(_run(graphs, x, beam), 0, T, ref)

@@ -50,6 +50,30 @@ def test_oracle_matches_brute_force():
     assert len({tuple(g["pdf"][p]) for p in paths}) > 4
 
 
+def test_oracle_without_stored_occupancies_is_identical():
+    """forward_backward keeps occ[T, A] only when asked to (it is hundreds of MB on the large graphs of
+    tests/graph_cases.py): the result without it is the one with it, and both are the occupancies summed by pdf."""
+    aligner = _aligner()
+    rng = np.random.default_rng(7)
+    words = [3, 5, 4, 2]
+    T = _min_frames(aligner, words) + 9
+    g = aligner.compile([words], [T]).export(0)
+    x = (2.0 * rng.standard_normal((T, PDFS))).astype(np.float32)
+    lp_a, gamma_a, occ = R.forward_backward(g, x, with_arcs=True)
+    lp_b, gamma_b = R.forward_backward(g, x)
+    assert lp_a == lp_b and np.array_equal(gamma_a, gamma_b)
+    want = np.zeros((T, PDFS))
+    for t in range(T):
+        np.add.at(want[t], g["pdf"], occ[t])
+    assert np.array_equal(gamma_b, want) and occ.shape == (T, g["src"].shape[0]) and (occ.sum(1) > 0.999).all()
+    # without a path of T frames: log p = -inf and no posterior, on either way through
+    T0 = _min_frames(aligner, words) - 1
+    lp, gamma, occ = R.forward_backward(g, x[:T0], with_arcs=True)
+    assert lp == -np.inf and not gamma.any() and not occ.any()
+    lp, gamma = R.forward_backward(g, x[:T0])
+    assert lp == -np.inf and not gamma.any()
+
+
 def test_oracle_gamma_is_autograd_gradient():
     aligner = _aligner(seed=22)
     rng = np.random.default_rng(6)
