@@ -585,6 +585,48 @@ int pk2_spec_augment(const float* in, float* out, const int64_t* row_off /* devi
                      float fill, void* stream);
 
 /* ------------------------------------------------------------------ *
+ * Mask-based MVDR beamforming of a ragged minibatch (csrc/beamform.hip; no counterpart in the reference).
+ * B utterances with their own frame counts N_b and common C channels (1 .. PK2_BF_MAX_CHANNELS), F bins and K masks
+ * (1 .. PK2_BF_MAX_MASKS).  Spectra are what pk2_stft_f32 writes for the C rows of one signal: (C, N_b, F, 2), channel- and
+ * frame-major; masks are f32 (N_b, F).  `spec`, `masks`, `phi_s`, `phi_n`, `w` (of pk2_bf_apply) and `out` are HOST arrays
+ * of device pointers, `frames` is a HOST array; more than PK2_BF_MAX_UTTS utterances take one launch per PK2_BF_MAX_UTTS.
+ * No atomics, no host synchronisation: a result is bit-identical from run to run and independent of the other utterances
+ * of its call.  Bad arguments (null pointers, B < 1, C, F, K or a frame count out of range, a workspace too small) return
+ * PK2_ERR_INVALID before the device is touched.
+ *
+ * pk2_bf_cov: Phi_k[f] = sum_t m_k[t, f] y y^H / max(sum_t m_k[t, f], 1e-10), y = Y[:, t, f].  masks: B * K pointers,
+ * utterance-major.  complement != 0 needs K == 1 and gives two matrices, for m and for 1 - m, from the same pass.
+ * phi: device (B, K', F, C, C, 2), K' = complement ? 2 : K; exactly Hermitian (one triangle computed in float32 over
+ * PK2_BF_FRAMES_PER_PART frames per workgroup, the parts added in order in float64, the other triangle mirrored; the
+ * diagonal is real).
+ *
+ * pk2_bf_mvdr_weights (Souden): Phi_n' = Phi_n + (diag_load Re tr(Phi_n) / C + 1e-10) I, G = Phi_n'^-1 Phi_s (Cholesky, in
+ * float64), w[f] = G[:, r] / tr G; w[f] = e_r where |tr G| <= 1e-20 or the bin's input is not finite (then nonfinite[b]
+ * becomes 1, else 0).  phi_s, phi_n: B pointers to (F, C, C, 2) each.  ref = r in [0, C), or PK2_BF_REF_SNR:
+ * r = argmax_c sum_f Re(w^(c)H Phi_s w^(c)) / sum_f Re(w^(c)H Phi_n' w^(c)), sums in bin order in float64, ties to the
+ * lowest c, chosen on the device.  w: device (B, F, C, 2); ref_index, nonfinite: device int32 [B].
+ *
+ * pk2_bf_apply: out_b[t, f] = sum_c conj(w_b[f, c]) Y_b[c, t, f], c ascending in float32; out_b: (N_b, F, 2).
+ *
+ * work: device memory of pk2_bf_workspace_bytes(frames, B, C, F, K, complement) bytes, enough for pk2_bf_cov and
+ * pk2_bf_mvdr_weights of that minibatch (frames == NULL: for pk2_bf_mvdr_weights alone; K and complement are then
+ * ignored); 0 for arguments the entries would refuse.
+ * ------------------------------------------------------------------ */
+#define PK2_BF_MAX_CHANNELS 8
+#define PK2_BF_MAX_MASKS 4
+#define PK2_BF_MAX_UTTS 32
+#define PK2_BF_FRAMES_PER_PART 32
+#define PK2_BF_REF_SNR (-1)
+size_t pk2_bf_workspace_bytes(const int32_t* frames, int32_t B, int32_t C, int32_t F, int32_t K, int32_t complement);
+int pk2_bf_cov(const float* const* spec, const float* const* masks, const int32_t* frames, int32_t B, int32_t C, int32_t F,
+               int32_t K, int32_t complement, void* work, size_t work_bytes, float* phi, void* stream);
+int pk2_bf_mvdr_weights(const float* const* phi_s, const float* const* phi_n, int32_t B, int32_t C, int32_t F, int32_t ref,
+                        double diag_load, void* work, size_t work_bytes, float* w, int32_t* ref_index, int32_t* nonfinite,
+                        void* stream);
+int pk2_bf_apply(const float* const* spec, const float* const* w, const int32_t* frames, int32_t B, int32_t C, int32_t F,
+                 float* const* out, void* stream);
+
+/* ------------------------------------------------------------------ *
  * Fused log-softmax + NLL + gradient.  Replaces nn.CrossEntropyLoss
  * (ignore_index=-100; reduction mean: reference bin/train_ce.py:134,189;
  * reduction sum: bin/train_se.py:214,235).

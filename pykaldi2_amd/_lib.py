@@ -60,6 +60,10 @@ RESAMPLE_MAX_JOBS = 32   # PK2_RESAMPLE_MAX_JOBS
 SPEC_MAX_FREQ_MASKS = 4  # PK2_SPEC_MAX_FREQ_MASKS
 SPEC_MAX_TIME_MASKS = 16                                                # PK2_SPEC_MAX_TIME_MASKS
 SPEC_PLAN_STRIDE = 2 + 2 * SPEC_MAX_FREQ_MASKS + 2 * SPEC_MAX_TIME_MASKS  # PK2_SPEC_PLAN_STRIDE
+BF_MAX_CHANNELS = 8      # PK2_BF_MAX_CHANNELS
+BF_MAX_MASKS = 4         # PK2_BF_MAX_MASKS
+BF_FRAMES_PER_PART = 32  # PK2_BF_FRAMES_PER_PART
+BF_REF_SNR = -1          # PK2_BF_REF_SNR
 
 _vp, _i32, _i64, _f32, _sz = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_size_t
 
@@ -195,6 +199,11 @@ SIGNATURES = {
     "pk2_pad_roll_subsample": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _vp]),
     "pk2_mvn_apply": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _vp, _vp]),
     "pk2_spec_augment": (C.c_int, [_vp, _vp, _vp, _i32, _i64, _vp, _i32, _f32, _vp]),
+    "pk2_bf_workspace_bytes": (_sz, [_vp, _i32, _i32, _i32, _i32, _i32]),
+    "pk2_bf_cov": (C.c_int, [C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_i32), _i32, _i32, _i32, _i32, _i32, _vp, _sz, _vp, _vp]),
+    "pk2_bf_mvdr_weights": (C.c_int, [C.POINTER(_vp), C.POINTER(_vp), _i32, _i32, _i32, _i32, C.c_double, _vp, _sz, _vp, _vp,
+                                      _vp, _vp]),
+    "pk2_bf_apply": (C.c_int, [C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_i32), _i32, _i32, _i32, C.POINTER(_vp), _vp]),
     "pk2_softmax_ce_fwd_bwd": (C.c_int, [_vp, _i64, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _i64, _vp, _vp]),
     "pk2_softmax_ce_fwd_bwd_mean": (C.c_int, [_vp, _i64, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _i64, _vp]),
     "pk2_scale_inplace_ratio": (C.c_int, [_vp, _i64, _vp, _vp, _vp]),

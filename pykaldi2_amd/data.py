@@ -227,7 +227,7 @@ class SimulationPool:
     one impulse response per file), or the synthetic generator."""
 
     def __init__(self, noises, rirs, use_reverb=True, use_noise=True, simulation_prob=0.5, gain_norm=False, snr_range=(0, 30),
-                 online_rir=False, t60_range=(0.1, 0.5)):
+                 online_rir=False, t60_range=(0.1, 0.5), beamform=None):
         from . import simulation
         self.noises = noises if use_noise else []
         self.online_rir = bool(online_rir and use_reverb)
@@ -237,6 +237,16 @@ class SimulationPool:
         self.sim = simulation.SimpleSimulator(use_rir=bool(self.rirs) or self.online_rir, use_noise=bool(self.noises),
                                               snr_range=snr_range)
         self._dev = {}
+        self.beamform = dict(beamform) if beamform else None      # data_config `beamform` (beamform.beamform_config)
+        if self.beamform:
+            from . import beamform as bf
+            if not self.online_rir:
+                raise ValueError("beamform: data_config online_rir and use_reverb must be true")
+            analyzer = simulation.SpectrumAnalyzer(do_dither=False)
+            self.mic_positions = bf.array_geometry(self.beamform["n_mics"], self.beamform["radius"])
+            self.sim_mc = simulation.SimpleSimulator(use_rir=True, use_noise=bool(self.noises), snr_range=snr_range,
+                                                     mask_estimator=simulation.MaskEstimator(analyzer))
+            self.beamformer = bf.MaskBeamformer(analyzer, self.beamform["ref"], self.beamform["diag_load"])
 
     @classmethod
     def from_config(cls, config, seed=0):
@@ -244,8 +254,12 @@ class SimulationPool:
         plus `dir_noise_paths` / `rir_paths` (bin/train_ce.py:73-76); None when the simulation is off.
         `online_rir: true` (with `use_reverb`) makes a RIR for every simulated utterance on the device instead of
         picking one from the pool (pykaldi2_amd.rirgen), T60 ~ U[`t60_range`] (default [0.1, 0.5]); it wins over
-        `rir_paths`."""
+        `rir_paths`.  `beamform` (true or a mapping, see pykaldi2_amd.beamform.beamform_config; needs `online_rir`,
+        `use_reverb` and `simulation_prob` > 0, ValueError otherwise): a simulated utterance is recorded by a circular
+        array in the sampled room and comes back as the output of a mask-based MVDR beamformer."""
+        from . import beamform as bf
         dc = config.get("data_config", {})
+        beamform = bf.beamform_config(config)
         prob = dc.get("simulation_prob", 0)
         if not prob or not (dc.get("use_dir_noise") or dc.get("use_reverb")):
             return None
@@ -262,7 +276,7 @@ class SimulationPool:
             noises = cls._read_zips(config.get("dir_noise_paths") or [], config.get("data_path", ""))
             rirs = cls._read_zips(config.get("rir_paths") or [], config.get("data_path", "")) if not online else []
         return cls(noises, rirs, dc.get("use_reverb", False), dc.get("use_dir_noise", False), prob, dc.get("gain_norm", False),
-                   dc.get("snr_range", (0, 30)), online, dc.get("t60_range", (0.1, 0.5)))
+                   dc.get("snr_range", (0, 30)), online, dc.get("t60_range", (0.1, 0.5)), beamform)
 
     @staticmethod
     def _read_zips(sources, data_path):
@@ -292,6 +306,8 @@ class SimulationPool:
         delays = []
         if self.noises:
             noise = self._on_device("n", int(np.random.choice(len(self.noises))), device)[0]
+        if self.beamform:
+            return self._simulate_array(x, noise, device)
         if self.online_rir:
             src_rir, noise_rir, delays = self.online_rirs(2 if noise is not None else 1, device)
         elif self.rirs:
@@ -304,6 +320,21 @@ class SimulationPool:
         y, _ = self.sim(x, [noise] if noise is not None else None, src_rir, [noise_rir] if noise_rir is not None else None,
                         normalize_gain=self.gain_norm, rir_delays=delays or None)
         return y
+
+    def _simulate_array(self, x, noise, device):
+        """The simulated utterance as an array hears it, beamformed back to one channel of the input's length: (nsrc, C, k)
+        RIRs of one sampled room, the multi-channel simulation with the speech source's ideal mask (channel 0, no dither),
+        and the MVDR beamformer with that mask and its complement.  The draws are those of the single-channel path, in
+        its order (sample_online_room draws the same with an array); nothing is read back to the host."""
+        from . import rirgen
+        n_src = 2 if noise is not None else 1
+        room, t60, mic, src = rirgen.sample_online_room(self.t60_range, n_src, mic_positions=self.mic_positions)
+        b = rirgen.rirgen_batch([dict(room=room, source_loc=src, mic_loc=mic, t60=t60)], device=device)
+        rirs, dl = b.rirs[0], b.delays[0]                      # (nsrc, C, k), (nsrc, C)
+        mixed, _, mask, _ = self.sim_mc(x, [noise] if noise is not None else None, rirs[0],
+                                        [rirs[1]] if noise is not None else None, normalize_gain=self.gain_norm,
+                                        rir_delays=[dl[s] for s in range(n_src)], gen_mask=True)
+        return self.beamformer(mixed, mask[0])
 
     def online_rirs(self, n_src, device):
         """RIRs of one sampled room (rirgen.sample_online_room: room, T60, mic at the array centre, the speech source and
