@@ -61,9 +61,10 @@ int pk2_den_graph_initial_probs(const pk2_den_graph* g, float* host_out);
  * 1 = state-x kernels, one launch per frame, 2 = state-x, persistent recursion kernel (one launch per call).  Reporting
  * only; the choice is the library's (reference: kaldi.chain.DenominatorComputation behind ops/ops.py:265). */
 int32_t pk2_den_graph_path(const pk2_den_graph* g, int32_t num_seqs);
-/* The form of the persistent recursion kernel behind path 2: 1 = every arc in registers and the whole state vector in LDS
- * (graphs up to ~1.05 M arc slots / ~36 k states), 2 = chunked LDS table whose copy overlaps the arcs, two resident passes
- * and streamed overflow (any graph with < 65536 states); 0 = none (paths 0 / 1).  PK2_DEN_PERSIST = 0 | 1 | 2 forces one. */
+/* The form of the persistent recursion kernel behind path 2: 2 = chunked LDS table whose copy overlaps the arcs, two
+ * resident passes and streamed overflow (any graph with < 65536 states); 0 = none (paths 0 / 1).  1 was the first such
+ * kernel (everything resident) and is no longer returned.  PK2_DEN_PERSIST = 0 | 2 forces one; 1 makes the calls fail
+ * with PK2_ERR_INVALID. */
 int32_t pk2_den_graph_persist_form(const pk2_den_graph* g, int32_t num_seqs);
 /* The route of a call on num_seqs sequences of at most max_frames frames, as the library decides it once per call
  * ("How a call is routed"): out = {family (0 = per-arc-pdf, 1 = state-x), persistent form, sequences per

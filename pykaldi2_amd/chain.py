@@ -83,8 +83,8 @@ class DenominatorGraph:
         return int(_lib.lib().pk2_den_graph_path(self._h, int(num_seqs)))
 
     def persist_form(self, num_seqs):
-        """Form of the persistent kernel behind kernel_path() == 2: 1 = everything resident, 2 = chunked table + streamed
-        overflow (csrc/chain_den_persist2.hip); 0 = none."""
+        """Form of the persistent kernel behind kernel_path() == 2: 2 = chunked table + streamed overflow
+        (csrc/chain_den_persist2.hip); 0 = none.  (1 was the retired first kernel and is no longer returned.)"""
         return int(_lib.lib().pk2_den_graph_persist_form(self._h, int(num_seqs)))
 
     PLAN_FIELDS = ("family", "form", "NG", "need_fill", "xgather", "prep_merged", "tail_mergeable", "gamma_kernel")
@@ -98,7 +98,7 @@ class DenominatorGraph:
         return dict(zip(self.PLAN_FIELDS, (int(v) for v in out)))
 
     def debug_persist2(self, which):
-        """Second persistent layout of an ordering (test hook; csrc/chain_internal.h: HostPersist2); None if absent."""
+        """Persistent layout of an ordering (test hook; csrc/chain_internal.h: HostPersist2); None if absent."""
         L = _lib.lib()
         info = np.zeros(32, dtype=np.int32)
         _lib.check(L.pk2_den_graph_debug_persist2(self._h, which, _lib.ptr(info), *([None] * 17)))
@@ -121,24 +121,6 @@ class DenominatorGraph:
         out.update(estep=int(info[1]), K=int(info[2]), R=int(info[3]), tfloats=int(info[4]), max_rows=int(info[5]),
                    max_groups=int(info[6]), pieces=pieces, cap=int(info[8]), cbeg=[int(v) for v in info[10:10 + MC + 1]],
                    lds_off=[int(v) for v in info[20:20 + MC]], SP=SP, W=W, T=T, slots=K, row_arrays=int(info[19]))
-        return out
-
-    def debug_persist(self, which):
-        """Layout of an ordering for the persistent kernel (test hook): which = 0 forward, 1 backward; None when the
-        graph does not fit it."""
-        L = _lib.lib()
-        info = np.zeros(9, dtype=np.int32)
-        _lib.check(L.pk2_den_graph_debug_persist(self._h, which, _lib.ptr(info), None, None, None, None, None, None, None, None))
-        if not info[0]:
-            return None
-        R, T, K, W, rows = (int(v) for v in info[3:8])
-        out = dict(arcs=np.empty((R, K, T, 2), dtype=np.int32), ends=np.empty((R, T), dtype=np.uint64),
-                   first_row=np.empty((R, T), dtype=np.int32), wcrow=np.empty((R, W), dtype=np.int32),
-                   row_begin=np.empty(R + 1, dtype=np.int32), grp_begin=np.empty(R + 1, dtype=np.int32),
-                   row_leak=np.empty(rows, dtype=np.float32), row_psum=np.empty(rows, dtype=np.float32))
-        _lib.check(L.pk2_den_graph_debug_persist(self._h, which, _lib.ptr(info), *[_lib.ptr(out[k]) for k in
-                   ("arcs", "ends", "first_row", "wcrow", "row_begin", "grp_begin", "row_leak", "row_psum")]))
-        out.update(max_rows=int(info[1]), max_groups=int(info[2]), estep=int(info[8]))
         return out
 
     def debug_ordering(self, which):

@@ -47,7 +47,7 @@ __global__ void debug_where_kernel(int32_t* out) {
 
 // What a ring / direct all-reduce kernel of the collective library does to the chip while a step runs, without a second GPU:
 // `blocks` workgroups of 256 threads stream dst[i] += src[i] over the bucket, `passes` times (pre-pricing the
-// co-residency of the persistent kernels with the exchange; tools/gpu_r05_peer.sh).  With src = zeros the bucket keeps its values.
+// co-residency of the persistent kernels with the exchange; profiles/r05_peer_coresidency.txt).  With src = zeros the bucket keeps its values.
 namespace pk2 {
 __global__ void __launch_bounds__(256) debug_peer_reduce_kernel(float* dst, const float* src, int64_t n, int passes) {
   const int64_t n4 = n / 4;

@@ -632,7 +632,7 @@ __global__ void __launch_bounds__(256) den_scales(DenParams p, const float* csum
 // instruction in its arithmetic (same partial sums in the same order: the per-frame sums of den_csum take one wave, the other
 // three contributed zeros there), with the frame normalisers handed from phase to phase in LDS.  `ctl` (optional): the
 // control block of the persistent launch that has just run -- every workgroup reads its verdict first, the last one to have
-// done so zeroes the block for the next launch (what den_persist2_check / den_persist_check did in a launch of their own).
+// done so zeroes the block for the next launch (what den_persist2_check does in a launch of its own).
 __global__ void __launch_bounds__(256) den_tail1(DenParams p, float* csum, float* den_lp, float* Kf, float* check, DenTailCheck ck) {
   extern __shared__ float cs[];            // [(Tmax + 1)][2]: cu, ratio
   __shared__ double redd[4], reda[4], wsum[4];
@@ -651,7 +651,7 @@ __global__ void __launch_bounds__(256) den_tail1(DenParams p, float* csum, float
       s_last = __hip_atomic_fetch_add(ck.count_word, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1u ? 1u : 0u;
     }
   }
-  // ---- den_csum.  The persistent kernels leave 32 partial pairs per frame (256 contiguous bytes): a THREAD per frame, added
+  // ---- den_csum.  The persistent kernel leaves 32 partial pairs per frame (256 contiguous bytes): a THREAD per frame, added
   // in the order of the 64-lane butterfly the kernel of its own used (offsets 16, 8, 4, 2, 1 over 32 values; the upper 32
   // lanes held zeros) -- the same bits, without a dependent round trip per frame (as a wave per frame this phase took 80 us)
   if (ncb == 32) {
@@ -1474,17 +1474,15 @@ static DenEnv den_env() {
   return e;
 }
 
-// Which recursion kernel a state-x call of N sequences takes: 0 = the launch-per-frame kernels, 1 = den_persist_kernel
-// (everything resident: graphs up to ~1.05 M arc slots and ~36 k states), 2 = den_persist2_kernel.  The forced one
-// (PK2_DEN_PERSIST) if it fits, else the frame kernels; unforced, the second form whenever the whole graph is resident in it
-// (it takes every graph the first form takes and is a little faster); when it has to stream pieces or rotate table chunks,
-// whichever of it and the frame kernels the measured cost model (profiles/r03_den_sweep.txt) predicts to be faster.
+// Which recursion kernel a state-x call of N sequences takes: 0 = the launch-per-frame kernels, 2 = den_persist2_kernel
+// (1 was its retired predecessor; the numbering is what the reporting hooks have always returned).  The forced one
+// (PK2_DEN_PERSIST) if it fits, else the frame kernels; unforced, the persistent kernel whenever the whole graph is resident
+// in it; when it has to stream pieces or rotate table chunks, whichever of it and the frame kernels the measured cost model
+// (profiles/r03_den_sweep.txt) predicts to be faster.
 static int den_plan_form(const pk2_den_graph* g, int want, int N) {
   if (want == 0 || N < 1 || 2 * N > kMaxTasks || device_cu_count() != 8 * kPR) return 0;
-  const bool ok1 = den_persist_usable(g), ok2 = den_persist2_usable(g);
-  if (want == 1) return ok1 ? 1 : 0;
-  if (want == 2) return ok2 ? 2 : 0;
-  if (!ok2) return ok1 ? 1 : 0;
+  if (!den_persist2_usable(g)) return 0;
+  if (want == 2) return 2;
   const HostPersist2& f = g->h_p2fwd; const HostPersist2& b = g->h_p2bwd;
   const int pieces = std::max(f.max_pieces, b.max_pieces), K = std::max(f.K, b.K);
   if (pieces == 0 && K == 2) return 2;
@@ -1496,7 +1494,7 @@ static int den_plan_form(const pk2_den_graph* g, int want, int N) {
   const double usf = 6.0 + 0.12 * S + 10.5 * A;
   // 2 N recursions on 8 XCDs (each sequence's two recursions side by side) against ceil(N / 4) groups of frame launches
   const double t2 = us2 * std::max(1.0, 2.0 * N / 8.0), tf = usf * ((N + 3) / 4);
-  return t2 <= tf ? 2 : (ok1 ? 1 : 0);
+  return t2 <= tf ? 2 : 0;
 }
 
 // Everything that follows from (family, form, NG).  Also the plan of the fallback after a failed first-use verification:
@@ -1532,16 +1530,17 @@ DenPlan den_plan(const pk2_den_graph* g, int N, int Tmax) {
   pl.env = den_env();
   pl.N = N; pl.Tmax = Tmax;
   pl.sx = pl.env.mode >= 0 ? pl.env.mode == 1 : (int64_t)g->V <= 4 * (int64_t)g->S;
-  const int form = pl.sx ? den_plan_form(g, pl.env.persist, N) : 0;
+  if (pl.env.persist == 1) pl.rc = PK2_ERR_INVALID;      // (the first persistent form is gone: den_compute reports it)
+  const int form = pl.sx && pl.rc == 0 ? den_plan_form(g, pl.env.persist, N) : 0;
   int ng = 0;      // the largest group whose LDS need is at most 160 KB
   for (int n : {1, 2, 4}) if (den_lds_bytes(g->P, n) <= 160 * 1024) ng = n;
-  if (ng == 0) { pl.rc = PK2_ERR_LIMIT; ng = 1; }      // (den_compute reports it; sizing and the hooks go on with NG = 1)
+  if (ng == 0) { pl.rc = PK2_ERR_LIMIT; ng = 1; }      // (den_compute reports it too; sizing and the hooks go on with NG = 1)
   pl.NG_frames = ng;
   den_plan_route(g, pl, form, form != 0 ? 1 : ng);
   return pl;
 }
 
-// (sized for NG-sequence groups of the plan's family; `persist`: with the persistent kernels' xv and kPR partial sums)
+// (sized for NG-sequence groups of the plan's family; `persist`: with the persistent kernel's xv and kPR partial sums)
 static size_t den_carve(const pk2_den_graph* g, const DenPlan& pl, int NG, bool persist, DenBuffers* buf, void* base) {
   const int Tmax = pl.Tmax;
   const bool sx = pl.sx;
@@ -1664,7 +1663,7 @@ static int den_prologue(const DenCall& c, const DenPlan& pl, const DenParams& p,
   PK2_DYN_LDS_ONCE(den_bwd_step<NG>, 160 * 1024);
   int rc = get_param_slot(g_den_slots, NG, stream, slot);
   if (rc) return rc;
-  // (the frame kernels read their parameters from this block; the persistent kernels carry their own)
+  // (the frame kernels read their parameters from this block; the persistent kernel carries its own)
   if (!(pl.env.merge && persist)) hipLaunchKernelGGL(param_block_store<DenParams>, dim3(1), dim3(1), 0, stream, p, (*slot)->params);
 
   const bool zero = zr != nullptr && zr->grad != nullptr;
@@ -1716,10 +1715,9 @@ static int den_recursions(const DenCall& c, const DenPlan& pl, const DenParams& 
   pk2_den_graph* g = c.g;
   hipStream_t stream = c.stream;
   const int Tmax = pl.Tmax, G = pl.G;
-  // both recursions of every sequence in one launch (chain_den_persist2.hip / chain_den_persist.hip)
+  // both recursions of every sequence in one launch (chain_den_persist2.hip)
   if (pl.form == 2)
     return den_persist2_launch(g, p, c.b.xv, c.lengths_host, pl.N, stream, ran, c.tail, pl.env.num_ride ? num_rode : nullptr, pl.xgather);
-  if (pl.form == 1) return den_persist_launch(g, p, c.b.xv, c.lengths_host, pl.N, stream, ran);
   *ran = true;
   const DenParams* pb = slot.params;
   const StepCounter* cnt = slot.counter;
@@ -1749,7 +1747,7 @@ static int den_recursions(const DenCall& c, const DenPlan& pl, const DenParams& 
 }
 
 // Phase 3: log-probability, consistency check, scales and occupancies from what the recursions of `pl` left (state-x: one
-// launch, den_tail1, unless the plan or the first persistent form rules it out), and the deferred numerator -- in the
+// launch, den_tail1, unless the plan rules it out), and the deferred numerator -- in the
 // occupancy kernel's launch on the state-x family, after den_check on the general one -- unless it rode already.
 template <int NG>
 static int den_epilogue(const DenCall& c, const DenPlan& pl, const DenParams& p, bool num_rode) {
@@ -1766,7 +1764,7 @@ static int den_epilogue(const DenCall& c, const DenPlan& pl, const DenParams& p,
 #ifdef PK2_DEN_PROFILE
   hipLaunchKernelGGL(den_prof_print, dim3(1), dim3(1), 0, stream, Tmax);
 #endif
-  if (pl.tail_mergeable && pl.form != 1) {
+  if (pl.tail_mergeable) {
     DenTailCheck ck{};      // (the persistent launch's check as a phase of the kernel)
     if (pl.form == 2 && !den_persist2_tail_check(stream, &ck)) ck = DenTailCheck{};
     if (ck.ctl && pl.env.test_fail) ck.ntasks = -1;      // (test hook: as if the persistent launch had given up)
@@ -1776,7 +1774,6 @@ static int den_epilogue(const DenCall& c, const DenPlan& pl, const DenParams& p,
     hipLaunchKernelGGL(den_csum<NG>, dim3(Tmax + 1, G), dim3(256), 0, stream, p, b.csum);
     hipLaunchKernelGGL(den_finalize<NG>, dim3(G, NG), dim3(256), 0, stream, p, b.den_lp);
     if (pl.form == 2) den_persist2_check_launch(b.den_lp, pl.N, stream);
-    else if (pl.form == 1) den_persist_check_launch(b.den_lp, pl.N, stream);
     hipLaunchKernelGGL(den_scales<NG>, dim3(G, NG), dim3(256), 0, stream, p, b.csum, b.kscale, b.check);
   }
   const size_t row_lds = (size_t)g->P * NG * sizeof(float);
@@ -1828,7 +1825,8 @@ int den_compute(pk2_den_graph* g, const float* logits, int64_t seq_stride, int64
   int rc = den_upload(g);
   if (rc) return rc;
   if (pl.rc) {
-    set_error("den graph: num_pdfs %d too large for the LDS-staged kernel", g->P);
+    if (pl.rc == PK2_ERR_INVALID) set_error("PK2_DEN_PERSIST=1 names the first persistent denominator kernel, which has been removed: use 0, 2 or leave it unset");
+    else set_error("den graph: num_pdfs %d too large for the LDS-staged kernel", g->P);
     return pl.rc;
   }
   const DenCall c{g, logits, seq_stride, frame_stride, lengths_host, b, leaky, stream, tail};
@@ -1880,8 +1878,8 @@ extern "C" int32_t pk2_den_graph_path(const pk2_den_graph* g, int32_t num_seqs) 
   return !pl.sx ? 0 : (pl.form != 0 ? 2 : 1);
 }
 
-// Form of the persistent recursion kernel: 0 = none (frame kernels), 1 = den_persist_kernel (everything resident),
-// 2 = den_persist2_kernel (chunked table, two resident passes, streamed overflow).
+// Form of the persistent recursion kernel: 0 = none (frame kernels), 2 = den_persist2_kernel (chunked table, two resident
+// passes, streamed overflow); 1 is no longer returned.
 extern "C" int32_t pk2_den_graph_persist_form(const pk2_den_graph* g, int32_t num_seqs) {
   return g ? den_plan(g, num_seqs, 1).form : -1;
 }

@@ -1,8 +1,9 @@
-// Persistent denominator recursion, second form: no capacity cliff, and half of the table copy under the arcs (gfx950).
+// Persistent denominator recursion: no capacity cliff, and half of the table copy under the arcs (gfx950).
 //
-// chain_den_persist.hip keeps ALL arcs of a recursion in registers and the WHOLE state vector in LDS, which bounds the
-// graphs it takes (~1.05 M arc slots, ~36 k states) -- one arc more and a call fell to the launch-per-frame kernels, 2.2x
-// slower.  Same recursion per XCD, same exchange through the XCD's L2 here, but a frame's row sums are built from PASSES:
+// Its predecessor (the first persistent kernel; in git history) kept ALL arcs of a recursion in registers and the
+// WHOLE state vector in LDS, which bounded the graphs it took (~1.05 M arc slots, ~36 k states) -- one arc more and a call
+// fell to the launch-per-frame kernels, 2.2x slower.  One recursion per XCD and the exchange through the XCD's L2 are its
+// design; a frame's row sums are built from PASSES:
 //  * the state vector is cut into table chunks (chain_internal.h: HostPersist2).  A vector that fits LDS has two, back to
 //    back: chunk 0 is copied (LDS-DMA) when the frame's words are valid; pass A -- 32 register slots per thread, arcs that
 //    gather from chunk 0 -- runs on it while the copy of chunk 1 is issued FROM INSIDE the pass, one instruction behind every
@@ -13,12 +14,12 @@
 //    again in every frame from the XCD's L2 in pieces of 8 slots per thread, the next piece on its way while one is summed.
 //    A graph a little too large costs a few pieces per frame, not a fall to another kernel family;
 //  * every pass sums complete rows in a lane / finishes rows crossing lanes by a segmented wave scan / leaves the wave's
-//    open tail as a carry, exactly as den_persist_kernel does for its single list; pass A and pass B store into their own
+//    open tail as a carry; pass A and pass B store into their own
 //    compact LDS row arrays (one plain store per row that has an arc in the list), streamed segments add into a row-indexed
 //    one, the row epilogue adds up the arrays and the carries of all segments.
 // Everything else -- teams by arrival order per XCD, the task queue, NaN-sentinel words, one exchange per frame in both
-// directions, history stores after the words other workgroups wait for, the 1 s poll timeout -- is chain_den_persist.hip's
-// (den_persist_dev.h).  Replaces the same DenominatorComputation (reference ops/ops.py:265, bin/train_chain.py:202).
+// directions, history stores after the words other workgroups wait for, the 1 s poll timeout -- is in den_persist_dev.h.
+// Replaces the same DenominatorComputation (reference ops/ops.py:265, bin/train_chain.py:202).
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -30,12 +31,6 @@
 #include "den_persist_dev.h"
 
 namespace pk2 {
-
-#if PK2_DP_LOADMODE == 0
-#define PK2_DMA_SC " sc1"
-#else
-#define PK2_DMA_SC ""
-#endif
 
 struct DenPersist2Params {
   DenParams d;
@@ -83,8 +78,7 @@ struct Lds2 {
   float* tot;      // [4]
   float* wcarry;   // [kSegs * kPW] open tail of wave w in segment s
   int* wcrow;      // [kSegs * kPW] the rank-local row it belongs to (-1: none)
-  int* abort;      // + rank, team, xcd, task; [8] = ranks whose words have been seen valid in the poll under way
-  uint32_t* need;  // [kP2NeedRows] ranks whose slices a 1 KB row of chunk 0 holds
+  int* abort;      // + rank, team, xcd, task
 };
 __device__ __forceinline__ Lds2 carve_lds2(int tfloats, int cap, int arrays) {
   Lds2 L;
@@ -94,7 +88,6 @@ __device__ __forceinline__ Lds2 carve_lds2(int tfloats, int cap, int arrays) {
   L.pdfv = L.mapB + cap; L.pdfl = L.pdfv + cap;
   L.red = L.aux + (arrays - 5) * cap; L.tot = L.red + 2 * kPW; L.wcarry = L.tot + 4;      // (without the pdfs: 7 arrays)
   L.wcrow = reinterpret_cast<int*>(L.wcarry + kSegs * kPW); L.abort = L.wcrow + kSegs * kPW;
-  L.need = reinterpret_cast<uint32_t*>(L.abort + 16);
   return L;
 }
 
@@ -102,13 +95,10 @@ __device__ __forceinline__ Lds2 carve_lds2(int tfloats, int cap, int arrays) {
 __device__ __forceinline__ void lds_only_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // Loads / stores of data touched once per call (x of the frames, the alpha / beta history): non-temporal in the kernels
-// WITHOUT streamed pieces (round 5; -DPK2_DP2_NT=0 for plain ones).  Measured (profiles/r05_den_stream.txt): the bench graph
-// 7.24 -> 7.04 us per frame -- the once-only lines no longer displace the state vectors the 32 ranks copy in every frame
-// from the XCD's L2; the streaming kernels got SLOWER with them (S = 30 k, 1.5 M arcs: 11.2 -> 12.7 us; the stores then go
-// out to memory at once, over the fabric the pieces come in by), so they keep plain accesses.
-#ifndef PK2_DP2_NT
-#define PK2_DP2_NT 1
-#endif
+// WITHOUT streamed pieces (NT = !STREAM).  Measured (profiles/r05_den_stream.txt): the bench graph 7.24 -> 7.04 us per frame
+// -- the once-only lines no longer displace the state vectors the 32 ranks copy in every frame from the XCD's L2; the
+// streaming kernels got SLOWER with them (S = 30 k, 1.5 M arcs: 11.2 -> 12.7 us; the stores then go out to memory at once,
+// over the fabric the pieces come in by), so they keep plain accesses.  Loads and stores apart: profiles/r06_den_nt.txt.
 // The history stores of a frame (alpha / beta-hat for the parallel passes: nobody in this kernel waits for them) follow the
 // publication of the rank's slice -- ahead of the next frame's poll, whose first answer (vmcnt counts in order) comes back
 // behind their acknowledgements.  Round 5, measured and left off (-DPK2_DP2_LATE_HISTORY=1): the stores leaving from the
@@ -116,6 +106,8 @@ __device__ __forceinline__ void lds_only_barrier() { asm volatile("s_waitcnt lgk
 // -- 7.16 us per frame against 7.07 on the bench graph, 5.10 against 5.03 at S = 10 k, two rounds each on one box
 // (profiles/r05_den_stream.txt): the poll's 0.6 us behind the stores is time the rank would spend waiting for the slowest
 // rank's words anyway, and the stores then compete with the x prefetch and pass B's row-end traffic.
+// (The switch is still here because the staging lambdas capture `history` through it: without that capture the streaming
+// kernels come out with another register allocation, and a change of their instructions wants a measurement of its own.)
 #ifndef PK2_DP2_LATE_HISTORY
 #define PK2_DP2_LATE_HISTORY 0
 #endif
@@ -123,21 +115,14 @@ __device__ __forceinline__ void lds_only_barrier() { asm volatile("s_waitcnt lgk
 #define PK2_DP2_LATE_STREAM 1          // ... in the kernels with streamed pieces too
 #endif
 template <bool STREAM> constexpr bool kLateHistory = PK2_DP2_LATE_HISTORY && (!STREAM || PK2_DP2_LATE_STREAM);
-// (round 6, VERDICT r5 #2c: loads and stores switchable apart -- -DPK2_DP2_NT_LOAD=0 / -DPK2_DP2_NT_STORE=0)
-#ifndef PK2_DP2_NT_LOAD
-#define PK2_DP2_NT_LOAD PK2_DP2_NT
-#endif
-#ifndef PK2_DP2_NT_STORE
-#define PK2_DP2_NT_STORE PK2_DP2_NT
-#endif
 template <bool NT>
 __device__ __forceinline__ float once_load(cgfloat* p) {
-  if constexpr (NT && PK2_DP2_NT_LOAD) return __builtin_nontemporal_load(p);
+  if constexpr (NT) return __builtin_nontemporal_load(p);
   else return *p;
 }
 template <bool NT>
 __device__ __forceinline__ void once_store(gfloat* p, float v) {
-  if constexpr (NT && PK2_DP2_NT_STORE) __builtin_nontemporal_store(v, p);
+  if constexpr (NT) __builtin_nontemporal_store(v, p);
   else *p = v;
 }
 
@@ -177,27 +162,19 @@ __device__ __forceinline__ void wait_vm(int n) {
 // LDS-DMA of table chunk c of the vector at `src` into its LDS buffer: 1 KB rows dealt to the waves round robin; every wave
 // issues the SAME number of instructions (a wave without a row of its own copies the last row again), which is returned: the
 // count a later s_waitcnt may leave in flight.
-// Round 5, measured and left off: the ranks of a team copy the SAME vector at the same time, starting at the same row --
-// would they be faster if rank r started `rank * rows / kPR` rows into the chunk and wrapped around, so that the 32 CUs ask
-// 32 different L2 channels at any moment (-DPK2_DP2_ROTATE=1)?  No: 7.30 us per frame against 7.22 (same job, two runs
-// each, profiles/r05_den_ab.txt).  Many CUs reading one line at about the same time is what an XCD's L2 serves best; the
-// copy rate of ~55 KB/us per CU is the CU's own limit (1 KB LDS-DMA instructions in flight x L2 latency), not a channel's.
-#ifndef PK2_DP2_ROTATE
-#define PK2_DP2_ROTATE 0
-#endif
-__device__ __forceinline__ int dma_rot(int rank, int rows) { return PK2_DP2_ROTATE ? (rank * rows) / kPR : 0; }
-__device__ __forceinline__ int dma_chunk(cgfloat* src, CDev2& o, int c, float* table, int rank) {
+// (Round 5, measured and dropped: every rank starting rank * rows / kPR rows into the chunk, so that the 32 CUs ask 32 different
+// L2 channels at any moment, was no faster -- 7.30 against 7.22 us per frame, profiles/r05_den_ab.txt.  Many CUs reading one
+// line at about the same time is what an XCD's L2 serves best; the copy rate of ~55 KB/us per CU is the CU's own limit.)
+__device__ __forceinline__ int dma_chunk(cgfloat* src, CDev2& o, int c, float* table) {
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int b = o.cbeg[c], e = o.cbeg[c + 1];
   const int rows = (e - b + 255) >> 8;
   const int n = (rows + kPW - 1) / kPW;
   const int e4 = (e + 3) & ~3;
-  const int rot = dma_rot(rank, rows);
   float* dst = table + o.lds_off[c];
   for (int k = 0; k < n; ++k) {
     int row = w + k * kPW;
     row = row < rows ? row : rows - 1;
-    row += rot; row = row >= rows ? row - rows : row;
     const int off = row << 8;
     if (b + off + lane * 4 < e4) dma256(src + b + off + lane * 4, dst + off);
   }
@@ -223,12 +200,10 @@ struct DmaPlan {
   uint32_t off4[8];  // byte offset of that row from the first row of chunk 1
   uint32_t dst;      // LDS byte address of row 0 of chunk 1
   int rows, efl, w;  // rows of the chunk; floats from its first to the (granule-rounded) end of the vector; wave
-  int rot;           // first row of this rank (dma_rot)
   uint32_t lane16;   // lane * 16: the per-lane part of the address
   __device__ __forceinline__ void place(int j, uint64_t* mask_out, uint32_t* off4_out) const {
     int row = w + j * kPW;                    // (every wave copies ceil(rows / kPW) rows, the last one again if it has
     row = row < rows ? row : rows - 1;        //  none of its own -- the counts stay equal across the waves)
-    row += rot; row = row >= rows ? row - rows : row;
     const int off = row << 8;
     int n = (efl - off + 3) >> 2;             // lanes (16 bytes each) inside the vector
     n = j * kPW < rows ? n : 0;
@@ -236,12 +211,11 @@ struct DmaPlan {
     *mask_out = n >= 64 ? ~0ull : ((1ull << n) - 1ull);
     *off4_out = (uint32_t)off * 4u;
   }
-  __device__ __forceinline__ void init(CDev2& o, const float* table, int rank) {
+  __device__ __forceinline__ void init(CDev2& o, const float* table) {
     const int b1 = o.cbeg[1], e1 = o.cbeg[2];
     dst = (uint32_t)__builtin_amdgcn_readfirstlane((int)lds_addr(table + o.lds_off[1]));
     rows = (e1 - b1 + 255) >> 8; efl = ((e1 + 3) & ~3) - b1; w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     lane16 = (threadIdx.x & 63u) * 16u;
-    rot = dma_rot(rank, rows);
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       place(j, &mask[j], &off4[j]);
@@ -258,7 +232,7 @@ __device__ __forceinline__ void dma_issue(uint64_t mask, uint32_t m0v, uint32_t 
   // parity A/B of this statement.)
   uint64_t saved;
   asm volatile("s_mov_b64 %0, exec\n\ts_mov_b64 exec, %1\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
-               "global_load_lds_dwordx4 %3, %4" PK2_DMA_SC "\n\ts_mov_b64 exec, %0"
+               "global_load_lds_dwordx4 %3, %4 sc1\n\ts_mov_b64 exec, %0"
                : "=&s"(saved) : "s"(mask), "s"(m0v), "v"(lane16), "s"(g) : "memory");
 }
 struct Chunk1Dma {
@@ -280,85 +254,10 @@ struct Chunk1Dma {
     dma_issue(mask, pl->dst + off4, pl->lane16, src + off4);
   }
 };
-// Round 5, measured and left off (-DPK2_DP2_POLLCOPY=1): the copy of chunk 0 FOLLOWING the poll.  The frame waits until the
-// words of all 32 ranks are valid and only then starts copying the vector -- 0.95 us of exposed copy behind ~0.7 us of poll,
-// although a rank's word says that ITS slice is in L2.  Here wave 0 publishes, in an LDS word, the ranks it has seen valid so
-// far, and waves 1..7 copy the 1 KB rows of chunk 0 (dealt to them round robin) as soon as the ranks whose slices a row holds
-// (L.need, formed once per task from the ranks' slice bounds) are all there.  Parity-green -- and no faster: 7.27 us per frame
-// against 7.20 (same job, two runs each; a first version whose copy loop read its need masks from LDS row by row: 8.2).
-// The 0.7 us of the poll are the PATH of a poll (own stores acknowledged, one L2 round trip), not waiting for a slow rank:
-// the ranks of a team arrive within ~0.1 us of each other, so there is nothing for the copy to hide under.
-template <typename SLICE>
-__device__ __forceinline__ void need_masks(const Lds2& L, CDev2& o, SLICE slice_begin) {      // slice_begin(r): first table index rank r publishes
-  const int b = o.cbeg[0], e = o.cbeg[1];
-  const int rows = (e - b + 255) >> 8;
-  for (int j = threadIdx.x; j < rows && j < kP2NeedRows; j += kPT) {
-    const int lo = b + (j << 8), hi = min(lo + 256, e);
-    uint32_t m = 0;
-    for (int r = 0; r < kPR; ++r)
-      if (slice_begin(r) < hi && slice_begin(r + 1) > lo) m |= 1u << r;
-    L.need[j] = m;
-  }
-  if (threadIdx.x == 0) L.abort[8] = 0;
-}
-// Wave 0: poll_words' loop, publishing its progress; waves 1..kPW-1: the copies.  Ends like poll_words (L.tot, L.abort) with
-// every row of chunk 0 issued; the caller's barrier and wait_vm(0) follow.  Returns false when chunk 0 has more rows than
-// L.need holds (the caller copies it the old way).
-__device__ __forceinline__ bool poll_and_copy0(cgfloat* ps, int nwords, Spin& spin, const Lds2& L, cgfloat* src, CDev2& o) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int b = o.cbeg[0], e = o.cbeg[1];
-  const int rows = (e - b + 255) >> 8;
-  volatile uint32_t* prog = reinterpret_cast<volatile uint32_t*>(L.abort + 8);
-  if (rows > kP2NeedRows) { poll_words(ps, 0, nwords, spin, L); return false; }
-  if (w == 0) {
-    const bool mine = (lane >> 5) < nwords;
-    cgfloat* wsrc = ps + (lane & (kPR - 1)) * kPWords + (lane >> 5);
-    float pv = mine ? ld_agent(wsrc) : 0.f;
-    bool ok = true;
-    for (;;) {
-      const unsigned long long bad = __ballot(mine && is_sentinel(pv));
-      // a rank is there when all its words are (backward: two)
-      const uint32_t have = ~((uint32_t)bad | (uint32_t)(bad >> 32));
-      if (lane == 0) *prog = have;
-      if (bad == 0ull) break;
-      if (spin.expired()) { ok = false; break; }
-      if (mine && is_sentinel(pv)) pv = ld_agent(wsrc);
-    }
-    if (!ok) { pv = 0.f; if (lane == 0) { *L.abort = 1; *prog = 0xFFFFFFFFu; } }
-    const float a = wave_sum_dpp(lane < kPR ? pv : 0.f), bsum = wave_sum_dpp(lane < kPR ? 0.f : pv);
-    if (lane == 0) { L.tot[0] = a; L.tot[1] = bsum; }
-  } else {
-    // this wave's rows: w-1, w-1 + (kPW-1), ...: lane k looks after row k of them (its need mask in a register for the task
-    // would be better still; an LDS read per poll sweep is what it costs here), one ballot says which are ready, and the
-    // ready ones are issued by scalar code (dma_issue: exec mask + m0 + scalar base, as the in-pass copy)
-    const int w1 = __builtin_amdgcn_readfirstlane(w - 1);        // (wave-uniform by construction: scalar registers below)
-    const int nmine = (rows - w1 + (kPW - 2)) / (kPW - 1);
-    const int myrow = w1 + lane * (kPW - 1);
-    const uint32_t myneed = lane < nmine ? L.need[myrow] : 0xFFFFFFFFu;
-    const int efl = ((e + 3) & ~3) - b;                 // floats from the chunk's first to the granule-rounded end
-    const uint32_t dst0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)lds_addr(L.table + o.lds_off[0]));
-    const uint64_t sb = (uint64_t)(src + b);
-    const uint64_t src0 = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(sb >> 32)) << 32) |
-                          (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)sb);
-    const uint32_t lane16 = (uint32_t)lane * 16u;
-    uint64_t pend = nmine >= 64 ? ~0ull : ((1ull << (nmine > 0 ? nmine : 0)) - 1ull);
-    while (pend) {
-      const uint32_t have = *prog;
-      uint64_t ready = __ballot((myneed & ~have) == 0u) & pend;
-      pend &= ~ready;
-      while (ready) {
-        const int k = __builtin_ctzll(ready);
-        ready &= ready - 1;
-        const int off = (w1 + k * (kPW - 1)) << 8;
-        int nl = (efl - off + 3) >> 2;                   // lanes (16 bytes each) inside the vector
-        nl = nl < 0 ? 0 : nl;
-        const uint64_t mask = nl >= 64 ? ~0ull : ((1ull << nl) - 1ull);
-        dma_issue(mask, dst0 + (uint32_t)off * 4u, lane16, src0 + (uint64_t)(uint32_t)off * 4u);
-      }
-    }
-  }
-  return true;
-}
+// (Round 5, measured and dropped: the copy of chunk 0 FOLLOWING the poll -- waves 1..7 copying the 1 KB rows whose ranks'
+// words wave 0 had already seen valid -- was parity-green and no faster, 7.27 against 7.20 us per frame
+// (profiles/r05_den_ab.txt): the 0.7 us of the poll are the PATH of a poll (own stores acknowledged, one L2 round trip), not
+// waiting for a slow rank: the ranks of a team arrive within ~0.1 us of each other, so there is nothing to hide the copy under.)
 
 struct NoDma { __device__ __forceinline__ void operator()(int) const {} };
 
@@ -515,28 +414,8 @@ __device__ __forceinline__ void pass_rows_any(int estep, const float (&prob)[kPK
 typedef float __attribute__((ext_vector_type(4))) f32x4;
 typedef uint32_t __attribute__((ext_vector_type(4))) u32x4v;
 struct Piece { f32x4 p0, p1; u32x4v ix; uint32_t ends; };
-#ifndef PK2_ST_SADDR
-#define PK2_ST_SADDR 0
-#endif
-#ifndef PK2_ST_OPAQUE
-#define PK2_ST_OPAQUE 1
-#endif
-#ifndef PK2_ST_PRIME_LATE
-#define PK2_ST_PRIME_LATE 0
-#endif
 __device__ __forceinline__ void piece_load(CDev2& o, int piece, Piece& q) {
   static_assert(kSP == 8, "a piece is two float4 of probabilities and one uint4 of packed offsets per thread");
-#if PK2_ST_SADDR
-  // uniform base (SGPR pair) + one 32-bit byte offset per thread
-  const uint32_t e4 = ((uint32_t)piece * kPT + threadIdx.x) * 4u;           // byte offset of the thread's row-end word
-  typedef __attribute__((address_space(1))) const char gchar;
-  const __attribute__((address_space(1))) f32x4* sp = (const __attribute__((address_space(1))) f32x4*)((gchar*)o.sprob + e4 * 8u);
-  const __attribute__((address_space(1))) u32x4v* si = (const __attribute__((address_space(1))) u32x4v*)((gchar*)o.sidx2 + e4 * 4u);
-  const __attribute__((address_space(1))) uint32_t* se = (const __attribute__((address_space(1))) uint32_t*)((gchar*)o.sends + e4);
-  q.p0 = sp[0]; q.p1 = sp[1];
-  q.ix = si[0];
-  q.ends = se[0];
-#else
   const size_t at = (size_t)piece * kPT + threadIdx.x;
   const __attribute__((address_space(1))) f32x4* sp = (const __attribute__((address_space(1))) f32x4*)o.sprob + at * (kSP / 4);
   const __attribute__((address_space(1))) u32x4v* si = (const __attribute__((address_space(1))) u32x4v*)o.sidx2 + at;
@@ -544,7 +423,6 @@ __device__ __forceinline__ void piece_load(CDev2& o, int piece, Piece& q) {
   q.p0 = sp[0]; q.p1 = sp[1];
   q.ix = si[0];
   q.ends = se[at];
-#endif
 }
 // Round 5: the piece's arithmetic in the form of the resident passes (gathers and waits as inline asm, a row-end place as
 // v_add_co + s_and_saveexec + one LDS instruction) -- with ds_add_f32 where a pass stores: the sums ADD to the row, and the
@@ -668,7 +546,7 @@ struct RowSpan { int nrows, uncA, ncA, uncB, ncB; };
 template <bool STREAM, typename ST, typename STAGE>
 __device__ __forceinline__ void frame_rows(CDev2& o, cgfloat* src, int rank, const RowSpan& rs, const FrameRegs& r,
                                            const DmaPlan& plan, ST& st, const Lds2& L, DpTimers& dp_, STAGE stage,
-                                           bool chunk0_issued = false, bool prime_next = false) {
+                                           bool prime_next = false) {
   const int tid = threadIdx.x;
   if constexpr (STREAM) {
     // the streamed segments add up in accS; compact rows past a truncated resident list get no store from their pass
@@ -676,7 +554,7 @@ __device__ __forceinline__ void frame_rows(CDev2& o, cgfloat* src, int rank, con
     for (int q = rs.uncA + tid; q < rs.ncA; q += kPT) L.accA[q] = 0.f;
     for (int q = rs.uncB + tid; q < rs.ncB; q += kPT) L.accB[q] = 0.f;
   }
-  if (!chunk0_issued) dma_chunk(src, o, 0, L.table, rank);      // (else: copied while the poll was under way)
+  dma_chunk(src, o, 0, L.table);
   DP_T(0);
   wait_vm(0);                            // chunk 0 has landed (this wave's part)
   lds_only_barrier();
@@ -706,14 +584,14 @@ __device__ __forceinline__ void frame_rows(CDev2& o, cgfloat* src, int rank, con
     int young = 0;
     if (pb[1] > pb[0]) young = streamed_segment(o, rank, 0, pb[0], pb[1], st, L);
     DP_T(8);
-    if (shared) { lds_only_barrier(); dma_chunk(src, o, 1, L.table, rank); young = 0; }
+    if (shared) { lds_only_barrier(); dma_chunk(src, o, 1, L.table); young = 0; }
     // chunk 1 has landed (this wave's part) -- the pieces requested behind its copy (the first ones of the next segment) stay
     // in flight through pass B: the barrier orders LDS only (a __syncthreads() would wait for vmcnt(0))
     wait_vm(kPieceLoads * (young < kPieceDepth ? young : kPieceDepth));
     stage();
     lds_only_barrier();                    // chunk 1 is complete, and buffer 0 is free
     DP_T(3);
-    if (K > 2) dma_chunk(src, o, 2, L.table, rank);
+    if (K > 2) dma_chunk(src, o, 2, L.table);
     pass_rows_any<kQ, STREAM>(o.estep, r.prob, r.addr, r.base, r.endsB, r.frowB, L.accB, L.wcarry + kPW, NoDma());
     DP_T(4);
     // (consecutive segments add to the same rows of accS: the barrier between two chunks separates them)
@@ -723,15 +601,15 @@ __device__ __forceinline__ void frame_rows(CDev2& o, cgfloat* src, int rank, con
       if (c >= K) break;
       wait_vm(0);
       __syncthreads();                     // chunk c is complete, and the buffer of chunk c-1 is free
-      if (c + 1 < K) dma_chunk(src, o, c + 1, L.table, rank);
+      if (c + 1 < K) dma_chunk(src, o, c + 1, L.table);
       if (pb[c + 1] > pb[c]) streamed_segment(o, rank, c, pb[c], pb[c + 1], st, L);
     }
     // the next frame's first pieces: requested now, into the registers the last segment has emptied -- they flow in while
     // the epilogue works on LDS (the caller's barrier orders LDS only); requested behind the publication instead, the
     // poll's answers queued behind them: +1.5 us per frame between "published" and "words valid" in the phase timers
-    if (prime_next && !PK2_ST_PRIME_LATE) stream_prime(o, st);
+    if (prime_next) stream_prime(o, st);
   } else {
-    if (shared) { lds_only_barrier(); dma_chunk(src, o, 1, L.table, rank); }
+    if (shared) { lds_only_barrier(); dma_chunk(src, o, 1, L.table); }
     wait_vm(0);
     stage();
     __syncthreads();                       // chunk 1 is complete
@@ -808,7 +686,7 @@ __device__ __noinline__ void run_fwd2(CParams2* pp_, DenPersistCtl* ctl_, DenPer
   FrameRegs fr;
   load_frame_regs<STREAM>(o, rank, fr, L.table);
   DmaPlan plan;
-  plan.init(o, L.table, rank);
+  plan.init(o, L.table);
   const int row0 = o.row_begin[rank], nrows = o.row_begin[rank + 1] - row0;
   const int g0 = o.grp_begin[rank], ngrp = o.grp_begin[rank + 1] - g0;
   RowSpan rs;
@@ -824,9 +702,6 @@ __device__ __noinline__ void run_fwd2(CParams2* pp_, DenPersistCtl* ctl_, DenPer
     for (int r = tid; r < ngrp; r += kPT) L.pdfl[r] = (short)p.loop_pdf[g0 + r];
   }
   if (tid < kSegs * kPW) L.wcrow[tid] = o.wcrow[(size_t)rank * kSegs * kPW + tid];
-#if PK2_DP2_POLLCOPY
-  need_masks(L, o, [&](int r) { return (int)o.grp_begin[r]; });        // rank r publishes the states of its groups
-#endif
   int st_lo[PSPT], st_hi[PSPT], st_o[PSPT]; float st_pl[PSPT], st_pi[PSPT]; bool st_ok[PSPT];
 #pragma unroll
   for (int i = 0; i < PSPT; ++i) {
@@ -870,7 +745,7 @@ __device__ __noinline__ void run_fwd2(CParams2* pp_, DenPersistCtl* ctl_, DenPer
       cgfloat* row = xp_g + (size_t)t * d.P;
 #pragma unroll
       for (int i = 0; i < PSPT; ++i) {
-        const int r = per_frame<STREAM && PK2_ST_OPAQUE>(tid + i * kPT);
+        const int r = per_frame<STREAM>(tid + i * kPT);
         const int pv = r < nrows ? L.pdfv[r] : -1, pl = st_ok[i] ? L.pdfl[r] : -1;
         xr[i] = r < nrows ? (pv >= 0 ? row[pv] : 1.f) : 0.f;
         xln[i] = st_ok[i] ? (pl >= 0 ? row[pl] : 1.f) : 0.f;
@@ -879,8 +754,8 @@ __device__ __noinline__ void run_fwd2(CParams2* pp_, DenPersistCtl* ctl_, DenPer
     }
 #pragma unroll
     for (int i = 0; i < PSPT; ++i) {
-      const int r = per_frame<STREAM && PK2_ST_OPAQUE>(tid + i * kPT);
-      if constexpr (STREAM && PK2_ST_OPAQUE) {
+      const int r = per_frame<STREAM>(tid + i * kPT);
+      if constexpr (STREAM) {
         xr[i] = r < nrows ? ld_uniform_base(xv_g + ((size_t)t * V + row0), r) : 0.f;
         xln[i] = st_ok[i] ? ld_uniform_base(xl_g + ((size_t)t * S + g0), r) : 0.f;
       } else {
@@ -923,22 +798,18 @@ __device__ __noinline__ void run_fwd2(CParams2* pp_, DenPersistCtl* ctl_, DenPer
     cgfloat* src;
     DP_TL(0, 0);
     DP_TLSET(0);
-    bool chunk0_issued = false;
     if (t == 0) {
       as = d.pi_sum;
       src = G(d.pi);
     } else {
       src = ring + (size_t)(t & 1) * p.rpad;
-#if PK2_DP2_POLLCOPY
-      chunk0_issued = poll_and_copy0(pring + (size_t)(t % 3) * kPR * kPWords, 1, spin, L, src, o);
-#else
       poll_words(pring + (size_t)(t % 3) * kPR * kPWords, 0, 1, spin, L);
-#endif
       __syncthreads();
       DP_TL(0, 1);
       if (*L.abort) return;
       as = L.tot[0];
-      if (tid == 0) L.abort[8] = 0;        // (every wave has left the poll: the next one starts from "nobody there")
+      if (tid == 0) L.abort[8] = 0;        // (word 8 had a reader in the dropped poll-copy experiment; the store stays so that
+                                           //  the kernel's instructions remain the measured ones: take it out with the next re-measurement)
     }
     // the word this rank will publish two frames from now must read "not yet written" by then: reset here, before the
     // copies (no store sits between them and their waits), long before the stores it has to precede
@@ -952,7 +823,7 @@ __device__ __noinline__ void run_fwd2(CParams2* pp_, DenPersistCtl* ctl_, DenPer
       }
       if (kLateHistory<STREAM> && t > 0) history(t - 1);
       if (publish) prefetch(t + 1);
-    }, chunk0_issued, publish);
+    }, publish);
     DP_TL(0, 4);
     if constexpr (STREAM) lds_only_barrier(); else __syncthreads();      // (the row sums are in LDS; a streaming frame has piece loads in flight)
     if (rank == 0 && tid == 0) G(d.asum)[f0 + t] = as;
@@ -982,7 +853,6 @@ __device__ __noinline__ void run_fwd2(CParams2* pp_, DenPersistCtl* ctl_, DenPer
     wait_stores();        // this rank's slice of frame t+1 (and the reset above) is in L2 before its partial sum says so
     block_sum2<kPW>(loc, unused, L.red);
     if (tid == 0 && publish) st_agent(word_of(pring, t + 1, rank, 0), loc);
-    if constexpr (STREAM && PK2_ST_PRIME_LATE) { if (publish) stream_prime(o, st); }
     DP_T(6);
     DP_TL(0, 6);
     hist_loc = loc;
@@ -997,7 +867,16 @@ __device__ __noinline__ void run_fwd2(CParams2* pp_, DenPersistCtl* ctl_, DenPer
   DP_FLUSH(0);
 }
 
-// btilde' recursion of sequence g, T-1 down to 0 (see chain_den_persist.hip: run_bwd for the algebra).
+// btilde' recursion of sequence g: den_beta_frame_sx<1> frame by frame, T-1 down to 0.  What a frame gathers is
+//   w[t+1][v] = x[t, pdf(v)] * betahat[t+1, state(v)],  betahat[t+1, s] = btilde'[t+1, s] / c[t+1] + leaky term of t+1,
+// and it is the PRODUCER of btilde'[t+1, .] that scales its slice (it needs x only for its own ~V/32 virtual states; a
+// consumer-side transform would have every workgroup read all of x[t, .]).  The scaling needs the frame's sums over ALL
+// states, lB[t] = sum_s pi[s] btilde'[t, s] and lU[t] = sum_s btilde'[t, s] -- which would cost a second exchange per frame
+// (partial sums out, totals back, only then the slices).  But btilde'[t, .] is linear in the vector the frame gathers:
+//   lB[t] = sum_v w[t+1][v] * (sum of pi[src] * prob over the arcs entering v)  +  sum_s pi[s] loop_s x_loop[t, s] betahat[t+1, s]
+// (lU alike without pi), and the per-virtual-state weights are constants of the graph (the forward layout's row_leak /
+// row_psum).  So the producer of w[t+1] publishes, WITH its slice, its share of the sums frame t is going to compute: a
+// frame knows c[t] before its first arc, scales its rows as soon as they are summed, and one exchange per frame is left.
 template <bool STREAM, int PSPT>
 __device__ __noinline__ void run_bwd2(CParams2* pp_, DenPersistCtl* ctl_, DenPersistCtl::Team* team_,
                                       unsigned* nbar, int g_, int T_, int rank_, float* ring_, float* pring_) {
@@ -1015,7 +894,7 @@ __device__ __noinline__ void run_bwd2(CParams2* pp_, DenPersistCtl* ctl_, DenPer
   FrameRegs fr;
   load_frame_regs<STREAM>(o, rank, fr, L.table);
   DmaPlan plan;
-  plan.init(o, L.table, rank);
+  plan.init(o, L.table);
   const int row0 = o.row_begin[rank], nrows = o.row_begin[rank + 1] - row0;
   const int vfirst = d.voff[row0], nvirt = d.voff[row0 + nrows] - vfirst;     // own virtual states: a contiguous range
   RowSpan rs;
@@ -1025,9 +904,6 @@ __device__ __noinline__ void run_bwd2(CParams2* pp_, DenPersistCtl* ctl_, DenPer
   typename std::conditional<STREAM, StreamState, NoStream>::type st;
   if constexpr (STREAM) stream_init(o, rank, st);
   if (tid < kSegs * kPW) L.wcrow[tid] = o.wcrow[(size_t)rank * kSegs * kPW + tid];
-#if PK2_DP2_POLLCOPY
-  need_masks(L, o, [&](int r) { return (int)d.voff[o.row_begin[r]]; });      // rank r publishes the virtual states of its states
-#endif
   int st_v0[PSPT], st_v1[PSPT]; float st_pl[PSPT], st_pi[PSPT]; bool st_ok[PSPT];
 #pragma unroll
   for (int i = 0; i < PSPT; ++i) {
@@ -1070,7 +946,7 @@ __device__ __noinline__ void run_bwd2(CParams2* pp_, DenPersistCtl* ctl_, DenPer
       cgfloat* row = xp_g + (size_t)t * d.P;
 #pragma unroll
       for (int i = 0; i < PSPT; ++i) {
-        const int r = per_frame<STREAM && PK2_ST_OPAQUE>(tid + i * kPT);
+        const int r = per_frame<STREAM>(tid + i * kPT);
         const int pl = st_ok[i] ? L.pdfl[r] : -1, pv = r < nvirt ? L.pdfv[r] : -1;
         xl_next[i] = st_ok[i] ? (pl >= 0 ? row[pl] : 1.f) : 0.f;
         xw[i] = r < nvirt ? (pv >= 0 ? row[pv] : 1.f) : 0.f;
@@ -1079,8 +955,8 @@ __device__ __noinline__ void run_bwd2(CParams2* pp_, DenPersistCtl* ctl_, DenPer
     }
 #pragma unroll
     for (int i = 0; i < PSPT; ++i) {
-      const int r = per_frame<STREAM && PK2_ST_OPAQUE>(tid + i * kPT);
-      if constexpr (STREAM && PK2_ST_OPAQUE) {
+      const int r = per_frame<STREAM>(tid + i * kPT);
+      if constexpr (STREAM) {
         xl_next[i] = st_ok[i] ? ld_uniform_base(xl_g + ((size_t)t * S + row0), r) : 0.f;
         xw[i] = r < nvirt ? ld_uniform_base(xv_g + ((size_t)t * V + vfirst), r) : 0.f;
       } else {
@@ -1147,17 +1023,12 @@ __device__ __noinline__ void run_bwd2(CParams2* pp_, DenPersistCtl* ctl_, DenPer
     DP_TL(1, 0);
     DP_TLSET(1);
     cgfloat* src_t = ring + (size_t)((t + 1) & 1) * p.rpad;
-#if PK2_DP2_POLLCOPY
-    const bool chunk0_issued = poll_and_copy0(pring + (size_t)((t + 1) % 3) * kPR * kPWords, 2, spin, L, src_t, o);
-#else
-    const bool chunk0_issued = false;
     poll_words(pring + (size_t)((t + 1) % 3) * kPR * kPWords, 0, 2, spin, L);
-#endif
     __syncthreads();
     DP_TL(1, 1);
     if (*L.abort) return;
     const float lB = L.tot[0], lU = L.tot[1];        // sums of btilde'[t, .], known before it is computed
-    if (tid == 0) L.abort[8] = 0;
+    if (tid == 0) L.abort[8] = 0;          // (as in run_fwd2: no reader left)
     const bool publish = t > 0;
     // the words this rank will publish two frames from now must read "not yet written" by then: reset here, before the
     // copies, long before the stores they have to precede (the waits of emit cover it)
@@ -1166,7 +1037,7 @@ __device__ __noinline__ void run_bwd2(CParams2* pp_, DenPersistCtl* ctl_, DenPer
       if (publish) stage_x();
       if (kLateHistory<STREAM> && t + 1 < T) history(t + 1);
       if (t >= 2) prefetch(t - 2);          // (xw is free again; xl_next becomes xl_prev at the end of the frame)
-    }, chunk0_issued, publish);
+    }, publish);
     DP_TL(1, 4);
     if constexpr (STREAM) lds_only_barrier(); else __syncthreads();
     // rows are source states: btilde'[t, s] = row + peeled loop, then beta-hat[t, s] with the sums received above
@@ -1186,7 +1057,6 @@ __device__ __noinline__ void run_bwd2(CParams2* pp_, DenPersistCtl* ctl_, DenPer
     DP_T(5);
     DP_TL(1, 5);
     if (publish) emit(t);
-    if constexpr (STREAM && PK2_ST_PRIME_LATE) { if (publish) stream_prime(o, st); }
     DP_T(6);
     DP_TL(1, 6);
 #pragma unroll
@@ -1299,10 +1169,40 @@ static int den2_rpad(const pk2_den_graph* g) { return (std::max(g->S, g->V) + 25
 static int den2_tfloats(const pk2_den_graph* g) { return std::max(g->h_p2fwd.tfloats, g->h_p2bwd.tfloats); }
 
 bool den_persist2_fits(const pk2_den_graph* g) {
-  return g->h_p2fwd.ok && g->h_p2bwd.ok && g->p2_cap > 0 && den_persist2_lds_bytes(den2_tfloats(g), g->p2_cap, g->p2_rowarrays) <= kDenPersistMaxLds;
+  return g->h_p2fwd.ok && g->h_p2bwd.ok && g->p2_cap > 0 && den_persist2_lds_bytes(den2_tfloats(g), g->p2_cap, g->p2_rowarrays) <= kDenPersist2MaxLds;
 }
 
 bool den_persist2_usable(const pk2_den_graph* g) { return g_den_persist2.usable() && den_persist2_fits(g); }
+
+// Allocates what is missing; *ring_bytes = size of a ring (re)allocated by this call for `rpad` floats per slot, else 0.
+static int den_persist_scratch_alloc(DenPersistScratch& sc, size_t params_bytes, int rpad, size_t* ring_bytes) {
+  *ring_bytes = 0;
+  if (!sc.ctl) PK2_HIP(hipMalloc(reinterpret_cast<void**>(&sc.ctl), sizeof(DenPersistCtl)));
+  if (!sc.params) PK2_HIP(hipMalloc(&sc.params, params_bytes));
+  if (!sc.pring) PK2_HIP(hipMalloc(reinterpret_cast<void**>(&sc.pring), (size_t)8 * kMaxTeams * 3 * kPR * kPWords * sizeof(float)));
+  if (sc.rpad < rpad) {
+    if (sc.ring) PK2_HIP(hipFree(sc.ring));
+    sc.ring = nullptr; sc.rpad = 0;
+    const size_t bytes = (size_t)8 * kMaxTeams * 2 * rpad * sizeof(float);
+    PK2_HIP(hipMalloc(reinterpret_cast<void**>(&sc.ring), bytes));
+    sc.rpad = rpad;
+    *ring_bytes = bytes;
+  }
+  return PK2_OK;
+}
+
+// The recursions of a minibatch, longest first: task k is direction task_dir[k] (0 forward, 1 backward) of sequence
+// task_seq[k]; sequences without frames have none.  Returns their number, the rest of the arrays is zeroed.
+static int den_persist_tasks(const int32_t* lengths_host, int N, short (&task_seq)[kMaxTasks], unsigned char (&task_dir)[kMaxTasks]) {
+  std::vector<std::pair<int, int>> order;    // (-T, task id = 2 n + dir)
+  for (int n = 0; n < N; ++n)
+    if (lengths_host[n] > 0) { order.push_back({-lengths_host[n], 2 * n}); order.push_back({-lengths_host[n], 2 * n + 1}); }
+  std::sort(order.begin(), order.end());
+  const int ntasks = (int)order.size();
+  for (int k = 0; k < kMaxTasks; ++k) { task_seq[k] = 0; task_dir[k] = 0; }
+  for (int k = 0; k < ntasks; ++k) { task_seq[k] = (short)(order[k].second >> 1); task_dir[k] = (unsigned char)(order[k].second & 1); }
+  return ntasks;
+}
 
 int den_persist2_launch(pk2_den_graph* g, const DenParams& dp, const float* xv, const int32_t* lengths_host, int N,
                         hipStream_t stream, bool* ran, const NumDeferred* tail, bool* num_ran, bool xgather) {
@@ -1352,7 +1252,7 @@ int den_persist2_launch(pk2_den_graph* g, const DenParams& dp, const float* xv, 
   hipLaunchKernelGGL(den_persist2_kernel, dim3(8 * kPR), dim3(kPT), lds, stream, params, sc.ctl);
 #ifdef PK2_DP_PROFILE
   { int tot = 0; for (int n = 0; n < N; ++n) tot += lengths_host[n];
-    hipLaunchKernelGGL(dp_prof_print, dim3(1), dim3(1), 0, stream, std::max(1, tot / 4), 2); }
+    hipLaunchKernelGGL(dp_prof_print, dim3(1), dim3(1), 0, stream, std::max(1, tot / 4)); }
 #endif
   PK2_LAUNCH_CHECK();
   bool ok = false;                             // first use on this device: every recursion done, nobody timed out?

@@ -152,170 +152,10 @@ static void build_ordering(int64_t A, int num_rows, const int32_t* key, const in
   out->n_chunks = (int)out->row0.size();
 }
 
-// Persistent-kernel layout of one ordering (chain_internal.h: HostPersist).  `key` = row of an arc, `idx` = what it
-// gathers, `group_of_row` (monotone, may be null: every row its own group) = the real state a row belongs to.
+// ---- persistent layout (chain_internal.h: HostPersist2; kernel: chain_den_persist2.hip) -----------------------------------
 //  * `estep`: every row is padded with null slots to a multiple of estep slots, so a row can only end at the slots
 //    j = estep-1 (mod estep) of a thread: the kernel runs its row-end code (an exec-masked LDS store and three VALU
-//    operations) at 64/estep places per thread instead of 64.  Costs slots: the caller takes the largest step that fits.
-//  * the arcs of a row that sit in one thread are dealt to its slots so that, for every slot index j, the 32 lanes of a
-//    half wave gather from as many different LDS banks as possible (ds_read_b32: a half wave per cycle, bank = index
-//    mod 32; random indices cost ~3.5 cycles per half wave).
-static bool build_persist_step(int64_t A, int num_rows, const int32_t* key, const int32_t* idx, const float* prob,
-                               const float* piprob, const int32_t* group_of_row, int num_groups, int estep, HostPersist* out) {
-  *out = HostPersist();
-  out->estep = estep;
-  std::vector<int64_t> ptr(num_rows + 1, 0);
-  for (int64_t i = 0; i < A; ++i) ptr[key[i] + 1]++;
-  for (int r = 0; r < num_rows; ++r) ptr[r + 1] += ptr[r];
-  std::vector<int64_t> perm(A);
-  {
-    std::vector<int64_t> cur(ptr.begin(), ptr.end() - 1);
-    for (int64_t i = 0; i < A; ++i) perm[cur[key[i]]++] = i;
-  }
-  auto slots_of = [&](int r) { return (std::max<int64_t>(1, ptr[r + 1] - ptr[r]) + estep - 1) / estep * estep; };
-  // rows of each group
-  std::vector<int32_t> grow(num_groups + 1, 0);
-  if (group_of_row) {
-    for (int r = 0; r < num_rows; ++r) grow[group_of_row[r] + 1]++;
-    for (int g = 0; g < num_groups; ++g) grow[g + 1] += grow[g];
-  } else {
-    for (int g = 0; g <= num_groups; ++g) grow[g] = g;
-  }
-  if (grow[num_groups] != num_rows) return false;
-  std::vector<int64_t> gslots(num_groups, 0);
-  int64_t total = 0;
-  for (int g = 0; g < num_groups; ++g) {
-    for (int r = grow[g]; r < grow[g + 1]; ++r) gslots[g] += slots_of(r);
-    total += gslots[g];
-  }
-  // contiguous ranges of whole groups, balanced by slots
-  out->row_begin.assign(kPR + 1, num_rows);
-  out->grp_begin.assign(kPR + 1, num_groups);
-  int g = 0;
-  int64_t left = total;
-  for (int r = 0; r < kPR; ++r) {
-    out->grp_begin[r] = g; out->row_begin[r] = grow[g];
-    const int64_t target = (left + (kPR - r) - 1) / (kPR - r);
-    int64_t have = 0; int rows = 0, groups = 0;
-    while (g < num_groups) {
-      const int gr = grow[g + 1] - grow[g];
-      if (have + gslots[g] > kPSlots || rows + gr > kPMaxRows || groups + 1 > kPMaxRows) break;
-      if (have >= target) break;
-      have += gslots[g]; rows += gr; ++groups; ++g;
-    }
-    left -= have;
-    out->max_rows = std::max(out->max_rows, rows);
-    out->max_groups = std::max(out->max_groups, groups);
-  }
-  if (g < num_groups) return false;       // does not fit
-  out->arcs.assign((size_t)kPR * kPSlots, make_int2(0, 0));
-  out->ends.assign((size_t)kPR * kPT, 0ull);
-  out->first_row.assign((size_t)kPR * kPT, 0);
-  out->wcrow.assign((size_t)kPR * kPW, -1);
-  out->row_leak.assign(num_rows, 0.f);
-  out->row_psum.assign(num_rows, 0.f);
-  std::vector<int32_t> srow; std::vector<int64_t> sarc; std::vector<char> send;
-  std::vector<int32_t> sidx;              // gathered index of a slot after the bank-aware deal (nulls get one too)
-  std::vector<int32_t> load((size_t)2 * kPK * 32);
-  std::vector<int64_t> cand;
-  for (int r = 0; r < kPR; ++r) {
-    const int row0 = out->row_begin[r], row1 = out->row_begin[r + 1];
-    srow.clear(); sarc.clear(); send.clear();
-    for (int q = row0; q < row1; ++q) {
-      double leak = 0.0, psum = 0.0;
-      for (int64_t k = ptr[q]; k < ptr[q + 1]; ++k) {
-        srow.push_back(q - row0); sarc.push_back(perm[k]); send.push_back(0);
-        leak += (double)piprob[perm[k]]; psum += (double)prob[perm[k]];
-      }
-      if (ptr[q] == ptr[q + 1]) { srow.push_back(q - row0); sarc.push_back(-1); send.push_back(0); }
-      while (srow.size() % estep) { srow.push_back(q - row0); sarc.push_back(-1); send.push_back(0); }
-      send.back() = 1;
-      out->row_leak[q] = (float)leak;
-      out->row_psum[q] = (float)psum;
-    }
-    const int64_t n = (int64_t)srow.size();
-    // bank-aware deal: inside a thread, the slots of one row are interchangeable
-    sidx.assign(n, 0);
-    for (int64_t wbase = 0; wbase < n; wbase += (int64_t)64 * kPK) {
-      std::fill(load.begin(), load.end(), 0);
-      for (int lane = 0; lane < 64; ++lane) {
-        const int half = lane >> 5;
-        int64_t s = wbase + (int64_t)lane * kPK;
-        const int64_t lane_end = std::min<int64_t>(n, s + kPK);
-        while (s < lane_end) {
-          int64_t e = s;
-          while (e < lane_end && srow[e] == srow[s]) ++e;
-          cand.assign(sarc.begin() + s, sarc.begin() + e);      // arcs (and nulls, -1) of this segment
-          for (int64_t pos = s; pos < e; ++pos) {
-            const int j = (int)(pos % kPK);
-            int32_t* ld = &load[((size_t)half * kPK + j) * 32];
-            size_t best = 0; int best_load = 1 << 30;
-            for (size_t c = 0; c < cand.size(); ++c) {
-              const int l = cand[c] < 0 ? -1 : ld[idx[cand[c]] & 31];     // a null slot goes wherever it is free
-              if (l < best_load) { best_load = l; best = c; }
-            }
-            const int64_t a = cand[best];
-            cand[best] = cand.back(); cand.pop_back();
-            sarc[pos] = a;
-            if (a >= 0) {
-              sidx[pos] = idx[a];
-            } else {
-              int bank = 0;
-              for (int b2 = 1; b2 < 32; ++b2) if (ld[b2] < ld[bank]) bank = b2;
-              sidx[pos] = bank;               // any valid entry: its probability is 0
-            }
-            ld[sidx[pos] & 31]++;
-          }
-          s = e;
-        }
-      }
-    }
-    for (int tid = 0; tid < kPT; ++tid) {
-      uint64_t e = 0;
-      for (int j = 0; j < kPK; ++j) {
-        const int64_t s = (int64_t)tid * kPK + j;
-        if (s >= n) break;
-        out->arcs[((size_t)r * kPK + j) * kPT + tid] = make_int2(sidx[s], sarc[s] >= 0 ? __builtin_bit_cast(int, prob[sarc[s]]) : 0);
-        if (send[s]) e |= 1ull << j;
-      }
-      out->ends[(size_t)r * kPT + tid] = e;
-      const int64_t s0 = (int64_t)tid * kPK;
-      out->first_row[(size_t)r * kPT + tid] = s0 < n ? srow[s0] : 0;
-    }
-    for (int w = 0; w < kPW; ++w) {
-      const int64_t last = (int64_t)(w + 1) * 64 * kPK - 1;
-      if (last < n && !send[last]) out->wcrow[(size_t)r * kPW + w] = srow[last];
-    }
-  }
-  // device form: probabilities and 16-bit indices apart
-  int max_idx = 0;
-  for (const int2& a : out->arcs) max_idx = std::max(max_idx, a.x);
-  if (max_idx >= 65536) return false;
-  out->prob.resize(out->arcs.size());
-  out->idx2.assign(out->arcs.size() / 2, 0u);
-  for (int r = 0; r < kPR; ++r)
-    for (int j = 0; j < kPK; ++j)
-      for (int tid = 0; tid < kPT; ++tid) {
-        const int2 a = out->arcs[((size_t)r * kPK + j) * kPT + tid];
-        out->prob[((size_t)r * kPK + j) * kPT + tid] = __builtin_bit_cast(float, a.y);
-        out->idx2[((size_t)r * (kPK / 2) + j / 2) * kPT + tid] |= (uint32_t)a.x << (16 * (j & 1));
-      }
-  out->ok = true;
-  return true;
-}
-
-static void build_persist(int64_t A, int num_rows, const int32_t* key, const int32_t* idx, const float* prob,
-                          const float* piprob, const int32_t* group_of_row, int num_groups, HostPersist* out) {
-  const char* env = getenv("PK2_DEN_ESTEP");
-  const int forced = env ? atoi(env) : 0;
-  for (int estep : {8, 4, 2, 1}) {
-    if (forced > 0 && estep != forced) continue;
-    if (build_persist_step(A, num_rows, key, idx, prob, piprob, group_of_row, num_groups, estep, out)) return;
-  }
-  *out = HostPersist();
-}
-
-// ---- second persistent layout (chain_internal.h: HostPersist2; kernel: chain_den_persist2.hip) ----------------------------
+//    operations) at 64/estep places per thread instead of 64.  Costs slots: build_persist2 takes the cheapest step.
 // Contiguous ranges of whole groups for the kPR ranks, balanced by arcs (+1 per row: every row costs a slot in every list).
 static bool persist2_assign(int64_t A, int num_rows, const int32_t* key, const int32_t* group_of_row, int num_groups,
                             int max_rows_per_rank, HostPersist2* out, bool by_rows = false) {
@@ -432,7 +272,8 @@ static bool persist2_chunks(int64_t A, const int32_t* idx, int R, int num_rows, 
 }
 
 // Deals the arcs of a row that sit in one thread to its slots so that, slot index by slot index, the 32 lanes of a half wave
-// gather from different LDS banks (as build_persist_step).  `spt` = consecutive sorted slots per thread.
+// gather from as many different LDS banks as possible (ds_read_b32: a half wave per cycle, bank = index mod 32; random
+// indices cost ~3.5 cycles per half wave).  `spt` = consecutive sorted slots per thread.
 static void persist2_deal(int64_t n, int spt, const std::vector<int32_t>& srow, std::vector<int64_t>& sarc, const int32_t* lidx,
                           std::vector<int32_t>& sidx, int null_base, int null_span) {
   sidx.assign(n, null_base);
@@ -746,7 +587,7 @@ static bool persist2_lists(int64_t A, int num_rows, const float* prob, const flo
   return true;
 }
 
-// Both orderings of the second persistent layout.  fkey / fidx: forward ordering (rows = virtual destination states,
+// Both orderings of the persistent layout.  fkey / fidx: forward ordering (rows = virtual destination states,
 // gathering source states); bkey / bidx: backward ordering (rows = source states, gathering virtual destination states).
 static void build_persist2(pk2_den_graph* g, int64_t A2, const int32_t* arc_v, const int32_t* src2, const float* prob2,
                            const float* piprob2, const int32_t* vstate) {
@@ -777,7 +618,7 @@ static void build_persist2(pk2_den_graph* g, int64_t A2, const int32_t* arc_v, c
   const int cap = (std::max({f.max_rows, f.max_groups, b.max_rows, b.max_groups, 1}) + 3) / 4 * 4;
   // The eighth row array (pdfs: the kernel then gathers x from plain exp(logits) rows) takes `cap` floats from the table: kept
   // unless it costs either direction a table chunk (S = 55 k at 1.0 M arcs: 16.5 -> 22.8 us per frame with it).
-  auto tcap_for = [&](int arrays) { return ((int64_t)kDenPersistMaxLds / 4 - arrays * (int64_t)cap - kP2FixedFloats) / 512 * 512; };
+  auto tcap_for = [&](int arrays) { return ((int64_t)kDenPersist2MaxLds / 4 - arrays * (int64_t)cap - kP2FixedFloats) / 512 * 512; };
   g->p2_rowarrays = kP2RowArrays;
   if (tcap_for(kP2RowArrays) >= 512) {
     for (int which = 0; which < 2; ++which) {
@@ -963,15 +804,7 @@ static int build_graph_ordered(int32_t S, int32_t P, int64_t A, const int32_t* s
                    false, true, true);
     build_ordering(A2, S, src2.data(), arc_v.data(), pdf2.data(), prob2.data(), piprob2.data(), &g->h_bwdv, nullptr, false,
                    true, true);
-    build_persist(A2, g->V, arc_v.data(), src2.data(), prob2.data(), piprob2.data(), vstate.data(), S, &g->h_pfwd);
-    build_persist(A2, S, src2.data(), arc_v.data(), prob2.data(), piprob2.data(), nullptr, S, &g->h_pbwd);
     build_persist2(g, A2, arc_v.data(), src2.data(), prob2.data(), piprob2.data(), vstate.data());
-    if (g->h_pbwd.ok) {     // the backward workgroups also stage x for their own virtual states: max_groups = how many
-      g->h_pbwd.max_groups = 0;
-      for (int r = 0; r < kPR; ++r)
-        g->h_pbwd.max_groups = std::max(g->h_pbwd.max_groups, g->voff[g->h_pbwd.row_begin[r + 1]] - g->voff[g->h_pbwd.row_begin[r]]);
-      if (g->h_pbwd.max_groups > kPMaxRows) g->h_pbwd.ok = false;
-    }
     g->po_off.assign(P + 1, 0);
     for (int o = 0; o < g->Vo; ++o) if (g->opdf[o] >= 0) g->po_off[g->opdf[o] + 1]++;
     for (int p = 0; p < P; ++p) g->po_off[p + 1] += g->po_off[p];
@@ -983,10 +816,10 @@ static int build_graph_ordered(int32_t S, int32_t P, int64_t A, const int32_t* s
   return PK2_OK;
 }
 
-// State numbering: the persistent kernels gather from LDS and only need the rows of their 32 workgroups balanced, which the
+// State numbering: the persistent kernel gathers from LDS and only needs the rows of its 32 workgroups balanced, which the
 // caller's numbering gives for any graph without a degree trend along the state ids (the in-degree order does the opposite:
 // its last workgroups would own thousands of rows); the launch-per-frame kernels gather from L2 and gain from the in-degree
-// order.  So: the caller's numbering when a persistent layout fits with it, else the in-degree order.
+// order.  So: the caller's numbering when the persistent layout fits with it, else the in-degree order.
 // PK2_DEN_ORDER = none | indegree | degree forces one.
 static int build_graph(int32_t S, int32_t P, int64_t A, const int32_t* src_in, const int32_t* dst_in,
                        const int32_t* pdf, const float* prob, int32_t start, pk2_den_graph** out) {
@@ -994,7 +827,7 @@ static int build_graph(int32_t S, int32_t P, int64_t A, const int32_t* src_in, c
   if (env) return build_graph_ordered(S, P, A, src_in, dst_in, pdf, prob, start, env, out);
   int rc = build_graph_ordered(S, P, A, src_in, dst_in, pdf, prob, start, "none", out);
   if (rc) return rc;
-  if (den_persist_fits(*out) || den_persist2_fits(*out)) return PK2_OK;
+  if (den_persist2_fits(*out)) return PK2_OK;
   delete *out;
   *out = nullptr;
   return build_graph_ordered(S, P, A, src_in, dst_in, pdf, prob, start, "indegree", out);
@@ -1007,22 +840,6 @@ static int upload_vec(pk2_den_graph* g, const std::vector<T>& v, const T** dptr)
   g->allocs.push_back(d);
   if (!v.empty()) PK2_HIP(hipMemcpy(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
   *dptr = static_cast<const T*>(d);
-  return PK2_OK;
-}
-
-static int upload_persist(pk2_den_graph* g, const HostPersist& h, DevPersist* d) {
-  if (!h.ok) return PK2_OK;
-  int rc;
-  if ((rc = upload_vec(g, h.prob, &d->prob))) return rc;
-  if ((rc = upload_vec(g, h.idx2, &d->idx2))) return rc;
-  if ((rc = upload_vec(g, h.ends, &d->ends))) return rc;
-  if ((rc = upload_vec(g, h.first_row, &d->first_row))) return rc;
-  if ((rc = upload_vec(g, h.wcrow, &d->wcrow))) return rc;
-  if ((rc = upload_vec(g, h.row_begin, &d->row_begin))) return rc;
-  if ((rc = upload_vec(g, h.grp_begin, &d->grp_begin))) return rc;
-  if ((rc = upload_vec(g, h.row_leak, &d->row_leak))) return rc;
-  if ((rc = upload_vec(g, h.row_psum, &d->row_psum))) return rc;
-  d->max_rows = h.max_rows; d->max_groups = h.max_groups; d->estep = h.estep;
   return PK2_OK;
 }
 
@@ -1080,8 +897,6 @@ int den_upload(pk2_den_graph* g) {
   if ((rc = upload_ordering(g, g->h_gam, &g->gam))) return rc;
   if ((rc = upload_ordering(g, g->h_fwdv, &g->fwdv))) return rc;
   if ((rc = upload_ordering(g, g->h_bwdv, &g->bwdv))) return rc;
-  if ((rc = upload_persist(g, g->h_pfwd, &g->pfwd))) return rc;
-  if ((rc = upload_persist(g, g->h_pbwd, &g->pbwd))) return rc;
   if ((rc = upload_persist2(g, g->h_p2fwd, &g->p2fwd))) return rc;
   if ((rc = upload_persist2(g, g->h_p2bwd, &g->p2bwd))) return rc;
   if ((rc = upload_vec(g, g->voff, &g->d_voff))) return rc;
@@ -1217,7 +1032,7 @@ extern "C" int pk2_den_graph_debug_virtual(const pk2_den_graph* g, int which, in
   return PK2_OK;
 }
 
-// Test hook: the second persistent layout of an ordering (which: 0 forward, 1 backward).  info[32] = {ok, estep, K, R,
+// Test hook: the persistent layout of an ordering (which: 0 forward, 1 backward).  info[32] = {ok, estep, K, R,
 // tfloats, max_rows, max_groups, pieces, cap, rows, cbeg[0..kMaxChunks] at 10.., row arrays of the LDS layout (8: with the pdfs
 // the x gather needs, 7: without) at 19, lds_off[0..kMaxChunks-1] at 20.., kPR, kPT, kPK, kPW, kSP, kSegs at 26..}; the arrays (may be null) are sized from it (chain_internal.h: HostPersist2).
 extern "C" int pk2_den_graph_debug_persist2(const pk2_den_graph* g, int which, int32_t* info, float* prob, uint32_t* idx2,
@@ -1246,29 +1061,5 @@ extern "C" int pk2_den_graph_debug_persist2(const pk2_den_graph* g, int which, i
   cp(wcrow, h.wcrow.data(), h.wcrow.size() * 4); cp(row_begin, h.row_begin.data(), h.row_begin.size() * 4);
   cp(grp_begin, h.grp_begin.data(), h.grp_begin.size() * 4); cp(row_leak, h.row_leak.data(), h.row_leak.size() * 4);
   cp(row_psum, h.row_psum.data(), h.row_psum.size() * 4);
-  return PK2_OK;
-}
-
-// Test hook: the persistent kernel's layout of an ordering (which: 0 = forward, rows = virtual destination states;
-// 1 = backward, rows = source states).  info = {ok, max_rows, max_groups, workgroups, threads, slots per thread, waves,
-// rows, estep}; the arrays (may be null) are sized from it: arcs [workgroups * slots * threads][2], ends / first_row
-// [workgroups * threads], wcrow [workgroups * waves], row_begin / grp_begin [workgroups + 1], row_leak / row_psum [rows].
-extern "C" int pk2_den_graph_debug_persist(const pk2_den_graph* g, int which, int32_t* info, int32_t* arcs_out,
-                                           uint64_t* ends_out, int32_t* first_row_out, int32_t* wcrow_out,
-                                           int32_t* row_begin_out, int32_t* grp_begin_out, float* row_leak_out,
-                                           float* row_psum_out) {
-  PK2_REQUIRE(g && (which == 0 || which == 1) && info, "den graph debug: bad arguments");
-  const HostPersist& h = which == 0 ? g->h_pfwd : g->h_pbwd;
-  info[0] = h.ok ? 1 : 0; info[1] = h.max_rows; info[2] = h.max_groups;
-  info[3] = kPR; info[4] = kPT; info[5] = kPK; info[6] = kPW; info[7] = (int32_t)h.row_leak.size(); info[8] = h.estep;
-  if (!h.ok) return PK2_OK;
-  if (arcs_out) memcpy(arcs_out, h.arcs.data(), h.arcs.size() * sizeof(int2));
-  if (ends_out) memcpy(ends_out, h.ends.data(), h.ends.size() * sizeof(uint64_t));
-  if (first_row_out) memcpy(first_row_out, h.first_row.data(), h.first_row.size() * sizeof(int32_t));
-  if (wcrow_out) memcpy(wcrow_out, h.wcrow.data(), h.wcrow.size() * sizeof(int32_t));
-  if (row_begin_out) memcpy(row_begin_out, h.row_begin.data(), h.row_begin.size() * sizeof(int32_t));
-  if (grp_begin_out) memcpy(grp_begin_out, h.grp_begin.data(), h.grp_begin.size() * sizeof(int32_t));
-  if (row_leak_out) memcpy(row_leak_out, h.row_leak.data(), h.row_leak.size() * sizeof(float));
-  if (row_psum_out) memcpy(row_psum_out, h.row_psum.data(), h.row_psum.size() * sizeof(float));
   return PK2_OK;
 }

@@ -66,15 +66,10 @@ struct DevOrdering {
   int n_chunks = 0;
 };
 
-// Layout of one arc ordering for the persistent denominator kernel (chain_den_persist.hip): the rows are dealt to the
-// kPR workgroups of a team (one per CU of an XCD) in contiguous ranges of whole groups (a group = the rows of one real
-// state), every workgroup keeps its <= kPSlots arc slots in registers for the whole call:
-//   thread `tid` of rank r owns the consecutive sorted slots tid*kPK .. tid*kPK + kPK-1 of the rank's list,
-//   arcs[(r*kPK + j)*kPT + tid] = {gathered index, probability bits}; a row without arcs has one null slot; on the device
-//   the probabilities are prob[(r*kPK + j)*kPT + tid] and the indices (< 32768: the LDS table) are packed two to a word,
-//   idx2[(r*kPK/2 + j/2)*kPT + tid] = idx(j even) | idx(j odd) << 16 -- 96 registers per thread instead of 128;
-//   bit j of ends[r*kPT + tid]: a row ends after the thread's slot j; first_row = rank-local row of its slot 0;
-//   wcrow[r*kPW + w]: rank-local row still open after the last slot of wave w (-1: none) -- the wave's carry-out is its.
+// Geometry of the persistent denominator kernel (chain_den_persist2.hip): the rows of an ordering are dealt to the kPR
+// workgroups of a team (one per CU of an XCD) in contiguous ranges of whole groups (a group = the rows of one real state);
+// thread `tid` of a rank owns consecutive sorted slots of the rank's lists and keeps kPK of them in registers for the whole
+// call, the probabilities as floats and the gathered indices packed two to a word (96 registers per thread instead of 128).
 constexpr int kPR = 32;                 // workgroups of a team = CUs of an XCD
 constexpr int kPT = 512;                // threads of a workgroup: 2 waves per SIMD, 256 VGPRs each (the arcs take 128)
 constexpr int kPW = kPT / 64;
@@ -82,36 +77,8 @@ constexpr int kPK = 64;                 // arc slots per thread
 constexpr int kPSlots = kPT * kPK;      // arc slots per workgroup
 constexpr int kPSPT = 4;                // states per thread in the row epilogues
 constexpr int kPMaxRows = kPSPT * kPT;  // rows, and groups, per workgroup
-struct HostPersist {
-  bool ok = false;                 // the graph fits (slots, rows per rank)
-  int max_rows = 0, max_groups = 0;
-  int estep = 1;                   // rows end only at slots j = estep-1 (mod estep) of a thread
-  std::vector<int2> arcs;
-  std::vector<float> prob;         // device form of `arcs`
-  std::vector<uint32_t> idx2;
-  std::vector<uint64_t> ends;
-  std::vector<int32_t> first_row;
-  std::vector<int32_t> wcrow;
-  std::vector<int32_t> row_begin;  // [kPR+1] first row of a rank
-  std::vector<int32_t> grp_begin;  // [kPR+1] first group (real state) of a rank
-  std::vector<float> row_leak;     // [rows]   sum of pi[src]*prob over the arcs of a row
-  std::vector<float> row_psum;     // [rows]   sum of prob over the arcs of a row
-};
-struct DevPersist {
-  const float* prob = nullptr;
-  const uint32_t* idx2 = nullptr;
-  const uint64_t* ends = nullptr;
-  const int32_t* first_row = nullptr;
-  const int32_t* wcrow = nullptr;
-  const int32_t* row_begin = nullptr;
-  const int32_t* grp_begin = nullptr;
-  const float* row_leak = nullptr;
-  const float* row_psum = nullptr;
-  int max_rows = 0, max_groups = 0;
-  int estep = 1;
-};
 
-// Second layout of the persistent kernel (chain_den_persist2.hip): no capacity limits.
+// Layout of one arc ordering for that kernel: no capacity limits.
 //  * The frame's state vector is cut into K table CHUNKS, contiguous index ranges [cbeg[c], cbeg[c+1]) (whole 1 KB LDS-DMA
 //    rows).  A vector that fits the LDS table has two, laid out back to back: the kernel starts both DMAs at once and runs the
 //    arcs that gather from chunk 0 while chunk 1 is still arriving.  A longer vector goes through two LDS buffers of half the
@@ -192,9 +159,7 @@ struct pk2_den_graph {
   std::vector<int32_t> ooff, opdf, ovirt; // [S+1], [Vo] pdf, [Vo] first virtual state of the occupancy state's state
   std::vector<int32_t> po_off, po_occ;    // occupancy states grouped by pdf (CSR over P)
   pk2::HostOrdering h_fwdv, h_bwdv;       // rows = virtual dst gathering src | rows = src gathering virtual dst
-  pk2::HostPersist h_pfwd, h_pbwd;        // the same two orderings for the persistent kernel
-  pk2::DevPersist pfwd, pbwd;
-  pk2::HostPersist2 h_p2fwd, h_p2bwd;     // ... and for its second form (chain_den_persist2.hip: chunked table, streamed overflow)
+  pk2::HostPersist2 h_p2fwd, h_p2bwd;     // the same two orderings for the persistent kernel (chain_den_persist2.hip)
   pk2::DevPersist2 p2fwd, p2bwd;
   int p2_cap = 0;                         // LDS row buffers of that kernel (rows / groups / own virtual states of a rank)
   int p2_rowarrays = 8;                   // LDS arrays of p2_cap floats: 8 with the pdfs the x gather needs, 7 without them
@@ -220,7 +185,7 @@ namespace pk2 {
 // Run-time switches of the denominator (the PK2_DEN_* variables of INTEGRATION.md), read once per call by den_plan.
 struct DenEnv {
   int mode = -1;          // PK2_DEN_MODE: 0 = general, 1 = sx, -1 = by the graph
-  int persist = -1;       // PK2_DEN_PERSIST: 0 | 1 | 2, -1 = by the cost model
+  int persist = -1;       // PK2_DEN_PERSIST: 0 | 2, -1 = by the cost model (1, the retired first form: den_plan refuses it)
   bool merge = true;      // PK2_DEN_MERGE=0: the round-5 launches in front of and behind the recursions
   bool xgather = true;    // PK2_DEN_XGATHER=0: x from the copies expanded per virtual state
   bool num_ride = true;   // PK2_DEN_NUM_RIDE=0: the numerator never rides in the persistent launch
@@ -235,17 +200,18 @@ enum DenExpKernel { kExpPrep1, kExpRows, kExpStatesLds, kExpStates, kExpTranspos
 // What one denominator call runs ("How a call is routed"): decided once, by den_plan, and read by the
 // workspace carve, the driver and the reporting hooks.
 struct DenPlan {
-  int rc = 0;     // PK2_ERR_LIMIT: no group size fits the LDS-staged kernels (the other fields then hold NG = 1)
+  int rc = 0;     // PK2_ERR_LIMIT: no group size fits the LDS-staged kernels (the other fields then hold NG = 1);
+                  // PK2_ERR_INVALID: PK2_DEN_PERSIST=1.  den_compute reports either
   int N, Tmax;
   int NG;         // sequences interleaved per group: 1 with a persistent form, else NG_frames
   int NG_frames;  // the frame kernels' group size: the largest of 4, 2, 1 whose LDS need is at most 160 KB
   int G;          // number of groups
   bool sx;        // family: the state-x kernels (else the general, per-arc-pdf ones)
-  int form;       // recursions: 0 = a launch per frame, 1 = den_persist_kernel, 2 = den_persist2_kernel (state-x only)
+  int form;       // recursions: 0 = a launch per frame, 2 = den_persist2_kernel (state-x only; 1 was its retired predecessor)
   bool need_fill;       // some alpha / beta / gamma rows accumulate with atomics: the buffers start at zero
   bool xgather;         // form 2 gathers x by pdf from plain exp(logits) rows in the xv buffer
   bool prep_merged;     // the passes in front of the recursions are one launch (den_prep1)
-  bool tail_mergeable;  // the passes behind them may be one (den_tail1): taken unless form 1 ran
+  bool tail_mergeable;  // the passes behind them are one (den_tail1)
   bool gamma_lds;       // occupancy kernel: the frame's row staged in LDS (else gathered)
   DenExpKernel exp_kernel;
   int ncf, ncb;   // partial sums per frame the recursions leave: kPR with a persistent form, else the chunk counts

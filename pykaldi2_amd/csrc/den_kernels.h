@@ -1,4 +1,4 @@
-// Pieces of the denominator kernels shared by chain_den.hip (a launch per frame) and chain_den_persist.hip (one launch
+// Pieces of the denominator kernels shared by chain_den.hip (a launch per frame) and chain_den_persist2.hip (one launch
 // per call): the parameter block and the cross-lane segmented-scan step.
 #pragma once
 #include "chain_internal.h"
@@ -49,8 +49,8 @@ struct DenParams {
   int S, P, Tmax;
   float leaky, pi_sum;
   float wu;    // kBetaFloor * sum(pi)/S: uniform floor of the backward normaliser's weights (state-x path)
-  int brec;    // floats per beta record and sequence: 2 = {btilde', x} (frame kernels, first persistent kernel), 1 = btilde' alone
-               // (second persistent kernel, round 4: nobody reads the x halves there; the occupancy pass gathers half the lines)
+  int brec;    // floats per beta record and sequence: 2 = {btilde', x} (frame kernels), 1 = btilde' alone
+               // (persistent kernel, round 4: nobody reads the x halves there; the occupancy pass gathers half the lines)
   float beta_seed;   // test hook (PK2_DEN_DEBUG_BETA_SEED, default 1): beta'(T) = beta_seed / tot -- scales every beta, the occupancies
                      // and the alpha-beta consistency product, so that a test can drive the abandon rule on real inputs
   int debug;   // PK2_DEN_DEBUG ablation bits (profiling only): 1 = all gathers hit state 0, 2 = skip the arc loop, 4 = load half of the arc records

@@ -1,4 +1,4 @@
-// Device-side helpers shared by the two persistent denominator kernels (chain_den_persist.hip, chain_den_persist2.hip):
+// Device-side helpers of the persistent denominator kernel (chain_den_persist2.hip):
 // the team control block, agent-scope loads / stores, the exchange words and their poll, LDS-DMA, wave reductions.
 #pragma once
 #include "den_persist.h"
@@ -22,24 +22,19 @@ static __device__ long long g_dp_tl[2][kPR][8];     // wall-clock (10 ns) timeli
 #define DP_TL(dir, k) do { if (g == 0 && t == 100 && threadIdx.x == 0) g_dp_tl[dir][rank][k] = wall_clock64(); } while (0)
 #define DP_TLSET(dir) do { dp_.tl_on = (g == 0 && t == 100) ? 1 : 0; dp_.tl_dir = dir; dp_.tl_rank = rank; } while (0)
 #define DP_TLF(k) do { if (dp_.tl_on && threadIdx.x == 0) g_dp_tl[dp_.tl_dir][dp_.tl_rank][k] = wall_clock64(); } while (0)
-static __global__ void dp_prof_print(int frames, int form) {
+static __global__ void dp_prof_print(int frames) {
   for (int dir = 0; dir < 2; ++dir) {
     long long t0 = g_dp_tl[dir][0][0];
     for (int r = 0; r < kPR; ++r) t0 = g_dp_tl[dir][r][0] < t0 ? g_dp_tl[dir][r][0] : t0;
-    printf("timeline %s frame 100 (10 ns ticks after the first rank entered the frame): rank: enter, partials valid, chunk 0 ready (v1: table), after pass A (v1: after barrier), arcs done, epilogue done, published\n", dir ? "bwd" : "fwd");
+    printf("timeline %s frame 100 (10 ns ticks after the first rank entered the frame): rank: enter, partials valid, chunk 0 ready, after pass A, arcs done, epilogue done, published\n", dir ? "bwd" : "fwd");
     for (int r = 0; r < kPR; ++r)
       printf("  %2d: %lld %lld %lld %lld %lld %lld %lld\n", r, g_dp_tl[dir][r][0] - t0, g_dp_tl[dir][r][1] - t0, g_dp_tl[dir][r][2] - t0,
              g_dp_tl[dir][r][3] - t0, g_dp_tl[dir][r][4] - t0, g_dp_tl[dir][r][5] - t0, g_dp_tl[dir][r][6] - t0);
   }
   for (int dir = 0; dir < 2; ++dir) {
-    if (form == 2)
-      printf("den_persist2 %s rank 0 thread 0, shader clocks per frame over %d frames: poll + sync + stage + copies issued %llu | chunk 0 landed + barrier %llu | pass A %llu | chunk 1 landed + barrier %llu | pass B (+ streamed) %llu | barrier + epilogue %llu | wait stores + block sum + publish %llu | history + prefetch %llu | streamed segment 0 %llu | streamed segments 1.. %llu\n",
-             dir ? "bwd" : "fwd", frames, g_dp_prof[dir][0] / frames, g_dp_prof[dir][1] / frames, g_dp_prof[dir][2] / frames,
-             g_dp_prof[dir][3] / frames, g_dp_prof[dir][4] / frames, g_dp_prof[dir][5] / frames, g_dp_prof[dir][6] / frames, g_dp_prof[dir][7] / frames, g_dp_prof[dir][8] / frames, g_dp_prof[dir][9] / frames);
-    else
-      printf("den_persist %s rank 0 thread 0, shader clocks per frame over %d frames: exchange (poll + table) %llu | barrier %llu | arcs %llu | barrier+fixup+barrier %llu | epilogue %llu | wait stores + block sum + publish %llu | prefetch %llu\n",
-             dir ? "bwd" : "fwd", frames, g_dp_prof[dir][0] / frames, g_dp_prof[dir][1] / frames, g_dp_prof[dir][2] / frames,
-             g_dp_prof[dir][3] / frames, g_dp_prof[dir][4] / frames, g_dp_prof[dir][5] / frames, g_dp_prof[dir][6] / frames);
+    printf("den_persist2 %s rank 0 thread 0, shader clocks per frame over %d frames: poll + sync + stage + copies issued %llu | chunk 0 landed + barrier %llu | pass A %llu | chunk 1 landed + barrier %llu | pass B (+ streamed) %llu | barrier + epilogue %llu | wait stores + block sum + publish %llu | history + prefetch %llu | streamed segment 0 %llu | streamed segments 1.. %llu\n",
+           dir ? "bwd" : "fwd", frames, g_dp_prof[dir][0] / frames, g_dp_prof[dir][1] / frames, g_dp_prof[dir][2] / frames,
+           g_dp_prof[dir][3] / frames, g_dp_prof[dir][4] / frames, g_dp_prof[dir][5] / frames, g_dp_prof[dir][6] / frames, g_dp_prof[dir][7] / frames, g_dp_prof[dir][8] / frames, g_dp_prof[dir][9] / frames);
     for (int k = 0; k < 10; ++k) g_dp_prof[dir][k] = 0;
   }
 }
@@ -66,22 +61,8 @@ struct DenPersistCtl {
   } team[8][kMaxTeams];
 };
 
-struct DenPersistParams {
-  DenParams d;
-  DevPersist fwd, bwd;
-  const float* xv;        // [G][Tmax][V]
-  float* ring;            // [8 * kMaxTeams][2][rpad]
-  float* pring;           // [8 * kMaxTeams][3][kPR][kPWords]
-  int rpad;               // floats per ring slot and of the LDS table
-  int cap;                // LDS row buffers
-  int ntasks;
-  short task_seq[kMaxTasks];
-  unsigned char task_dir[kMaxTasks];
-};
-
 // The parameter block is read through the constant address space: uniform fields become scalar loads (SGPRs), and no
 // store of the kernel can be assumed to clobber them.
-typedef __attribute__((address_space(4))) const DenPersistParams CParams;
 typedef __attribute__((address_space(4))) const DenParams CDenParams;
 
 // Arguments of a (non-inlined) device function arrive in VGPRs: the compiler must treat them -- and everything loaded
@@ -94,12 +75,6 @@ __device__ __forceinline__ T* uni(T* p) {
   const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)v);
   const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(v >> 32));
   return (T*)(((unsigned long long)hi << 32) | lo);
-}
-__device__ __forceinline__ CParams* uni(CParams* p) {
-  const unsigned long long v = (unsigned long long)p;
-  const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)v);
-  const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(v >> 32));
-  return (CParams*)(((unsigned long long)hi << 32) | lo);
 }
 
 __device__ __forceinline__ unsigned den_xcc_id() {
@@ -117,17 +92,13 @@ __device__ __forceinline__ gfloat* G(float* p) { return (gfloat*)p; }
 __device__ __forceinline__ cgfloat* G(const float* p) { return (cgfloat*)p; }
 __device__ __forceinline__ gunsigned* G(unsigned* p) { return (gunsigned*)p; }
 __device__ __forceinline__ float ld_agent(cgfloat* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void st_agent(gfloat* p, float v) {      // the exchange words (and their resets)
-#if PK2_DP_STOREMODE == 1
-  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#else
+__device__ __forceinline__ void st_agent(gfloat* p, float v) {      // the exchange words (and their resets): plain, see below
   asm volatile("global_store_dword %0, %1, off" : : "v"(p), "v"(v) : "memory");
-#endif
 }
 __device__ __forceinline__ unsigned ld_agent_u(gunsigned* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ bool is_sentinel(float v) { return __float_as_uint(v) == kRingSentinel; }
 __device__ __forceinline__ void wait_stores() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-// How the state vectors travel (build-time switches for A/B runs).  Loads: agent-scope (sc1, L1-bypassing); plain loads
+// How the state vectors travel.  Loads: agent-scope (sc1, L1-bypassing; the LDS-DMA copies carry the same bit); plain loads
 // behind `buffer_inv sc0` were no faster (11.77 vs 11.75 ms per call) and keep stale lines.  Stores: PLAIN since round 4.
 // A recursion's team lives on one XCD, whose L2 is the coherence point of its 32 CUs: the write-through vector L1
 // forwards a plain store there and vmcnt acknowledges it there, so "slice stored -> s_waitcnt vmcnt(0) -> barrier -> word"
@@ -135,34 +106,8 @@ __device__ __forceinline__ void wait_stores() { asm volatile("s_waitcnt vmcnt(0)
 // multi-XCD part and its acknowledgement waits for that.  tools/ubench/handoff_plain.hip hammers exactly this protocol
 // (32 workgroups of one XCD, uneven load): 0 stale words in 10^11 reads, for plain data + agent-scope flag and for plain
 // data + plain flag alike; round 2's "the announcing word overtakes the data on small graphs" did not reproduce on the
-// round-3/4 kernels (3 x 78 chain tests, small graphs included).  -DPK2_DP_STOREMODE=1 restores the agent-scope stores.
-#ifndef PK2_DP_LOADMODE
-#define PK2_DP_LOADMODE 0      // 0: agent-scope loads; 1: buffer_inv sc0 + plain loads; 2: buffer_inv sc1 + plain loads
-#endif
-#ifndef PK2_DP_STOREMODE
-#define PK2_DP_STOREMODE 0     // 0: plain stores; 1: agent-scope stores
-#endif
-__device__ __forceinline__ void invalidate_l1() {
-#if PK2_DP_LOADMODE == 1
-  asm volatile("buffer_inv sc0" ::: "memory");
-#elif PK2_DP_LOADMODE == 2
-  asm volatile("buffer_inv sc1" ::: "memory");
-#endif
-}
-__device__ __forceinline__ float ring_load(cgfloat* p) {
-#if PK2_DP_LOADMODE == 0
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#else
-  return *p;
-#endif
-}
-__device__ __forceinline__ void ring_store(gfloat* p, float v) {
-#if PK2_DP_STOREMODE == 1
-  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#else
-  *p = v;
-#endif
-}
+// round-3/4 kernels (3 x 78 chain tests, small graphs included).
+__device__ __forceinline__ void ring_store(gfloat* p, float v) { *p = v; }
 
 // Sum over the 64 lanes with DPP moves (full-rate VALU; __shfl_xor is a ds_bpermute round trip per step), the total
 // broadcast from lane 63: the same bits in every lane.
@@ -215,7 +160,7 @@ __device__ __forceinline__ bool team_barrier(DenPersistCtl* ctl, DenPersistCtl::
 // wave instruction, no VGPR round trip; asynchronous (vmcnt).  Both addresses 16-byte aligned.
 __device__ __forceinline__ void dma256(cgfloat* gsrc_lane, float* lds_wave_base) {
   __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc_lane,
-                                   (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, PK2_DP_LOADMODE == 0 ? 16 : 0);
+                                   (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 16);      // (aux 16 = sc1)
 }
 
 // Exchange.  Every rank owns four words per frame slot: {partial sum 0, partial sum 1, "slice ready", -}.  A rank
@@ -244,17 +189,5 @@ __device__ __forceinline__ void poll_words(cgfloat* ps, int first, int nwords, S
 __device__ __forceinline__ gfloat* word_of(gfloat* pring, int frame, int rank, int word) {
   return pring + (((frame % 3) * kPR + rank) * kPWords + word);
 }
-
-// Vector in global memory -> LDS table by LDS-DMA, 1 KB rows dealt to the waves round robin (complete vector; the
-// reader's L1 may hold lines of the buffer's previous use).  R is rounded up to whole 16-byte granules: source and table
-// are padded accordingly.
-__device__ __forceinline__ void dma_table(cgfloat* src, int R, float* table) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  invalidate_l1();
-  for (int off = w * 256; off < R; off += kPW * 256)
-    if (off + lane * 4 < R) dma256(src + off + lane * 4, table + off);
-}
-__device__ __forceinline__ void dma_wait() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-
 
 }  // namespace pk2

@@ -214,7 +214,7 @@ _peer_zeros = {}
 
 
 def _fake_peer(t, st):
-    """PK2_HVD_FAKE_PEER="blocks,passes" (one-GPU boxes: DESIGN.md 6, tools/gpu_r05_peer.sh): in front of every all-reduce
+    """PK2_HVD_FAKE_PEER="blocks,passes" (one-GPU boxes: DESIGN.md 6, profiles/r05_peer_coresidency.txt): in front of every all-reduce
     call, on its stream, a kernel that does to the chip what the all-reduce kernel of an 8-rank job would -- `blocks`
     workgroups streaming a reduce-copy over the bucket `passes` times -- so that the schedules can be priced, and the
     persistent kernels' time-outs provoked, without a second GPU.  The bucket keeps its values (it adds zeros)."""

@@ -201,108 +201,6 @@ def test_den_graph_virtual_state_orderings(case, monkeypatch):
     assert np.abs(got - np.bincount(src, weights=be[dst] * prob * x[pdf], minlength=S_)).max() < 1e-9
 
 
-def _emulate_persist(lay, table):
-    """numpy model of arc_rows + row_sum of chain_den_persist.hip: the value of every row of an ordering."""
-    R_, K, T, _ = lay["arcs"].shape
-    W = T // 64
-    out = np.zeros(lay["row_begin"][-1])
-    for r in range(R_):
-        row0, row1 = lay["row_begin"][r], lay["row_begin"][r + 1]
-        acc = np.full(max(row1 - row0, 1), np.nan)
-        idx = lay["arcs"][r, :, :, 0]
-        prob = lay["arcs"][r, :, :, 1].copy().view(np.float32).astype(np.float64)
-        tails, has_end = np.zeros(T), np.zeros(T, bool)
-        for tid in range(T):
-            e, c, s = int(lay["ends"][r, tid]), int(lay["first_row"][r, tid]), 0.0
-            assert all((j + 1) % lay["estep"] == 0 for j in range(K) if (e >> j) & 1)     # rows end only at the aligned slots
-            for j in range(K):
-                s += table[idx[j, tid]] * prob[j, tid]
-                if (e >> j) & 1:
-                    acc[c] = s; c += 1; s = 0.0
-            tails[tid], has_end[tid] = s, e != 0
-        wcarry = np.zeros(W)
-        for w in range(W):          # segmented scan over the lanes of a wave: the open tails reach the next row end
-            x = 0.0
-            for lane in range(64):
-                tid = w * 64 + lane
-                if has_end[tid]:
-                    acc[lay["first_row"][r, tid]] += x
-                    x = tails[tid]
-                else:
-                    x += tails[tid]
-            wcarry[w] = x
-        for k in range(W):          # what is still open at the end of a wave belongs to row wcrow
-            if lay["wcrow"][r, k] >= 0:
-                acc[lay["wcrow"][r, k]] += wcarry[k]
-        out[row0:row1] = acc[:row1 - row0]
-    return out
-
-
-@pytest.mark.parametrize("case", ["chain_topology", "multi_entry", "bigstate", "no_peel"])
-@pytest.mark.parametrize("estep", [0, 1, 4])
-def test_den_graph_persistent_layouts(case, estep, monkeypatch):
-    """The persistent kernel's layouts (chain_internal.h: HostPersist): 32 workgroups x 512 threads x 64 register-resident
-    arc slots, rows ending only at aligned slots, wave carries.  A numpy model of the kernel's row sums over these tables
-    reproduces alpha[d] = sum_arcs alpha[src] prob x[pdf] and beta[s] = sum_arcs prob x[pdf] beta[dst] -- including a state
-    whose 30000 entering arcs span several waves."""
-    S, A, P, seed = 300, 6000, 23, 7
-    kw = dict(chain_topology=dict(loop_pdf_differs=True), multi_entry=dict(loop_pdf_differs=True, multi_entry_frac=0.3),
-              bigstate=dict(loop_pdf_differs=True), no_peel=dict(loop_pdf_differs=True))[case]
-    monkeypatch.setenv("PK2_DEN_ORDER", "none")
-    if estep:
-        monkeypatch.setenv("PK2_DEN_ESTEP", str(estep))
-    if case == "no_peel":
-        monkeypatch.setenv("PK2_DEN_PEEL", "0")
-    if case == "bigstate":
-        S, A = 200, 40000
-    g = synth.den_graph_arcs(S, A, P, seed, **kw)
-    if case == "bigstate":
-        g["dst"][:30000] = 5
-        g["pdf"][:20000] = 1; g["pdf"][20000:28000] = 2; g["pdf"][28000:30000] = 3
-    G = chain.DenominatorGraph(g, P)
-    of = G.debug_ordering(3)
-    voff, vpdf, lpdf, lprob = of["voff"], of["vpdf"], of["loop_pdf"], of["loop_prob"].astype(np.float64)
-    S_, V = g["num_states"], len(of["vpdf"])
-    vstate = np.repeat(np.arange(S_), np.diff(voff))
-    rng = np.random.default_rng(1)
-    al, be, x = rng.random(S_), rng.random(S_), rng.random(P)
-    xv = np.where(vpdf >= 0, x[np.maximum(vpdf, 0)], 1.0)
-    xl = np.where(lpdf >= 0, x[np.maximum(lpdf, 0)], 1.0)
-    src, dst, pdf, prob = g["src"], g["dst"], g["pdf"], g["prob"].astype(np.float64)
-    pf, pb = G.debug_persist(0), G.debug_persist(1)
-    assert pf is not None and pb is not None
-    if estep:
-        assert pf["estep"] == estep and pb["estep"] == estep
-    else:
-        assert pf["estep"] == 8       # small graphs leave room for the widest alignment
-    assert pf["grp_begin"][-1] == S_ and pf["row_begin"][-1] == V and pb["row_begin"][-1] == S_
-    assert (np.diff(pf["grp_begin"]) >= 0).all() and (voff[pf["grp_begin"]] == pf["row_begin"]).all()   # whole states per workgroup
-    rows = _emulate_persist(pf, al)
-    got = np.bincount(vstate, weights=rows * xv, minlength=S_) + al * lprob * xl
-    assert np.abs(got - np.bincount(dst, weights=al[src] * prob * x[pdf], minlength=S_)).max() < 1e-9
-    pi = G.initial_probs().astype(np.float64)
-    keep = np.ones(len(src), bool)
-    if case != "no_peel":
-        seen = set()
-        for i in np.flatnonzero(src == dst):
-            if int(src[i]) not in seen:
-                seen.add(int(src[i])); keep[i] = False
-    want_leak = np.zeros(S_)
-    np.add.at(want_leak, dst[keep], pi[src[keep]] * prob[keep])
-    assert np.abs(np.bincount(vstate, weights=pf["row_leak"], minlength=S_) - want_leak).max() < 1e-6
-    want_psum = np.zeros(S_)
-    np.add.at(want_psum, dst[keep], prob[keep])
-    assert np.abs(np.bincount(vstate, weights=pf["row_psum"], minlength=S_) - want_psum).max() < 1e-5
-    # the backward kernel predicts a frame's sums over the states from the vector it gathers (one exchange per frame):
-    # sum_s pi[s] b'[s] = sum_v w[v] row_leak[v] + the peeled loops, sum_s b'[s] = sum_v w[v] row_psum[v] + loops
-    w = be[vstate] * xv
-    b_new = _emulate_persist(pb, w) + lprob * xl * be
-    assert abs((pi * b_new).sum() - ((w * pf["row_leak"]).sum() + (pi * lprob * xl * be).sum())) < 1e-6 * max(1.0, (pi * b_new).sum())
-    assert abs(b_new.sum() - ((w * pf["row_psum"]).sum() + (lprob * xl * be).sum())) < 1e-5 * max(1.0, b_new.sum())
-    got = _emulate_persist(pb, be[vstate] * xv) + lprob * xl * be
-    assert np.abs(got - np.bincount(src, weights=be[dst] * prob * x[pdf], minlength=S_)).max() < 1e-9
-
-
 def _emulate_persist2(lay, table):
     """numpy model of frame_rows + row_val of chain_den_persist2.hip over the host layout (chain_internal.h: HostPersist2):
     chunked LDS table (entries never copied are NaN: a null slot must not touch them), pass A / pass B with plain stores,
@@ -404,15 +302,28 @@ def _emulate_persist2(lay, table):
 
 
 @pytest.mark.parametrize("case", ["default", "bigstate", "overflow", "overflow_estep1", "chunks", "chunks_overflow", "res1", "res2_chunks",
-                                  "res2_shared", "shared", "rows7"])
+                                  "res2_shared", "shared", "rows7", "multi_entry", "no_peel"] +
+                         [c + e for c in ("default", "multi_entry", "bigstate", "no_peel") for e in ("_estep1", "_estep4")])
 def test_den_graph_persistent2_layouts(case, monkeypatch):
-    """Second persistent layout (chain_den_persist2.hip): table chunks, two resident passes, streamed overflow.  The numpy
+    """The persistent kernel's layout (chain_den_persist2.hip): table chunks, two resident passes, streamed overflow.  The numpy
     model of the kernel's frame reproduces both recursions' row sums: back-to-back chunks (default), a row spanning several
     waves (bigstate), lists longer than the resident slots (overflow: PK2_DP2_RES=8 leaves 8 register slots per pass), a
-    vector longer than the LDS table (chunks: PK2_DP2_TCAP=512 -> two 256-entry buffers, up to 6 chunks), and both."""
+    vector longer than the LDS table (chunks: PK2_DP2_TCAP=512 -> two 256-entry buffers, up to 6 chunks), and both; states
+    entered with several pdfs (multi_entry), self-loops left in the arc lists (no_peel: PK2_DEN_PEEL=0), and rows padded to a
+    forced width (_estep1 / _estep4: PK2_DEN_ESTEP).  The per-row constants row_leak / row_psum are those of the graph, and the
+    backward recursion's prediction of a frame's sums from them holds."""
     S, A, P, seed = 300, 6000, 23, 7
     kw = dict(loop_pdf_differs=True)
     monkeypatch.setenv("PK2_DEN_ORDER", "none")
+    estep = 0
+    if "_estep" in case and not case.startswith("overflow"):
+        case, e = case.rsplit("_", 1)
+        estep = int(e[len("estep"):])
+        monkeypatch.setenv("PK2_DEN_ESTEP", str(estep))
+    if case == "multi_entry":
+        kw["multi_entry_frac"] = 0.3
+    if case == "no_peel":
+        monkeypatch.setenv("PK2_DEN_PEEL", "0")
     if case == "bigstate":
         S, A = 200, 40000
     if case.startswith("overflow"):
@@ -457,9 +368,14 @@ def test_den_graph_persistent2_layouts(case, monkeypatch):
     pf, pb = G.debug_persist2(0), G.debug_persist2(1)
     assert pf is not None and pb is not None
     assert pf["R"] == S_ and pb["R"] == V and pf["row_begin"][-1] == V and pb["row_begin"][-1] == S_
-    assert (voff[pf["grp_begin"]] == pf["row_begin"]).all()                     # whole states per workgroup
+    assert pf["grp_begin"][-1] == S_
+    assert (np.diff(pf["grp_begin"]) >= 0).all() and (voff[pf["grp_begin"]] == pf["row_begin"]).all()   # whole states per workgroup
+    if estep:
+        assert pf["estep"] == estep and pb["estep"] == estep
+    elif case in ("default", "multi_entry", "bigstate", "no_peel"):
+        assert pf["estep"] == 8       # small graphs leave room for the widest alignment
     assert pf["row_arrays"] == (7 if case == "rows7" else 8)      # (small graphs: the eighth array never costs a chunk)
-    if case in ("default", "bigstate", "rows7"):
+    if case in ("default", "bigstate", "rows7", "multi_entry", "no_peel"):
         assert pf["K"] == 2 and pb["K"] == 2 and pf["pieces"] == 0 and pb["pieces"] == 0
         assert pf["lds_off"][1] == pf["cbeg"][1] or pf["cbeg"][1] == pf["cbeg"][2]      # back to back
     if case.startswith("overflow"):
@@ -482,13 +398,29 @@ def test_den_graph_persistent2_layouts(case, monkeypatch):
     got = np.bincount(vstate, weights=rows * xv, minlength=S_) + al * lprob * xl
     want = np.bincount(dst, weights=al[src] * prob * x[pdf], minlength=S_)
     assert np.abs(got - want).max() < 1e-9 * max(1.0, np.abs(want).max())
-    got = _emulate_persist2(pb, be[vstate] * xv) + lprob * xl * be
+    w = be[vstate] * xv
+    b_new = _emulate_persist2(pb, w) + lprob * xl * be
     want = np.bincount(src, weights=be[dst] * prob * x[pdf], minlength=S_)
-    assert np.abs(got - want).max() < 1e-9 * max(1.0, np.abs(want).max())
-    # the per-row constants the backward recursion predicts its sums with are those of the first layout
-    p1 = G.debug_persist(0)
-    if p1 is not None:
-        assert np.array_equal(p1["row_leak"], pf["row_leak"]) and np.array_equal(p1["row_psum"], pf["row_psum"])
+    assert np.abs(b_new - want).max() < 1e-9 * max(1.0, np.abs(want).max())
+    # the per-row constants, recomputed from the graph: sums over the arcs entering a state but its peeled self-loop (the
+    # first one in arc order, unless peeling is off)
+    pi = G.initial_probs().astype(np.float64)
+    keep = np.ones(len(src), bool)
+    if case != "no_peel":
+        seen = set()
+        for i in np.flatnonzero(src == dst):
+            if int(src[i]) not in seen:
+                seen.add(int(src[i])); keep[i] = False
+    want_leak = np.zeros(S_)
+    np.add.at(want_leak, dst[keep], pi[src[keep]] * prob[keep])
+    assert np.abs(np.bincount(vstate, weights=pf["row_leak"], minlength=S_) - want_leak).max() < 1e-6
+    want_psum = np.zeros(S_)
+    np.add.at(want_psum, dst[keep], prob[keep])
+    assert np.abs(np.bincount(vstate, weights=pf["row_psum"], minlength=S_) - want_psum).max() < 1e-5
+    # the backward kernel predicts a frame's sums over the states from the vector it gathers (one exchange per frame):
+    # sum_s pi[s] b'[s] = sum_v w[v] row_leak[v] + the peeled loops, sum_s b'[s] = sum_v w[v] row_psum[v] + loops
+    assert abs((pi * b_new).sum() - ((w * pf["row_leak"]).sum() + (pi * lprob * xl * be).sum())) < 1e-6 * max(1.0, (pi * b_new).sum())
+    assert abs(b_new.sum() - ((w * pf["row_psum"]).sum() + (lprob * xl * be).sum())) < 1e-5 * max(1.0, b_new.sum())
 
 
 def test_den_graph_internal_state_order_is_invisible():

@@ -24,8 +24,7 @@ _KIND = dict(chain_topology=dict(loop_pdf_differs=True), multi_entry=dict(loop_p
 
 @pytest.mark.parametrize("path", ["state_x", "general_forced", "arc_pdf", "chain_topology", "multi_entry", "arc_pdf_sx_forced",
                                   "chain_topology_general", "state_x_frames", "chain_topology_frames", "multi_entry_frames",
-                                  "chain_topology_persist1", "multi_entry_persist1", "chain_topology_p2stream",
-                                  "multi_entry_p2stream", "chain_topology_p2chunks", "multi_entry_p2chunkstream",
+                                  "chain_topology_p2stream", "multi_entry_p2stream", "chain_topology_p2chunks", "multi_entry_p2chunkstream",
                                   "chain_topology_p2shared", "multi_entry_p2sharedstream",
                                   "chain_topology_p2expanded", "multi_entry_p2rows7"])
 @pytest.mark.parametrize("S,A,P,lens,leaky", [
@@ -50,14 +49,14 @@ def test_denominator_matches_oracle(S, A, P, lens, leaky, path, monkeypatch):
     frames = path.endswith("_frames")       # the launch-per-frame state-x kernels (the default is the persistent kernel)
     if frames:
         monkeypatch.setenv("PK2_DEN_PERSIST", "0")
-    # forms of the persistent kernel: the first (everything resident: csrc/chain_den_persist.hip) and variants of the second
-    # (csrc/chain_den_persist2.hip, the default) that these small graphs would not reach by themselves: 1 or 2 register slots
+    # variants of the persistent kernel (csrc/chain_den_persist2.hip, the default) that these small graphs would not reach by
+    # themselves: 1 or 2 register slots
     # per resident pass (everything else streamed in pieces), an LDS table of 1024 entries (4 - 6 table chunks through two
     # buffers; `shared`: a vector of up to twice the table as two chunks taking turns in ONE buffer, round 4), both.  The
     # layout variables are read when the graph is created.
     # `expanded`: x read from the copies expanded per virtual state / state instead of gathered by pdf (round 4's default);
     # `rows7`: the LDS layout without the pdf arrays (a graph the eighth row array would cost a table chunk), which implies it.
-    form = {"persist1": 1, "p2stream": 2, "p2chunks": 2, "p2chunkstream": 2, "p2shared": 2, "p2sharedstream": 2, "p2expanded": 2,
+    form = {"p2stream": 2, "p2chunks": 2, "p2chunkstream": 2, "p2shared": 2, "p2sharedstream": 2, "p2expanded": 2,
             "p2rows7": 2}.get(path.rsplit("_", 1)[-1], 0)
     if form:
         monkeypatch.setenv("PK2_DEN_PERSIST", str(form))
@@ -463,6 +462,24 @@ def test_bench_size_objective_with_alignment_built_supervisions_matches_c_oracle
     assert np.abs(grad.cpu().numpy() - want_grad).max() < 1e-4
 
 
+def test_retired_first_persistent_form_is_refused(monkeypatch):
+    """PK2_DEN_PERSIST=1 named the first persistent kernel, which is gone: a call fails with an error that names the variable
+    (before anything is launched) instead of silently taking another route; without the variable the same call succeeds."""
+    from pykaldi2_amd._lib import Pk2Error
+    g, G, ref = _mk(8, 30, 5, seed=8)
+    lens, leaky = [6], 1e-2
+    lg = np.random.default_rng(1).normal(0, 3, size=(1, 6, 5)).astype(np.float32)
+    x = torch.from_numpy(lg).cuda()
+    monkeypatch.setenv("PK2_DEN_PERSIST", "1")
+    with pytest.raises(Pk2Error, match="PK2_DEN_PERSIST"):
+        chain.den_forward_backward(G, x, lens, leaky)
+    monkeypatch.delenv("PK2_DEN_PERSIST")
+    lp, gamma = chain.den_forward_backward(G, x, lens, leaky)
+    want_lp, want_g, _ = R.den_forward_backward(lg[0].astype(np.float64), ref, leaky)
+    assert abs(lp.cpu().numpy()[0] - want_lp) <= 1e-3 * abs(want_lp) + 1e-4
+    assert np.abs(gamma.cpu().numpy()[0] - want_g).max() < 1e-4
+
+
 def test_graph_beyond_the_register_slots_streams_its_overflow():
     """A graph with more arcs than the ~1.05 M register slots of a team (no capacity cliff): the persistent
     kernel keeps 2 x 32 slots per thread resident and streams the rest in pieces (csrc/chain_den_persist2.hip) instead of
@@ -475,7 +492,7 @@ def test_graph_beyond_the_register_slots_streams_its_overflow():
     lens = [41, 17, 30]
     assert G.kernel_path(len(lens)) == 2 and G.persist_form(len(lens)) == 2
     lay = G.debug_persist2(0)
-    assert lay["pieces"] > 0 and lay["K"] == 2 and G.debug_persist(0) is None       # the first form does not hold this graph
+    assert lay["pieces"] > 0 and lay["K"] == 2
     pi = R.initial_probs_ref(g["num_states"], g["src"].astype(np.int64), g["dst"].astype(np.int64),
                              g["prob"].astype(np.float64), 0)
     rng = np.random.default_rng(4)

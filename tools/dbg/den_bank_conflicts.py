@@ -1,4 +1,4 @@
-"""LDS bank conflicts of the persistent denominator layouts on the bench graph (CPU, no GPU needed): cycles a 32-lane half
+"""LDS bank conflicts of the persistent denominator layout on the bench graph (CPU, no GPU needed): cycles a 32-lane half
 wave needs for one ds_read_b32 of the arc loop = the largest number of DISTINCT addresses that fall into one of the 32 banks
 (lanes reading the same address are served by one broadcast)."""
 import sys
@@ -32,10 +32,6 @@ for w in (0, 1):
     idx = np.empty((R, K2 * 2, T), np.int64)
     idx[:, 0::2] = idx2 & 0xffff
     idx[:, 1::2] = idx2 >> 16
-    print("second form, ordering %d: %.3f cycles per half-wave gather (pass A %.3f, pass B %.3f)" %
+    print("ordering %d: %.3f cycles per half-wave gather (pass A %.3f, pass B %.3f)" %
           (w, cycles(idx), cycles(idx[:, :K2]), cycles(idx[:, K2:])))
-for w in (0, 1):
-    p1 = G.debug_persist(w)
-    if p1 is not None:
-        print("first form, ordering %d: %.3f" % (w, cycles(p1["arcs"][..., 0].astype(np.int64))))
 print("random offsets: %.3f" % cycles(np.random.default_rng(0).integers(0, 30000, size=(32, 64, 512))))

@@ -5,7 +5,7 @@ import numpy as np, torch
 from pykaldi2_amd import chain, synth
 
 def run(G, x, lens, leaky, persist):
-    os.environ["PK2_DEN_PERSIST"] = "1" if persist else "0"
+    os.environ["PK2_DEN_PERSIST"] = "2" if persist else "0"
     lp, gamma = chain.den_forward_backward(G, x, lens, leaky)
     torch.cuda.synchronize()
     return lp.cpu().numpy(), gamma.cpu().numpy()
