@@ -18,7 +18,7 @@ import torch as th
 import yaml
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from pykaldi2_amd import _lib, augment, beamform, data, fbank, hvd, lstm, ops, optim, utils  # noqa: E402
+from pykaldi2_amd import _lib, augment, beamform, data, dereverb, fbank, hvd, lstm, ops, optim, utils  # noqa: E402
 
 
 class ChunkPool:
@@ -94,6 +94,7 @@ def main():
     augment.refuse_time_warp(config, "train_ce.py")
     args.spec = augment.SpecAugment.from_config(config)     # None without data_config spec_augment
     beamform.require_beamform_config(config, os.path.basename(sys.argv[0]))      # data_config beamform needs online_rir
+    dereverb.require_wpe_config(config, os.path.basename(sys.argv[0]))           # data_config wpe needs use_reverb
 
     if args.hvd:
         hvd.init()

@@ -37,7 +37,7 @@ import torch as th
 import yaml
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from pykaldi2_amd import augment, beamform, chain, data, fbank, hvd, lstm, ops, optim, synth, utils  # noqa: E402
+from pykaldi2_amd import augment, beamform, chain, data, dereverb, fbank, hvd, lstm, ops, optim, synth, utils  # noqa: E402
 from pykaldi2_amd.lattice import TransitionModel  # noqa: E402
 from pykaldi2_amd.tree import ContextDependency  # noqa: E402
 
@@ -106,6 +106,7 @@ def main():
         augment.refuse_time_warp(config, "train_chain.py without -e2e")
     args.spec = augment.SpecAugment.from_config(config)      # None without data_config spec_augment
     beamform.require_beamform_config(config, os.path.basename(sys.argv[0]))      # data_config beamform needs online_rir
+    dereverb.require_wpe_config(config, os.path.basename(sys.argv[0]))           # data_config wpe needs use_reverb
 
     hvd.init()
     th.cuda.set_device(hvd.local_rank())

@@ -24,7 +24,7 @@ import torch as th
 import yaml
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from pykaldi2_amd import augment, beamform, data, fbank, hvd, lattice, lstm, ops, optim, se, synth, transformer, utils  # noqa: E402
+from pykaldi2_amd import augment, beamform, data, dereverb, fbank, hvd, lattice, lstm, ops, optim, se, synth, transformer, utils  # noqa: E402
 
 
 def parse_config(argv=None, arch="blstm"):
@@ -92,6 +92,7 @@ def main(arch="blstm"):
     augment.refuse_time_warp(config, "train_transformer_se.py" if arch == "transformer" else "train_se.py")
     args.spec = augment.SpecAugment.from_config(config)      # None without data_config spec_augment
     beamform.require_beamform_config(config, os.path.basename(sys.argv[0]))      # data_config beamform needs online_rir
+    dereverb.require_wpe_config(config, os.path.basename(sys.argv[0]))           # data_config wpe needs use_reverb
 
     hvd.init()
     th.cuda.set_device(hvd.local_rank())

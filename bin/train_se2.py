@@ -39,7 +39,7 @@ import torch as th
 import yaml
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from pykaldi2_amd import augment, beamform, chain, data, fbank, hvd, lattice, lstm, ops, optim, se, synth, utils  # noqa: E402
+from pykaldi2_amd import augment, beamform, chain, data, dereverb, fbank, hvd, lattice, lstm, ops, optim, se, synth, utils  # noqa: E402
 
 
 def parse_config(argv=None):
@@ -95,6 +95,7 @@ def main():
     augment.refuse_time_warp(config, "train_se2.py")
     args.spec = augment.SpecAugment.from_config(config)      # None without data_config spec_augment
     beamform.require_beamform_config(config, os.path.basename(sys.argv[0]))      # data_config beamform needs online_rir
+    dereverb.require_wpe_config(config, os.path.basename(sys.argv[0]))           # data_config wpe needs use_reverb
     hvd.init()
     th.cuda.set_device(hvd.local_rank())
     dev = th.device("cuda", hvd.local_rank())

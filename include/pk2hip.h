@@ -628,6 +628,56 @@ int pk2_bf_apply(const float* const* spec, const float* const* w, const int32_t*
                  float* const* out, void* stream);
 
 /* ------------------------------------------------------------------ *
+ * WPE dereverberation of a ragged minibatch (csrc/wpe.hip; no counterpart in the reference): weighted
+ * prediction error, multi-channel linear prediction per frequency bin.  B utterances with their own frame counts N_b and
+ * common C channels (1 .. PK2_WPE_MAX_CHANNELS), F bins, K = taps and a prediction delay (1 .. PK2_WPE_MAX_DELAY);
+ * D = C K <= PK2_WPE_MAX_ORDER.  Spectra are (C, N_b, F, 2) as for the beamformer.  The stacked past of frame t is
+ * y~(t)[k C + c] = Y[c, t - delay - k, f], zero before the first frame.  `spec`, `weight`, `power`, `out` and `power_out`
+ * are HOST arrays of device pointers, `frames` is a HOST array; more than PK2_WPE_MAX_UTTS utterances take one launch per
+ * PK2_WPE_MAX_UTTS.  No atomics, no host synchronisation: a result is bit-identical from run to run and independent of
+ * the other utterances of its call.  Bad arguments return PK2_ERR_INVALID before the device is touched.
+ *
+ * pk2_wpe_power: power_b[t, f] = max((sum_c |Y[c, t, f]|^2) / C, 1e-10), the sum a float32 fmaf chain over c (re, then im).
+ *
+ * pk2_wpe_corr: R[f] = sum_t y~ y~^H / weight[t, f] (D x D), P[f] = sum_t y~ Y(t)^H / weight[t, f] (D x C).  The rows are
+ * multiplied by the float32 reciprocal of the weight.  Frames are split into parts of PK2_WPE_FRAMES_PER_PART; a part is a
+ * float32 chain in frame order on the f32 MFMA, the parts are added in part order in float64 and rounded once.  R is
+ * exactly Hermitian with a real diagonal.  R: device (B, F, D, D, 2); P: device (B, F, D, C, 2).
+ *
+ * pk2_wpe_solve: R' = R + (diag_load Re tr R / D + 1e-10) I, G = R'^-1 P by Cholesky in float64, rounded once.  A bin whose
+ * R or P is not finite, or whose factorisation or solution is not (R' not positive definite), gets G = 0 and sets
+ * nonfinite[b] = 1 (else 0).  G: device (B, F, D, C, 2); nonfinite: device int32 [B].
+ *
+ * pk2_wpe_filter: out_b[c, t, f] = Y[c, t, f] - sum_d conj(G[f, d, c]) y~(t)[d], float32 fmaf chains in ascending d.
+ * A bin whose G is all zero is copied, so it passes through bit for bit even where its past holds a NaN.
+ * power_out (NULL, or B pointers to (N_b, F)): pk2_wpe_power of `out`, from the same pass.  out must not alias spec.
+ *
+ * pk2_wpe: X^0 = Y; iteration i = 1 .. iters: weight = power of X^(i-1), corr, solve, X^i = filter of Y.  out_b = X^iters;
+ * nonfinite[b] = 1 when a bin of any iteration was not finite.  Nothing is read back.
+ *
+ * work: device memory of pk2_wpe_workspace_bytes(frames, B, C, F, taps, delay) bytes, enough for every entry on that
+ * minibatch; 0 for arguments the entries would refuse.
+ * ------------------------------------------------------------------ */
+#define PK2_WPE_MAX_CHANNELS 8
+#define PK2_WPE_MAX_ORDER 80
+#define PK2_WPE_MAX_DELAY 8
+#define PK2_WPE_MAX_ITERS 8
+#define PK2_WPE_MAX_UTTS 32
+#define PK2_WPE_FRAMES_PER_PART 1024
+size_t pk2_wpe_workspace_bytes(const int32_t* frames, int32_t B, int32_t C, int32_t F, int32_t taps, int32_t delay);
+int pk2_wpe_power(const float* const* spec, const int32_t* frames, int32_t B, int32_t C, int32_t F, float* const* power,
+                  void* stream);
+int pk2_wpe_corr(const float* const* spec, const float* const* weight, const int32_t* frames, int32_t B, int32_t C, int32_t F,
+                 int32_t taps, int32_t delay, void* work, size_t work_bytes, float* R, float* P, void* stream);
+int pk2_wpe_solve(const float* R, const float* P, int32_t B, int32_t C, int32_t F, int32_t taps, double diag_load, void* work,
+                  size_t work_bytes, float* G, int32_t* nonfinite, void* stream);
+int pk2_wpe_filter(const float* const* spec, const float* G, const int32_t* frames, int32_t B, int32_t C, int32_t F,
+                   int32_t taps, int32_t delay, float* const* out, float* const* power_out, void* stream);
+int pk2_wpe(const float* const* spec, const int32_t* frames, int32_t B, int32_t C, int32_t F, int32_t taps, int32_t delay,
+            int32_t iters, double diag_load, void* work, size_t work_bytes, float* const* out, int32_t* nonfinite,
+            void* stream);
+
+/* ------------------------------------------------------------------ *
  * Fused log-softmax + NLL + gradient.  Replaces nn.CrossEntropyLoss
  * (ignore_index=-100; reduction mean: reference bin/train_ce.py:134,189;
  * reduction sum: bin/train_se.py:214,235).

@@ -64,6 +64,11 @@ BF_MAX_CHANNELS = 8      # PK2_BF_MAX_CHANNELS
 BF_MAX_MASKS = 4         # PK2_BF_MAX_MASKS
 BF_FRAMES_PER_PART = 32  # PK2_BF_FRAMES_PER_PART
 BF_REF_SNR = -1          # PK2_BF_REF_SNR
+WPE_MAX_CHANNELS = 8     # PK2_WPE_MAX_CHANNELS
+WPE_MAX_ORDER = 80       # PK2_WPE_MAX_ORDER
+WPE_MAX_DELAY = 8        # PK2_WPE_MAX_DELAY
+WPE_MAX_ITERS = 8        # PK2_WPE_MAX_ITERS
+WPE_FRAMES_PER_PART = 1024  # PK2_WPE_FRAMES_PER_PART
 
 _vp, _i32, _i64, _f32, _sz = C.c_void_p, C.c_int32, C.c_int64, C.c_float, C.c_size_t
 
@@ -203,6 +208,15 @@ SIGNATURES = {
     "pk2_bf_mvdr_weights": (C.c_int, [C.POINTER(_vp), C.POINTER(_vp), _i32, _i32, _i32, _i32, C.c_double, _vp, _sz, _vp, _vp,
                                       _vp, _vp]),
     "pk2_bf_apply": (C.c_int, [C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_i32), _i32, _i32, _i32, C.POINTER(_vp), _vp]),
+    "pk2_wpe_workspace_bytes": (_sz, [_vp, _i32, _i32, _i32, _i32, _i32]),
+    "pk2_wpe_power": (C.c_int, [C.POINTER(_vp), C.POINTER(_i32), _i32, _i32, _i32, C.POINTER(_vp), _vp]),
+    "pk2_wpe_corr": (C.c_int, [C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_i32), _i32, _i32, _i32, _i32, _i32, _vp, _sz, _vp, _vp,
+                               _vp]),
+    "pk2_wpe_solve": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, C.c_double, _vp, _sz, _vp, _vp, _vp]),
+    "pk2_wpe_filter": (C.c_int, [C.POINTER(_vp), _vp, C.POINTER(_i32), _i32, _i32, _i32, _i32, _i32, C.POINTER(_vp),
+                                 C.POINTER(_vp), _vp]),
+    "pk2_wpe": (C.c_int, [C.POINTER(_vp), C.POINTER(_i32), _i32, _i32, _i32, _i32, _i32, _i32, C.c_double, _vp, _sz,
+                          C.POINTER(_vp), _vp, _vp]),
     "pk2_softmax_ce_fwd_bwd": (C.c_int, [_vp, _i64, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _i64, _vp, _vp]),
     "pk2_softmax_ce_fwd_bwd_mean": (C.c_int, [_vp, _i64, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _i64, _vp]),
     "pk2_scale_inplace_ratio": (C.c_int, [_vp, _i64, _vp, _vp, _vp]),

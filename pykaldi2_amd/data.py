@@ -227,7 +227,7 @@ class SimulationPool:
     one impulse response per file), or the synthetic generator."""
 
     def __init__(self, noises, rirs, use_reverb=True, use_noise=True, simulation_prob=0.5, gain_norm=False, snr_range=(0, 30),
-                 online_rir=False, t60_range=(0.1, 0.5), beamform=None):
+                 online_rir=False, t60_range=(0.1, 0.5), beamform=None, wpe=None):
         from . import simulation
         self.noises = noises if use_noise else []
         self.online_rir = bool(online_rir and use_reverb)
@@ -247,6 +247,12 @@ class SimulationPool:
             self.sim_mc = simulation.SimpleSimulator(use_rir=True, use_noise=bool(self.noises), snr_range=snr_range,
                                                      mask_estimator=simulation.MaskEstimator(analyzer))
             self.beamformer = bf.MaskBeamformer(analyzer, self.beamform["ref"], self.beamform["diag_load"])
+        self.wpe = dict(wpe) if wpe else None                     # data_config `wpe` (dereverb.wpe_config)
+        if self.wpe:
+            from . import dereverb
+            if not use_reverb:
+                raise ValueError("wpe: data_config use_reverb must be true")
+            self.dereverb = dereverb.Dereverberator(simulation.SpectrumAnalyzer(do_dither=False), **self.wpe)
 
     @classmethod
     def from_config(cls, config, seed=0):
@@ -256,10 +262,14 @@ class SimulationPool:
         picking one from the pool (pykaldi2_amd.rirgen), T60 ~ U[`t60_range`] (default [0.1, 0.5]); it wins over
         `rir_paths`.  `beamform` (true or a mapping, see pykaldi2_amd.beamform.beamform_config; needs `online_rir`,
         `use_reverb` and `simulation_prob` > 0, ValueError otherwise): a simulated utterance is recorded by a circular
-        array in the sampled room and comes back as the output of a mask-based MVDR beamformer."""
-        from . import beamform as bf
+        array in the sampled room and comes back as the output of a mask-based MVDR beamformer.  `wpe` (true or a mapping,
+        see pykaldi2_amd.dereverb.wpe_config; needs `use_reverb` and `simulation_prob` > 0, ValueError otherwise): a
+        simulated utterance is dereverberated by WPE, as one channel, or with `beamform` on the array's spectrum in front of
+        the beamformer."""
+        from . import beamform as bf, dereverb
         dc = config.get("data_config", {})
         beamform = bf.beamform_config(config)
+        wpe = dereverb.wpe_config(config)
         prob = dc.get("simulation_prob", 0)
         if not prob or not (dc.get("use_dir_noise") or dc.get("use_reverb")):
             return None
@@ -276,7 +286,7 @@ class SimulationPool:
             noises = cls._read_zips(config.get("dir_noise_paths") or [], config.get("data_path", ""))
             rirs = cls._read_zips(config.get("rir_paths") or [], config.get("data_path", "")) if not online else []
         return cls(noises, rirs, dc.get("use_reverb", False), dc.get("use_dir_noise", False), prob, dc.get("gain_norm", False),
-                   dc.get("snr_range", (0, 30)), online, dc.get("t60_range", (0.1, 0.5)), beamform)
+                   dc.get("snr_range", (0, 30)), online, dc.get("t60_range", (0.1, 0.5)), beamform, wpe)
 
     @staticmethod
     def _read_zips(sources, data_path):
@@ -319,6 +329,8 @@ class SimulationPool:
                 delays.append(d1)
         y, _ = self.sim(x, [noise] if noise is not None else None, src_rir, [noise_rir] if noise_rir is not None else None,
                         normalize_gain=self.gain_norm, rir_delays=delays or None)
+        if self.wpe and y.shape[0] >= self.dereverb.analyzer.frame_len:      # shorter than one analysis frame: as it is
+            y = self.dereverb(y)
         return y
 
     def _simulate_array(self, x, noise, device):
@@ -334,7 +346,14 @@ class SimulationPool:
         mixed, _, mask, _ = self.sim_mc(x, [noise] if noise is not None else None, rirs[0],
                                         [rirs[1]] if noise is not None else None, normalize_gain=self.gain_norm,
                                         rir_delays=[dl[s] for s in range(n_src)], gen_mask=True)
-        return self.beamformer(mixed, mask[0])
+        if not self.wpe:
+            return self.beamformer(mixed, mask[0])
+        # WPE on the array spectrum, then the beamformer's own stages on the result: no inverse and forward transform between
+        from . import beamform as bf
+        spec = self.dereverb.spectrum(self.beamformer.analyze(mixed))
+        phi = bf.spatial_covariance(spec, mask[0], complement=True)
+        w, _ = bf.mvdr_weights(phi[0], phi[1], self.beamformer.ref, self.beamformer.diag_load)
+        return self.beamformer.analyzer.synthesize(bf.apply_weights(spec, w))[:mixed.shape[1]]
 
     def online_rirs(self, n_src, device):
         """RIRs of one sampled room (rirgen.sample_online_room: room, T60, mic at the array centre, the speech source and
