@@ -95,7 +95,33 @@ class DenominatorGraph:
         row / 0 = gather; the rest are flags."""
         out = np.zeros(8, dtype=np.int32)
         _lib.check(_lib.lib().pk2_den_graph_plan(self._h, int(num_seqs), int(max_frames), _lib.ptr(out)))
-        return dict(zip(self.PLAN_FIELDS, (int(v) for v in out)))
+        pl = dict(zip(self.PLAN_FIELDS, (int(v) for v in out)))
+        # what the persistent kernel copies into LDS per frame on THIS graph (csrc/chain_internal.h: kDirectDeg): entries of
+        # the table prefix / of the whole vector, and the arcs that read the vector in L2 instead, per direction
+        for name, which in (("fwd", 0), ("bwd", 1)):
+            info = np.zeros(8, dtype=np.int32)
+            _lib.check(_lib.lib().pk2_den_graph_debug_persist2_table(self._h, which, _lib.ptr(info), None, None, None))
+            pl[name + "_table"] = (int(info[0]), int(info[1]))
+            pl[name + "_direct_arcs"] = int(info[3])
+        return pl
+
+    def debug_persist2_table(self, which):
+        """Table prefix of an ordering of the persistent layout (test hook; csrc/chain_internal.h: kDirectDeg): Rt, R, the
+        position of every entry of the published vector and the direct-arc records [rank][record][thread]; None if the
+        graph has no persistent layout.  Rt == R: the whole vector is the table."""
+        L = _lib.lib()
+        info = np.zeros(8, dtype=np.int32)
+        _lib.check(L.pk2_den_graph_debug_persist2_table(self._h, which, _lib.ptr(info), None, None, None))
+        if not info[1]:
+            return None
+        lay = self.debug_persist2(which)
+        nr, nd, nt = lay["prob"].shape[0], int(info[5]), int(info[7])
+        pos = np.empty(int(info[1]), np.int32)
+        dprob, dpr = np.empty((nr, nd, nt), np.float32), np.empty((nr, nd, nt), np.uint32)
+        _lib.check(L.pk2_den_graph_debug_persist2_table(self._h, which, _lib.ptr(info), _lib.ptr(pos), _lib.ptr(dprob), _lib.ptr(dpr)))
+        return dict(Rt=int(info[0]), R=int(info[1]), table_entries=int(info[2]), direct_arcs=int(info[3]),
+                    max_direct=int(info[4]), kDirect=nd, kDirectDeg=int(info[6]), pos=pos, dprob=dprob,
+                    dpos=(dpr & 0xffff).astype(np.int64), drow=(dpr >> 16).astype(np.int64))
 
     def debug_persist2(self, which):
         """Persistent layout of an ordering (test hook; csrc/chain_internal.h: HostPersist2); None if absent."""

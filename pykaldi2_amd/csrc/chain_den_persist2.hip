@@ -49,6 +49,8 @@ struct DenPersist2Params {
   NumParams np;                 // the minibatch's numerator forward-backward, if it rides in this launch
   int fwd_stream, bwd_stream;   // the ordering has streamed pieces (or more than two table chunks)
   int pspt;                     // 2 or kPSPT: epilogue entries per thread
+  int fwd_direct, bwd_direct;   // the ordering has a table prefix and direct arcs (chain_internal.h: kDirectDeg)
+  const float* pi_pos;          // pi at the forward ordering's vector positions (fwd_direct)
   short task_seq[kMaxTasks];
   unsigned char task_dir[kMaxTasks];
 };
@@ -543,10 +545,39 @@ struct RowSpan { int nrows, uncA, ncA, uncB, ncB; };
 // `stage`: the caller's LDS staging of values it prefetched from memory (x of own rows).  It runs behind the wait for chunk 1,
 // where every older memory operation has completed anyway: placed before the copies, the wait for those prefetches -- and
 // with it, vmcnt being in order, for the previous frame's history stores -- would delay the copies.
-template <bool STREAM, typename ST, typename STAGE>
+// DIRECT (chain_internal.h: kDirectDeg; only without streamed pieces): the chunks cover the table prefix of the vector, and
+// every thread fetches the entries of its direct arcs from the vector itself -- L1-bypassing loads like the copies', issued
+// when chunk 0 has landed (vmcnt counts in order: ahead of chunk 0's copies they would sit in front of the wait for it), so
+// that pass A hides their round trip; the wait that precedes pass B covers them.  A direct arc belongs to the thread that
+// owns its row in the row epilogue, which adds prob x value to the row's sum in registers (DirectRegs::add_to).  (First
+// form, measured and dropped: records dealt round robin and added into the row-indexed array accS with ds_add_f32 -- the
+// 1024 LDS float atomics per CU and frame cost 0.28 us of a 6.9 us frame, profiles/den_table.txt.)
+struct DirectRegs {
+  float prob[kDirect]; uint32_t off[kDirect]; int row[kDirect];      // byte offset in the vector; rank-local row (0xffff: none)
+  float val[kDirect];                                                // the frame's entries
+  __device__ __forceinline__ float add_to(int q, float v) const {
+#pragma unroll
+    for (int j = 0; j < kDirect; ++j) v += row[j] == q ? prob[j] * val[j] : 0.f;
+    return v;
+  }
+};
+struct NoDirect { };
+__device__ __forceinline__ void load_direct_regs(CDev2& o, int rank, DirectRegs& d) {
+#pragma unroll
+  for (int j = 0; j < kDirect; ++j) {
+    const size_t at = ((size_t)rank * kDirect + j) * kPT + threadIdx.x;
+    const uint32_t pr = o.dpr[at];
+    d.prob[j] = o.dprob[at];
+    d.off[j] = (pr & 0xffffu) * 4u;
+    d.row[j] = (int)(pr >> 16);
+    d.val[j] = 0.f;
+  }
+}
+template <bool STREAM, bool DIRECT, typename DR, typename ST, typename STAGE>
 __device__ __forceinline__ void frame_rows(CDev2& o, cgfloat* src, int rank, const RowSpan& rs, const FrameRegs& r,
-                                           const DmaPlan& plan, ST& st, const Lds2& L, DpTimers& dp_, STAGE stage,
+                                           const DmaPlan& plan, DR& dr, ST& st, const Lds2& L, DpTimers& dp_, STAGE stage,
                                            bool prime_next = false) {
+  static_assert(!(STREAM && DIRECT), "direct arcs exist in the fully resident form only");
   const int tid = threadIdx.x;
   if constexpr (STREAM) {
     // the streamed segments add up in accS; compact rows past a truncated resident list get no store from their pass
@@ -560,6 +591,11 @@ __device__ __forceinline__ void frame_rows(CDev2& o, cgfloat* src, int rank, con
   lds_only_barrier();
   DP_T(1);
   DP_TLF(2);
+  if constexpr (DIRECT) {
+    typedef __attribute__((address_space(1))) const char gchar;
+#pragma unroll
+    for (int j = 0; j < kDirect; ++j) dr.val[j] = ld_agent((cgfloat*)((gchar*)src + dr.off[j]));
+  }
   Chunk1Dma c1;
   {
     const uint64_t sb = (uint64_t)(src + o.cbeg[1]);
@@ -611,7 +647,9 @@ __device__ __forceinline__ void frame_rows(CDev2& o, cgfloat* src, int rank, con
   } else {
     if (shared) { lds_only_barrier(); dma_chunk(src, o, 1, L.table); }
     wait_vm(0);
+    DP_T(8);                               // (phase timers, no streamed piece: slot 8 = the wait for chunk 1 alone,
     stage();
+    DP_T(9);                               //  slot 9 = the staging, slot 3 = the barrier that follows)
     __syncthreads();                       // chunk 1 is complete
     DP_T(3);
     pass_rows_any<kQ, STREAM>(o.estep, r.prob, r.addr, r.base, r.endsB, r.frowB, L.accB, L.wcarry + kPW, NoDma());
@@ -668,7 +706,7 @@ __device__ __forceinline__ void load_frame_regs(CDev2& o, int rank, FrameRegs& r
 }
 
 // alpha recursion of sequence g (T frames).
-template <bool STREAM, int PSPT>
+template <bool STREAM, int PSPT, bool DIRECT>
 __device__ __noinline__ void run_fwd2(CParams2* pp_, DenPersistCtl* ctl_, DenPersistCtl::Team* team_,
                                       unsigned* nbar, int g_, int T_, int rank_, float* ring_, float* pring_) {
   CParams2* pp = uni(pp_);
@@ -687,6 +725,8 @@ __device__ __noinline__ void run_fwd2(CParams2* pp_, DenPersistCtl* ctl_, DenPer
   load_frame_regs<STREAM>(o, rank, fr, L.table);
   DmaPlan plan;
   plan.init(o, L.table);
+  typename std::conditional<DIRECT, DirectRegs, NoDirect>::type dr;
+  if constexpr (DIRECT) load_direct_regs(o, rank, dr);
   const int row0 = o.row_begin[rank], nrows = o.row_begin[rank + 1] - row0;
   const int g0 = o.grp_begin[rank], ngrp = o.grp_begin[rank + 1] - g0;
   RowSpan rs;
@@ -703,15 +743,18 @@ __device__ __noinline__ void run_fwd2(CParams2* pp_, DenPersistCtl* ctl_, DenPer
   }
   if (tid < kSegs * kPW) L.wcrow[tid] = o.wcrow[(size_t)rank * kSegs * kPW + tid];
   int st_lo[PSPT], st_hi[PSPT], st_o[PSPT]; float st_pl[PSPT], st_pi[PSPT]; bool st_ok[PSPT];
+  int st_pos[PSPT];                        // DIRECT: where the own state's alpha goes in the published vector
 #pragma unroll
   for (int i = 0; i < PSPT; ++i) {
     const int r = tid + i * kPT;
     st_ok[i] = r < ngrp;
     st_lo[i] = st_hi[i] = st_o[i] = 0; st_pl[i] = st_pi[i] = 0.f;
+    st_pos[i] = 0;
     if (st_ok[i]) {
       const int dd = g0 + r;
       st_lo[i] = d.voff[dd] - row0; st_hi[i] = d.voff[dd + 1] - row0; st_o[i] = d.ooff[dd];
       st_pl[i] = d.loop_prob[dd]; st_pi[i] = d.pi[dd];
+      if constexpr (DIRECT) st_pos[i] = o.pos[dd];
     }
   }
   // own words of the three frame slots start as "not yet written"
@@ -800,7 +843,7 @@ __device__ __noinline__ void run_fwd2(CParams2* pp_, DenPersistCtl* ctl_, DenPer
     DP_TLSET(0);
     if (t == 0) {
       as = d.pi_sum;
-      src = G(d.pi);
+      src = DIRECT ? G(p.pi_pos) : G(d.pi);
     } else {
       src = ring + (size_t)(t & 1) * p.rpad;
       poll_words(pring + (size_t)(t % 3) * kPR * kPWords, 0, 1, spin, L);
@@ -815,7 +858,7 @@ __device__ __noinline__ void run_fwd2(CParams2* pp_, DenPersistCtl* ctl_, DenPer
     // copies (no store sits between them and their waits), long before the stores it has to precede
     const bool publish = t + 1 < T;
     if (tid == 0 && publish) st_agent(word_of(pring, t + 2, rank, 0), __uint_as_float(kRingSentinel));
-    frame_rows<STREAM>(o, src, rank, rs, fr, plan, st, L, dp_, [&]() {
+    frame_rows<STREAM, DIRECT>(o, src, rank, rs, fr, plan, dr, st, L, dp_, [&]() {
 #pragma unroll
       for (int i = 0; i < PSPT; ++i) {
         const int r = tid + i * kPT;
@@ -838,12 +881,15 @@ __device__ __noinline__ void run_fwd2(CParams2* pp_, DenPersistCtl* ctl_, DenPer
       if (!st_ok[i]) continue;
       float sum = 0.f;
       for (int q = st_lo[i]; q < st_hi[i]; ++q) {
-        const float v = (row_val<STREAM>(L, cmask, q) + lk * L.leak[q]) * L.xown[q] * inv_as;
+        float rv = row_val<STREAM>(L, cmask, q);
+        if constexpr (DIRECT) rv = dr.add_to(q, rv);
+        const float v = (rv + lk * L.leak[q]) * L.xown[q] * inv_as;
         L.aux[q] = v;          // (the row belongs to this thread alone: kept for the history stores below)
         sum += v;
       }
       if (st_pl[i] > 0.f) { loopv[i] = (own_a[i] + lk * st_pi[i]) * st_pl[i] * xlr[i] * inv_as; sum += loopv[i]; }
-      if (publish) ring_store(ring_n + g0 + tid + i * kPT, sum);
+      if constexpr (DIRECT) { if (publish) ring_store(ring_n + st_pos[i], sum); }
+      else { if (publish) ring_store(ring_n + g0 + tid + i * kPT, sum); }
       outv[i] = sum;
       own_a[i] = sum;          // alpha[t+1] of the own state: the next frame's loop term
       loc += sum;
@@ -877,7 +923,7 @@ __device__ __noinline__ void run_fwd2(CParams2* pp_, DenPersistCtl* ctl_, DenPer
 // (lU alike without pi), and the per-virtual-state weights are constants of the graph (the forward layout's row_leak /
 // row_psum).  So the producer of w[t+1] publishes, WITH its slice, its share of the sums frame t is going to compute: a
 // frame knows c[t] before its first arc, scales its rows as soon as they are summed, and one exchange per frame is left.
-template <bool STREAM, int PSPT>
+template <bool STREAM, int PSPT, bool DIRECT>
 __device__ __noinline__ void run_bwd2(CParams2* pp_, DenPersistCtl* ctl_, DenPersistCtl::Team* team_,
                                       unsigned* nbar, int g_, int T_, int rank_, float* ring_, float* pring_) {
   CParams2* pp = uni(pp_);
@@ -895,6 +941,8 @@ __device__ __noinline__ void run_bwd2(CParams2* pp_, DenPersistCtl* ctl_, DenPer
   load_frame_regs<STREAM>(o, rank, fr, L.table);
   DmaPlan plan;
   plan.init(o, L.table);
+  typename std::conditional<DIRECT, DirectRegs, NoDirect>::type dr;
+  if constexpr (DIRECT) load_direct_regs(o, rank, dr);
   const int row0 = o.row_begin[rank], nrows = o.row_begin[rank + 1] - row0;
   const int vfirst = d.voff[row0], nvirt = d.voff[row0 + nrows] - vfirst;     // own virtual states: a contiguous range
   RowSpan rs;
@@ -905,14 +953,17 @@ __device__ __noinline__ void run_bwd2(CParams2* pp_, DenPersistCtl* ctl_, DenPer
   if constexpr (STREAM) stream_init(o, rank, st);
   if (tid < kSegs * kPW) L.wcrow[tid] = o.wcrow[(size_t)rank * kSegs * kPW + tid];
   int st_v0[PSPT], st_v1[PSPT]; float st_pl[PSPT], st_pi[PSPT]; bool st_ok[PSPT];
+  int st_p0[PSPT];                         // DIRECT: vector position of the own state's first virtual state (the others: o.pos)
 #pragma unroll
   for (int i = 0; i < PSPT; ++i) {
     const int r = tid + i * kPT;
     st_ok[i] = r < nrows;
     st_v0[i] = st_v1[i] = 0; st_pl[i] = st_pi[i] = 0.f;
+    st_p0[i] = 0;
     if (st_ok[i]) {
       const int s = row0 + r;
       st_v0[i] = d.voff[s] - vfirst; st_v1[i] = d.voff[s + 1] - vfirst; st_pl[i] = d.loop_prob[s]; st_pi[i] = d.pi[s];
+      if constexpr (DIRECT) st_p0[i] = o.pos[vfirst + st_v0[i]];
     }
   }
   // what an own virtual state contributes to the next frame's sums (virtual states are the forward layout's rows)
@@ -980,7 +1031,8 @@ __device__ __noinline__ void run_bwd2(CParams2* pp_, DenPersistCtl* ctl_, DenPer
       if (!st_ok[i]) continue;
       for (int q = st_v0[i]; q < st_v1[i]; ++q) {
         const float w = L.xown[q] * bh[i];
-        ring_store(ring_n + q, w);
+        if constexpr (DIRECT) ring_store(ring_n - vfirst + (q == st_v0[i] ? st_p0[i] : o.pos[vfirst + q]), w);
+        else ring_store(ring_n + q, w);
         pB = fmaf(w, L.leak[q], pB); pU = fmaf(w, L.aux[q], pU);
       }
       if (st_pl[i] > 0.f) { const float lp = st_pl[i] * xl_prev[i] * bh[i]; pB = fmaf(st_pi[i], lp, pB); pU += lp; }
@@ -1033,7 +1085,7 @@ __device__ __noinline__ void run_bwd2(CParams2* pp_, DenPersistCtl* ctl_, DenPer
     // the words this rank will publish two frames from now must read "not yet written" by then: reset here, before the
     // copies, long before the stores they have to precede (the waits of emit cover it)
     if (tid < 2 && publish) st_agent(word_of(pring, t + 2, rank, tid), __uint_as_float(kRingSentinel));   // (t-1) % 3 == (t+2) % 3
-    frame_rows<STREAM>(o, src_t, rank, rs, fr, plan, st, L, dp_, [&]() {
+    frame_rows<STREAM, DIRECT>(o, src_t, rank, rs, fr, plan, dr, st, L, dp_, [&]() {
       if (publish) stage_x();
       if (kLateHistory<STREAM> && t + 1 < T) history(t + 1);
       if (t >= 2) prefetch(t - 2);          // (xw is free again; xl_next becomes xl_prev at the end of the frame)
@@ -1050,6 +1102,7 @@ __device__ __noinline__ void run_bwd2(CParams2* pp_, DenPersistCtl* ctl_, DenPer
       vs[i] = 0.f;
       if (!st_ok[i]) continue;
       float v = row_val<STREAM>(L, cmask, tid + i * kPT);
+      if constexpr (DIRECT) v = dr.add_to(tid + i * kPT, v);
       if (st_pl[i] > 0.f) v += st_pl[i] * xl_cur[i] * bh[i];
       vs[i] = v;
       bh[i] = v * inv_c + lkr;
@@ -1136,11 +1189,13 @@ __global__ void __launch_bounds__(kPT) den_persist2_kernel(const DenPersist2Para
     // 2 * kPT of any of them: the per-state constants then take half the registers)
     if (p.task_dir[k] == 0) {
       // (three entries per thread since round 4: graphs of 33 - 49 k states have 1025 .. 1536 rows per rank)
-      if (p.fwd_stream) { if (p.pspt == 2) run_fwd2<true, 2>(pp, ctl, team, &nbar, g, T, rank, ring, pring); else if (p.pspt == 3) run_fwd2<true, 3>(pp, ctl, team, &nbar, g, T, rank, ring, pring); else run_fwd2<true, kPSPT>(pp, ctl, team, &nbar, g, T, rank, ring, pring); }
-      else { if (p.pspt == 2) run_fwd2<false, 2>(pp, ctl, team, &nbar, g, T, rank, ring, pring); else if (p.pspt == 3) run_fwd2<false, 3>(pp, ctl, team, &nbar, g, T, rank, ring, pring); else run_fwd2<false, kPSPT>(pp, ctl, team, &nbar, g, T, rank, ring, pring); }
+      if (p.fwd_stream) { if (p.pspt == 2) run_fwd2<true, 2, false>(pp, ctl, team, &nbar, g, T, rank, ring, pring); else if (p.pspt == 3) run_fwd2<true, 3, false>(pp, ctl, team, &nbar, g, T, rank, ring, pring); else run_fwd2<true, kPSPT, false>(pp, ctl, team, &nbar, g, T, rank, ring, pring); }
+      else if (p.fwd_direct) { if (p.pspt == 2) run_fwd2<false, 2, true>(pp, ctl, team, &nbar, g, T, rank, ring, pring); else if (p.pspt == 3) run_fwd2<false, 3, true>(pp, ctl, team, &nbar, g, T, rank, ring, pring); else run_fwd2<false, kPSPT, true>(pp, ctl, team, &nbar, g, T, rank, ring, pring); }
+      else { if (p.pspt == 2) run_fwd2<false, 2, false>(pp, ctl, team, &nbar, g, T, rank, ring, pring); else if (p.pspt == 3) run_fwd2<false, 3, false>(pp, ctl, team, &nbar, g, T, rank, ring, pring); else run_fwd2<false, kPSPT, false>(pp, ctl, team, &nbar, g, T, rank, ring, pring); }
     } else {
-      if (p.bwd_stream) { if (p.pspt == 2) run_bwd2<true, 2>(pp, ctl, team, &nbar, g, T, rank, ring, pring); else if (p.pspt == 3) run_bwd2<true, 3>(pp, ctl, team, &nbar, g, T, rank, ring, pring); else run_bwd2<true, kPSPT>(pp, ctl, team, &nbar, g, T, rank, ring, pring); }
-      else { if (p.pspt == 2) run_bwd2<false, 2>(pp, ctl, team, &nbar, g, T, rank, ring, pring); else if (p.pspt == 3) run_bwd2<false, 3>(pp, ctl, team, &nbar, g, T, rank, ring, pring); else run_bwd2<false, kPSPT>(pp, ctl, team, &nbar, g, T, rank, ring, pring); }
+      if (p.bwd_stream) { if (p.pspt == 2) run_bwd2<true, 2, false>(pp, ctl, team, &nbar, g, T, rank, ring, pring); else if (p.pspt == 3) run_bwd2<true, 3, false>(pp, ctl, team, &nbar, g, T, rank, ring, pring); else run_bwd2<true, kPSPT, false>(pp, ctl, team, &nbar, g, T, rank, ring, pring); }
+      else if (p.bwd_direct) { if (p.pspt == 2) run_bwd2<false, 2, true>(pp, ctl, team, &nbar, g, T, rank, ring, pring); else if (p.pspt == 3) run_bwd2<false, 3, true>(pp, ctl, team, &nbar, g, T, rank, ring, pring); else run_bwd2<false, kPSPT, true>(pp, ctl, team, &nbar, g, T, rank, ring, pring); }
+      else { if (p.pspt == 2) run_bwd2<false, 2, false>(pp, ctl, team, &nbar, g, T, rank, ring, pring); else if (p.pspt == 3) run_bwd2<false, 3, false>(pp, ctl, team, &nbar, g, T, rank, ring, pring); else run_bwd2<false, kPSPT, false>(pp, ctl, team, &nbar, g, T, rank, ring, pring); }
     }
     __syncthreads();
     if (s_abort) return;
@@ -1225,6 +1280,9 @@ int den_persist2_launch(pk2_den_graph* g, const DenParams& dp, const float* xv, 
   p.pspt = g->p2_cap <= 2 * kPT ? 2 : (g->p2_cap <= 3 * kPT ? 3 : kPSPT);
   p.fwd_stream = (!g->h_p2fwd.sends.empty() || g->h_p2fwd.K > 2) ? 1 : 0;
   p.bwd_stream = (!g->h_p2bwd.sends.empty() || g->h_p2bwd.K > 2) ? 1 : 0;
+  p.fwd_direct = (!p.fwd_stream && g->h_p2fwd.Rt < g->h_p2fwd.R) ? 1 : 0;
+  p.bwd_direct = (!p.bwd_stream && g->h_p2bwd.Rt < g->h_p2bwd.R) ? 1 : 0;
+  p.pi_pos = g->d_pi_pos;
   p.ntasks = den_persist_tasks(lengths_host, N, p.task_seq, p.task_dir);
   sc.ntasks = 0;
   if (p.ntasks == 0) { *ran = true; return PK2_OK; }

@@ -587,6 +587,88 @@ static bool persist2_lists(int64_t A, int num_rows, const float* prob, const flo
   return true;
 }
 
+// The table prefix of an ordering (chain_internal.h: kDirectDeg, kDirect): which entries of the vector the table keeps, the
+// position of every entry, and the arcs split into those that gather below Rt (key / idx / prob / piprob, idx = POSITIONS)
+// and the direct ones (indices into the full arc list).  The ranks (h.row_begin) are those of the full arc list.
+struct P2Split {
+  int Rt = 0, table_entries = 0;
+  std::vector<int32_t> pos, key, idx;
+  std::vector<float> prob, piprob;
+  std::vector<int64_t> direct;
+};
+// The thread of its rank that owns row q in the row epilogue (run_fwd2: a thread per real state = group of rows; run_bwd2: a
+// thread per row): local index % kPT.  A direct arc is fetched and added by the owner of its row -- in registers, no LDS.
+static inline int persist2_owner(const HostPersist2& h, const int32_t* group_of_row, int rank, int q) {
+  return (group_of_row ? group_of_row[q] - h.grp_begin[rank] : q - h.row_begin[rank]) % kPT;
+}
+// false: nothing to leave out -- the prefix would not be shorter than the vector by a whole 256-entry DMA row.
+static bool persist2_table_split(int64_t A, const int32_t* key, const int32_t* idx, const float* prob, const float* piprob, int R,
+                                 const int32_t* group_of_row, const HostPersist2& h, P2Split* sp) {
+  const int full_rows = (R + 255) / 256;
+  std::vector<int32_t> cnt(R, 0);
+  for (int64_t i = 0; i < A; ++i) cnt[idx[i]]++;
+  std::vector<char> tab(R);
+  for (int e = 0; e < R; ++e) tab[e] = cnt[e] > kDirectDeg;
+  const int num_rows = h.row_begin[kPR];
+  std::vector<int32_t> slot_of(num_rows, 0);             // rank * kPT + owner thread of a row
+  for (int r = 0; r < kPR; ++r)
+    for (int q = h.row_begin[r]; q < h.row_begin[r + 1]; ++q) slot_of[q] = r * kPT + persist2_owner(h, group_of_row, r, q);
+  std::vector<int32_t>& pos = sp->pos;
+  pos.assign(R, 0);
+  for (;;) {
+    int nt = 0;
+    for (int e = 0; e < R; ++e) nt += tab[e];
+    const int Rt = std::max(256, (nt + 255) / 256 * 256);
+    if (Rt / 256 >= full_rows) return false;
+    int pt = 0, pn = nt;
+    for (int e = 0; e < R; ++e) pos[e] = tab[e] ? pt++ : pn++;
+    sp->Rt = Rt; sp->table_entries = nt;
+    // a thread over the cap: the most-read of the entries its direct arcs gather go back into the table until it fits
+    std::vector<std::pair<int32_t, int32_t>> mine;      // (thread slot, entry) of every direct arc
+    for (int64_t i = 0; i < A; ++i) if (pos[idx[i]] >= Rt) mine.push_back({slot_of[key[i]], idx[i]});
+    std::stable_sort(mine.begin(), mine.end(), [&](const std::pair<int32_t, int32_t>& x, const std::pair<int32_t, int32_t>& y) {
+      return x.first != y.first ? x.first < y.first : cnt[x.second] > cnt[y.second];
+    });
+    bool fits = true;
+    for (size_t k = 0; k < mine.size();) {
+      size_t e = k;
+      while (e < mine.size() && mine[e].first == mine[k].first) ++e;
+      if (e - k > (size_t)kDirect) {
+        fits = false;
+        for (size_t m = k; m + kDirect < e; ++m) tab[mine[m].second] = 1;
+      }
+      k = e;
+    }
+    if (fits) break;
+  }
+  sp->key.clear(); sp->idx.clear(); sp->prob.clear(); sp->piprob.clear(); sp->direct.clear();
+  for (int64_t i = 0; i < A; ++i) {
+    if (pos[idx[i]] >= sp->Rt) { sp->direct.push_back(i); continue; }
+    sp->key.push_back(key[i]); sp->idx.push_back(pos[idx[i]]); sp->prob.push_back(prob[i]); sp->piprob.push_back(piprob[i]);
+  }
+  return !sp->key.empty();
+}
+
+// The direct arcs as records of the threads that own their rows (at most kDirect each: persist2_table_split).
+static void persist2_direct(const P2Split& sp, const int32_t* key, const int32_t* idx, const float* prob, const int32_t* group_of_row,
+                            HostPersist2* h) {
+  h->dprob.assign((size_t)kPR * kDirect * kPT, 0.f);
+  h->dpr.assign((size_t)kPR * kDirect * kPT, 0xffff0000u);      // (no arc: probability 0, position 0 -- a table entry --, no row)
+  h->ndirect = (int64_t)sp.direct.size();
+  h->max_direct = 0;
+  std::vector<int32_t> used((size_t)kPR * kPT, 0), per_rank(kPR, 0);
+  for (int64_t i : sp.direct) {
+    int r = 0;
+    while (key[i] >= h->row_begin[r + 1]) ++r;
+    const int tid = persist2_owner(*h, group_of_row, r, key[i]);
+    const int j = used[(size_t)r * kPT + tid]++;
+    const size_t at = ((size_t)r * kDirect + j) * kPT + tid;
+    h->dprob[at] = prob[i];
+    h->dpr[at] = (uint32_t)sp.pos[idx[i]] | ((uint32_t)(key[i] - h->row_begin[r]) << 16);
+    h->max_direct = std::max(h->max_direct, ++per_rank[r]);
+  }
+}
+
 // Both orderings of the persistent layout.  fkey / fidx: forward ordering (rows = virtual destination states,
 // gathering source states); bkey / bidx: backward ordering (rows = source states, gathering virtual destination states).
 static void build_persist2(pk2_den_graph* g, int64_t A2, const int32_t* arc_v, const int32_t* src2, const float* prob2,
@@ -643,28 +725,32 @@ static void build_persist2(pk2_den_graph* g, int64_t A2, const int32_t* arc_v, c
   // per frame, in microseconds: what the arcs of the two resident passes cost with row-end code at 64 / estep places
   // (measured for 1 and 2 on the BASELINE graph), a streamed piece, a segment's extra barrier
   auto arcs_us = [](int e) { return e == 1 ? 3.1 : e == 2 ? 1.8 : e == 4 ? 1.55 : 1.45; };
-  for (int which = 0; which < 2; ++which) {
-    HostPersist2& h = which == 0 ? f : b;
-    const int rows = which == 0 ? V : S, R = which == 0 ? S : V;
-    const int32_t* key = which == 0 ? arc_v : src2;
-    const int32_t* idx = which == 0 ? src2 : arc_v;
-    if (!persist2_chunks(A2, idx, R, rows, (int)tcap, &h)) { if (getenv("PK2_DP2_DEBUG")) fprintf(stderr, "persist2: bail at line %d\n", __LINE__); f.ok = b.ok = false; return; }
-    std::vector<int64_t> ptr(rows + 1, 0);
-    for (int64_t i = 0; i < A2; ++i) ptr[key[i] + 1]++;
+  // The table prefix (chain_internal.h: kDirectDeg) is for the fully resident form with nothing forced: an
+  // explicit state order or any of the layout variables keeps the whole vector in the table, as PK2_DP2_TABLE=full does.
+  bool prefix_ok = !getenv("PK2_DEN_ORDER") && !getenv("PK2_DP2_RES") && !getenv("PK2_DP2_TCAP") && !getenv("PK2_DP2_SHARED") &&
+                   !getenv("PK2_DP2_ROWARRAYS");
+  if (const char* env = getenv("PK2_DP2_TABLE")) prefix_ok = prefix_ok && strcmp(env, "full") != 0;
+  struct ArcSet { int64_t A; const int32_t* key; const int32_t* idx; const float* prob; const float* piprob; };
+  struct RowIndex { std::vector<int64_t> ptr, perm; };
+  auto index_rows = [](const ArcSet& a, int rows, RowIndex* out) {
+    std::vector<int64_t>& ptr = out->ptr; std::vector<int64_t>& perm = out->perm;
+    ptr.assign(rows + 1, 0);
+    for (int64_t i = 0; i < a.A; ++i) ptr[a.key[i] + 1]++;
     for (int r = 0; r < rows; ++r) ptr[r + 1] += ptr[r];
-    std::vector<int64_t> perm(A2);
-    {
-      std::vector<int64_t> cur(ptr.begin(), ptr.end() - 1);
-      for (int64_t i = 0; i < A2; ++i) perm[cur[key[i]]++] = i;
-    }
-    // the widest row padding without a streamed piece; if every width streams, the cheapest frame
+    perm.assign(a.A, 0);
+    std::vector<int64_t> cur(ptr.begin(), ptr.end() - 1);
+    for (int64_t i = 0; i < a.A; ++i) perm[cur[a.key[i]]++] = i;
+  };
+  // The widest row padding without a streamed piece; if every width streams, the cheapest frame.  0: no layout.
+  auto pick_estep = [&](const ArcSet& a, const RowIndex& ri, int rows, const HostPersist2& h, bool* resident) {
     int best_estep = 0; double best_cost = 1e30;
+    *resident = false;
     std::vector<uint8_t> list_of; std::vector<int32_t> lidx;
     for (int estep : {8, 4, 2, 1}) {        // sizing runs (no bank-aware deal)
       if ((forced > 0 && estep != forced) || res % estep != 0) continue;      // (a cut must fall between whole rows' slots)
       HostPersist2 cand = h;
-      if (!persist2_arc_lists(A2, idx, cand, estep, ptr, perm, &list_of, &lidx) ||
-          !persist2_lists(A2, rows, prob2, piprob2, ptr, perm, list_of, lidx, estep, res, false, &cand)) { if (getenv("PK2_DP2_DEBUG")) fprintf(stderr, "persist2: bail at line %d\n", __LINE__); f.ok = b.ok = false; return; }
+      if (!persist2_arc_lists(a.A, a.idx, cand, estep, ri.ptr, ri.perm, &list_of, &lidx) ||
+          !persist2_lists(a.A, rows, a.prob, a.piprob, ri.ptr, ri.perm, list_of, lidx, estep, res, false, &cand)) return 0;
       // (round 4: the FIRST streamed piece costs ~5 us per frame -- the streaming variant of the frame: zeroed row arrays,
       // spill reloads behind the piece loads -- and ~0.9 each after it (profiles/r04_den_sweep.txt: S = 30 k, 1.0 -> 1.5 M
       // arcs = 4 pieces: 7.75 -> 15.1); the old 0.3 + 0.6 per piece chose padded rows + one piece over unpadded rows)
@@ -675,12 +761,57 @@ static void build_persist2(pk2_den_graph* g, int64_t A2, const int32_t* arc_v, c
       // the pieces in flight)
       const double cost = arcs_us(estep) + (cand.max_pieces ? 4.5 + 0.9 * cand.max_pieces : 0.0);
       if (cost < best_cost) { best_cost = cost; best_estep = estep; }
-      if (cand.max_pieces == 0 && cand.K == 2) break;
+      if (cand.max_pieces == 0 && cand.K == 2) { *resident = true; break; }
     }
+    return best_estep;
+  };
+  auto lay_out = [&](const ArcSet& a, const RowIndex& ri, int rows, int estep, HostPersist2* h) {
+    std::vector<uint8_t> list_of; std::vector<int32_t> lidx;
+    return persist2_arc_lists(a.A, a.idx, *h, estep, ri.ptr, ri.perm, &list_of, &lidx) &&
+           persist2_lists(a.A, rows, a.prob, a.piprob, ri.ptr, ri.perm, list_of, lidx, estep, res, true, h);
+  };
+  for (int which = 0; which < 2; ++which) {
+    HostPersist2& h = which == 0 ? f : b;
+    const int rows = which == 0 ? V : S, R = which == 0 ? S : V;
+    const ArcSet full{A2, which == 0 ? arc_v : src2, which == 0 ? src2 : arc_v, prob2, piprob2};
+    if (!persist2_chunks(A2, full.idx, R, rows, (int)tcap, &h)) { if (getenv("PK2_DP2_DEBUG")) fprintf(stderr, "persist2: bail at line %d\n", __LINE__); f.ok = b.ok = false; return; }
+    RowIndex ri;
+    index_rows(full, rows, &ri);
+    bool resident = false;
+    const int best_estep = pick_estep(full, ri, rows, h, &resident);
     if (best_estep == 0) { if (getenv("PK2_DP2_DEBUG")) fprintf(stderr, "persist2: bail at line %d\n", __LINE__); f.ok = b.ok = false; return; }
-    if (!persist2_arc_lists(A2, idx, h, best_estep, ptr, perm, &list_of, &lidx) ||
-        !persist2_lists(A2, rows, prob2, piprob2, ptr, perm, list_of, lidx, best_estep, res, true, &h)) { f.ok = b.ok = false; return; }
-    if (getenv("PK2_DP2_DEBUG")) fprintf(stderr, "persist2: %s rows padded to %d slots, %d table chunks, at most %d streamed pieces per rank\n", which == 0 ? "fwd" : "bwd", best_estep, h.K, h.max_pieces);
+    // The table prefix: where the graph has entries to leave out, and the layout is fully resident with the whole vector
+    // (two back-to-back chunks, no streamed piece) and with the prefix.
+    bool done = false;
+    P2Split sp;
+    if (prefix_ok && resident && h.flexible && persist2_table_split(full.A, full.key, full.idx, full.prob, full.piprob, R, which == 0 ? vstate : nullptr, h, &sp)) {
+      HostPersist2 hp = h;
+      const ArcSet tab{(int64_t)sp.key.size(), sp.key.data(), sp.idx.data(), sp.prob.data(), sp.piprob.data()};
+      RowIndex rt;
+      index_rows(tab, rows, &rt);
+      bool res_p = false;
+      int ep = 0;
+      if (persist2_chunks(tab.A, tab.idx, sp.Rt, rows, (int)tcap, &hp) && hp.flexible && (ep = pick_estep(tab, rt, rows, hp, &res_p)) != 0 &&
+          res_p && lay_out(tab, rt, rows, ep, &hp)) {
+        // the chunks cover [0, Rt); the vector, the LDS table and the per-row constants of the graph stay what they are
+        hp.R = R; hp.tfloats = h.tfloats; hp.Rt = sp.Rt; hp.table_entries = sp.table_entries;
+        hp.pos = sp.pos;
+        for (int q = 0; q < rows; ++q) {
+          double leak = 0.0, psum = 0.0;
+          for (int64_t k = ri.ptr[q]; k < ri.ptr[q + 1]; ++k) { leak += (double)piprob2[ri.perm[k]]; psum += (double)prob2[ri.perm[k]]; }
+          hp.row_leak[q] = (float)leak; hp.row_psum[q] = (float)psum;
+        }
+        persist2_direct(sp, full.key, full.idx, full.prob, which == 0 ? vstate : nullptr, &hp);
+        h = hp;
+        done = true;
+        if (getenv("PK2_DP2_DEBUG")) fprintf(stderr, "persist2: %s table prefix %d of %d entries, %lld direct arcs (at most %d per rank)\n", which == 0 ? "fwd" : "bwd", h.Rt, R, (long long)h.ndirect, h.max_direct);
+      }
+    }
+    if (!done) {
+      if (!lay_out(full, ri, rows, best_estep, &h)) { f.ok = b.ok = false; return; }
+      h.Rt = R; h.table_entries = R;
+    }
+    if (getenv("PK2_DP2_DEBUG")) fprintf(stderr, "persist2: %s rows padded to %d slots, %d table chunks, at most %d streamed pieces per rank\n", which == 0 ? "fwd" : "bwd", h.estep, h.K, h.max_pieces);
   }
   if (!(f.ok && b.ok)) { if (getenv("PK2_DP2_DEBUG")) fprintf(stderr, "persist2: bail at line %d\n", __LINE__); f.ok = b.ok = false; return; }
   g->p2_cap = cap;
@@ -865,6 +996,11 @@ static int upload_persist2(pk2_den_graph* g, const HostPersist2& h, DevPersist2*
   if ((rc = upload_vec(g, h.row_leak, &d->row_leak))) return rc;
   if ((rc = upload_vec(g, h.row_psum, &d->row_psum))) return rc;
   d->estep = h.estep; d->K = h.K; d->R = h.R;
+  if (h.Rt < h.R) {
+    if ((rc = upload_vec(g, h.pos, &d->pos))) return rc;
+    if ((rc = upload_vec(g, h.dprob, &d->dprob))) return rc;
+    if ((rc = upload_vec(g, h.dpr, &d->dpr))) return rc;
+  }
   for (int c = 0; c <= kMaxChunks; ++c) d->cbeg[c] = h.cbeg[c];
   for (int c = 0; c < kMaxChunks; ++c) d->lds_off[c] = h.lds_off[c];
   return PK2_OK;
@@ -915,6 +1051,11 @@ int den_upload(pk2_den_graph* g) {
     if ((rc = upload_vec(g, pi_pad, &dpi))) return rc;
   }
   g->d_pi = const_cast<float*>(dpi);
+  if (g->h_p2fwd.ok && g->h_p2fwd.Rt < g->h_p2fwd.R) {      // the first frame's alpha where the forward recursion copies it from
+    std::vector<float> pi_pos((g->pi.size() + 255) / 256 * 256 + 256, 0.f);
+    for (size_t s = 0; s < g->pi.size(); ++s) pi_pos[g->h_p2fwd.pos[s]] = g->pi[s];
+    if ((rc = upload_vec(g, pi_pos, &g->d_pi_pos))) return rc;
+  }
   g->uploaded = true;
   return PK2_OK;
 }
@@ -1061,5 +1202,25 @@ extern "C" int pk2_den_graph_debug_persist2(const pk2_den_graph* g, int which, i
   cp(wcrow, h.wcrow.data(), h.wcrow.size() * 4); cp(row_begin, h.row_begin.data(), h.row_begin.size() * 4);
   cp(grp_begin, h.grp_begin.data(), h.grp_begin.size() * 4); cp(row_leak, h.row_leak.data(), h.row_leak.size() * 4);
   cp(row_psum, h.row_psum.data(), h.row_psum.size() * 4);
+  return PK2_OK;
+}
+
+// Test / reporting hook: the table prefix of an ordering (chain_internal.h: kDirectDeg).  info[8] = {Rt, R, entries chosen for
+// the table, direct arcs, most direct arcs of a rank, kDirect, kDirectDeg, kPT}; pos[R] = position of every entry in the
+// published vector; dprob / dpr [kPR][kDirect][kPT] = the direct-arc records (probability; position | rank-local row << 16).
+// Rt == R: the whole vector is the table, pos is the identity and there are no records.  The arrays may be null.
+extern "C" int pk2_den_graph_debug_persist2_table(const pk2_den_graph* g, int which, int32_t* info, int32_t* pos, float* dprob,
+                                                  uint32_t* dpr) {
+  PK2_REQUIRE(g && (which == 0 || which == 1) && info, "den graph debug: bad arguments");
+  const HostPersist2& h = which == 0 ? g->h_p2fwd : g->h_p2bwd;
+  const bool prefix = h.ok && h.Rt < h.R;
+  const int32_t v[8] = {h.ok ? h.Rt : 0, h.ok ? h.R : 0, h.ok ? h.table_entries : 0, prefix ? (int32_t)h.ndirect : 0, prefix ? h.max_direct : 0,
+                        kDirect, kDirectDeg, kPT};
+  std::copy(v, v + 8, info);
+  if (!h.ok) return PK2_OK;
+  if (pos) for (int e = 0; e < h.R; ++e) pos[e] = prefix ? h.pos[e] : e;
+  const size_t n = (size_t)kPR * kDirect * kPT;
+  if (dprob) { if (prefix) memcpy(dprob, h.dprob.data(), n * 4); else memset(dprob, 0, n * 4); }
+  if (dpr) { if (prefix) memcpy(dpr, h.dpr.data(), n * 4); else memset(dpr, 0, n * 4); }
   return PK2_OK;
 }

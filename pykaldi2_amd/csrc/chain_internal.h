@@ -96,6 +96,13 @@ constexpr int kQ = kPK / 2;             // register slots per thread of one resi
 constexpr int kSP = 8;                  // slots per thread of a streamed piece
 constexpr int kMaxChunks = 6;
 constexpr int kSegs = 2 + kMaxChunks;   // row-sum segments of a frame: pass A, pass B, streamed segment of chunk 0 .. K-1
+// Table prefix.  An entry of the vector that at most kDirectDeg arcs gather from does not have to be copied
+// into every CU's LDS in every frame: the published vector gets a position order of its own -- the entries that more arcs
+// read first ("table", positions [0, Rt), whole 256-entry DMA rows), the rest behind them, the caller's order kept inside each
+// part -- and only [0, Rt) is copied.  An arc whose entry lies at or beyond Rt is a DIRECT arc of the rank that owns its row:
+// a thread fetches the entry from the vector in L2 and adds prob x value to the row's sum, at most kDirect arcs per thread.
+constexpr int kDirectDeg = 1;
+constexpr int kDirect = 2;
 struct HostPersist2 {
   bool ok = false;
   int estep = 1;
@@ -123,6 +130,14 @@ struct HostPersist2 {
   std::vector<int32_t> wcrow;            // [(r*kSegs + seg)*kPW + w] rank-local row open after the last slot of wave w (-1: none)
   std::vector<int32_t> row_begin, grp_begin;
   std::vector<float> row_leak, row_psum;
+  // table prefix: Rt == R and no direct arcs = the whole vector is the table (every layout but the fully resident one)
+  int Rt = 0;                            // positions [0, Rt) are copied into LDS; cbeg[K] == Rt
+  int table_entries = 0;                 // entries chosen for the table (Rt rounds them up to whole DMA rows)
+  int max_direct = 0;                    // most direct arcs of one rank
+  int64_t ndirect = 0;
+  std::vector<int32_t> pos;              // [R] position of an entry in the published vector (empty: the identity)
+  std::vector<float> dprob;              // [(r*kDirect + j)*kPT + tid] probability of a direct arc (0: none)
+  std::vector<uint32_t> dpr;             // [(r*kDirect + j)*kPT + tid] vector position | rank-local row << 16
 };
 struct DevPersist2 {
   const float* prob = nullptr; const uint32_t* idx2 = nullptr; const uint32_t* ends = nullptr; const int32_t* first_row = nullptr;
@@ -134,6 +149,7 @@ struct DevPersist2 {
   int estep = 1, K = 0, R = 0;
   int cbeg[kMaxChunks + 1] = {0};
   int lds_off[kMaxChunks] = {0};
+  const int32_t* pos = nullptr; const float* dprob = nullptr; const uint32_t* dpr = nullptr;      // table prefix (null: none)
 };
 
 }  // namespace pk2
@@ -177,6 +193,7 @@ struct pk2_den_graph {
   int device = -1;
   pk2::DevOrdering fwd, bwd, gam, fwdv, bwdv;
   float* d_pi = nullptr;
+  const float* d_pi_pos = nullptr;        // pi at the forward table-prefix positions (null: the prefix is the whole vector)
   std::vector<void*> allocs;
 };
 
