@@ -8,6 +8,9 @@ latgen-faster-mapped reads), running on libpk2hip.so: fbank + CMN + BLSTM forwar
 
 Checkpoints of the reference's NnetAM(LSTMStack) (keys `nnet.lstm.*`) and of LSTMAM (`lstm.*`), with or without
 DataParallel's `module.` prefix, load unchanged.  -synthetic draws seeded utterances and uses uniform priors.
+-array_frontend mvdr | wpe_mvdr reads every channel of the recordings (the 7-channel LibriCSS evaluation) and puts each
+utterance through (WPE ->) cGMM masks -> MVDR on the device before the filterbank (pykaldi2_amd.cgmm.ArrayFrontEnd); with
+-synthetic the utterances are first recorded by a simulated 7-microphone array.
 """
 import argparse
 import json
@@ -19,7 +22,42 @@ import torch as th
 import yaml
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from pykaldi2_amd import data, fbank, kaldi_io, lstm, se  # noqa: E402
+from pykaldi2_amd import cgmm, data, fbank, kaldi_io, lstm, se  # noqa: E402
+
+
+def synthetic_array(wav, index, dev):
+    """A seeded 7-channel recording of a synthetic utterance, so that -array_frontend runs without data: the utterance and
+    a directional noise in a sampled room (rirgen, the circular array of beamform.array_geometry()), mixed by
+    MultiSourceSimulator.  (C, n) CUDA float32, n the utterance's length; numpy's generator is left as it was."""
+    from pykaldi2_amd import _lib, beamform, rirgen, simulation, synth
+    state = np.random.get_state()
+    np.random.seed(20161 + index)
+    try:
+        room, t60, mic, src = rirgen.sample_online_room((0.1, 0.5), 2, mic_positions=beamform.array_geometry())
+        b = rirgen.rirgen_batch([dict(room=room, source_loc=src, mic_loc=mic, t60=t60)], device=dev)
+        rirs, dl = b.rirs[0], b.delays[0]
+        noise = np.ascontiguousarray(synth.waveform(np.random.default_rng(977 + index), wav.shape[0] / 16000.0 + 0.5), np.float32)
+        sim = simulation.MultiSourceSimulator(use_rir=True, use_noise=True, n_source_range=(1, 1))
+        mixed = sim([_lib.h2d(wav, dev)], [_lib.h2d(noise, dev)], [rirs[0]], [rirs[1]], rir_delays=[dl[0], dl[1]])[0]
+    finally:
+        np.random.set_state(state)
+    n = wav.shape[0]
+    if mixed.shape[1] < n:
+        mixed = th.nn.functional.pad(mixed, (0, n - mixed.shape[1]))
+    return mixed[:, :n].contiguous()
+
+
+def enhance(frontend, arrays, dev):
+    """arrays: host or device (C, n) signals of one batch -> list of device float32 (n,): the array front end on the
+    utterances with more than one channel, grouped by their channel count (one launch per stage and group); a
+    one-channel signal passes through."""
+    arrays = [a if isinstance(a, th.Tensor) else th.from_numpy(a).to(dev) for a in arrays]
+    out = [None] * len(arrays)
+    for C in sorted(set(a.shape[0] for a in arrays)):
+        idx = [i for i, a in enumerate(arrays) if a.shape[0] == C]
+        for i, y in zip(idx, frontend([arrays[i] for i in idx])):
+            out[i] = y
+    return out
 
 
 def main():
@@ -36,6 +74,9 @@ def main():
     parser.add_argument("-frame_subsampling_factor", default=1, type=int, help="the factor to subsample the features (decode.py)")
     parser.add_argument("-gpuid", default=0, type=int, help="GPU ID (decode.py)")
     parser.add_argument("-synthetic", type=int, default=0, help="dump this many seeded synthetic utterances instead")
+    parser.add_argument("-array_frontend", default="none", choices=list(cgmm.FRONT_ENDS),
+                        help="multi-channel front end in front of the filterbank: mvdr (cGMM masks -> MVDR) or wpe_mvdr (WPE "
+                             "first); every channel of a WAV is read (default none: channel 0)")
     args = parser.parse_args()
 
     with open(args.config) as f:
@@ -61,9 +102,22 @@ def main():
     transform = None
     if args.transform and os.path.isfile(args.transform):
         transform = fbank.GlobalMeanVarianceNormalization.load(args.transform)
+    frontend = cgmm.ArrayFrontEnd(args.array_frontend) if args.array_frontend != "none" else None
     if args.synthetic:
         source = data.SyntheticSource(P, seed=11)
         utts = [source.draw() for _ in range(args.synthetic)]
+        if frontend:
+            utts = [(synthetic_array(u[0], i, dev),) + tuple(u[1:]) for i, u in enumerate(utts)]
+    elif frontend:
+        source = data.ZipWavSource([dict(wav=args.data_path)])
+        utts = []
+        for z, m, u, _, _ in source.items:
+            source._read(z, m)                        # opens the archive and checks the rate
+            utts.append((data.decode_wav_channels(source._zips[z].read(m))[0], None, None, u))
+        if any(u[0].shape[0] == 1 for u in utts):
+            import warnings
+            warnings.warn("-array_frontend %s: %d of %d files have one channel and pass through as they are"
+                          % (args.array_frontend, sum(u[0].shape[0] == 1 for u in utts), len(utts)))
     else:
         source = data.ZipWavSource([dict(wav=args.data_path)])
         utts = [(source._read(z, m), None, None, u) for z, m, u, _, _ in source.items]
@@ -73,8 +127,13 @@ def main():
     with th.no_grad(), kaldi_io.MatrixWriter("ark:" + args.out_file) as llout:
         for i in range(n_batches):
             chunk = utts[i * args.batch_size:(i + 1) * args.batch_size]
-            lens = [u[0].shape[0] for u in chunk]
-            wav = th.from_numpy(np.concatenate([u[0] for u in chunk])).to(dev)
+            if frontend:
+                waves = enhance(frontend, [u[0] for u in chunk], dev)
+                lens = [int(w.shape[0]) for w in waves]
+                wav = th.cat(waves)
+            else:
+                lens = [u[0].shape[0] for u in chunk]
+                wav = th.from_numpy(np.concatenate([u[0] for u in chunk])).to(dev)
             feats, frames, row_off = fb(wav, lens)
             if transform is not None:
                 feats = transform(feats)

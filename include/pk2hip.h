@@ -678,7 +678,59 @@ int pk2_wpe(const float* const* spec, const int32_t* frames, int32_t B, int32_t 
             void* stream);
 
 /* ------------------------------------------------------------------ *
- * Fused log-softmax + NLL + gradient.  Replaces nn.CrossEntropyLoss
+ * cGMM mask estimation of a ragged minibatch (csrc/cgmm.hip; no counterpart in the reference): per bin an
+ * EM over the frames of a mixture of K complex Gaussians y ~ N(0, phi_k[t] R_k) with weights alpha_k (Higuchi et al. 2016),
+ * optionally guided by a per-class frame activity.  B utterances with their own frame counts N_b and common C channels
+ * (1 .. PK2_BF_MAX_CHANNELS), F bins and K classes (2 .. PK2_BF_MAX_MASKS).  Spectra are (C, N_b, F, 2) as for the
+ * beamformer; masks, `init`, `lam` and `phi` planes are f32 (K, N_b, F); `activity` is f32 (K, N_b), >= 0, or NULL (all
+ * ones).  `spec`, `init`, `activity`, `masks`, `lam` and `phi` are HOST arrays of B device pointers, `frames` is a HOST
+ * array; more than PK2_BF_MAX_UTTS utterances take one launch per stage per PK2_BF_MAX_UTTS.  R: device (B, K, F, C, C, 2),
+ * exactly Hermitian with a real diagonal; log_alpha: device (B, K, F).  No atomics, no host synchronisation: a result is
+ * bit-identical from run to run and independent of the other utterances of its call.  Bad arguments return
+ * PK2_ERR_INVALID before the device is touched.
+ *
+ * M-step (pk2_cgmm_update): R_k[f] = sum_t (lam_k / phi_k) y y^H / max(sum_t lam_k, 1e-10), summed as pk2_bf_cov sums;
+ * alpha_k[f] = max(sum_t lam_k / max(N_act, 1), 1e-10), N_act the number of frames with an active class.
+ *
+ * pk2_cgmm_init: init == NULL (K = 2): R_0 = sum_t y y^H / N, R_1 = (Re tr R_0 / C) I, alpha = 1 / 2; else the M-step
+ * with lam = init and phi = 1.
+ *
+ * pk2_cgmm_factor: R' = R + (diag_load Re tr R / C + 1e-10) I = L L^H in float64; linv (B, K, C (C + 1), F): the lower
+ * triangle of L^-1 row by row as (re, im) planes over the bins, rounded once; bias (B, K, F) = log alpha - 2 sum log L_jj.
+ * bad (B, K, F) int32: 1 where R is not finite or R' not positive definite (then L^-1 = I, bias = 0); nonfinite[b]: any.
+ *
+ * pk2_cgmm_posteriors: z = L^-1 y (fmaf chains, ascending column), q = sum |z_j|^2, phi_k = max(q / C, 1e-10),
+ * l_k = bias_k + log a_k[t] - C log phi_k, lam = softmax_k l_k.  A class with a_k[t] = 0 gets lam = 0, a frame without an
+ * active class lam = 0 for every class; a bin with a bad class lam = 1 / K on every frame.  ll[b] = the float64 sum over
+ * t and f of max_k l_k + log sum_k exp(l_k - max) (frames without an active class and bad bins add nothing).
+ *
+ * pk2_cgmm: init, then iters (1 .. PK2_CGMM_MAX_ITERS) times factor, posteriors, M-step.  masks_b (K, N_b, F): the lam of
+ * the last posteriors; R and log_alpha: the M-step of those; ll: device f64 (B, iters); nonfinite[b] = 1 when a bin of any
+ * iteration was bad.  purity != 0 (K = 2): per bin, class 0 becomes the class with the larger ||R_k||_F^2 / (Re tr R_k)^2
+ * (a tie keeps the order; a swap exchanges masks, R and log_alpha of that bin).
+ *
+ * work: device memory of pk2_cgmm_workspace_bytes(frames, B, C, F, K) bytes, enough for every entry on that minibatch; 0
+ * for arguments the entries would refuse.
+ * ------------------------------------------------------------------ */
+#define PK2_CGMM_MAX_ITERS 32
+size_t pk2_cgmm_workspace_bytes(const int32_t* frames, int32_t B, int32_t C, int32_t F, int32_t K);
+int pk2_cgmm_init(const float* const* spec, const float* const* init, const float* const* activity, const int32_t* frames,
+                  int32_t B, int32_t C, int32_t F, int32_t K, void* work, size_t work_bytes, float* R, float* log_alpha,
+                  void* stream);
+int pk2_cgmm_factor(const float* R, const float* log_alpha, int32_t B, int32_t C, int32_t F, int32_t K, double diag_load,
+                    float* linv, float* bias, int32_t* bad, int32_t* nonfinite, void* stream);
+int pk2_cgmm_posteriors(const float* const* spec, const float* const* activity, const int32_t* frames, int32_t B, int32_t C,
+                        int32_t F, int32_t K, const float* linv, const float* bias, const int32_t* bad, void* work,
+                        size_t work_bytes, float* const* lam, float* const* phi, double* ll, void* stream);
+int pk2_cgmm_update(const float* const* spec, const float* const* lam, const float* const* phi, const float* const* activity,
+                    const int32_t* frames, int32_t B, int32_t C, int32_t F, int32_t K, void* work, size_t work_bytes, float* R,
+                    float* log_alpha, void* stream);
+int pk2_cgmm(const float* const* spec, const float* const* init, const float* const* activity, const int32_t* frames, int32_t B,
+             int32_t C, int32_t F, int32_t K, int32_t iters, double diag_load, int32_t purity, void* work, size_t work_bytes,
+             float* const* masks, float* R, float* log_alpha, double* ll, int32_t* nonfinite, void* stream);
+
+/* ------------------------------------------------------------------ *
+ * Fused log-softmax + NLL + gradient. Replaces nn.CrossEntropyLoss
  * (ignore_index=-100; reduction mean: reference bin/train_ce.py:134,189;
  * reduction sum: bin/train_se.py:214,235).
  * loss_sum, count: device f32[1] / int32[1] accumulators (zeroed inside);

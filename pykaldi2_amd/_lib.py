@@ -64,6 +64,7 @@ BF_MAX_CHANNELS = 8      # PK2_BF_MAX_CHANNELS
 BF_MAX_MASKS = 4         # PK2_BF_MAX_MASKS
 BF_FRAMES_PER_PART = 32  # PK2_BF_FRAMES_PER_PART
 BF_REF_SNR = -1          # PK2_BF_REF_SNR
+CGMM_MAX_ITERS = 32      # PK2_CGMM_MAX_ITERS
 WPE_MAX_CHANNELS = 8     # PK2_WPE_MAX_CHANNELS
 WPE_MAX_ORDER = 80       # PK2_WPE_MAX_ORDER
 WPE_MAX_DELAY = 8        # PK2_WPE_MAX_DELAY
@@ -218,6 +219,16 @@ SIGNATURES = {
                                  C.POINTER(_vp), _vp]),
     "pk2_wpe": (C.c_int, [C.POINTER(_vp), C.POINTER(_i32), _i32, _i32, _i32, _i32, _i32, _i32, C.c_double, _vp, _sz,
                           C.POINTER(_vp), _vp, _vp]),
+    "pk2_cgmm_workspace_bytes": (_sz, [_vp, _i32, _i32, _i32, _i32]),
+    "pk2_cgmm_init": (C.c_int, [C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_i32), _i32, _i32, _i32, _i32, _vp, _sz,
+                                _vp, _vp, _vp]),
+    "pk2_cgmm_factor": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, C.c_double, _vp, _vp, _vp, _vp, _vp]),
+    "pk2_cgmm_posteriors": (C.c_int, [C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_i32), _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp,
+                                      _sz, C.POINTER(_vp), C.POINTER(_vp), _vp, _vp]),
+    "pk2_cgmm_update": (C.c_int, [C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_i32), _i32, _i32,
+                                  _i32, _i32, _vp, _sz, _vp, _vp, _vp]),
+    "pk2_cgmm": (C.c_int, [C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_i32), _i32, _i32, _i32, _i32, _i32,
+                           C.c_double, _i32, _vp, _sz, C.POINTER(_vp), _vp, _vp, _vp, _vp, _vp]),
     "pk2_softmax_ce_fwd_bwd": (C.c_int, [_vp, _i64, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _i64, _vp, _vp]),
     "pk2_softmax_ce_fwd_bwd_mean": (C.c_int, [_vp, _i64, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _i64, _vp]),
     "pk2_scale_inplace_ratio": (C.c_int, [_vp, _i64, _vp, _vp, _vp]),

@@ -27,6 +27,7 @@ from . import _lib
 MAX_CHANNELS, MAX_MASKS = _lib.BF_MAX_CHANNELS, _lib.BF_MAX_MASKS
 FRAMES_PER_PART = _lib.BF_FRAMES_PER_PART      # frames per workgroup of the covariance pass
 CONFIG_DEFAULTS = dict(n_mics=7, radius=0.0425, ref=0, diag_load=0.001)
+MASK_KEYS = ("mask", "cgmm_iterations")        # optional: present in beamform_config's result only when the mapping has one
 
 last_nonfinite = None      # CUDA int32 (B,) of the last mvdr_weights call: 1 where an utterance had a non-finite bin
 
@@ -201,12 +202,18 @@ class MaskBeamformer:
     of the speech mask and of the noise mask (None: 1 - speech_mask, from the same pass), MVDR weights, the weighted sum and
     the inverse STFT cut to n.  `batch` does it for a ragged list with one launch per beamforming stage (the STFT entries
     take one length per call).  `last_weights` ((F, C), or the list), `last_ref` and `last_nonfinite` (CUDA int32, one entry
-    per utterance) keep the last call's and are not read back."""
+    per utterance) keep the last call's and are not read back.  mask_estimator (cgmm.CgmmMaskEstimator, or any object
+    whose masks(list of spectra) returns one (speech mask, noise mask) per spectrum): with it speech_mask may be None and
+    both masks are estimated from the array spectrum; without it None is a ValueError.  Calls that pass masks never use it."""
 
-    def __init__(self, analyzer, ref=0, diag_load=1e-3):
+    def __init__(self, analyzer, ref=0, diag_load=1e-3, mask_estimator=None):
         self.analyzer = analyzer
         _ref_arg(ref, None, "MaskBeamformer")
         self.ref, self.diag_load = ref, _diag_load_arg(diag_load, "MaskBeamformer")
+        if mask_estimator is not None and not callable(getattr(mask_estimator, "masks", None)):
+            raise ValueError("MaskBeamformer: mask_estimator must have masks(list of spectra) -> list of (speech mask, noise "
+                             "mask), like cgmm.CgmmMaskEstimator")
+        self.mask_estimator = mask_estimator
         self.last_weights = self.last_ref = self.last_nonfinite = None
 
     def analyze(self, wav):
@@ -219,11 +226,21 @@ class MaskBeamformer:
         return torch.view_as_complex(simulation._stft_rows(list(wav.unbind(0)), a.fft_size, a.frame_len, a.frame_shift,
                                                            a._window(wav.device)))
 
-    def batch(self, wavs, speech_masks, noise_masks=None):
-        wavs, speech_masks = list(wavs), list(speech_masks)
-        if len(speech_masks) != len(wavs) or (noise_masks is not None and len(noise_masks) != len(wavs)):
-            raise ValueError("MaskBeamformer: one speech mask (and noise mask) per waveform")
-        specs = [self.analyze(x) for x in wavs]
+    def batch(self, wavs, speech_masks=None, noise_masks=None):
+        wavs = list(wavs)
+        if speech_masks is None:
+            if self.mask_estimator is None:
+                raise ValueError("MaskBeamformer: no speech mask and no mask_estimator")
+            if noise_masks is not None:
+                raise ValueError("MaskBeamformer: a noise mask without a speech mask")
+            specs = [self.analyze(x) for x in wavs]
+            pairs = self.mask_estimator.masks(specs)
+            speech_masks, noise_masks = [p[0] for p in pairs], [p[1] for p in pairs]
+        else:
+            speech_masks = list(speech_masks)
+            if len(speech_masks) != len(wavs) or (noise_masks is not None and len(noise_masks) != len(wavs)):
+                raise ValueError("MaskBeamformer: one speech mask (and noise mask) per waveform")
+            specs = [self.analyze(x) for x in wavs]
         if noise_masks is None:
             phi = spatial_covariance(specs, speech_masks, complement=True)
         else:
@@ -233,8 +250,8 @@ class MaskBeamformer:
         enhanced = apply_weights(specs, w)
         return [self.analyzer.synthesize(X)[:x.shape[1]] for X, x in zip(enhanced, wavs)]
 
-    def __call__(self, wav, speech_mask, noise_mask=None):
-        out = self.batch([wav], [speech_mask], None if noise_mask is None else [noise_mask])[0]
+    def __call__(self, wav, speech_mask=None, noise_mask=None):
+        out = self.batch([wav], None if speech_mask is None else [speech_mask], None if noise_mask is None else [noise_mask])[0]
         self.last_weights = self.last_weights[0]
         return out
 
@@ -254,7 +271,8 @@ def array_geometry(n_mics=7, radius=0.0425):
 
 def beamform_config(config):
     """data_config `beamform`: true (the defaults n_mics 7, radius 0.0425 m, ref 0, diag_load 0.001) or a mapping over them;
-    None when the key is absent or false.  Raises ValueError for a bad value and for a configuration that cannot honour the
+    None when the key is absent or false.  The mapping may also hold `mask: ideal | cgmm` (default ideal: the simulated
+    source's ideal mask; cgmm: masks estimated from the array spectrum, pykaldi2_amd.cgmm) and `cgmm_iterations` (10). Raises ValueError for a bad value and for a configuration that cannot honour the
     key: it needs `online_rir: true`, `use_reverb: true` and `simulation_prob` > 0.  Needs no GPU."""
     dc = config.get("data_config") or {}
     bf = dc.get("beamform")
@@ -265,9 +283,12 @@ def beamform_config(config):
     if not isinstance(bf, dict):
         raise ValueError("beamform: expected true or a mapping, got %r" % (bf,))
     for k in bf:
-        if k not in CONFIG_DEFAULTS:
-            raise ValueError("beamform: unknown key %r (known: %s)" % (k, ", ".join(CONFIG_DEFAULTS)))
+        if k not in CONFIG_DEFAULTS and k not in MASK_KEYS:
+            raise ValueError("beamform: unknown key %r (known: %s)" % (k, ", ".join(tuple(CONFIG_DEFAULTS) + MASK_KEYS)))
     out = dict(CONFIG_DEFAULTS, **bf)
+    if any(k in bf for k in MASK_KEYS):
+        from . import cgmm
+        out["mask"], out["cgmm_iterations"] = cgmm.cgmm_config(bf)
     n = out["n_mics"]
     if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 1 <= n <= MAX_CHANNELS:
         raise ValueError("beamform: n_mics must be an integer in [1, %d], got %r" % (MAX_CHANNELS, n))

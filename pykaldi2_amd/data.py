@@ -49,6 +49,17 @@ def decode_wav(data):
     return (pcm.astype(np.float32) / 32768.0), sr
 
 
+def decode_wav_channels(data):
+    """RIFF PCM16 -> (float32 (C, n) in [-1, 1), every channel of the file, and the sample rate): what an array front end
+    (bin/dump_loglikes.py -array_frontend) reads where decode_wav keeps channel 0."""
+    with wave.open(io.BytesIO(data)) as w:
+        assert w.getsampwidth() == 2, "only 16-bit PCM wav is supported"
+        n, ch = w.getnframes(), w.getnchannels()
+        pcm = np.frombuffer(w.readframes(n), dtype="<i2").reshape(-1, ch)
+        sr = w.getframerate()
+    return np.ascontiguousarray(pcm.T.astype(np.float32) / 32768.0), sr
+
+
 class ZipWavSource:
     def __init__(self, sources, data_path="", seed=0, rank=0, world=1):
         self.items = []   # (zip path, member, utt_id, labels, aux)
@@ -238,6 +249,7 @@ class SimulationPool:
                                               snr_range=snr_range)
         self._dev = {}
         self.beamform = dict(beamform) if beamform else None      # data_config `beamform` (beamform.beamform_config)
+        self.cgmm = None                                          # `beamform: {mask: cgmm}`: the masks' estimator
         if self.beamform:
             from . import beamform as bf
             if not self.online_rir:
@@ -247,6 +259,9 @@ class SimulationPool:
             self.sim_mc = simulation.SimpleSimulator(use_rir=True, use_noise=bool(self.noises), snr_range=snr_range,
                                                      mask_estimator=simulation.MaskEstimator(analyzer))
             self.beamformer = bf.MaskBeamformer(analyzer, self.beamform["ref"], self.beamform["diag_load"])
+            if self.beamform.get("mask", "ideal") == "cgmm":
+                from . import cgmm
+                self.cgmm = cgmm.CgmmMaskEstimator(analyzer, self.beamform.get("cgmm_iterations", 10))
         self.wpe = dict(wpe) if wpe else None                     # data_config `wpe` (dereverb.wpe_config)
         if self.wpe:
             from . import dereverb
@@ -262,7 +277,9 @@ class SimulationPool:
         picking one from the pool (pykaldi2_amd.rirgen), T60 ~ U[`t60_range`] (default [0.1, 0.5]); it wins over
         `rir_paths`.  `beamform` (true or a mapping, see pykaldi2_amd.beamform.beamform_config; needs `online_rir`,
         `use_reverb` and `simulation_prob` > 0, ValueError otherwise): a simulated utterance is recorded by a circular
-        array in the sampled room and comes back as the output of a mask-based MVDR beamformer.  `wpe` (true or a mapping,
+        array in the sampled room and comes back as the output of a mask-based MVDR beamformer; its masks are the simulated
+        source's ideal mask, or with `beamform: {mask: cgmm}` estimated from the array spectrum (pykaldi2_amd.cgmm,
+        `cgmm_iterations`, default 10), as they have to be on a recording.  `wpe` (true or a mapping,
         see pykaldi2_amd.dereverb.wpe_config; needs `use_reverb` and `simulation_prob` > 0, ValueError otherwise): a
         simulated utterance is dereverberated by WPE, as one channel, or with `beamform` on the array's spectrum in front of
         the beamformer."""
@@ -343,6 +360,18 @@ class SimulationPool:
         room, t60, mic, src = rirgen.sample_online_room(self.t60_range, n_src, mic_positions=self.mic_positions)
         b = rirgen.rirgen_batch([dict(room=room, source_loc=src, mic_loc=mic, t60=t60)], device=device)
         rirs, dl = b.rirs[0], b.delays[0]                      # (nsrc, C, k), (nsrc, C)
+        if self.cgmm is not None:
+            # mask: cgmm -- what a recording allows: no ideal mask is made, both masks come from the array spectrum (after
+            # WPE when that is on); the simulation draws what it draws with the ideal mask
+            mixed, _ = self.sim_mc(x, [noise] if noise is not None else None, rirs[0], [rirs[1]] if noise is not None else None,
+                                   normalize_gain=self.gain_norm, rir_delays=[dl[s] for s in range(n_src)])
+            from . import beamform as bf
+            spec = self.beamformer.analyze(mixed)
+            if self.wpe:
+                spec = self.dereverb.spectrum(spec)
+            phi = bf.spatial_covariance(spec, list(self.cgmm.masks(spec)))
+            w, _ = bf.mvdr_weights(phi[0], phi[1], self.beamformer.ref, self.beamformer.diag_load)
+            return self.beamformer.analyzer.synthesize(bf.apply_weights(spec, w))[:mixed.shape[1]]
         mixed, _, mask, _ = self.sim_mc(x, [noise] if noise is not None else None, rirs[0],
                                         [rirs[1]] if noise is not None else None, normalize_gain=self.gain_norm,
                                         rir_delays=[dl[s] for s in range(n_src)], gen_mask=True)
