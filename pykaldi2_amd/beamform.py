@@ -15,7 +15,6 @@ in device tensors.  Nothing is read back to the host.
   beamform_config(config) / require_beamform_config(config, prog)     the data_config key `beamform` (needs no GPU)
   array_geometry(n_mics, radius)                                      the (3, C) microphone offsets of that key
 """
-import ctypes as C
 import math
 import sys
 
@@ -23,6 +22,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._array import _as_list, _check_specs, _diag_load_arg, _frames, _table, analyze_channels
 
 MAX_CHANNELS, MAX_MASKS = _lib.BF_MAX_CHANNELS, _lib.BF_MAX_MASKS
 FRAMES_PER_PART = _lib.BF_FRAMES_PER_PART      # frames per workgroup of the covariance pass
@@ -30,41 +30,6 @@ CONFIG_DEFAULTS = dict(n_mics=7, radius=0.0425, ref=0, diag_load=0.001)
 MASK_KEYS = ("mask", "cgmm_iterations")        # optional: present in beamform_config's result only when the mapping has one
 
 last_nonfinite = None      # CUDA int32 (B,) of the last mvdr_weights call: 1 where an utterance had a non-finite bin
-
-
-def _table(tensors):
-    return (C.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
-
-
-def _frames(frames):
-    return (C.c_int32 * len(frames))(*frames)
-
-
-def _as_list(x):
-    """(list, was a list)"""
-    if isinstance(x, (list, tuple)):
-        if not x:
-            raise ValueError("beamform: the list of utterances is empty")
-        return list(x), True
-    return [x], False
-
-
-def _check_spec(spec, who, i):
-    if not (isinstance(spec, torch.Tensor) and spec.is_cuda and spec.dtype == torch.complex64 and spec.dim() == 3
-            and spec.is_contiguous() and spec.numel() > 0):
-        raise ValueError("%s: utterance %d: expected a contiguous CUDA complex64 (C, N, F) spectrum" % (who, i))
-    if spec.shape[0] > MAX_CHANNELS:
-        raise ValueError("%s: utterance %d has %d channels, at most %d" % (who, i, spec.shape[0], MAX_CHANNELS))
-    return spec
-
-
-def _check_common(specs, who):
-    C0, F0, dev = specs[0].shape[0], specs[0].shape[2], specs[0].device
-    for i, s in enumerate(specs):
-        if s.shape[0] != C0 or s.shape[2] != F0 or s.device != dev:
-            raise ValueError("%s: utterance %d is (C, F) = (%d, %d) on %s, the first one (%d, %d) on %s"
-                             % (who, i, s.shape[0], s.shape[2], s.device, C0, F0, dev))
-    return C0, F0, dev
 
 
 def _workspace(frames, B, Cn, F, K, complement, dev):
@@ -80,12 +45,10 @@ def spatial_covariance(spec, masks, complement=False):
     (K, F, C, C), exactly Hermitian; complement=True (one mask m): (2, F, C, C), for m and for 1 - m, from one pass.
     Lists of both (one entry per utterance): one launch, and a list of results."""
     _lib.require_gpu()
-    specs, many = _as_list(spec)
+    specs, many, Cn, F, dev = _check_specs(spec, "spatial_covariance", MAX_CHANNELS)
     mlist = list(masks) if many else [masks]
     if len(mlist) != len(specs):
         raise ValueError("spatial_covariance: %d spectra, %d entries of masks" % (len(specs), len(mlist)))
-    specs = [_check_spec(s, "spatial_covariance", i) for i, s in enumerate(specs)]
-    Cn, F, dev = _check_common(specs, "spatial_covariance")
     rows, K = [], None
     for i, (s, m) in enumerate(zip(specs, mlist)):
         if isinstance(m, torch.Tensor):
@@ -129,13 +92,6 @@ def _ref_arg(ref, Cn, who):
     return int(ref)
 
 
-def _diag_load_arg(diag_load, who):
-    if isinstance(diag_load, bool) or not isinstance(diag_load, (int, float, np.integer, np.floating)) \
-            or not math.isfinite(float(diag_load)) or float(diag_load) < 0:
-        raise ValueError("%s: diag_load must be a finite number >= 0, got %r" % (who, diag_load))
-    return float(diag_load)
-
-
 def mvdr_weights(phi_s, phi_n, ref=0, diag_load=1e-3):
     """phi_s, phi_n: complex64 (F, C, C) (the two matrices of spatial_covariance).  Returns (w complex64 (F, C), ref_index
     CUDA int32 (1,)); for lists, (list of w, ref_index (B,)).  The solve runs in float64 on the device.  A bin with an empty
@@ -143,7 +99,7 @@ def mvdr_weights(phi_s, phi_n, ref=0, diag_load=1e-3):
     (CUDA int32, one entry per utterance) tells the latter apart and is not read back here."""
     global last_nonfinite
     _lib.require_gpu()
-    ps, many = _as_list(phi_s)
+    ps, many = _as_list(phi_s, "mvdr_weights")
     pn = list(phi_n) if many else [phi_n]
     if len(ps) != len(pn):
         raise ValueError("mvdr_weights: %d speech covariances, %d noise covariances" % (len(ps), len(pn)))
@@ -175,12 +131,10 @@ def mvdr_weights(phi_s, phi_n, ref=0, diag_load=1e-3):
 def apply_weights(spec, w):
     """spec: complex64 (C, N, F); w: complex64 (F, C).  Returns complex64 (N, F); lists -> one launch, a list."""
     _lib.require_gpu()
-    specs, many = _as_list(spec)
+    specs, many, Cn, F, dev = _check_specs(spec, "apply_weights", MAX_CHANNELS)
     ws = list(w) if many else [w]
     if len(ws) != len(specs):
         raise ValueError("apply_weights: %d spectra, %d weight matrices" % (len(specs), len(ws)))
-    specs = [_check_spec(s, "apply_weights", i) for i, s in enumerate(specs)]
-    Cn, F, dev = _check_common(specs, "apply_weights")
     for i, wi in enumerate(ws):
         if not (isinstance(wi, torch.Tensor) and wi.is_cuda and wi.dtype == torch.complex64 and wi.is_contiguous()
                 and wi.device == dev):
@@ -218,13 +172,7 @@ class MaskBeamformer:
 
     def analyze(self, wav):
         """(C, n) CUDA float32 -> complex64 (C, N, F), without dither"""
-        from . import simulation
-        a = self.analyzer
-        wav = simulation._check_mc(wav, "MaskBeamformer: wav")
-        if wav.shape[0] > MAX_CHANNELS:
-            raise ValueError("MaskBeamformer: wav has %d channels, at most %d" % (wav.shape[0], MAX_CHANNELS))
-        return torch.view_as_complex(simulation._stft_rows(list(wav.unbind(0)), a.fft_size, a.frame_len, a.frame_shift,
-                                                           a._window(wav.device)))
+        return analyze_channels(self.analyzer, wav, "MaskBeamformer", MAX_CHANNELS)
 
     def batch(self, wavs, speech_masks=None, noise_masks=None):
         wavs = list(wavs)

@@ -22,61 +22,15 @@ and got the masks 1 / K) keep the last cgmm_masks call's; they are device tensor
 
   cgmm_config(beamform_config)      validation of the data_config keys `beamform: {mask, cgmm_iterations}` (needs no GPU)
 """
-import ctypes as C
-import math
-
-import numpy as np
 import torch
 
 from . import _lib
+from ._array import _as_list, _check_specs, _diag_load_arg, _frames, _int_arg, _table, analyze_channels
 
 MAX_CHANNELS, MAX_CLASSES, MAX_ITERS = _lib.BF_MAX_CHANNELS, _lib.BF_MAX_MASKS, _lib.CGMM_MAX_ITERS
 MASK_KINDS = ("ideal", "cgmm")
 
 last_ll = last_cov = last_log_alpha = last_nonfinite = None
-
-
-def _table(tensors):
-    return (C.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
-
-
-def _frames(frames):
-    return (C.c_int32 * len(frames))(*frames)
-
-
-def _as_list(x, who):
-    if isinstance(x, (list, tuple)):
-        if not x:
-            raise ValueError("%s: the list of utterances is empty" % who)
-        return list(x), True
-    return [x], False
-
-
-def _int_arg(v, lo, hi, who, name):
-    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
-        raise ValueError("%s: %s must be an integer in [%d, %d], got %r" % (who, name, lo, hi, v))
-    return int(v)
-
-
-def _diag_load_arg(diag_load, who):
-    if isinstance(diag_load, bool) or not isinstance(diag_load, (int, float, np.integer, np.floating)) \
-            or not math.isfinite(float(diag_load)) or float(diag_load) < 0:
-        raise ValueError("%s: diag_load must be a finite number >= 0, got %r" % (who, diag_load))
-    return float(diag_load)
-
-
-def _check_specs(spec, who):
-    specs, many = _as_list(spec, who)
-    for i, s in enumerate(specs):
-        if not (isinstance(s, torch.Tensor) and s.is_cuda and s.dtype == torch.complex64 and s.dim() == 3 and s.is_contiguous()
-                and s.numel() > 0):
-            raise ValueError("%s: utterance %d: expected a contiguous CUDA complex64 (C, N, F) spectrum" % (who, i))
-        if s.shape[0] != specs[0].shape[0] or s.shape[2] != specs[0].shape[2] or s.device != specs[0].device:
-            raise ValueError("%s: utterance %d is (C, F) = (%d, %d) on %s, the first one (%d, %d) on %s"
-                             % (who, i, s.shape[0], s.shape[2], s.device, specs[0].shape[0], specs[0].shape[2], specs[0].device))
-    if specs[0].shape[0] > MAX_CHANNELS:
-        raise ValueError("%s: %d channels, at most %d" % (who, specs[0].shape[0], MAX_CHANNELS))
-    return specs, many, specs[0].shape[0], specs[0].shape[2], specs[0].device
 
 
 def _per_utt(x, many, n, who, name):
@@ -147,7 +101,7 @@ def cgmm_masks(spec, num_classes=2, iterations=10, init=None, activity=None, dia
     `last_ll`, `last_cov`, `last_log_alpha` and `last_nonfinite`.  Nothing is read back."""
     global last_ll, last_cov, last_log_alpha, last_nonfinite
     who = "cgmm_masks"
-    specs, many, Cn, F, dev = _check_specs(spec, who)
+    specs, many, Cn, F, dev = _check_specs(spec, who, MAX_CHANNELS)
     K = _int_arg(num_classes, 2, MAX_CLASSES, who, "num_classes")
     iterations = _int_arg(iterations, 1, MAX_ITERS, who, "iterations")
     diag_load = _diag_load_arg(diag_load, who)
@@ -186,7 +140,7 @@ def cgmm_init(spec, init=None, activity=None):
     Without `init`, K = 2: R_0 = sum_t y y^H / N, R_1 = (Re tr R_0 / C) I, alpha = 1 / 2; with it, cgmm_update with
     lam = init and phi = 1."""
     who = "cgmm_init"
-    specs, many, Cn, F, dev = _check_specs(spec, who)
+    specs, many, Cn, F, dev = _check_specs(spec, who, MAX_CHANNELS)
     inits, K = _per_utt(init, many, len(specs), who, "init"), 2
     if inits is not None:
         inits, K = _planes(inits, specs, None, who, "init")
@@ -251,7 +205,7 @@ def cgmm_posteriors(spec, factor, activity=None):
     """spec: complex64 (C, N, F); factor: what cgmm_factor returned.  Returns (lam float32 (K, N, F), phi float32 (K, N, F),
     ll float64 (): the log-likelihood up to its constant); lists -> (list, list, ll (B,))."""
     who = "cgmm_posteriors"
-    specs, many, Cn, F, dev = _check_specs(spec, who)
+    specs, many, Cn, F, dev = _check_specs(spec, who, MAX_CHANNELS)
     facs = list(factor) if many else [factor]
     if len(facs) != len(specs):
         raise ValueError("%s: %d spectra, %d factors" % (who, len(specs), len(facs)))
@@ -289,7 +243,7 @@ def cgmm_update(spec, lam, phi, activity=None):
     log alpha_k[f] = log max(sum_t lam_k / N_act, 1e-10), N_act the number of frames with an active class (all of them
     without `activity`).  Returns (R complex64 (K, F, C, C), log_alpha float32 (K, F)); lists -> lists."""
     who = "cgmm_update"
-    specs, many, Cn, F, dev = _check_specs(spec, who)
+    specs, many, Cn, F, dev = _check_specs(spec, who, MAX_CHANNELS)
     lams, K = _planes(_per_utt(lam, many, len(specs), who, "lam"), specs, None, who, "lam")
     phis, _ = _planes(_per_utt(phi, many, len(specs), who, "phi"), specs, K, who, "phi")
     acts = _activity(activity, specs, many, K, who)
@@ -320,13 +274,7 @@ class CgmmMaskEstimator:
 
     def analyze(self, wav):
         """(C, n) CUDA float32 -> complex64 (C, N, F), without dither"""
-        from . import simulation
-        a = self.analyzer
-        wav = simulation._check_mc(wav, "CgmmMaskEstimator: wav")
-        if wav.shape[0] > MAX_CHANNELS:
-            raise ValueError("CgmmMaskEstimator: wav has %d channels, at most %d" % (wav.shape[0], MAX_CHANNELS))
-        return torch.view_as_complex(simulation._stft_rows(list(wav.unbind(0)), a.fft_size, a.frame_len, a.frame_shift,
-                                                           a._window(wav.device)))
+        return analyze_channels(self.analyzer, wav, "CgmmMaskEstimator", MAX_CHANNELS)
 
     def masks(self, spec):
         m = cgmm_masks(spec, 2, self.iterations, diag_load=self.diag_load)

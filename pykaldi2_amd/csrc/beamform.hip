@@ -1,11 +1,8 @@
 // Mask-based MVDR beamforming for a ragged minibatch (include/pk2hip.h): masked spatial covariances, Souden's
 // MVDR weights, and the weighted sum over the channels.
 //
-//   pk2_bf_cov           lanes on bins, one wave per (utterance, PK2_BF_FRAMES_PER_PART frames, 64 bins): the spectrum is read
-//                        once, coalesced along f, for all masks; the C (C + 1) / 2 complex sums per mask and the mask sums
-//                        live in registers (C and the number of masks are template parameters) and go to the workspace as one
-//                        partial per part.  A second kernel adds the partials in part order in float64, divides by the mask
-//                        sum and writes both triangles.  No atomics: a result depends on its utterance alone.
+//   pk2_bf_cov           the covariance pass of array_internal.h (cov_kernel, cov_reduce_kernel) weighted with the masks:
+//                        MaskWeights below.  C and the number of masks are template parameters.
 //   pk2_bf_mvdr_weights  one thread per (utterance, bin): float32 in, float64 arithmetic (loading, Cholesky, C solves, trace),
 //                        complex64 out.  For the 'snr' reference it leaves every candidate's weights and SNR terms in the
 //                        workspace; one workgroup per utterance then adds the terms over f in bin order, picks the channel
@@ -13,145 +10,47 @@
 //   pk2_bf_apply         lanes on bins, the C weights of a bin in registers, one pass over the spectrum.
 #include <algorithm>
 
-#include "common.h"
+#include "array_internal.h"
 
 namespace pk2 {
 
 constexpr int kBfLanes = 64;                        // bins per workgroup (one wave)
-constexpr int kBfPart = PK2_BF_FRAMES_PER_PART;     // frames per workgroup of the covariance pass
 constexpr int kBfApplyFrames = 32;                  // frames per workgroup of the apply pass
 
 struct BfCovTab {
   const float2* spec[PK2_BF_MAX_UTTS];
   const float* mask[PK2_BF_MAX_UTTS * PK2_BF_MAX_MASKS];
-  int32_t frames[PK2_BF_MAX_UTTS];
-  int32_t part_off[PK2_BF_MAX_UTTS + 1];            // first part of every utterance in this launch
+  Ragged rag;
 };
 struct BfApplyTab {
   const float2* spec[PK2_BF_MAX_UTTS];
   const float2* w[PK2_BF_MAX_UTTS];
   float2* out[PK2_BF_MAX_UTTS];
-  int32_t frames[PK2_BF_MAX_UTTS];
-  int32_t part_off[PK2_BF_MAX_UTTS + 1];
+  Ragged rag;
 };
 struct BfPhiTab {
   const float2* phi_s[PK2_BF_MAX_UTTS];
   const float2* phi_n[PK2_BF_MAX_UTTS];
 };
 
-__host__ __device__ constexpr int bf_pairs(int C) { return C * (C + 1) / 2; }
-// floats of one (part, mask) partial per bin: the lower triangle (re, im) row by row, then the mask sum
-__host__ __device__ constexpr int bf_entries(int C) { return 2 * bf_pairs(C) + 1; }
-
-template <int N>
-__device__ __forceinline__ int bf_find(const int32_t (&off)[N], int n, int part) {
-  int b = 0;
-  while (b + 1 < n && off[b + 1] <= part) ++b;
-  return b;
-}
-
-// grid (parts of the launch, ceil(F / 64)).  KA: accumulated masks; COMP: KA == 2 from one mask m: (m, 1 - m).
-// partial layout: [part][KA][bf_entries(C)][F] float32
-// amdgpu_waves_per_eu(1, 2): without it the register allocator aims at the occupancy of a 64-lane workgroup's default
-// budget and spills 100 to 340 bytes per lane to scratch for C = 5 .. 7; with it every instantiation is scratch-free
-// (C = 8 with four masks keeps 68 values in AGPRs).  Small C still get the occupancy their register count allows.
-template <int C, int KA, bool COMP>
-__global__ void __launch_bounds__(kBfLanes) __attribute__((amdgpu_waves_per_eu(1, 2)))
-bf_cov_kernel(const BfCovTab tab, int B, int F, float* __restrict__ work) {
-  const int part = blockIdx.x;
-  const int b = bf_find(tab.part_off, B, part);
-  const int f = blockIdx.y * kBfLanes + threadIdx.x;
-  if (f >= F) return;
-  const int N = tab.frames[b];
-  const int t0 = (part - tab.part_off[b]) * kBfPart, t1 = min(t0 + kBfPart, N);
-  const float2* __restrict__ Y = tab.spec[b];
-  constexpr int KM = COMP ? 1 : KA;
+// The weights of cov_kernel: KA_ masks, each its own normaliser; COMP: KA_ == 2 from one mask m: (m, 1 - m).
+template <int KA_, bool COMP>
+struct MaskWeights {
+  using Tab = BfCovTab;
+  static constexpr int KA = KA_, KM = COMP ? 1 : KA_;
   const float* __restrict__ M[KM];
+  __device__ __forceinline__ MaskWeights(const Tab& tab, int b) {
 #pragma unroll
-  for (int k = 0; k < KM; ++k) M[k] = tab.mask[b * PK2_BF_MAX_MASKS + k];
-
-  float re[KA][bf_pairs(C)], im[KA][bf_pairs(C)], ms[KA];
-#pragma unroll
-  for (int k = 0; k < KA; ++k) {
-    ms[k] = 0.f;
-#pragma unroll
-    for (int p = 0; p < bf_pairs(C); ++p) re[k][p] = im[k][p] = 0.f;
+    for (int k = 0; k < KM; ++k) M[k] = tab.mask[b * PK2_BF_MAX_MASKS + k];
   }
-  const int64_t NF = (int64_t)N * F;
-  for (int t = t0; t < t1; ++t) {
-    const int64_t o = (int64_t)t * F + f;
-    float2 y[C];
-#pragma unroll
-    for (int c = 0; c < C; ++c) y[c] = Y[c * NF + o];
-    float m[KA];
+  __device__ __forceinline__ void load(int64_t o, int64_t, float (&m)[KA], float (&ms)[KA]) const {
 #pragma unroll
     for (int k = 0; k < KM; ++k) m[k] = M[k][o];
     if (COMP) m[KA - 1] = 1.f - m[0];
 #pragma unroll
     for (int k = 0; k < KA; ++k) ms[k] += m[k];
-    int p = 0;
-#pragma unroll
-    for (int i = 0; i < C; ++i) {
-#pragma unroll
-      for (int j = 0; j <= i; ++j, ++p) {
-        // y_i conj(y_j)
-        const float pr = fmaf(y[i].x, y[j].x, y[i].y * y[j].y);
-        const float pi = fmaf(y[i].y, y[j].x, -(y[i].x * y[j].y));
-#pragma unroll
-        for (int k = 0; k < KA; ++k) {
-          re[k][p] = fmaf(m[k], pr, re[k][p]);
-          if (i != j) im[k][p] = fmaf(m[k], pi, im[k][p]);
-        }
-      }
-    }
   }
-  constexpr int E = bf_entries(C);
-  float* __restrict__ dst = work + (int64_t)part * KA * E * F + f;
-#pragma unroll
-  for (int k = 0; k < KA; ++k) {
-#pragma unroll
-    for (int p = 0; p < bf_pairs(C); ++p) {
-      dst[(int64_t)(k * E + 2 * p) * F] = re[k][p];
-      dst[(int64_t)(k * E + 2 * p + 1) * F] = im[k][p];
-    }
-    dst[(int64_t)(k * E + E - 1) * F] = ms[k];
-  }
-}
-
-// grid (ceil(F / 64), pairs, utterances of the launch * KA): one element of the lower triangle and its mirror image
-__global__ void __launch_bounds__(kBfLanes) bf_cov_reduce_kernel(const BfCovTab tab, int C, int KA, int F,
-                                                                 const float* __restrict__ work, float2* __restrict__ phi) {
-  const int f = blockIdx.x * kBfLanes + threadIdx.x;
-  if (f >= F) return;
-  const int p = blockIdx.y, b = blockIdx.z / KA, k = blockIdx.z % KA;
-  int i = 0;
-  while ((i + 1) * (i + 2) / 2 <= p) ++i;
-  const int j = p - i * (i + 1) / 2;
-  const int E = bf_entries(C);
-  const int part0 = tab.part_off[b], part1 = tab.part_off[b + 1];
-  double sr = 0.0, si = 0.0, sm = 0.0;
-  for (int part = part0; part < part1; ++part) {
-    const float* __restrict__ src = work + ((int64_t)part * KA + k) * E * F + f;
-    sr += (double)src[(int64_t)(2 * p) * F];
-    si += (double)src[(int64_t)(2 * p + 1) * F];
-    sm += (double)src[(int64_t)(E - 1) * F];
-  }
-  const double den = fmax(sm, 1e-10);
-  const float vr = (float)(sr / den), vi = i == j ? 0.f : (float)(si / den);
-  float2* __restrict__ out = phi + (((int64_t)b * KA + k) * F + f) * C * C;
-  out[i * C + j] = make_float2(vr, vi);
-  if (i != j) out[j * C + i] = make_float2(vr, -vi);
-}
-
-struct cd {
-  double x, y;
 };
-__device__ __forceinline__ cd cmul(cd a, cd b) { return cd{a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x}; }
-__device__ __forceinline__ cd cmulc(cd a, cd b) { return cd{a.x * b.x + a.y * b.y, a.y * b.x - a.x * b.y}; }   // a conj(b)
-__device__ __forceinline__ cd cdivc(cd a, cd b) {
-  const double d = b.x * b.x + b.y * b.y;
-  return cd{(a.x * b.x + a.y * b.y) / d, (a.y * b.x - a.x * b.y) / d};
-}
 
 // One thread per (utterance, bin).  ref >= 0: w (B, F, C) gets the weights of that channel.  ref < 0 ('snr'): cand
 // (B, C, F, C) gets every candidate's weights and terms (B, C, 2, F) the numerator and denominator of its SNR at this bin.
@@ -176,20 +75,7 @@ __global__ void __launch_bounds__(kBfLanes) bf_weights_kernel(const BfPhiTab tab
       if (i == j) tr += (double)a.x;
     }
   const double load = diag_load * tr / C + 1e-10;
-  for (int i = 0; i < C; ++i) { A[i][i].x += load; A[i][i].y = 0.0; }
-  // Cholesky A = L L^H in the lower triangle of A
-  for (int j = 0; j < C && ok; ++j) {
-    double d = A[j][j].x;
-    for (int k = 0; k < j; ++k) d -= A[j][k].x * A[j][k].x + A[j][k].y * A[j][k].y;
-    if (!(d > 0.0) || !isfinite(d)) { ok = false; break; }
-    const double l = sqrt(d), inv = 1.0 / l;
-    A[j][j] = cd{l, 0.0};
-    for (int i = j + 1; i < C; ++i) {
-      cd s = A[i][j];
-      for (int k = 0; k < j; ++k) { const cd q = cmulc(A[i][k], A[j][k]); s.x -= q.x; s.y -= q.y; }
-      A[i][j] = cd{s.x * inv, s.y * inv};
-    }
-  }
+  hermitian_cholesky(A, C, load, ok);
   cd trg{0.0, 0.0};
   if (ok) {
     // G = A^-1 Phi_s column by column: L y = s, then L^H g = y
@@ -293,11 +179,11 @@ __global__ void __launch_bounds__(256) bf_select_kernel(int C, int F, int ref, c
 template <int C>
 __global__ void __launch_bounds__(kBfLanes) bf_apply_kernel(const BfApplyTab tab, int B, int F) {
   const int part = blockIdx.x;
-  const int b = bf_find(tab.part_off, B, part);
+  const int b = find_utt(tab.rag.part_off, B, part);
   const int f = blockIdx.y * kBfLanes + threadIdx.x;
   if (f >= F) return;
-  const int N = tab.frames[b];
-  const int t0 = (part - tab.part_off[b]) * kBfApplyFrames, t1 = min(t0 + kBfApplyFrames, N);
+  const int N = tab.rag.frames[b];
+  const int t0 = (part - tab.rag.part_off[b]) * kBfApplyFrames, t1 = min(t0 + kBfApplyFrames, N);
   const float2* __restrict__ Y = tab.spec[b];
   float2* __restrict__ X = tab.out[b];
   float2 wv[C];
@@ -318,33 +204,19 @@ __global__ void __launch_bounds__(kBfLanes) bf_apply_kernel(const BfApplyTab tab
 }
 
 template <int C>
-static void bf_cov_launch(int KA, bool comp, dim3 grid, hipStream_t stream, const BfCovTab& tab, int B, int F, float* work) {
-  const dim3 block(kBfLanes);
-  if (comp) hipLaunchKernelGGL((bf_cov_kernel<C, 2, true>), grid, block, 0, stream, tab, B, F, work);
-  else if (KA == 1) hipLaunchKernelGGL((bf_cov_kernel<C, 1, false>), grid, block, 0, stream, tab, B, F, work);
-  else if (KA == 2) hipLaunchKernelGGL((bf_cov_kernel<C, 2, false>), grid, block, 0, stream, tab, B, F, work);
-  else if (KA == 3) hipLaunchKernelGGL((bf_cov_kernel<C, 3, false>), grid, block, 0, stream, tab, B, F, work);
-  else hipLaunchKernelGGL((bf_cov_kernel<C, 4, false>), grid, block, 0, stream, tab, B, F, work);
-}
-
-static int bf_check_shape(const char* who, int32_t B, int32_t C, int32_t F) {
-  PK2_REQUIRE(B >= 1, "%s: no utterance (B = %d)", who, B);
-  PK2_REQUIRE(C >= 1 && C <= PK2_BF_MAX_CHANNELS, "%s: %d channels (1 to %d)", who, C, PK2_BF_MAX_CHANNELS);
-  PK2_REQUIRE(F >= 1 && F <= 4097, "%s: %d bins (1 to 4097)", who, F);
-  return PK2_OK;
-}
-
-static int bf_check_frames(const char* who, const int32_t* frames, int32_t B) {
-  PK2_REQUIRE(frames, "%s: frames is null", who);
-  for (int b = 0; b < B; ++b)
-    PK2_REQUIRE(frames[b] >= 1 && frames[b] <= (1 << 24), "%s: utterance %d has %d frames (1 to 2^24)", who, b, frames[b]);
-  return PK2_OK;
+static void bf_cov_launch(int KA, bool comp, const BfCovTab& tab, int nb, int64_t parts, int F, float* work, float2* phi,
+                          hipStream_t stream) {
+  if (comp) cov_launch<C, MaskWeights<2, true>>(tab, nb, parts, F, work, phi, nullptr, nullptr, stream);
+  else if (KA == 1) cov_launch<C, MaskWeights<1, false>>(tab, nb, parts, F, work, phi, nullptr, nullptr, stream);
+  else if (KA == 2) cov_launch<C, MaskWeights<2, false>>(tab, nb, parts, F, work, phi, nullptr, nullptr, stream);
+  else if (KA == 3) cov_launch<C, MaskWeights<3, false>>(tab, nb, parts, F, work, phi, nullptr, nullptr, stream);
+  else cov_launch<C, MaskWeights<4, false>>(tab, nb, parts, F, work, phi, nullptr, nullptr, stream);
 }
 
 static size_t bf_cov_bytes(const int32_t* frames, int32_t B, int32_t C, int32_t F, int32_t KA) {
   int64_t parts = 0;
-  for (int b = 0; b < B; ++b) parts += (frames[b] + kBfPart - 1) / kBfPart;
-  return align_up((size_t)parts * KA * bf_entries(C) * F * sizeof(float), 256);
+  for (int b = 0; b < B; ++b) parts += (frames[b] + kCovPart - 1) / kCovPart;
+  return align_up((size_t)parts * KA * cov_entries(C) * F * sizeof(float), 256);
 }
 
 static size_t bf_weights_bytes(int32_t B, int32_t C, int32_t F) {
@@ -373,11 +245,11 @@ extern "C" size_t pk2_bf_workspace_bytes(const int32_t* frames, int32_t B, int32
 
 extern "C" int pk2_bf_cov(const float* const* spec, const float* const* masks, const int32_t* frames, int32_t B, int32_t C,
                           int32_t F, int32_t K, int32_t complement, void* work, size_t work_bytes, float* phi, void* stream_) {
-  if (int rc = bf_check_shape("bf_cov", B, C, F)) return rc;
+  if (int rc = check_shape("bf_cov", B, C, F)) return rc;
   PK2_REQUIRE(K >= 1 && K <= PK2_BF_MAX_MASKS, "bf_cov: %d masks (1 to %d)", K, PK2_BF_MAX_MASKS);
   PK2_REQUIRE(!complement || K == 1, "bf_cov: complement needs exactly one mask, got %d", K);
   PK2_REQUIRE(spec && masks && work && phi, "bf_cov: null pointer");
-  if (int rc = bf_check_frames("bf_cov", frames, B)) return rc;
+  if (int rc = check_frames("bf_cov", frames, B)) return rc;
   for (int b = 0; b < B; ++b) {
     PK2_REQUIRE(spec[b], "bf_cov: spectrum %d is null", b);
     for (int k = 0; k < K; ++k) PK2_REQUIRE(masks[b * K + k], "bf_cov: mask %d of utterance %d is null", k, b);
@@ -386,39 +258,21 @@ extern "C" int pk2_bf_cov(const float* const* spec, const float* const* masks, c
   PK2_REQUIRE(work_bytes >= bf_cov_bytes(frames, B, C, F, KA), "bf_cov: workspace of %zu bytes, %zu needed", work_bytes,
               bf_cov_bytes(frames, B, C, F, KA));
   hipStream_t stream = static_cast<hipStream_t>(stream_);
-  const unsigned tiles = (unsigned)((F + kBfLanes - 1) / kBfLanes);
   float* wk = static_cast<float*>(work);
   for (int b0 = 0; b0 < B; b0 += PK2_BF_MAX_UTTS) {
     const int nb = std::min<int>(PK2_BF_MAX_UTTS, B - b0);
     BfCovTab tab;
     memset(&tab, 0, sizeof(tab));
-    int64_t parts = 0;
     for (int b = 0; b < nb; ++b) {
       tab.spec[b] = reinterpret_cast<const float2*>(spec[b0 + b]);
       for (int k = 0; k < K; ++k) tab.mask[b * PK2_BF_MAX_MASKS + k] = masks[(b0 + b) * K + k];
-      tab.frames[b] = frames[b0 + b];
-      tab.part_off[b] = (int32_t)parts;
-      parts += (frames[b0 + b] + kBfPart - 1) / kBfPart;
-      PK2_REQUIRE(parts <= INT32_MAX / 2, "bf_cov: too many frames in one launch");
     }
-    for (int b = nb; b <= PK2_BF_MAX_UTTS; ++b) tab.part_off[b] = (int32_t)parts;
-    const dim3 grid((unsigned)parts, tiles);
-    switch (C) {
-      case 1: bf_cov_launch<1>(KA, complement != 0, grid, stream, tab, nb, F, wk); break;
-      case 2: bf_cov_launch<2>(KA, complement != 0, grid, stream, tab, nb, F, wk); break;
-      case 3: bf_cov_launch<3>(KA, complement != 0, grid, stream, tab, nb, F, wk); break;
-      case 4: bf_cov_launch<4>(KA, complement != 0, grid, stream, tab, nb, F, wk); break;
-      case 5: bf_cov_launch<5>(KA, complement != 0, grid, stream, tab, nb, F, wk); break;
-      case 6: bf_cov_launch<6>(KA, complement != 0, grid, stream, tab, nb, F, wk); break;
-      case 7: bf_cov_launch<7>(KA, complement != 0, grid, stream, tab, nb, F, wk); break;
-      default: bf_cov_launch<8>(KA, complement != 0, grid, stream, tab, nb, F, wk); break;
-    }
+    int64_t parts;
+    if (int rc = fill_ragged("bf_cov", tab.rag, frames, b0, nb, kCovPart, &parts)) return rc;
+    float2* out = reinterpret_cast<float2*>(phi) + (int64_t)b0 * KA * F * C * C;
+    dispatch_channels(C, [&](auto c) { bf_cov_launch<decltype(c)::value>(KA, complement != 0, tab, nb, parts, F, wk, out, stream); });
     PK2_LAUNCH_CHECK();
-    const dim3 rgrid(tiles, (unsigned)bf_pairs(C), (unsigned)(nb * KA));
-    hipLaunchKernelGGL(bf_cov_reduce_kernel, rgrid, dim3(kBfLanes), 0, stream, tab, C, KA, F, wk,
-                       reinterpret_cast<float2*>(phi) + (int64_t)b0 * KA * F * C * C);
-    PK2_LAUNCH_CHECK();
-    wk += parts * KA * bf_entries(C) * F;
+    wk += parts * KA * cov_entries(C) * F;
   }
   return PK2_OK;
 }
@@ -426,7 +280,7 @@ extern "C" int pk2_bf_cov(const float* const* spec, const float* const* masks, c
 extern "C" int pk2_bf_mvdr_weights(const float* const* phi_s, const float* const* phi_n, int32_t B, int32_t C, int32_t F,
                                    int32_t ref, double diag_load, void* work, size_t work_bytes, float* w, int32_t* ref_index,
                                    int32_t* nonfinite, void* stream_) {
-  if (int rc = bf_check_shape("bf_mvdr_weights", B, C, F)) return rc;
+  if (int rc = check_shape("bf_mvdr_weights", B, C, F)) return rc;
   PK2_REQUIRE(ref == PK2_BF_REF_SNR || (ref >= 0 && ref < C), "bf_mvdr_weights: ref %d outside [0, %d) and not PK2_BF_REF_SNR",
               ref, C);
   PK2_REQUIRE(diag_load >= 0.0 && diag_load < 1e30, "bf_mvdr_weights: diag_load %g must be finite and >= 0", diag_load);
@@ -462,9 +316,9 @@ extern "C" int pk2_bf_mvdr_weights(const float* const* phi_s, const float* const
 
 extern "C" int pk2_bf_apply(const float* const* spec, const float* const* w, const int32_t* frames, int32_t B, int32_t C,
                             int32_t F, float* const* out, void* stream_) {
-  if (int rc = bf_check_shape("bf_apply", B, C, F)) return rc;
+  if (int rc = check_shape("bf_apply", B, C, F)) return rc;
   PK2_REQUIRE(spec && w && out, "bf_apply: null pointer");
-  if (int rc = bf_check_frames("bf_apply", frames, B)) return rc;
+  if (int rc = check_frames("bf_apply", frames, B)) return rc;
   for (int b = 0; b < B; ++b) PK2_REQUIRE(spec[b] && w[b] && out[b], "bf_apply: a pointer of utterance %d is null", b);
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   const unsigned tiles = (unsigned)((F + kBfLanes - 1) / kBfLanes);
@@ -472,28 +326,17 @@ extern "C" int pk2_bf_apply(const float* const* spec, const float* const* w, con
     const int nb = std::min<int>(PK2_BF_MAX_UTTS, B - b0);
     BfApplyTab tab;
     memset(&tab, 0, sizeof(tab));
-    int64_t parts = 0;
     for (int b = 0; b < nb; ++b) {
       tab.spec[b] = reinterpret_cast<const float2*>(spec[b0 + b]);
       tab.w[b] = reinterpret_cast<const float2*>(w[b0 + b]);
       tab.out[b] = reinterpret_cast<float2*>(out[b0 + b]);
-      tab.frames[b] = frames[b0 + b];
-      tab.part_off[b] = (int32_t)parts;
-      parts += (frames[b0 + b] + kBfApplyFrames - 1) / kBfApplyFrames;
-      PK2_REQUIRE(parts <= INT32_MAX / 2, "bf_apply: too many frames in one launch");
     }
-    for (int b = nb; b <= PK2_BF_MAX_UTTS; ++b) tab.part_off[b] = (int32_t)parts;
+    int64_t parts;
+    if (int rc = fill_ragged("bf_apply", tab.rag, frames, b0, nb, kBfApplyFrames, &parts)) return rc;
     const dim3 grid((unsigned)parts, tiles), block(kBfLanes);
-    switch (C) {
-      case 1: hipLaunchKernelGGL(bf_apply_kernel<1>, grid, block, 0, stream, tab, nb, F); break;
-      case 2: hipLaunchKernelGGL(bf_apply_kernel<2>, grid, block, 0, stream, tab, nb, F); break;
-      case 3: hipLaunchKernelGGL(bf_apply_kernel<3>, grid, block, 0, stream, tab, nb, F); break;
-      case 4: hipLaunchKernelGGL(bf_apply_kernel<4>, grid, block, 0, stream, tab, nb, F); break;
-      case 5: hipLaunchKernelGGL(bf_apply_kernel<5>, grid, block, 0, stream, tab, nb, F); break;
-      case 6: hipLaunchKernelGGL(bf_apply_kernel<6>, grid, block, 0, stream, tab, nb, F); break;
-      case 7: hipLaunchKernelGGL(bf_apply_kernel<7>, grid, block, 0, stream, tab, nb, F); break;
-      default: hipLaunchKernelGGL(bf_apply_kernel<8>, grid, block, 0, stream, tab, nb, F); break;
-    }
+    dispatch_channels(C, [&](auto c) {
+      hipLaunchKernelGGL(bf_apply_kernel<decltype(c)::value>, grid, block, 0, stream, tab, nb, F);
+    });
     PK2_LAUNCH_CHECK();
   }
   return PK2_OK;

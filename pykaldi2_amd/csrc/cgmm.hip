@@ -8,11 +8,12 @@
 //               phi = max(q / C, 1e-10), l = b + log a - C log phi; l and phi go to the workspace.
 //   softmax     one wave per (utterance, 32 frames, 64 bins): lambda over the classes with the maximum subtracted, the frame
 //               terms of the log-likelihood summed in float64 per (part, bin).
-//   M-step      the covariance pass of beamform.hip with the weight lambda / phi and the normaliser sum lambda: float32 chains
-//               in frame order per 32-frame part, the parts added in part order in float64, the mirror the exact conjugate.
+//   M-step      the covariance pass of array_internal.h (cov_kernel, cov_reduce_kernel) with the weight lambda / phi and the
+//               normaliser sum lambda (PosteriorWeights below): float32 chains in frame order per 32-frame part, the parts
+//               added in part order in float64, the mirror the exact conjugate; the reduce kernel also writes log alpha.
 #include <algorithm>
 
-#include "common.h"
+#include "array_internal.h"
 
 namespace pk2 {
 
@@ -26,24 +27,31 @@ struct CgTab {
   float* ell[PK2_BF_MAX_UTTS];                      // (K, N, F): what the E-pass writes and the softmax reads
   float* lam[PK2_BF_MAX_UTTS];                      // (K, N, F): what the softmax writes and the M-step reads (null: 1)
   float* phi[PK2_BF_MAX_UTTS];                      // (K, N, F) (null in the M-step: 1)
-  int32_t frames[PK2_BF_MAX_UTTS];
-  int32_t part_off[PK2_BF_MAX_UTTS + 1];            // first part of every utterance in this launch
+  Ragged rag;
 };
 
-__host__ __device__ constexpr int cg_pairs(int C) { return C * (C + 1) / 2; }
-// floats of one (part, class) partial per bin: the lower triangle (re, im) row by row, then sum lambda
-__host__ __device__ constexpr int cg_entries(int C) { return 2 * cg_pairs(C) + 1; }
-
-__device__ __forceinline__ int cg_find(const int32_t (&off)[PK2_BF_MAX_UTTS + 1], int n, int part) {
-  int b = 0;
-  while (b + 1 < n && off[b + 1] <= part) ++b;
-  return b;
-}
+// The weights of cov_kernel in the M-step: lambda_k / phi_k, the normaliser sum lambda_k; a null plane is 1.
+template <int KA_>
+struct PosteriorWeights {
+  using Tab = CgTab;
+  static constexpr int KA = KA_;
+  const float* __restrict__ L;
+  const float* __restrict__ P;
+  __device__ __forceinline__ PosteriorWeights(const Tab& tab, int b) : L(tab.lam[b]), P(tab.phi[b]) {}
+  __device__ __forceinline__ void load(int64_t o, int64_t NF, float (&m)[KA], float (&ms)[KA]) const {
+#pragma unroll
+    for (int k = 0; k < KA; ++k) {
+      const float l = L ? L[k * NF + o] : 1.f;
+      ms[k] += l;
+      m[k] = P ? l / P[k * NF + o] : l;
+    }
+  }
+};
 
 // grid (utterances of the launch): the number of frames on which any class is active
 __global__ void __launch_bounds__(256) cg_nact_kernel(const CgTab tab, int K, int32_t* __restrict__ nact) {
   __shared__ int s_n[256];
-  const int b = blockIdx.x, tid = threadIdx.x, N = tab.frames[b];
+  const int b = blockIdx.x, tid = threadIdx.x, N = tab.rag.frames[b];
   const float* __restrict__ a = tab.act[b];
   int n = 0;
   if (a) {
@@ -60,98 +68,6 @@ __global__ void __launch_bounds__(256) cg_nact_kernel(const CgTab tab, int K, in
     __syncthreads();
   }
   if (tid == 0) nact[b] = a ? s_n[0] : N;
-}
-
-// grid (parts of the launch, ceil(F / 64)).  partial layout: [part][KA][cg_entries(C)][F] float32.
-// amdgpu_waves_per_eu(1, 2) for the reason given at bf_cov_kernel: the sums of all classes stay in registers.
-template <int C, int KA>
-__global__ void __launch_bounds__(kCgLanes) __attribute__((amdgpu_waves_per_eu(1, 2)))
-cg_cov_kernel(const CgTab tab, int B, int F, float* __restrict__ work) {
-  const int part = blockIdx.x;
-  const int b = cg_find(tab.part_off, B, part);
-  const int f = blockIdx.y * kCgLanes + threadIdx.x;
-  if (f >= F) return;
-  const int N = tab.frames[b];
-  const int t0 = (part - tab.part_off[b]) * kCgPart, t1 = min(t0 + kCgPart, N);
-  const float2* __restrict__ Y = tab.spec[b];
-  const float* __restrict__ L = tab.lam[b];
-  const float* __restrict__ P = tab.phi[b];
-
-  float re[KA][cg_pairs(C)], im[KA][cg_pairs(C)], ms[KA];
-#pragma unroll
-  for (int k = 0; k < KA; ++k) {
-    ms[k] = 0.f;
-#pragma unroll
-    for (int p = 0; p < cg_pairs(C); ++p) re[k][p] = im[k][p] = 0.f;
-  }
-  const int64_t NF = (int64_t)N * F;
-  for (int t = t0; t < t1; ++t) {
-    const int64_t o = (int64_t)t * F + f;
-    float2 y[C];
-#pragma unroll
-    for (int c = 0; c < C; ++c) y[c] = Y[c * NF + o];
-    float m[KA];
-#pragma unroll
-    for (int k = 0; k < KA; ++k) {
-      const float l = L ? L[k * NF + o] : 1.f;
-      ms[k] += l;
-      m[k] = P ? l / P[k * NF + o] : l;
-    }
-    int p = 0;
-#pragma unroll
-    for (int i = 0; i < C; ++i) {
-#pragma unroll
-      for (int j = 0; j <= i; ++j, ++p) {
-        // y_i conj(y_j)
-        const float pr = fmaf(y[i].x, y[j].x, y[i].y * y[j].y);
-        const float pi = fmaf(y[i].y, y[j].x, -(y[i].x * y[j].y));
-#pragma unroll
-        for (int k = 0; k < KA; ++k) {
-          re[k][p] = fmaf(m[k], pr, re[k][p]);
-          if (i != j) im[k][p] = fmaf(m[k], pi, im[k][p]);
-        }
-      }
-    }
-  }
-  constexpr int E = cg_entries(C);
-  float* __restrict__ dst = work + (int64_t)part * KA * E * F + f;
-#pragma unroll
-  for (int k = 0; k < KA; ++k) {
-#pragma unroll
-    for (int p = 0; p < cg_pairs(C); ++p) {
-      dst[(int64_t)(k * E + 2 * p) * F] = re[k][p];
-      dst[(int64_t)(k * E + 2 * p + 1) * F] = im[k][p];
-    }
-    dst[(int64_t)(k * E + E - 1) * F] = ms[k];
-  }
-}
-
-// grid (ceil(F / 64), pairs, utterances of the launch * K): one element of the lower triangle and its mirror image; the
-// workgroups of element 0 also write log alpha.  R: (nb, K, F, C, C), log_alpha: (nb, K, F).
-__global__ void __launch_bounds__(kCgLanes) cg_reduce_kernel(const CgTab tab, int C, int K, int F,
-                                                             const float* __restrict__ work, const int32_t* __restrict__ nact,
-                                                             float2* __restrict__ R, float* __restrict__ log_alpha) {
-  const int f = blockIdx.x * kCgLanes + threadIdx.x;
-  if (f >= F) return;
-  const int p = blockIdx.y, b = blockIdx.z / K, k = blockIdx.z % K;
-  int i = 0;
-  while ((i + 1) * (i + 2) / 2 <= p) ++i;
-  const int j = p - i * (i + 1) / 2;
-  const int E = cg_entries(C);
-  const int part0 = tab.part_off[b], part1 = tab.part_off[b + 1];
-  double sr = 0.0, si = 0.0, sm = 0.0;
-  for (int part = part0; part < part1; ++part) {
-    const float* __restrict__ src = work + ((int64_t)part * K + k) * E * F + f;
-    sr += (double)src[(int64_t)(2 * p) * F];
-    si += (double)src[(int64_t)(2 * p + 1) * F];
-    sm += (double)src[(int64_t)(E - 1) * F];
-  }
-  const double den = fmax(sm, 1e-10);
-  const float vr = (float)(sr / den), vi = i == j ? 0.f : (float)(si / den);
-  float2* __restrict__ out = R + (((int64_t)b * K + k) * F + f) * C * C;
-  out[i * C + j] = make_float2(vr, vi);
-  if (i != j) out[j * C + i] = make_float2(vr, -vi);
-  if (p == 0) log_alpha[((int64_t)b * K + k) * F + f] = (float)log(fmax(sm / (double)max(nact[b], 1), 1e-10));
 }
 
 // grid (ceil(F / 64), utterances of the launch), K = 2: R_1 = (Re tr R_0 / C) I and alpha_k = 1 / 2
@@ -171,10 +87,6 @@ __global__ void __launch_bounds__(kCgLanes) cg_init_noise_kernel(int C, int F, f
   log_alpha[((int64_t)b * 2 + 1) * F + f] = la;
 }
 
-struct cgd {
-  double x, y;
-};
-
 // grid (ceil(F / 64), utterances of the launch * K).  R (nb, K, F, C, C), log_alpha (nb, K, F) -> linv (nb, K, 2 pairs, F):
 // the lower triangle of L^-1 row by row, (re, im); bias (nb, K, F); bad (nb, K, F): 1 where R is not finite or R' not positive
 // definite (then L^-1 = I and b = 0); bad_acc: the same, or-ed over the iterations of one pk2_cgmm call.
@@ -187,55 +99,37 @@ __global__ void __launch_bounds__(kCgLanes) cg_factor_kernel(int C, int F, doubl
   if (f >= F) return;
   constexpr int kC = PK2_BF_MAX_CHANNELS;
   const float2* __restrict__ src = R + (bk * F + f) * C * C;
-  cgd A[kC][kC], X[kC][kC];
+  cd A[kC][kC], X[kC][kC];
   bool ok = true;
   double tr = 0.0;
   for (int i = 0; i < C; ++i)
     for (int j = 0; j < C; ++j) {
       const float2 a = src[i * C + j];
-      A[i][j] = cgd{(double)a.x, (double)a.y};
+      A[i][j] = cd{(double)a.x, (double)a.y};
       ok = ok && isfinite(a.x) && isfinite(a.y);
       if (i == j) tr += (double)a.x;
     }
-  const double load = diag_load * tr / C + 1e-10;
-  for (int i = 0; i < C; ++i) { A[i][i].x += load; A[i][i].y = 0.0; }
   double logdet = 0.0;
-  // Cholesky A = L L^H in the lower triangle of A
-  for (int j = 0; j < C && ok; ++j) {
-    double d = A[j][j].x;
-    for (int k = 0; k < j; ++k) d -= A[j][k].x * A[j][k].x + A[j][k].y * A[j][k].y;
-    if (!(d > 0.0) || !isfinite(d)) { ok = false; break; }
-    const double l = sqrt(d), inv = 1.0 / l;
-    logdet += log(l);
-    A[j][j] = cgd{l, 0.0};
-    for (int i = j + 1; i < C; ++i) {
-      cgd s = A[i][j];
-      for (int k = 0; k < j; ++k) {      // L[i][k] conj(L[j][k])
-        s.x -= A[i][k].x * A[j][k].x + A[i][k].y * A[j][k].y;
-        s.y -= A[i][k].y * A[j][k].x - A[i][k].x * A[j][k].y;
-      }
-      A[i][j] = cgd{s.x * inv, s.y * inv};
-    }
-  }
+  hermitian_cholesky(A, C, diag_load * tr / C + 1e-10, ok, &logdet);
   // X = L^-1, column by column: X[j][j] = 1 / L[j][j], X[i][j] = -(sum_{k = j}^{i - 1} L[i][k] X[k][j]) / L[i][i]
   if (ok) {
     for (int j = 0; j < C; ++j) {
-      X[j][j] = cgd{1.0 / A[j][j].x, 0.0};
+      X[j][j] = cd{1.0 / A[j][j].x, 0.0};
       for (int i = j + 1; i < C; ++i) {
-        cgd s{0.0, 0.0};
+        cd s{0.0, 0.0};
         for (int k = j; k < i; ++k) {
           s.x += A[i][k].x * X[k][j].x - A[i][k].y * X[k][j].y;
           s.y += A[i][k].x * X[k][j].y + A[i][k].y * X[k][j].x;
         }
         const double inv = -1.0 / A[i][i].x;
-        X[i][j] = cgd{s.x * inv, s.y * inv};
+        X[i][j] = cd{s.x * inv, s.y * inv};
         ok = ok && isfinite(X[i][j].x) && isfinite(X[i][j].y);
       }
       ok = ok && isfinite(X[j][j].x);
     }
     ok = ok && isfinite(logdet);
   }
-  const int P2 = 2 * cg_pairs(C);
+  const int P2 = 2 * tri_pairs(C);
   float* __restrict__ dst = linv + bk * P2 * F + f;
   int p = 0;
   for (int i = 0; i < C; ++i)
@@ -253,14 +147,14 @@ template <int C>
 __global__ void __launch_bounds__(kCgLanes) cg_e_kernel(const CgTab tab, int B, int F, int K, const float* __restrict__ linv,
                                                         const float* __restrict__ bias) {
   const int part = blockIdx.x, k = blockIdx.z;
-  const int b = cg_find(tab.part_off, B, part);
+  const int b = find_utt(tab.rag.part_off, B, part);
   const int f = blockIdx.y * kCgLanes + threadIdx.x;
   if (f >= F) return;
-  const int N = tab.frames[b];
-  const int t0 = (part - tab.part_off[b]) * kCgPart, t1 = min(t0 + kCgPart, N);
+  const int N = tab.rag.frames[b];
+  const int t0 = (part - tab.rag.part_off[b]) * kCgPart, t1 = min(t0 + kCgPart, N);
   const float2* __restrict__ Y = tab.spec[b];
   const float* __restrict__ A = tab.act[b];
-  constexpr int P = cg_pairs(C);
+  constexpr int P = tri_pairs(C);
   const int64_t bk = (int64_t)b * K + k;
   const float* __restrict__ src = linv + bk * 2 * P * F + f;
   float lr[P], li[P];
@@ -306,11 +200,11 @@ __global__ void __launch_bounds__(kCgLanes) cg_e_kernel(const CgTab tab, int B, 
 __global__ void __launch_bounds__(kCgLanes) cg_softmax_kernel(const CgTab tab, int B, int F, int K, const int32_t* __restrict__ bad,
                                                               double* __restrict__ ll_part) {
   const int part = blockIdx.x;
-  const int b = cg_find(tab.part_off, B, part);
+  const int b = find_utt(tab.rag.part_off, B, part);
   const int f = blockIdx.y * kCgLanes + threadIdx.x;
   if (f >= F) return;
-  const int N = tab.frames[b];
-  const int t0 = (part - tab.part_off[b]) * kCgPart, t1 = min(t0 + kCgPart, N);
+  const int N = tab.rag.frames[b];
+  const int t0 = (part - tab.rag.part_off[b]) * kCgPart, t1 = min(t0 + kCgPart, N);
   const int64_t NF = (int64_t)N * F;
   const float* ell = tab.ell[b];      // lam may be the same plane: a frame's l_k are all read before its lambda_k are written
   float* lam = tab.lam[b];
@@ -354,7 +248,7 @@ __global__ void __launch_bounds__(256) cg_ll_kernel(const CgTab tab, int F, cons
   const int b = blockIdx.x, tid = threadIdx.x;
   double v = 0.0;
   for (int f = tid; f < F; f += 256)
-    for (int part = tab.part_off[b]; part < tab.part_off[b + 1]; ++part) v += ll_part[(int64_t)part * F + f];
+    for (int part = tab.rag.part_off[b]; part < tab.rag.part_off[b + 1]; ++part) v += ll_part[(int64_t)part * F + f];
   s_v[tid] = v;
   __syncthreads();
   if (tid == 0) {
@@ -395,7 +289,7 @@ __global__ void __launch_bounds__(kCgLanes) cg_order_kernel(const CgTab tab, int
   const float a = *a0;
   *a0 = *a1;
   *a1 = a;
-  const int N = tab.frames[b];
+  const int N = tab.rag.frames[b];
   float* __restrict__ lam = tab.lam[b];
   const int64_t NF = (int64_t)N * F;
   for (int t = 0; t < N; ++t) {
@@ -406,75 +300,9 @@ __global__ void __launch_bounds__(kCgLanes) cg_order_kernel(const CgTab tab, int
   }
 }
 
-// grid (utterances of the launch): nonfinite[b] = any of bad (K F entries per utterance)
-__global__ void __launch_bounds__(256) cg_flag_kernel(int KF, const int32_t* __restrict__ bad, int32_t* __restrict__ nonfinite) {
-  __shared__ int s_any[256];
-  const int b = blockIdx.x, tid = threadIdx.x;
-  int any = 0;
-  for (int i = tid; i < KF; i += 256) any |= bad[(int64_t)b * KF + i];
-  s_any[tid] = any;
-  __syncthreads();
-  if (tid == 0) {
-    int a = 0;
-    for (int i = 0; i < 256; ++i) a |= s_any[i];
-    nonfinite[b] = a ? 1 : 0;
-  }
-}
-
-template <int C>
-static void cg_cov_launch(int K, dim3 grid, hipStream_t stream, const CgTab& tab, int B, int F, float* work) {
-  const dim3 block(kCgLanes);
-  if (K == 2) hipLaunchKernelGGL((cg_cov_kernel<C, 2>), grid, block, 0, stream, tab, B, F, work);
-  else if (K == 3) hipLaunchKernelGGL((cg_cov_kernel<C, 3>), grid, block, 0, stream, tab, B, F, work);
-  else hipLaunchKernelGGL((cg_cov_kernel<C, 4>), grid, block, 0, stream, tab, B, F, work);
-}
-
-static void cg_cov_dispatch(int C, int K, dim3 grid, hipStream_t stream, const CgTab& tab, int B, int F, float* work) {
-  switch (C) {
-    case 1: cg_cov_launch<1>(K, grid, stream, tab, B, F, work); break;
-    case 2: cg_cov_launch<2>(K, grid, stream, tab, B, F, work); break;
-    case 3: cg_cov_launch<3>(K, grid, stream, tab, B, F, work); break;
-    case 4: cg_cov_launch<4>(K, grid, stream, tab, B, F, work); break;
-    case 5: cg_cov_launch<5>(K, grid, stream, tab, B, F, work); break;
-    case 6: cg_cov_launch<6>(K, grid, stream, tab, B, F, work); break;
-    case 7: cg_cov_launch<7>(K, grid, stream, tab, B, F, work); break;
-    default: cg_cov_launch<8>(K, grid, stream, tab, B, F, work); break;
-  }
-}
-
-static void cg_e_dispatch(int C, dim3 grid, hipStream_t stream, const CgTab& tab, int B, int F, int K, const float* linv,
-                          const float* bias) {
-  const dim3 block(kCgLanes);
-  switch (C) {
-    case 1: hipLaunchKernelGGL(cg_e_kernel<1>, grid, block, 0, stream, tab, B, F, K, linv, bias); break;
-    case 2: hipLaunchKernelGGL(cg_e_kernel<2>, grid, block, 0, stream, tab, B, F, K, linv, bias); break;
-    case 3: hipLaunchKernelGGL(cg_e_kernel<3>, grid, block, 0, stream, tab, B, F, K, linv, bias); break;
-    case 4: hipLaunchKernelGGL(cg_e_kernel<4>, grid, block, 0, stream, tab, B, F, K, linv, bias); break;
-    case 5: hipLaunchKernelGGL(cg_e_kernel<5>, grid, block, 0, stream, tab, B, F, K, linv, bias); break;
-    case 6: hipLaunchKernelGGL(cg_e_kernel<6>, grid, block, 0, stream, tab, B, F, K, linv, bias); break;
-    case 7: hipLaunchKernelGGL(cg_e_kernel<7>, grid, block, 0, stream, tab, B, F, K, linv, bias); break;
-    default: hipLaunchKernelGGL(cg_e_kernel<8>, grid, block, 0, stream, tab, B, F, K, linv, bias); break;
-  }
-}
-
 static int cg_check_shape(const char* who, int32_t B, int32_t C, int32_t F, int32_t K) {
-  PK2_REQUIRE(B >= 1, "%s: no utterance (B = %d)", who, B);
-  PK2_REQUIRE(C >= 1 && C <= PK2_BF_MAX_CHANNELS, "%s: %d channels (1 to %d)", who, C, PK2_BF_MAX_CHANNELS);
-  PK2_REQUIRE(F >= 1 && F <= 4097, "%s: %d bins (1 to 4097)", who, F);
+  if (int rc = check_shape(who, B, C, F)) return rc;
   PK2_REQUIRE(K >= 2 && K <= PK2_BF_MAX_MASKS, "%s: %d classes (2 to %d)", who, K, PK2_BF_MAX_MASKS);
-  return PK2_OK;
-}
-
-static int cg_check_frames(const char* who, const int32_t* frames, int32_t B) {
-  PK2_REQUIRE(frames, "%s: frames is null", who);
-  for (int b = 0; b < B; ++b)
-    PK2_REQUIRE(frames[b] >= 1 && frames[b] <= (1 << 24), "%s: utterance %d has %d frames (1 to 2^24)", who, b, frames[b]);
-  return PK2_OK;
-}
-
-static int cg_check_table(const char* who, const char* what, const float* const* p, int32_t B) {
-  PK2_REQUIRE(p, "%s: %s is null", who, what);
-  for (int b = 0; b < B; ++b) PK2_REQUIRE(p[b], "%s: %s of utterance %d is null", who, what, b);
   return PK2_OK;
 }
 
@@ -500,9 +328,9 @@ static CgWork cg_carve(void* base, const int32_t* frames, int32_t B, int32_t C, 
   CgWork w;
   w.ell = cv.take<float>((size_t)total * K * F);
   w.phi = cv.take<float>((size_t)total * K * F);
-  w.cov_part = cv.take<float>((size_t)parts * K * cg_entries(C) * F);
+  w.cov_part = cv.take<float>((size_t)parts * K * cov_entries(C) * F);
   w.ll_part = cv.take<double>((size_t)parts * F);
-  w.linv = cv.take<float>((size_t)B * K * 2 * cg_pairs(C) * F);
+  w.linv = cv.take<float>((size_t)B * K * 2 * tri_pairs(C) * F);
   w.bias = cv.take<float>((size_t)B * K * F);
   w.bad = cv.take<int32_t>((size_t)B * K * F);
   w.bad_acc = cv.take<int32_t>((size_t)B * K * F);
@@ -511,19 +339,11 @@ static CgWork cg_carve(void* base, const int32_t* frames, int32_t B, int32_t C, 
   return w;
 }
 
-// fills the table of utterances [b0, b0 + nb); returns the number of parts, or -1 when there are too many
-static int64_t cg_fill(CgTab& tab, const float* const* spec, const int32_t* frames, int b0, int nb) {
+// the table of utterances [b0, b0 + nb) with its spectra and header; *parts: the parts of the launch
+static int cg_fill(const char* who, CgTab& tab, const float* const* spec, const int32_t* frames, int b0, int nb, int64_t* parts) {
   memset(&tab, 0, sizeof(tab));
-  int64_t parts = 0;
-  for (int b = 0; b < nb; ++b) {
-    tab.spec[b] = spec ? reinterpret_cast<const float2*>(spec[b0 + b]) : nullptr;
-    tab.frames[b] = frames[b0 + b];
-    tab.part_off[b] = (int32_t)parts;
-    parts += (frames[b0 + b] + kCgPart - 1) / kCgPart;
-    if (parts > INT32_MAX / 2) return -1;
-  }
-  for (int b = nb; b <= PK2_BF_MAX_UTTS; ++b) tab.part_off[b] = (int32_t)parts;
-  return parts;
+  for (int b = 0; b < nb; ++b) tab.spec[b] = reinterpret_cast<const float2*>(spec[b0 + b]);
+  return fill_ragged(who, tab.rag, frames, b0, nb, kCgPart, parts);
 }
 
 static unsigned cg_tiles(int F) { return (unsigned)((F + kCgLanes - 1) / kCgLanes); }
@@ -531,15 +351,21 @@ static unsigned cg_tiles(int F) { return (unsigned)((F + kCgLanes - 1) / kCgLane
 // The M-step of one launch: tab.lam / tab.phi -> R and log_alpha of the nb utterances (pointers already at b0)
 static void cg_mstep(const CgTab& tab, int nb, int64_t parts, int C, int F, int K, float* cov_part, const int32_t* nact,
                      float2* R, float* log_alpha, hipStream_t stream) {
-  cg_cov_dispatch(C, K, dim3((unsigned)parts, cg_tiles(F)), stream, tab, nb, F, cov_part);
-  hipLaunchKernelGGL(cg_reduce_kernel, dim3(cg_tiles(F), (unsigned)cg_pairs(C), (unsigned)(nb * K)), dim3(kCgLanes), 0, stream,
-                     tab, C, K, F, cov_part, nact, R, log_alpha);
+  dispatch_channels(C, [&](auto c) {
+    constexpr int Cc = decltype(c)::value;
+    if (K == 2) cov_launch<Cc, PosteriorWeights<2>>(tab, nb, parts, F, cov_part, R, nact, log_alpha, stream);
+    else if (K == 3) cov_launch<Cc, PosteriorWeights<3>>(tab, nb, parts, F, cov_part, R, nact, log_alpha, stream);
+    else cov_launch<Cc, PosteriorWeights<4>>(tab, nb, parts, F, cov_part, R, nact, log_alpha, stream);
+  });
 }
 
 // The E-step of one launch: linv / bias / bad (at b0) and the spectra -> tab.ell, tab.phi, tab.lam, ll[b * stride]
 static void cg_estep(const CgTab& tab, int nb, int64_t parts, int C, int F, int K, const float* linv, const float* bias,
                      const int32_t* bad, double* ll_part, double* ll, int stride, hipStream_t stream) {
-  cg_e_dispatch(C, dim3((unsigned)parts, cg_tiles(F), (unsigned)K), stream, tab, nb, F, K, linv, bias);
+  const dim3 egrid((unsigned)parts, cg_tiles(F), (unsigned)K);
+  dispatch_channels(C, [&](auto c) {
+    hipLaunchKernelGGL(cg_e_kernel<decltype(c)::value>, egrid, dim3(kCgLanes), 0, stream, tab, nb, F, K, linv, bias);
+  });
   hipLaunchKernelGGL(cg_softmax_kernel, dim3((unsigned)parts, cg_tiles(F)), dim3(kCgLanes), 0, stream, tab, nb, F, K, bad,
                      ll_part);
   hipLaunchKernelGGL(cg_ll_kernel, dim3((unsigned)nb), dim3(256), 0, stream, tab, F, ll_part, ll, stride);
@@ -562,20 +388,20 @@ extern "C" int pk2_cgmm_init(const float* const* spec, const float* const* init,
   if (int rc = cg_check_shape("cgmm_init", B, C, F, K)) return rc;
   PK2_REQUIRE(init || K == 2, "cgmm_init: %d classes need initial masks (without them K = 2)", K);
   PK2_REQUIRE(work && R && log_alpha, "cgmm_init: null pointer");
-  if (int rc = cg_check_frames("cgmm_init", frames, B)) return rc;
-  if (int rc = cg_check_table("cgmm_init", "the spectrum", spec, B)) return rc;
+  if (int rc = check_frames("cgmm_init", frames, B)) return rc;
+  if (int rc = check_table("cgmm_init", "the spectrum", spec, B)) return rc;
   if (init)
-    if (int rc = cg_check_table("cgmm_init", "the initial masks", init, B)) return rc;
+    if (int rc = check_table("cgmm_init", "the initial masks", init, B)) return rc;
   if (activity)
-    if (int rc = cg_check_table("cgmm_init", "the activity", activity, B)) return rc;
+    if (int rc = check_table("cgmm_init", "the activity", activity, B)) return rc;
   const CgWork w = cg_carve(work, frames, B, C, F, K);
   PK2_REQUIRE(work_bytes >= w.bytes, "cgmm_init: workspace of %zu bytes, %zu needed", work_bytes, w.bytes);
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   for (int b0 = 0; b0 < B; b0 += PK2_BF_MAX_UTTS) {
     const int nb = std::min<int>(PK2_BF_MAX_UTTS, B - b0);
     CgTab tab;
-    const int64_t parts = cg_fill(tab, spec, frames, b0, nb);
-    PK2_REQUIRE(parts >= 0, "cgmm_init: too many frames in one launch");
+    int64_t parts;
+    if (int rc = cg_fill("cgmm_init", tab, spec, frames, b0, nb, &parts)) return rc;
     for (int b = 0; b < nb; ++b) {
       tab.lam[b] = init ? const_cast<float*>(init[b0 + b]) : nullptr;
       tab.act[b] = activity ? activity[b0 + b] : nullptr;
@@ -604,7 +430,7 @@ extern "C" int pk2_cgmm_factor(const float* R, const float* log_alpha, int32_t B
   hipLaunchKernelGGL(cg_factor_kernel, dim3(cg_tiles(F), (unsigned)(B * K)), dim3(kCgLanes), 0, stream, C, F, diag_load, 1,
                      reinterpret_cast<const float2*>(R), log_alpha, linv, bias, bad, (int32_t*)nullptr);
   PK2_LAUNCH_CHECK();
-  hipLaunchKernelGGL(cg_flag_kernel, dim3((unsigned)B), dim3(256), 0, stream, K * F, bad, nonfinite);
+  hipLaunchKernelGGL(any_flag_kernel<256>, dim3((unsigned)B), dim3(256), 0, stream, bad, K * F, nonfinite);
   PK2_LAUNCH_CHECK();
   return PK2_OK;
 }
@@ -615,27 +441,27 @@ extern "C" int pk2_cgmm_posteriors(const float* const* spec, const float* const*
                                    void* stream_) {
   if (int rc = cg_check_shape("cgmm_posteriors", B, C, F, K)) return rc;
   PK2_REQUIRE(linv && bias && bad && work && ll, "cgmm_posteriors: null pointer");
-  if (int rc = cg_check_frames("cgmm_posteriors", frames, B)) return rc;
-  if (int rc = cg_check_table("cgmm_posteriors", "the spectrum", spec, B)) return rc;
-  if (int rc = cg_check_table("cgmm_posteriors", "lam", lam, B)) return rc;
-  if (int rc = cg_check_table("cgmm_posteriors", "phi", phi, B)) return rc;
+  if (int rc = check_frames("cgmm_posteriors", frames, B)) return rc;
+  if (int rc = check_table("cgmm_posteriors", "the spectrum", spec, B)) return rc;
+  if (int rc = check_table("cgmm_posteriors", "lam", lam, B)) return rc;
+  if (int rc = check_table("cgmm_posteriors", "phi", phi, B)) return rc;
   if (activity)
-    if (int rc = cg_check_table("cgmm_posteriors", "the activity", activity, B)) return rc;
+    if (int rc = check_table("cgmm_posteriors", "the activity", activity, B)) return rc;
   const CgWork w = cg_carve(work, frames, B, C, F, K);
   PK2_REQUIRE(work_bytes >= w.bytes, "cgmm_posteriors: workspace of %zu bytes, %zu needed", work_bytes, w.bytes);
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   for (int b0 = 0; b0 < B; b0 += PK2_BF_MAX_UTTS) {
     const int nb = std::min<int>(PK2_BF_MAX_UTTS, B - b0);
     CgTab tab;
-    const int64_t parts = cg_fill(tab, spec, frames, b0, nb);
-    PK2_REQUIRE(parts >= 0, "cgmm_posteriors: too many frames in one launch");
+    int64_t parts;
+    if (int rc = cg_fill("cgmm_posteriors", tab, spec, frames, b0, nb, &parts)) return rc;
     for (int b = 0; b < nb; ++b) {
       tab.act[b] = activity ? activity[b0 + b] : nullptr;
       tab.ell[b] = tab.lam[b] = lam[b0 + b];      // l_k is replaced by lambda_k in place
       tab.phi[b] = phi[b0 + b];
     }
     const int64_t kf = (int64_t)b0 * K * F;
-    cg_estep(tab, nb, parts, C, F, K, linv + kf * 2 * cg_pairs(C), bias + kf, bad + kf, w.ll_part, ll + b0, 1, stream);
+    cg_estep(tab, nb, parts, C, F, K, linv + kf * 2 * tri_pairs(C), bias + kf, bad + kf, w.ll_part, ll + b0, 1, stream);
     PK2_LAUNCH_CHECK();
   }
   return PK2_OK;
@@ -646,20 +472,20 @@ extern "C" int pk2_cgmm_update(const float* const* spec, const float* const* lam
                                void* work, size_t work_bytes, float* R, float* log_alpha, void* stream_) {
   if (int rc = cg_check_shape("cgmm_update", B, C, F, K)) return rc;
   PK2_REQUIRE(work && R && log_alpha, "cgmm_update: null pointer");
-  if (int rc = cg_check_frames("cgmm_update", frames, B)) return rc;
-  if (int rc = cg_check_table("cgmm_update", "the spectrum", spec, B)) return rc;
-  if (int rc = cg_check_table("cgmm_update", "lam", lam, B)) return rc;
-  if (int rc = cg_check_table("cgmm_update", "phi", phi, B)) return rc;
+  if (int rc = check_frames("cgmm_update", frames, B)) return rc;
+  if (int rc = check_table("cgmm_update", "the spectrum", spec, B)) return rc;
+  if (int rc = check_table("cgmm_update", "lam", lam, B)) return rc;
+  if (int rc = check_table("cgmm_update", "phi", phi, B)) return rc;
   if (activity)
-    if (int rc = cg_check_table("cgmm_update", "the activity", activity, B)) return rc;
+    if (int rc = check_table("cgmm_update", "the activity", activity, B)) return rc;
   const CgWork w = cg_carve(work, frames, B, C, F, K);
   PK2_REQUIRE(work_bytes >= w.bytes, "cgmm_update: workspace of %zu bytes, %zu needed", work_bytes, w.bytes);
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   for (int b0 = 0; b0 < B; b0 += PK2_BF_MAX_UTTS) {
     const int nb = std::min<int>(PK2_BF_MAX_UTTS, B - b0);
     CgTab tab;
-    const int64_t parts = cg_fill(tab, spec, frames, b0, nb);
-    PK2_REQUIRE(parts >= 0, "cgmm_update: too many frames in one launch");
+    int64_t parts;
+    if (int rc = cg_fill("cgmm_update", tab, spec, frames, b0, nb, &parts)) return rc;
     for (int b = 0; b < nb; ++b) {
       tab.act[b] = activity ? activity[b0 + b] : nullptr;
       tab.lam[b] = const_cast<float*>(lam[b0 + b]);
@@ -684,13 +510,13 @@ extern "C" int pk2_cgmm(const float* const* spec, const float* const* init, cons
   PK2_REQUIRE(init || K == 2, "cgmm: %d classes need initial masks (without them K = 2)", K);
   PK2_REQUIRE(!purity || K == 2, "cgmm: the purity order is defined for two classes, not %d", K);
   PK2_REQUIRE(work && R && log_alpha && ll && nonfinite, "cgmm: null pointer");
-  if (int rc = cg_check_frames("cgmm", frames, B)) return rc;
-  if (int rc = cg_check_table("cgmm", "the spectrum", spec, B)) return rc;
-  if (int rc = cg_check_table("cgmm", "the masks", masks, B)) return rc;
+  if (int rc = check_frames("cgmm", frames, B)) return rc;
+  if (int rc = check_table("cgmm", "the spectrum", spec, B)) return rc;
+  if (int rc = check_table("cgmm", "the masks", masks, B)) return rc;
   if (init)
-    if (int rc = cg_check_table("cgmm", "the initial masks", init, B)) return rc;
+    if (int rc = check_table("cgmm", "the initial masks", init, B)) return rc;
   if (activity)
-    if (int rc = cg_check_table("cgmm", "the activity", activity, B)) return rc;
+    if (int rc = check_table("cgmm", "the activity", activity, B)) return rc;
   const CgWork w = cg_carve(work, frames, B, C, F, K);
   PK2_REQUIRE(work_bytes >= w.bytes, "cgmm: workspace of %zu bytes, %zu needed", work_bytes, w.bytes);
   hipStream_t stream = static_cast<hipStream_t>(stream_);
@@ -698,12 +524,12 @@ extern "C" int pk2_cgmm(const float* const* spec, const float* const* init, cons
   for (int b0 = 0; b0 < B; b0 += PK2_BF_MAX_UTTS) {
     const int nb = std::min<int>(PK2_BF_MAX_UTTS, B - b0);
     CgTab tab;
-    const int64_t parts = cg_fill(tab, spec, frames, b0, nb);
-    PK2_REQUIRE(parts >= 0, "cgmm: too many frames in one launch");
+    int64_t parts;
+    if (int rc = cg_fill("cgmm", tab, spec, frames, b0, nb, &parts)) return rc;
     const int64_t kf = (int64_t)b0 * K * F;
     float2* Rb = reinterpret_cast<float2*>(R) + kf * C * C;
     float* lab = log_alpha + kf;
-    float* linv = w.linv + kf * 2 * cg_pairs(C);
+    float* linv = w.linv + kf * 2 * tri_pairs(C);
     for (int b = 0; b < nb; ++b) {
       tab.act[b] = activity ? activity[b0 + b] : nullptr;
       tab.lam[b] = init ? const_cast<float*>(init[b0 + b]) : nullptr;
@@ -737,7 +563,7 @@ extern "C" int pk2_cgmm(const float* const* spec, const float* const* init, cons
       hipLaunchKernelGGL(cg_order_kernel, dim3(cg_tiles(F), (unsigned)nb), dim3(kCgLanes), 0, stream, tab, C, F, Rb, lab);
       PK2_LAUNCH_CHECK();
     }
-    hipLaunchKernelGGL(cg_flag_kernel, dim3((unsigned)nb), dim3(256), 0, stream, K * F, w.bad_acc + kf, nonfinite + b0);
+    hipLaunchKernelGGL(any_flag_kernel<256>, dim3((unsigned)nb), dim3(256), 0, stream, w.bad_acc + kf, K * F, nonfinite + b0);
     PK2_LAUNCH_CHECK();
   }
   return PK2_OK;

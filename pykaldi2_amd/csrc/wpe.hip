@@ -16,9 +16,12 @@
 //                    4 frames a sliding window in registers, fmaf chains in ascending d; the power of the result from the same
 //                    registers.  A bin whose G is all zero is copied.
 //   pk2_wpe          the iterations: the bin-major spectrum is made once, the intermediate iterations write only the power.
+//
+// The ragged-launch header and its fill, the argument checks, find_utt, the complex double, any_flag_kernel and
+// dispatch_channels are array_internal.h's, shared with beamform.hip and cgmm.hip.
 #include <algorithm>
 
-#include "common.h"
+#include "array_internal.h"
 
 namespace pk2 {
 
@@ -39,15 +42,8 @@ struct WpeTab {
   float* power[PK2_WPE_MAX_UTTS];
   int64_t yoff[PK2_WPE_MAX_UTTS];                   // float2 offset of the utterance's (F, C, N) copy
   int64_t woff[PK2_WPE_MAX_UTTS];                   // float offset of its (F, N) reciprocal weights
-  int32_t frames[PK2_WPE_MAX_UTTS];
-  int32_t part_off[PK2_WPE_MAX_UTTS + 1];           // first part of every utterance in this launch
+  Ragged rag;
 };
-
-__device__ __forceinline__ int wpe_find(const int32_t (&off)[PK2_WPE_MAX_UTTS + 1], int n, int part) {
-  int b = 0;
-  while (b + 1 < n && off[b + 1] <= part) ++b;
-  return b;
-}
 
 __host__ __device__ constexpr int wpe_tiles(int E) { return (E + 31) / 32; }
 __host__ __device__ constexpr int wpe_pairs(int E) { return wpe_tiles(E) * (wpe_tiles(E) + 1) / 2; }
@@ -55,11 +51,11 @@ __host__ __device__ constexpr int wpe_pairs(int E) { return wpe_tiles(E) * (wpe_
 // grid (parts of 32 frames, ceil(F / 64)): tab.power[b][t, f]
 __global__ void __launch_bounds__(64) wpe_power_kernel(const WpeTab tab, int B, int C, int F) {
   const int part = blockIdx.x;
-  const int b = wpe_find(tab.part_off, B, part);
+  const int b = find_utt(tab.rag.part_off, B, part);
   const int f = blockIdx.y * 64 + threadIdx.x;
   if (f >= F) return;
-  const int N = tab.frames[b];
-  const int t0 = (part - tab.part_off[b]) * 32, t1 = min(t0 + 32, N);
+  const int N = tab.rag.frames[b];
+  const int t0 = (part - tab.rag.part_off[b]) * 32, t1 = min(t0 + 32, N);
   const float2* __restrict__ Y = tab.spec[b];
   float* __restrict__ pw = tab.power[b];
   const int64_t NF = (int64_t)N * F;
@@ -82,9 +78,9 @@ __global__ void __launch_bounds__(256) wpe_transpose_kernel(const WpeTab tab, in
                                                             float2* __restrict__ yt, float* __restrict__ wt) {
   __shared__ float2 tile[32][33];
   const int part = blockIdx.x;
-  const int b = wpe_find(tab.part_off, B, part);
-  const int N = tab.frames[b];
-  const int t0 = (part - tab.part_off[b]) * 32, f0 = blockIdx.y * 32;
+  const int b = find_utt(tab.rag.part_off, B, part);
+  const int N = tab.rag.frames[b];
+  const int t0 = (part - tab.rag.part_off[b]) * 32, f0 = blockIdx.y * 32;
   const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
   const int plane = blockIdx.z;
   const bool is_spec = do_spec && plane < C;
@@ -119,9 +115,9 @@ __global__ void __launch_bounds__(64 * kWpeMaxPairs) wpe_corr_kernel(const WpeTa
   __shared__ float2 ys[kWpeStage];
   __shared__ float ws[kWpeChunk];
   const int part = blockIdx.x, f = blockIdx.y;
-  const int b = wpe_find(tab.part_off, B, part);
-  const int N = tab.frames[b];
-  const int t0 = (part - tab.part_off[b]) * kWpePart, t1 = min(t0 + kWpePart, N);
+  const int b = find_utt(tab.rag.part_off, B, part);
+  const int N = tab.rag.frames[b];
+  const int t0 = (part - tab.rag.part_off[b]) * kWpePart, t1 = min(t0 + kWpePart, N);
   const int D = C * K, E = D + C;
   const int halo = delay + K - 1, LW = kWpeChunk + halo;
   const int tid = threadIdx.x, nthreads = blockDim.x;
@@ -180,7 +176,7 @@ __global__ void __launch_bounds__(256) wpe_corr_reduce_kernel(const WpeTab tab, 
                                                               float2* __restrict__ P) {
   const int f = blockIdx.x, b = blockIdx.y;
   const int D = C * K, E = D + C, npairs = wpe_pairs(E);
-  const int part0 = tab.part_off[b], part1 = tab.part_off[b + 1];
+  const int part0 = tab.rag.part_off[b], part1 = tab.rag.part_off[b + 1];
   float2* __restrict__ Rb = R + ((int64_t)b * F + f) * D * D;
   float2* __restrict__ Pb = P + ((int64_t)b * F + f) * D * C;
   for (int idx = blockIdx.z * 256 + threadIdx.x; idx < E * D; idx += 256 * gridDim.z) {
@@ -204,17 +200,14 @@ __global__ void __launch_bounds__(256) wpe_corr_reduce_kernel(const WpeTab tab, 
   }
 }
 
-struct wpe_cd {
-  double x, y;
-};
 __device__ __forceinline__ int wpe_tri(int i, int k) { return i * (i + 1) / 2 + k; }
 
 // grid (F, B), block 256.  bad[(b * slots + slot) * F + f] = 1 where the bin got G = 0 for a non-finite value.
 __global__ void __launch_bounds__(256) wpe_solve_kernel(const float2* __restrict__ R, const float2* __restrict__ P, int C, int F,
                                                         int K, double diag_load, float2* __restrict__ G,
                                                         int32_t* __restrict__ bad, int slots, int slot) {
-  __shared__ wpe_cd A[kWpeTri];
-  __shared__ wpe_cd X[PK2_WPE_MAX_ORDER * PK2_WPE_MAX_CHANNELS];
+  __shared__ cd A[kWpeTri];
+  __shared__ cd X[PK2_WPE_MAX_ORDER * PK2_WPE_MAX_CHANNELS];
   const int f = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
   const int D = C * K, DC = D * C;
   const float2* __restrict__ Rb = R + ((int64_t)b * F + f) * D * D;
@@ -225,12 +218,12 @@ __global__ void __launch_bounds__(256) wpe_solve_kernel(const float2* __restrict
     const float2 v = Rb[idx];
     nonfinite |= !(isfinite(v.x) && isfinite(v.y));
     const int i = idx / D, k = idx - i * D;
-    if (k <= i) A[wpe_tri(i, k)] = wpe_cd{(double)v.x, (double)v.y};
+    if (k <= i) A[wpe_tri(i, k)] = cd{(double)v.x, (double)v.y};
   }
   for (int idx = tid; idx < DC; idx += 256) {
     const float2 v = Pb[idx];
     nonfinite |= !(isfinite(v.x) && isfinite(v.y));
-    X[idx] = wpe_cd{(double)v.x, (double)v.y};
+    X[idx] = cd{(double)v.x, (double)v.y};
   }
   int fail = __syncthreads_or(nonfinite);
   if (!fail) {
@@ -239,8 +232,8 @@ __global__ void __launch_bounds__(256) wpe_solve_kernel(const float2* __restrict
     const double load = diag_load * tr / D + 1e-10;
     __syncthreads();
     if (tid < D) {
-      wpe_cd& a = A[wpe_tri(tid, tid)];
-      a = wpe_cd{a.x + load, 0.0};
+      cd& a = A[wpe_tri(tid, tid)];
+      a = cd{a.x + load, 0.0};
     }
     // right-looking Cholesky, R' = L L^H in place; two barriers per column.  The trailing update runs on a 16 x 16 grid of
     // threads over (row, column) of the lower triangle, so no index is divided.
@@ -251,20 +244,20 @@ __global__ void __launch_bounds__(256) wpe_solve_kernel(const float2* __restrict
       if (!(d > 0.0) || !isfinite(d)) { fail = 1; break; }      // the same value in every thread
       const double l = sqrt(d), inv = 1.0 / l;
       for (int i = j + 1 + tid; i < D; i += 256) {
-        wpe_cd& a = A[wpe_tri(i, j)];
-        a = wpe_cd{a.x * inv, a.y * inv};
+        cd& a = A[wpe_tri(i, j)];
+        a = cd{a.x * inv, a.y * inv};
       }
       __syncthreads();
-      if (tid == 0) A[wpe_tri(j, j)] = wpe_cd{l, 0.0};          // nobody reads the pivot before the substitutions
+      if (tid == 0) A[wpe_tri(j, j)] = cd{l, 0.0};          // nobody reads the pivot before the substitutions
       const int m = D - j - 1;
       for (int u = ty; u < m; u += 16) {
         const int i = j + 1 + u;
-        const wpe_cd p = A[wpe_tri(i, j)];
+        const cd p = A[wpe_tri(i, j)];
         for (int v = tx; v <= u; v += 16) {
           const int k = j + 1 + v;
-          const wpe_cd q = A[wpe_tri(k, j)];
-          wpe_cd& a = A[wpe_tri(i, k)];                            // a -= p conj(q)
-          a = wpe_cd{a.x - (p.x * q.x + p.y * q.y), i == k ? 0.0 : a.y - (p.y * q.x - p.x * q.y)};
+          const cd q = A[wpe_tri(k, j)];
+          cd& a = A[wpe_tri(i, k)];                            // a -= p conj(q)
+          a = cd{a.x - (p.x * q.x + p.y * q.y), i == k ? 0.0 : a.y - (p.y * q.x - p.x * q.y)};
         }
       }
     }
@@ -277,20 +270,20 @@ __global__ void __launch_bounds__(256) wpe_solve_kernel(const float2* __restrict
     __syncthreads();
     if (tid < C) {
       const double inv = 1.0 / A[wpe_tri(0, 0)].x;
-      wpe_cd& x = X[tid];
-      x = wpe_cd{x.x * inv, x.y * inv};
+      cd& x = X[tid];
+      x = cd{x.x * inv, x.y * inv};
     }
     for (int i = 0; i + 1 < D; ++i) {
       __syncthreads();
       if (sc < C) {
-        const wpe_cd z = X[i * C + sc];
+        const cd z = X[i * C + sc];
         for (int rr = i + 1 + sr; rr < D; rr += 32) {
-          const wpe_cd l = A[wpe_tri(rr, i)];
-          wpe_cd x = X[rr * C + sc];                               // x -= l z
-          x = wpe_cd{x.x - (l.x * z.x - l.y * z.y), x.y - (l.x * z.y + l.y * z.x)};
+          const cd l = A[wpe_tri(rr, i)];
+          cd x = X[rr * C + sc];                               // x -= l z
+          x = cd{x.x - (l.x * z.x - l.y * z.y), x.y - (l.x * z.y + l.y * z.x)};
           if (rr == i + 1) {
             const double inv = 1.0 / A[wpe_tri(rr, rr)].x;
-            x = wpe_cd{x.x * inv, x.y * inv};
+            x = cd{x.x * inv, x.y * inv};
           }
           X[rr * C + sc] = x;
         }
@@ -299,20 +292,20 @@ __global__ void __launch_bounds__(256) wpe_solve_kernel(const float2* __restrict
     __syncthreads();
     if (tid < C) {
       const double inv = 1.0 / A[wpe_tri(D - 1, D - 1)].x;
-      wpe_cd& x = X[(D - 1) * C + tid];
-      x = wpe_cd{x.x * inv, x.y * inv};
+      cd& x = X[(D - 1) * C + tid];
+      x = cd{x.x * inv, x.y * inv};
     }
     for (int i = D - 1; i > 0; --i) {
       __syncthreads();
       if (sc < C) {
-        const wpe_cd g = X[i * C + sc];
+        const cd g = X[i * C + sc];
         for (int rr = i - 1 - sr; rr >= 0; rr -= 32) {
-          const wpe_cd l = A[wpe_tri(i, rr)];
-          wpe_cd x = X[rr * C + sc];                               // x -= conj(l) g
-          x = wpe_cd{x.x - (l.x * g.x + l.y * g.y), x.y - (l.x * g.y - l.y * g.x)};
+          const cd l = A[wpe_tri(i, rr)];
+          cd x = X[rr * C + sc];                               // x -= conj(l) g
+          x = cd{x.x - (l.x * g.x + l.y * g.y), x.y - (l.x * g.y - l.y * g.x)};
           if (rr == i - 1) {
             const double inv = 1.0 / A[wpe_tri(rr, rr)].x;
-            x = wpe_cd{x.x * inv, x.y * inv};
+            x = cd{x.x * inv, x.y * inv};
           }
           X[rr * C + sc] = x;
         }
@@ -328,15 +321,6 @@ __global__ void __launch_bounds__(256) wpe_solve_kernel(const float2* __restrict
   if (tid == 0) bad[((int64_t)b * slots + slot) * F + f] = fail ? 1 : 0;
 }
 
-// grid (B), block 256: nonfinite[b] = any of the utterance's slots * F flags
-__global__ void __launch_bounds__(256) wpe_flag_kernel(const int32_t* __restrict__ bad, int count, int32_t* __restrict__ nonfinite) {
-  const int b = blockIdx.x;
-  int any = 0;
-  for (int i = threadIdx.x; i < count; i += 256) any |= bad[(int64_t)b * count + i];
-  any = __syncthreads_or(any);
-  if (threadIdx.x == 0) nonfinite[b] = any ? 1 : 0;
-}
-
 // grid (parts of 128 frames, ceil(F / 8)), block 256.  tab.out[b] and tab.power[b] may be null (not both).
 template <int C>
 __global__ void __launch_bounds__(256) wpe_filter_kernel(const WpeTab tab, int B, int F, int K, int delay,
@@ -344,10 +328,10 @@ __global__ void __launch_bounds__(256) wpe_filter_kernel(const WpeTab tab, int B
   __shared__ float2 Gs[PK2_WPE_MAX_ORDER * PK2_WPE_MAX_CHANNELS * kWpeFB];
   __shared__ int live[kWpeFB];
   const int part = blockIdx.x;
-  const int b = wpe_find(tab.part_off, B, part);
+  const int b = find_utt(tab.rag.part_off, B, part);
   const int tid = threadIdx.x, fl = tid & (kWpeFB - 1), tr = tid / kWpeFB;
   const int f0 = blockIdx.y * kWpeFB, f = f0 + fl;
-  const int N = tab.frames[b];
+  const int N = tab.rag.frames[b];
   const int DC = C * K * C;
   const int nbins = min(kWpeFB, F - f0);
   const float2* __restrict__ Gb = G + ((int64_t)b * F + f0) * DC;
@@ -360,7 +344,7 @@ __global__ void __launch_bounds__(256) wpe_filter_kernel(const WpeTab tab, int B
     if (g.x != 0.f || g.y != 0.f) live[bl] = 1;        // every writer stores the same value
   }
   __syncthreads();
-  const int tb = (part - tab.part_off[b]) * kWpeFilterFrames + tr * kWpeTF;
+  const int tb = (part - tab.rag.part_off[b]) * kWpeFilterFrames + tr * kWpeTF;
   if (f >= F || tb >= N) return;
   const float2* __restrict__ Y = tab.spec[b];
   const int64_t NF = (int64_t)N * F;
@@ -430,25 +414,10 @@ __global__ void __launch_bounds__(256) wpe_filter_kernel(const WpeTab tab, int B
 // host side
 // ---------------------------------------------------------------------------------------------------------------------
 static int wpe_check_shape(const char* who, int32_t B, int32_t C, int32_t F, int32_t K, int32_t delay) {
-  PK2_REQUIRE(B >= 1, "%s: no utterance (B = %d)", who, B);
-  PK2_REQUIRE(C >= 1 && C <= PK2_WPE_MAX_CHANNELS, "%s: %d channels (1 to %d)", who, C, PK2_WPE_MAX_CHANNELS);
-  PK2_REQUIRE(F >= 1 && F <= 4097, "%s: %d bins (1 to 4097)", who, F);
+  if (int rc = check_shape(who, B, C, F)) return rc;
   PK2_REQUIRE(K >= 1 && (int64_t)C * K <= PK2_WPE_MAX_ORDER, "%s: %d taps on %d channels: the order C * taps must be in 1 to %d",
               who, K, C, PK2_WPE_MAX_ORDER);
   PK2_REQUIRE(delay >= 1 && delay <= PK2_WPE_MAX_DELAY, "%s: delay %d (1 to %d)", who, delay, PK2_WPE_MAX_DELAY);
-  return PK2_OK;
-}
-
-static int wpe_check_frames(const char* who, const int32_t* frames, int32_t B) {
-  PK2_REQUIRE(frames, "%s: frames is null", who);
-  for (int b = 0; b < B; ++b)
-    PK2_REQUIRE(frames[b] >= 1 && frames[b] <= (1 << 24), "%s: utterance %d has %d frames (1 to 2^24)", who, b, frames[b]);
-  return PK2_OK;
-}
-
-static int wpe_check_table(const char* who, const char* what, const void* const* p, int32_t B) {
-  PK2_REQUIRE(p, "%s: %s is null", who, what);
-  for (int b = 0; b < B; ++b) PK2_REQUIRE(p[b], "%s: %s of utterance %d is null", who, what, b);
   return PK2_OK;
 }
 
@@ -489,20 +458,14 @@ static size_t wpe_solve_bytes(int32_t B, int32_t F) { return align_up((size_t)B 
 // fills the table of one group; `gran` frames per part
 static int wpe_fill(WpeTab& tab, const char* who, int32_t nb, int32_t C, int32_t F, const int32_t* frames, int gran,
                     int64_t* parts_out) {
-  int64_t parts = 0, yoff = 0, woff = 0;
+  int64_t yoff = 0, woff = 0;
   for (int b = 0; b < nb; ++b) {
-    tab.frames[b] = frames[b];
-    tab.part_off[b] = (int32_t)parts;
     tab.yoff[b] = yoff;
     tab.woff[b] = woff;
-    parts += (frames[b] + gran - 1) / gran;
     yoff += (int64_t)frames[b] * C * F;
     woff += (int64_t)frames[b] * F;
-    PK2_REQUIRE(parts <= INT32_MAX / 2, "%s: too many frames in one launch", who);
   }
-  for (int b = nb; b <= PK2_WPE_MAX_UTTS; ++b) tab.part_off[b] = (int32_t)parts;
-  *parts_out = parts;
-  return PK2_OK;
+  return fill_ragged(who, tab.rag, frames, 0, nb, gran, parts_out);
 }
 
 static int wpe_launch_power(WpeTab& tab, int nb, int C, int F, const int32_t* frames, hipStream_t stream) {
@@ -546,16 +509,9 @@ static int wpe_launch_filter(WpeTab& tab, int nb, int C, int F, int K, int delay
   int64_t parts;
   if (int rc = wpe_fill(tab, "wpe_filter", nb, C, F, frames, kWpeFilterFrames, &parts)) return rc;
   const dim3 grid((unsigned)parts, (unsigned)((F + kWpeFB - 1) / kWpeFB)), block(256);
-  switch (C) {
-    case 1: hipLaunchKernelGGL(wpe_filter_kernel<1>, grid, block, 0, stream, tab, nb, F, K, delay, G); break;
-    case 2: hipLaunchKernelGGL(wpe_filter_kernel<2>, grid, block, 0, stream, tab, nb, F, K, delay, G); break;
-    case 3: hipLaunchKernelGGL(wpe_filter_kernel<3>, grid, block, 0, stream, tab, nb, F, K, delay, G); break;
-    case 4: hipLaunchKernelGGL(wpe_filter_kernel<4>, grid, block, 0, stream, tab, nb, F, K, delay, G); break;
-    case 5: hipLaunchKernelGGL(wpe_filter_kernel<5>, grid, block, 0, stream, tab, nb, F, K, delay, G); break;
-    case 6: hipLaunchKernelGGL(wpe_filter_kernel<6>, grid, block, 0, stream, tab, nb, F, K, delay, G); break;
-    case 7: hipLaunchKernelGGL(wpe_filter_kernel<7>, grid, block, 0, stream, tab, nb, F, K, delay, G); break;
-    default: hipLaunchKernelGGL(wpe_filter_kernel<8>, grid, block, 0, stream, tab, nb, F, K, delay, G); break;
-  }
+  dispatch_channels(C, [&](auto c) {
+    hipLaunchKernelGGL(wpe_filter_kernel<decltype(c)::value>, grid, block, 0, stream, tab, nb, F, K, delay, G);
+  });
   PK2_LAUNCH_CHECK();
   return PK2_OK;
 }
@@ -586,9 +542,9 @@ extern "C" size_t pk2_wpe_workspace_bytes(const int32_t* frames, int32_t B, int3
 extern "C" int pk2_wpe_power(const float* const* spec, const int32_t* frames, int32_t B, int32_t C, int32_t F,
                              float* const* power, void* stream_) {
   if (int rc = wpe_check_shape("wpe_power", B, C, F, 1, 1)) return rc;
-  if (int rc = wpe_check_frames("wpe_power", frames, B)) return rc;
-  if (int rc = wpe_check_table("wpe_power", "the spectrum", reinterpret_cast<const void* const*>(spec), B)) return rc;
-  if (int rc = wpe_check_table("wpe_power", "the power", reinterpret_cast<const void* const*>(power), B)) return rc;
+  if (int rc = check_frames("wpe_power", frames, B)) return rc;
+  if (int rc = check_table("wpe_power", "the spectrum", spec, B)) return rc;
+  if (int rc = check_table("wpe_power", "the power", power, B)) return rc;
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   for (int b0 = 0; b0 < B; b0 += PK2_WPE_MAX_UTTS) {
     const int nb = std::min<int>(PK2_WPE_MAX_UTTS, B - b0);
@@ -607,9 +563,9 @@ extern "C" int pk2_wpe_corr(const float* const* spec, const float* const* weight
                             int32_t F, int32_t taps, int32_t delay, void* work, size_t work_bytes, float* R, float* P,
                             void* stream_) {
   if (int rc = wpe_check_shape("wpe_corr", B, C, F, taps, delay)) return rc;
-  if (int rc = wpe_check_frames("wpe_corr", frames, B)) return rc;
-  if (int rc = wpe_check_table("wpe_corr", "the spectrum", reinterpret_cast<const void* const*>(spec), B)) return rc;
-  if (int rc = wpe_check_table("wpe_corr", "the weight", reinterpret_cast<const void* const*>(weight), B)) return rc;
+  if (int rc = check_frames("wpe_corr", frames, B)) return rc;
+  if (int rc = check_table("wpe_corr", "the spectrum", spec, B)) return rc;
+  if (int rc = check_table("wpe_corr", "the weight", weight, B)) return rc;
   PK2_REQUIRE(work && R && P, "wpe_corr: null pointer");
   const size_t need = wpe_total_bytes(frames, B, C, F, taps);
   PK2_REQUIRE(work_bytes >= need, "wpe_corr: workspace of %zu bytes, %zu needed", work_bytes, need);
@@ -647,7 +603,7 @@ extern "C" int pk2_wpe_solve(const float* R, const float* P, int32_t B, int32_t 
   hipLaunchKernelGGL(wpe_solve_kernel, dim3((unsigned)F, (unsigned)B), dim3(256), 0, stream, reinterpret_cast<const float2*>(R),
                      reinterpret_cast<const float2*>(P), C, F, taps, diag_load, reinterpret_cast<float2*>(G), bad, 1, 0);
   PK2_LAUNCH_CHECK();
-  hipLaunchKernelGGL(wpe_flag_kernel, dim3((unsigned)B), dim3(256), 0, stream, bad, F, nonfinite);
+  hipLaunchKernelGGL(any_flag_kernel<256>, dim3((unsigned)B), dim3(256), 0, stream, bad, F, nonfinite);
   PK2_LAUNCH_CHECK();
   return PK2_OK;
 }
@@ -655,11 +611,11 @@ extern "C" int pk2_wpe_solve(const float* R, const float* P, int32_t B, int32_t 
 extern "C" int pk2_wpe_filter(const float* const* spec, const float* G, const int32_t* frames, int32_t B, int32_t C, int32_t F,
                               int32_t taps, int32_t delay, float* const* out, float* const* power_out, void* stream_) {
   if (int rc = wpe_check_shape("wpe_filter", B, C, F, taps, delay)) return rc;
-  if (int rc = wpe_check_frames("wpe_filter", frames, B)) return rc;
-  if (int rc = wpe_check_table("wpe_filter", "the spectrum", reinterpret_cast<const void* const*>(spec), B)) return rc;
-  if (int rc = wpe_check_table("wpe_filter", "the output", reinterpret_cast<const void* const*>(out), B)) return rc;
+  if (int rc = check_frames("wpe_filter", frames, B)) return rc;
+  if (int rc = check_table("wpe_filter", "the spectrum", spec, B)) return rc;
+  if (int rc = check_table("wpe_filter", "the output", out, B)) return rc;
   if (power_out)
-    if (int rc = wpe_check_table("wpe_filter", "the power", reinterpret_cast<const void* const*>(power_out), B)) return rc;
+    if (int rc = check_table("wpe_filter", "the power", power_out, B)) return rc;
   PK2_REQUIRE(G, "wpe_filter: G is null");
   for (int b = 0; b < B; ++b) PK2_REQUIRE(out[b] != spec[b], "wpe_filter: the output of utterance %d is its spectrum", b);
   hipStream_t stream = static_cast<hipStream_t>(stream_);
@@ -686,9 +642,9 @@ extern "C" int pk2_wpe(const float* const* spec, const int32_t* frames, int32_t 
   if (int rc = wpe_check_shape("wpe", B, C, F, taps, delay)) return rc;
   PK2_REQUIRE(iters >= 1 && iters <= PK2_WPE_MAX_ITERS, "wpe: %d iterations (1 to %d)", iters, PK2_WPE_MAX_ITERS);
   PK2_REQUIRE(diag_load >= 0.0 && diag_load < 1e30, "wpe: diag_load %g must be finite and >= 0", diag_load);
-  if (int rc = wpe_check_frames("wpe", frames, B)) return rc;
-  if (int rc = wpe_check_table("wpe", "the spectrum", reinterpret_cast<const void* const*>(spec), B)) return rc;
-  if (int rc = wpe_check_table("wpe", "the output", reinterpret_cast<const void* const*>(out), B)) return rc;
+  if (int rc = check_frames("wpe", frames, B)) return rc;
+  if (int rc = check_table("wpe", "the spectrum", spec, B)) return rc;
+  if (int rc = check_table("wpe", "the output", out, B)) return rc;
   PK2_REQUIRE(work && nonfinite, "wpe: null pointer");
   for (int b = 0; b < B; ++b) PK2_REQUIRE(out[b] != spec[b], "wpe: the output of utterance %d is its spectrum", b);
   const size_t need = wpe_total_bytes(frames, B, C, F, taps);
@@ -725,7 +681,7 @@ extern "C" int pk2_wpe(const float* const* spec, const int32_t* frames, int32_t 
       }
       if (int rc = wpe_launch_filter(tab, nb, C, F, taps, delay, fr, wk.G, stream)) return rc;
     }
-    hipLaunchKernelGGL(wpe_flag_kernel, dim3((unsigned)nb), dim3(256), 0, stream, wk.bad, iters * F, nonfinite + b0);
+    hipLaunchKernelGGL(any_flag_kernel<256>, dim3((unsigned)nb), dim3(256), 0, stream, wk.bad, iters * F, nonfinite + b0);
     PK2_LAUNCH_CHECK();
   }
   return PK2_OK;

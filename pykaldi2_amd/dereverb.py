@@ -16,14 +16,13 @@ flag of that stays in the device tensor `last_nonfinite`, which the library neve
 
   wpe_config(config) / require_wpe_config(config, prog)     the data_config key `wpe` (needs no GPU)
 """
-import ctypes as C
-import math
 import sys
 
 import numpy as np
 import torch
 
 from . import _lib
+from ._array import _as_list, _check_specs, _diag_load_arg, _frames, _int_arg, _table, analyze_channels
 
 MAX_CHANNELS, MAX_ORDER = _lib.WPE_MAX_CHANNELS, _lib.WPE_MAX_ORDER
 MAX_DELAY, MAX_ITERS = _lib.WPE_MAX_DELAY, _lib.WPE_MAX_ITERS
@@ -31,35 +30,6 @@ FRAMES_PER_PART = _lib.WPE_FRAMES_PER_PART      # frames per float32 chain of th
 CONFIG_DEFAULTS = dict(taps=10, delay=3, iterations=3, diag_load=0.001)
 
 last_nonfinite = None      # CUDA int32 (B,) of the last wpe / wpe_filter_taps call: 1 where an utterance had a non-finite bin
-
-
-def _table(tensors):
-    return (C.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
-
-
-def _frames(frames):
-    return (C.c_int32 * len(frames))(*frames)
-
-
-def _as_list(x, who):
-    if isinstance(x, (list, tuple)):
-        if not x:
-            raise ValueError("%s: the list of utterances is empty" % who)
-        return list(x), True
-    return [x], False
-
-
-def _int_arg(v, lo, hi, who, name):
-    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= int(v) <= hi:
-        raise ValueError("%s: %s must be an integer in [%d, %d], got %r" % (who, name, lo, hi, v))
-    return int(v)
-
-
-def _diag_load_arg(diag_load, who):
-    if isinstance(diag_load, bool) or not isinstance(diag_load, (int, float, np.integer, np.floating)) \
-            or not math.isfinite(float(diag_load)) or float(diag_load) < 0:
-        raise ValueError("%s: diag_load must be a finite number >= 0, got %r" % (who, diag_load))
-    return float(diag_load)
 
 
 def _check_params(who, taps, delay, iterations=1, diag_load=0.0, channels=None):
@@ -75,20 +45,6 @@ def _check_params(who, taps, delay, iterations=1, diag_load=0.0, channels=None):
     return taps, delay, iterations, diag_load
 
 
-def _check_specs(spec, who):
-    specs, many = _as_list(spec, who)
-    for i, s in enumerate(specs):
-        if not (isinstance(s, torch.Tensor) and s.is_cuda and s.dtype == torch.complex64 and s.dim() == 3 and s.is_contiguous()
-                and s.numel() > 0):
-            raise ValueError("%s: utterance %d: expected a contiguous CUDA complex64 (C, N, F) spectrum" % (who, i))
-        if s.shape[0] != specs[0].shape[0] or s.shape[2] != specs[0].shape[2] or s.device != specs[0].device:
-            raise ValueError("%s: utterance %d is (C, F) = (%d, %d) on %s, the first one (%d, %d) on %s"
-                             % (who, i, s.shape[0], s.shape[2], s.device, specs[0].shape[0], specs[0].shape[2], specs[0].device))
-    if specs[0].shape[0] > MAX_CHANNELS:
-        raise ValueError("%s: %d channels, at most %d" % (who, specs[0].shape[0], MAX_CHANNELS))
-    return specs, many, specs[0].shape[0], specs[0].shape[2], specs[0].device
-
-
 def _workspace(frames, Cn, F, taps, delay, dev):
     nbytes = _lib.lib().pk2_wpe_workspace_bytes(_frames(frames), len(frames), Cn, F, taps, delay)
     if nbytes == 0:
@@ -101,7 +57,7 @@ def wpe(spec, taps=10, delay=3, iterations=3, diag_load=1e-3):
     dereverberated spectra, new tensors of the same shapes.  `last_nonfinite` (CUDA int32, one entry per utterance) tells
     whether a bin of any iteration passed through for a non-finite value; it is not read back here."""
     global last_nonfinite
-    specs, many, Cn, F, dev = _check_specs(spec, "wpe")
+    specs, many, Cn, F, dev = _check_specs(spec, "wpe", MAX_CHANNELS)
     taps, delay, iterations, diag_load = _check_params("wpe", taps, delay, iterations, diag_load, Cn)
     _lib.require_gpu()
     frames = [int(s.shape[1]) for s in specs]
@@ -117,7 +73,7 @@ def wpe(spec, taps=10, delay=3, iterations=3, diag_load=1e-3):
 
 def wpe_power(spec):
     """complex64 (C, N, F) -> float32 (N, F): the mean power over the channels, floored at 1e-10; lists -> a list."""
-    specs, many, Cn, F, dev = _check_specs(spec, "wpe_power")
+    specs, many, Cn, F, dev = _check_specs(spec, "wpe_power", MAX_CHANNELS)
     _lib.require_gpu()
     frames = [int(s.shape[1]) for s in specs]
     outs = [torch.empty(n, F, dtype=torch.float32, device=dev) for n in frames]
@@ -129,7 +85,7 @@ def wpe_power(spec):
 def wpe_correlations(spec, weight, taps=10, delay=3):
     """spec: complex64 (C, N, F); weight: float32 (N, F), applied as its reciprocal (wpe_power's lambda).  Returns
     (R complex64 (F, D, D), exactly Hermitian, P complex64 (F, D, C)); lists -> (list of R, list of P), one launch."""
-    specs, many, Cn, F, dev = _check_specs(spec, "wpe_correlations")
+    specs, many, Cn, F, dev = _check_specs(spec, "wpe_correlations", MAX_CHANNELS)
     taps, delay, _, _ = _check_params("wpe_correlations", taps, delay, channels=Cn)
     ws = list(weight) if many else [weight]
     if len(ws) != len(specs):
@@ -186,7 +142,7 @@ def wpe_filter_taps(R, P, diag_load=1e-3):
 def wpe_apply(spec, G, delay=3, with_power=False):
     """spec: complex64 (C, N, F); G: complex64 (F, D, C).  Returns X complex64 (C, N, F), a new tensor, and with
     with_power=True (X, wpe_power(X)) from the same pass; lists -> lists."""
-    specs, many, Cn, F, dev = _check_specs(spec, "wpe_apply")
+    specs, many, Cn, F, dev = _check_specs(spec, "wpe_apply", MAX_CHANNELS)
     Gs = list(G) if many else [G]
     if len(Gs) != len(specs):
         raise ValueError("wpe_apply: %d spectra, %d filters" % (len(specs), len(Gs)))
@@ -223,12 +179,9 @@ class Dereverberator:
 
     def analyze(self, wav):
         """(C, n) CUDA float32 -> complex64 (C, N, F), without dither"""
-        from . import simulation
-        a = self.analyzer
-        wav = simulation._check_mc(wav, "Dereverberator: wav")
-        _check_params("Dereverberator", self.taps, self.delay, channels=wav.shape[0])
-        return torch.view_as_complex(simulation._stft_rows(list(wav.unbind(0)), a.fft_size, a.frame_len, a.frame_shift,
-                                                           a._window(wav.device)))
+        spec = analyze_channels(self.analyzer, wav, "Dereverberator", MAX_CHANNELS)
+        _check_params("Dereverberator", self.taps, self.delay, channels=spec.shape[0])
+        return spec
 
     def spectrum(self, spec):
         out = wpe(spec, self.taps, self.delay, self.iterations, self.diag_load)

@@ -317,6 +317,22 @@ def test_35_utterances_take_two_launches_per_stage(want):
     assert flag.tolist() == [0] * 35
 
 
+# (C, K, N, F).  (3, 2, 33, 65): the second 32-frame part holds one frame, the second 64-bin tile one lane.
+# (8, 4, 98, 17): the one instantiation that keeps sums in AGPRs; four parts, the last short.
+@pytest.mark.parametrize("shape", [(3, 2, 33, 65), (8, 4, 98, 17)])
+def test_the_m_step_with_phi_one_is_the_masked_covariance_bit_for_bit(shape):
+    """The M-step and the beamformer's covariances are one pass (csrc/array_internal.h) under two weights: with phi = 1 the
+    weight lam / 1.0f is lam exactly, the normaliser is the same float32 chain and the reduce the same float64 sum."""
+    Cn, K, N, F = shape
+    g = torch.Generator().manual_seed(1234 + Cn)
+    Y = torch.complex(torch.randn(Cn, N, F, generator=g), torch.randn(Cn, N, F, generator=g)).cuda()
+    lam = (torch.rand(K, N, F, generator=g) * 0.998 + 0.001).cuda()      # in (0, 1); need not sum to one over the classes
+    Rk, _ = cgmm.cgmm_update(Y, lam, torch.ones_like(lam))
+    phi = beamform.spatial_covariance(Y, lam)
+    assert tuple(Rk.shape) == (K, F, Cn, Cn) and torch.isfinite(torch.view_as_real(Rk)).all()
+    assert torch.equal(Rk, phi)
+
+
 @pytest.mark.parametrize("name", [n for n in list(R.CASES) + R.RAGGED if R._shape(n)[3] == 2 and R._shape(n)[0] > 1])
 def test_the_class_order_matches_the_restatement(name, want):
     """on the bins whose purities differ by >= 1 % in the restatement (most bins: the host test)"""
