@@ -10,7 +10,10 @@ Checkpoints of the reference's NnetAM(LSTMStack) (keys `nnet.lstm.*`) and of LST
 DataParallel's `module.` prefix, load unchanged.  -synthetic draws seeded utterances and uses uniform priors.
 -array_frontend mvdr | wpe_mvdr reads every channel of the recordings (the 7-channel LibriCSS evaluation) and puts each
 utterance through (WPE ->) cGMM masks -> MVDR on the device before the filterbank (pykaldi2_amd.cgmm.ArrayFrontEnd); with
--synthetic the utterances are first recorded by a simulated 7-microphone array.
+-synthetic the utterances are first recorded by a simulated 7-microphone array.  -array_frontend sep_mvdr | wpe_sep_mvdr
+separates overlapped speech instead (pykaldi2_amd.separate: blind cGMM masks aligned over the bins, one MVDR per speaker):
+every recording writes one matrix per stream under the keys <utt>_s0 .. <utt>_s{S-1}, S = -num_speakers; with -synthetic
+the recording is the utterance overlapped by a second seeded one in the same simulated room.
 """
 import argparse
 import json
@@ -25,10 +28,12 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from pykaldi2_amd import cgmm, data, fbank, kaldi_io, lstm, se  # noqa: E402
 
 
-def synthetic_array(wav, index, dev):
+def synthetic_array(wav, index, dev, overlap=False):
     """A seeded 7-channel recording of a synthetic utterance, so that -array_frontend runs without data: the utterance and
     a directional noise in a sampled room (rirgen, the circular array of beamform.array_geometry()), mixed by
-    MultiSourceSimulator.  (C, n) CUDA float32, n the utterance's length; numpy's generator is left as it was."""
+    MultiSourceSimulator.  overlap=True (the separating front ends): the second position of the same room holds a second
+    seeded utterance instead of the noise, and the mixer places the two as overlapping sources.  (C, n) CUDA float32, n the
+    utterance's length; numpy's generator is left as it was."""
     from pykaldi2_amd import _lib, beamform, rirgen, simulation, synth
     state = np.random.get_state()
     np.random.seed(20161 + index)
@@ -36,9 +41,15 @@ def synthetic_array(wav, index, dev):
         room, t60, mic, src = rirgen.sample_online_room((0.1, 0.5), 2, mic_positions=beamform.array_geometry())
         b = rirgen.rirgen_batch([dict(room=room, source_loc=src, mic_loc=mic, t60=t60)], device=dev)
         rirs, dl = b.rirs[0], b.delays[0]
-        noise = np.ascontiguousarray(synth.waveform(np.random.default_rng(977 + index), wav.shape[0] / 16000.0 + 0.5), np.float32)
-        sim = simulation.MultiSourceSimulator(use_rir=True, use_noise=True, n_source_range=(1, 1))
-        mixed = sim([_lib.h2d(wav, dev)], [_lib.h2d(noise, dev)], [rirs[0]], [rirs[1]], rir_delays=[dl[0], dl[1]])[0]
+        if overlap:
+            other = np.ascontiguousarray(synth.waveform(np.random.default_rng(977 + index), wav.shape[0] / 16000.0), np.float32)
+            sim = simulation.MultiSourceSimulator(use_rir=True, use_noise=False, n_source_range=(2, 2))
+            mixed = sim([_lib.h2d(wav, dev), _lib.h2d(other, dev)], None, [rirs[0], rirs[1]], None, rir_delays=[dl[0], dl[1]])[0]
+        else:
+            noise = np.ascontiguousarray(synth.waveform(np.random.default_rng(977 + index), wav.shape[0] / 16000.0 + 0.5),
+                                         np.float32)
+            sim = simulation.MultiSourceSimulator(use_rir=True, use_noise=True, n_source_range=(1, 1))
+            mixed = sim([_lib.h2d(wav, dev)], [_lib.h2d(noise, dev)], [rirs[0]], [rirs[1]], rir_delays=[dl[0], dl[1]])[0]
     finally:
         np.random.set_state(state)
     n = wav.shape[0]
@@ -50,7 +61,7 @@ def synthetic_array(wav, index, dev):
 def enhance(frontend, arrays, dev):
     """arrays: host or device (C, n) signals of one batch -> list of device float32 (n,): the array front end on the
     utterances with more than one channel, grouped by their channel count (one launch per stage and group); a
-    one-channel signal passes through."""
+    one-channel signal passes through.  A separating front end gives a list of waveforms per signal."""
     arrays = [a if isinstance(a, th.Tensor) else th.from_numpy(a).to(dev) for a in arrays]
     out = [None] * len(arrays)
     for C in sorted(set(a.shape[0] for a in arrays)):
@@ -60,7 +71,7 @@ def enhance(frontend, arrays, dev):
     return out
 
 
-def main():
+def arg_parser():
     parser = argparse.ArgumentParser()
     parser.add_argument("-config")
     parser.add_argument("-model_path")
@@ -76,8 +87,15 @@ def main():
     parser.add_argument("-synthetic", type=int, default=0, help="dump this many seeded synthetic utterances instead")
     parser.add_argument("-array_frontend", default="none", choices=list(cgmm.FRONT_ENDS),
                         help="multi-channel front end in front of the filterbank: mvdr (cGMM masks -> MVDR) or wpe_mvdr (WPE "
-                             "first); every channel of a WAV is read (default none: channel 0)")
-    args = parser.parse_args()
+                             "first); sep_mvdr | wpe_sep_mvdr: blind separation, one stream per speaker under the keys "
+                             "<utt>_s0 ...; every channel of a WAV is read (default none: channel 0)")
+    parser.add_argument("-num_speakers", default=2, type=int,
+                        help="streams per recording of -array_frontend sep_mvdr | wpe_sep_mvdr (default 2)")
+    return parser
+
+
+def main():
+    args = arg_parser().parse_args()
 
     with open(args.config) as f:
         config = yaml.safe_load(f)
@@ -102,12 +120,15 @@ def main():
     transform = None
     if args.transform and os.path.isfile(args.transform):
         transform = fbank.GlobalMeanVarianceNormalization.load(args.transform)
-    frontend = cgmm.ArrayFrontEnd(args.array_frontend) if args.array_frontend != "none" else None
+    separates = args.array_frontend in ("sep_mvdr", "wpe_sep_mvdr")
+    frontend = None
+    if args.array_frontend != "none":
+        frontend = cgmm.ArrayFrontEnd(args.array_frontend, **(dict(num_speakers=args.num_speakers) if separates else {}))
     if args.synthetic:
         source = data.SyntheticSource(P, seed=11)
         utts = [source.draw() for _ in range(args.synthetic)]
         if frontend:
-            utts = [(synthetic_array(u[0], i, dev),) + tuple(u[1:]) for i, u in enumerate(utts)]
+            utts = [(synthetic_array(u[0], i, dev, overlap=separates),) + tuple(u[1:]) for i, u in enumerate(utts)]
     elif frontend:
         source = data.ZipWavSource([dict(wav=args.data_path)])
         utts = []
@@ -127,8 +148,13 @@ def main():
     with th.no_grad(), kaldi_io.MatrixWriter("ark:" + args.out_file) as llout:
         for i in range(n_batches):
             chunk = utts[i * args.batch_size:(i + 1) * args.batch_size]
+            keys = [u[3] for u in chunk]
             if frontend:
                 waves = enhance(frontend, [u[0] for u in chunk], dev)
+                if separates:      # one matrix per stream; a one-channel file came back once and keeps its key
+                    keys = [k if u[0].shape[0] == 1 else "%s_s%d" % (k, s) for k, u, st in zip(keys, chunk, waves)
+                            for s in range(len(st))]
+                    waves = [w for st in waves for w in st]
                 lens = [int(w.shape[0]) for w in waves]
                 wav = th.cat(waves)
             else:
@@ -143,8 +169,8 @@ def main():
                 frames = [int(t) // sub for t in frames]
             prediction = model.forward_time_major(x).transpose(0, 1)
             # save only the unpadded part of each utterance in the batch
-            for j in range(len(chunk)):
-                llout[chunk[j][3]] = prediction[j, :frames[j], :] - log_prior
+            for j in range(len(keys)):
+                llout[keys[j]] = prediction[j, :frames[j], :] - log_prior
             print("Process batch [{}/{}]".format(i + 1, n_batches))
 
 

@@ -730,6 +730,34 @@ int pk2_cgmm(const float* const* spec, const float* const* init, const float* co
              float* const* masks, float* R, float* log_alpha, double* ll, int32_t* nonfinite, void* stream);
 
 /* ------------------------------------------------------------------ *
+ * Frequency permutation alignment of cGMM masks of a ragged minibatch (csrc/perm_align.hip; no counterpart
+ * in the reference): a blind EM runs per bin, so its classes are unrelated from bin to bin; this finds one permutation
+ * pi_f of the K classes (2 .. PK2_BF_MAX_MASKS) per bin from how the posteriors move over time (Sawada et al. 2011) and
+ * writes out_masks_b[a, t, f] = masks_b[pi_f[a], t, f], out of place.  masks, out_masks: HOST arrays of B device pointers
+ * to f32 (K, N_b, F); frames: HOST array.  cov (B, K, F, C, C, 2) and log_alpha (B, K, F), device, are optional (both or
+ * neither, with out_cov and out_log_alpha) and are gathered the same way.  perm: device int32 (B, F, K) = pi_f[a];
+ * margin: device f32 (B, F).
+ *
+ * u[f][k] = pearson(masks[k, :, f]), pearson(v) = (v - mean v) / max(||v - mean v||_2, 1e-10), float64 sums, stored as
+ * f32 (F, K, N_b).  best(S) of a K x K score matrix: the permutation p maximising sum_a S[a][p[a]], the K! candidates in
+ * lexicographic order, the first maximum wins.  Tree: level 0 has one group per bin (centroid u[f], weight 1); a level
+ * merges the neighbours (2j, 2j + 1): S[a][b] = <cL[a], cR[b]>, p = best(S), every bin of the right group gets
+ * pi_f <- pi_f o p (new pi_f[a] = old pi_f[p[a]]), the merged centroid is pearson(wL cL[a] + wR cR[p[a]]) with weight
+ * wL + wR; a last odd group passes up.  Then `refine` (1 .. PK2_PERM_ALIGN_MAX_REFINE) rounds:
+ * c[a] = pearson(sum_f u[f][pi_f[a]]); per bin S[a][b] = <c[a], u[f][pi_f[b]]>, p = best(S), pi_f <- pi_f o p.
+ * margin[f]: the best score minus the second best of the last round.  noise_last != 0 with cov: the stream with the
+ * smallest sum over the bins of ||R||_F^2 / (Re tr R)^2 (where finite) moves to position K - 1 (a tie keeps the first),
+ * the others keep their order.  No atomics, no host synchronisation: bit-identical from run to run and independent of the
+ * other utterances of the call; more than PK2_BF_MAX_UTTS utterances take one launch per stage per PK2_BF_MAX_UTTS.
+ * work: device memory of pk2_perm_align_workspace_bytes(frames, B, F, K) bytes; 0 for arguments the entry would refuse.
+ * ------------------------------------------------------------------ */
+#define PK2_PERM_ALIGN_MAX_REFINE 8
+size_t pk2_perm_align_workspace_bytes(const int32_t* frames, int32_t B, int32_t F, int32_t K);
+int pk2_perm_align(const float* const* masks, const float* cov, const float* log_alpha, const int32_t* frames, int32_t B,
+                   int32_t C, int32_t F, int32_t K, int32_t refine, int32_t noise_last, void* work, size_t work_bytes,
+                   float* const* out_masks, float* out_cov, float* out_log_alpha, int32_t* perm, float* margin, void* stream);
+
+/* ------------------------------------------------------------------ *
  * Fused log-softmax + NLL + gradient. Replaces nn.CrossEntropyLoss
  * (ignore_index=-100; reduction mean: reference bin/train_ce.py:134,189;
  * reduction sum: bin/train_se.py:214,235).

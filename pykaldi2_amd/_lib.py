@@ -65,6 +65,7 @@ BF_MAX_MASKS = 4         # PK2_BF_MAX_MASKS
 BF_FRAMES_PER_PART = 32  # PK2_BF_FRAMES_PER_PART
 BF_REF_SNR = -1          # PK2_BF_REF_SNR
 CGMM_MAX_ITERS = 32      # PK2_CGMM_MAX_ITERS
+PERM_ALIGN_MAX_REFINE = 8  # PK2_PERM_ALIGN_MAX_REFINE
 WPE_MAX_CHANNELS = 8     # PK2_WPE_MAX_CHANNELS
 WPE_MAX_ORDER = 80       # PK2_WPE_MAX_ORDER
 WPE_MAX_DELAY = 8        # PK2_WPE_MAX_DELAY
@@ -229,6 +230,9 @@ SIGNATURES = {
                                   _i32, _i32, _vp, _sz, _vp, _vp, _vp]),
     "pk2_cgmm": (C.c_int, [C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_i32), _i32, _i32, _i32, _i32, _i32,
                            C.c_double, _i32, _vp, _sz, C.POINTER(_vp), _vp, _vp, _vp, _vp, _vp]),
+    "pk2_perm_align_workspace_bytes": (_sz, [_vp, _i32, _i32, _i32]),
+    "pk2_perm_align": (C.c_int, [C.POINTER(_vp), _vp, _vp, C.POINTER(_i32), _i32, _i32, _i32, _i32, _i32, _i32, _vp, _sz,
+                                 C.POINTER(_vp), _vp, _vp, _vp, _vp, _vp]),
     "pk2_softmax_ce_fwd_bwd": (C.c_int, [_vp, _i64, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _i64, _vp, _vp]),
     "pk2_softmax_ce_fwd_bwd_mean": (C.c_int, [_vp, _i64, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _i64, _vp]),
     "pk2_scale_inplace_ratio": (C.c_int, [_vp, _i64, _vp, _vp, _vp]),

@@ -3,7 +3,7 @@ beamformer needs on a recording, where no clean source exists for simulation.Mas
 an EM over the frames of a mixture of K complex Gaussians y ~ N(0, phi_k[t] R_k) with weights alpha_k (Higuchi et al.
 2016); with a per-class frame activity it is the guided form used for overlapped speech.
 
-  cgmm_masks(spec, num_classes, iterations, init, activity, diag_load, order)   the whole EM: float32 masks (K, N, F)
+  cgmm_masks(spec, num_classes, iterations, init, activity, diag_load, order, seed)   the whole EM: float32 masks (K, N, F)
   cgmm_init(spec, init, activity)              the start state (R complex64 (K, F, C, C), log_alpha float32 (K, F))
   cgmm_factor(R, log_alpha, diag_load)         R' = L L^H in float64: (L^-1 planes, b = log alpha - 2 sum log L_jj, bad)
   cgmm_posteriors(spec, factor, activity)      (lambda (K, N, F), phi (K, N, F), log-likelihood float64 ())
@@ -12,9 +12,12 @@ an EM over the frames of a mixture of K complex Gaussians y ~ N(0, phi_k[t] R_k)
 
 Spectra are complex64 (C, N, F) as MaskBeamformer.analyze returns them; 1 <= C <= 8, 2 <= K <= 4, 1 <= iterations <= 32.
 `init` is K masks (a (K, N, F) tensor or K tensors (N, F)); without it K = 2 and class 0 starts from the observed
-covariance, class 1 from a scaled identity.  `activity` is float32 (K, N), >= 0: a class with activity 0 on a frame gets a
-zero mask there.  order='purity' (K = 2, the default without `init`) makes class 0, bin by bin, the class whose covariance is
-closer to rank one: the directional source; 'keep' (the default with `init`) leaves the classes as they are.  Every function
+covariance, class 1 from a scaled identity.  init='random' is the blind start for any K: seeded uniform masks drawn on the
+host (random_init(K, N, F, seed, i) for utterance i of the call), in the order 'keep': the classes of different bins are then
+unrelated, and pykaldi2_amd.separate.align_permutations puts them in one order.  `activity` is float32 (K, N), >= 0: a
+class with activity 0 on a frame gets a zero mask there.  order='purity' (K = 2, the default without `init`) makes class 0,
+bin by bin, the class whose covariance is closer to rank one: the directional source; 'keep' (the default with `init`)
+leaves the classes as they are.  Every function
 also takes lists, one entry per utterance of a ragged minibatch (common C, F and K), and then makes one launch per stage for
 the list.  `last_ll` (float64 (iterations,), or (B, iterations)), `last_cov` ((K, F, C, C): the M-step of the returned
 masks), `last_log_alpha` and `last_nonfinite` (int32, one entry per utterance: a bin was not finite or not positive definite
@@ -22,6 +25,7 @@ and got the masks 1 / K) keep the last cgmm_masks call's; they are device tensor
 
   cgmm_config(beamform_config)      validation of the data_config keys `beamform: {mask, cgmm_iterations}` (needs no GPU)
 """
+import numpy as np
 import torch
 
 from . import _lib
@@ -95,7 +99,14 @@ def _order_arg(order, init, K, who):
     return order == "purity"
 
 
-def cgmm_masks(spec, num_classes=2, iterations=10, init=None, activity=None, diag_load=1e-3, order=None):
+def random_init(K, N, F, seed, index=0):
+    """The blind start of cgmm_masks(init='random', seed) for utterance `index` of a call: numpy float32 (K, N, F), uniform
+    draws of numpy.random.default_rng([seed, index]) plus 0.05, normalised over the classes.  Needs no GPU."""
+    x = np.random.default_rng([seed, index]).random((K, N, F), np.float32) + np.float32(0.05)
+    return (x / x.sum(axis=0, keepdims=True)).astype(np.float32)
+
+
+def cgmm_masks(spec, num_classes=2, iterations=10, init=None, activity=None, diag_load=1e-3, order=None, seed=0):
     """spec: complex64 (C, N, F), or a list of them (one launch per stage and iteration for the list).  Returns float32
     (K, N, F): the posteriors of the last E-step; for a list, a list.  See the module text for the arguments and for
     `last_ll`, `last_cov`, `last_log_alpha` and `last_nonfinite`.  Nothing is read back."""
@@ -105,6 +116,12 @@ def cgmm_masks(spec, num_classes=2, iterations=10, init=None, activity=None, dia
     K = _int_arg(num_classes, 2, MAX_CLASSES, who, "num_classes")
     iterations = _int_arg(iterations, 1, MAX_ITERS, who, "iterations")
     diag_load = _diag_load_arg(diag_load, who)
+    if isinstance(init, str):
+        if init != "random":
+            raise ValueError("%s: init must be masks or 'random', got %r" % (who, init))
+        seed = _int_arg(seed, 0, 2 ** 63 - 1, who, "seed")
+        draws = [_lib.h2d(random_init(K, int(s.shape[1]), F, seed, i), dev) for i, s in enumerate(specs)]
+        init = draws if many else draws[0]
     inits = _per_utt(init, many, len(specs), who, "init")
     if inits is not None:
         inits, Ki = _planes(inits, specs, None, who, "init")
@@ -290,33 +307,48 @@ class CgmmMaskEstimator:
         return self.masks(self.analyze(wav))
 
 
-FRONT_ENDS = ("none", "mvdr", "wpe_mvdr")
+FRONT_ENDS = ("none", "mvdr", "wpe_mvdr", "sep_mvdr", "wpe_sep_mvdr")
 
 
 class ArrayFrontEnd:
     """The multi-channel front end of a recording (bin/dump_loglikes.py -array_frontend): kind 'mvdr': cGMM masks -> MVDR;
     'wpe_mvdr': WPE on the array spectrum first.  __call__(wavs): a list of (C, n) CUDA float32 signals (common C) -> a
     list of (n,) enhanced waveforms; one forward and one inverse transform per utterance, and between them one launch per
-    stage for the whole list.  A one-channel signal has nothing to beamform and comes back as it is."""
+    stage for the whole list.  A one-channel signal has nothing to beamform and comes back as it is.  The kinds 'sep_mvdr'
+    and 'wpe_sep_mvdr' separate overlapped speech (pykaldi2_amd.separate): blind cGMM masks for num_speakers speakers and
+    the noise, aligned over the bins, and one MVDR beamformer per speaker; the result is then a list of num_speakers
+    waveforms per recording (a one-channel signal comes back once, as a list of one)."""
 
-    def __init__(self, kind, analyzer=None, iterations=10, ref=0, diag_load=1e-3, wpe=None):
+    def __init__(self, kind, analyzer=None, iterations=None, ref=0, diag_load=1e-3, wpe=None, num_speakers=2, seed=0):
         from . import beamform, dereverb, simulation
         if kind not in FRONT_ENDS[1:]:
             raise ValueError("ArrayFrontEnd: kind must be one of %s, got %r" % (" | ".join(FRONT_ENDS[1:]), kind))
         self.kind = kind
+        self.separates = kind in ("sep_mvdr", "wpe_sep_mvdr")
+        if self.separates:
+            self.num_speakers = _int_arg(num_speakers, 1, MAX_CLASSES - 1, "ArrayFrontEnd", "num_speakers")
         self.analyzer = analyzer if analyzer is not None else simulation.SpectrumAnalyzer(do_dither=False)
-        self.estimator = CgmmMaskEstimator(self.analyzer, iterations)
         self.beamformer = beamform.MaskBeamformer(self.analyzer, ref, diag_load)
-        self.dereverb = dereverb.Dereverberator(self.analyzer, **(wpe or {})) if kind == "wpe_mvdr" else None
+        if self.separates:
+            from . import separate
+            self.estimator = separate.CgmmSeparator(self.analyzer, self.num_speakers, 20 if iterations is None else iterations,
+                                                    seed=seed)
+        else:
+            self.estimator = CgmmMaskEstimator(self.analyzer, 10 if iterations is None else iterations)
+        self.dereverb = dereverb.Dereverberator(self.analyzer, **(wpe or {})) if kind.startswith("wpe_") else None
 
     def __call__(self, wavs):
         from . import beamform
         wavs = list(wavs)
         if all(x.shape[0] == 1 for x in wavs):
-            return [x[0] for x in wavs]
+            return [[x[0]] for x in wavs] if self.separates else [x[0] for x in wavs]
         specs = [self.beamformer.analyze(x) for x in wavs]
         if self.dereverb is not None:
             specs = self.dereverb.spectrum(specs)
+        if self.separates:
+            from . import separate
+            streams = separate.separate(specs, self.estimator.masks(specs), self.beamformer.ref, self.beamformer.diag_load)
+            return [[self.analyzer.synthesize(X)[:x.shape[1]] for X in st] for st, x in zip(streams, wavs)]
         phi = beamform.spatial_covariance(specs, [list(p) for p in self.estimator.masks(specs)])
         w, _ = beamform.mvdr_weights([p[0] for p in phi], [p[1] for p in phi], self.beamformer.ref, self.beamformer.diag_load)
         enhanced = beamform.apply_weights(specs, w)
