@@ -843,6 +843,23 @@ int pk2_gemm_get_arith(void);
  * the buffer holds the gradient so far).  Replaces pk2_gemm_f32(1, 0, ...) followed by pk2_colsum_f32(A, ..., beta = 1). */
 int pk2_gemm_f32_tn_colsum(int32_t M, int32_t N, int32_t K, float alpha, const float* A, int64_t lda, const float* B,
                            int64_t ldb, float beta, float* C, int64_t ldc, float* colsum, void* stream);
+/* Row-mapped products: only the rows a map lists take part.  rmap is a device int32 array of Mv ASCENDING row indices of a
+ * row-major matrix with M_total (K_total) rows -- for a time-major [T * B, .] minibatch the rows t * B + b with t < len_b, i.e.
+ * the frames that are not padding.  Rows the map leaves out are neither read (they may hold anything, NaN included) nor
+ * written.  rmap == NULL or Mv == the total row count is the unmapped entry, unchanged.
+ *   pk2_gemm_f32_rows:            C[rmap[m], :] = alpha * A[rmap[m], :] * op(B) + beta * C[rmap[m], :] + bias,  m < Mv
+ *                                 (A row-major [M_total, K]; transb as in pk2_gemm_f32; tiles / bands / K slices chosen for Mv rows)
+ *   pk2_gemm_f32_tn_colsum_rows:  C = alpha * sum_{k<Kv} A[rmap[k], :]^T B[rmap[k], :] + beta * C,  colsum[m] += sum_{k<Kv} A[rmap[k]][m]
+ *   pk2_rows_zero:                X[rows[i], 0..N) = 0, i < n  (the rows a mapped product did not write, without a fill of all of X)
+ *   pk2_rows_pack:                out[i, 0..N) = X[rows[i], 0..N), i < n  (valid rows gathered into a dense matrix) */
+int pk2_gemm_f32_rows(int32_t transb, int32_t M_total, int32_t N, int32_t K, float alpha, const float* A, int64_t lda,
+                      const float* B, int64_t ldb, float beta, float* C, int64_t ldc, const float* bias,
+                      const int32_t* rmap, int32_t Mv, void* stream);
+int pk2_gemm_f32_tn_colsum_rows(int32_t M, int32_t N, int32_t K_total, float alpha, const float* A, int64_t lda, const float* B,
+                                int64_t ldb, float beta, float* C, int64_t ldc, float* colsum, const int32_t* rmap, int32_t Kv,
+                                void* stream);
+int pk2_rows_zero(float* X, int64_t ldx, int32_t N, const int32_t* rows, int32_t n, void* stream);
+int pk2_rows_pack(const float* X, int64_t ldx, int32_t N, const int32_t* rows, int32_t n, float* out, int64_t ldo, void* stream);
 /* out[n] (+)= sum_m A[m][n]  (bias gradients). */
 int pk2_colsum_f32(const float* A, int64_t lda, int32_t M, int32_t N, float beta, float* out,
                    void* stream);

@@ -91,11 +91,17 @@ template <bool KC, int TILES> struct PieceMap {
   }
 };
 
-template <bool KC, int TILES>
+// MAP (gemm_tile.h): kMapRows -- the clamped row of a k-contiguous operand goes through the map; kMapK -- column offsets only,
+// the memory row of each k comes from the map slab by slab (tile_mainloop_bf16x3).
+template <bool KC, int TILES, int MAP = kMapNone>
 __device__ __forceinline__ void xslab_pointers(const PieceMap<KC, TILES>& pm, const float* __restrict__ base, int64_t ld, int r0,
-                                               int k0, int R, const float* (&ptr)[2], int64_t* step) {
+                                               int k0, int R, const float* (&ptr)[2], int64_t* step, const int* __restrict__ rmap = nullptr) {
+  static_assert(MAP == kMapNone || (MAP == kMapRows && KC) || (MAP == kMapK && !KC), "which operand layout a map applies to");
 #pragma unroll
   for (int h = 0; h < 2; ++h) {
+    if constexpr (MAP == kMapRows) ptr[h] = base + (int64_t)rmap[min(r0 + pm.row[h], R - 1)] * ld + k0 + pm.k[h];
+    else if constexpr (MAP == kMapK) ptr[h] = base + min(r0 + pm.row[h], R - 4);
+    else
     if (KC) ptr[h] = base + (int64_t)min(r0 + pm.row[h], R - 1) * ld + k0 + pm.k[h];
     else    ptr[h] = base + (int64_t)(k0 + pm.k[h]) * ld + min(r0 + pm.row[h], R - 4);
   }
@@ -103,13 +109,37 @@ __device__ __forceinline__ void xslab_pointers(const PieceMap<KC, TILES>& pm, co
 }
 
 // General (bounds-checked, zero-filling) loader of a thread's two pieces.
-template <bool KC, int TILES>
+template <bool KC, int TILES, int MAP = kMapNone>
 __device__ __forceinline__ void xload_general(const PieceMap<KC, TILES>& pm, const float* __restrict__ base, int64_t ld, int r0,
-                                              int k0, int R, int K, bool vec, float4 (&reg)[2]) {
+                                              int k0, int R, int K, bool vec, float4 (&reg)[2], const int* __restrict__ rmap = nullptr) {
+  static_assert(MAP == kMapNone || (MAP == kMapRows && KC) || (MAP == kMapK && !KC), "which operand layout a map applies to");
 #pragma unroll
   for (int h = 0; h < 2; ++h) {
     const int gr = r0 + pm.row[h], gk = k0 + pm.k[h];
     float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    if constexpr (MAP == kMapRows) {
+      if (gr < R) {
+        const float* p = base + (int64_t)rmap[gr] * ld + gk;
+        if (vec && gk + 3 < K) v = *reinterpret_cast<const float4*>(p);
+        else {
+          if (gk + 0 < K) v.x = p[0];
+          if (gk + 1 < K) v.y = p[1];
+          if (gk + 2 < K) v.z = p[2];
+          if (gk + 3 < K) v.w = p[3];
+        }
+      }
+    } else if constexpr (MAP == kMapK) {
+      if (gk < K) {
+        const float* p = base + (int64_t)rmap[gk] * ld + gr;
+        if (vec && gr + 3 < R) v = *reinterpret_cast<const float4*>(p);
+        else {
+          if (gr + 0 < R) v.x = p[0];
+          if (gr + 1 < R) v.y = p[1];
+          if (gr + 2 < R) v.z = p[2];
+          if (gr + 3 < R) v.w = p[3];
+        }
+      }
+    } else
     if (KC) {
       if (gr < R) {
         const float* p = base + (int64_t)gr * ld + gk;
@@ -175,13 +205,15 @@ __device__ __forceinline__ void xstore(const PieceMap<KC, TILES>& pm, u32x4_t* _
 
 // acc (zeroed here) = A[m0.., kbeg..K) * B[kbeg..K), n0..], f32-accurate through the three-way bf16 split.
 // As / Bs: two LDS stages of GeoX<TILES>::slots<KC?>() 16-byte slots each.  Ends behind a barrier.
-template <bool KCA, bool KCB, int TILES>
+template <bool KCA, bool KCB, int TILES, int MAP = kMapNone>
 __device__ __forceinline__ void tile_mainloop_bf16x3(const float* __restrict__ A, int64_t lda, const float* __restrict__ B, int64_t ldb,
                                                      int m0, int n0, int kbeg, int K, int M, int N, bool vecA, bool vecB,
                                                      u32x4_t (*As)[GeoX<TILES>::template slots<KCA>()],
                                                      u32x4_t (*Bs)[GeoX<TILES>::template slots<KCB>()],
                                                      f32x16 (&acc)[TILES][TILES], float* __restrict__ colsum = nullptr,
-                                                     bool zero_acc = true) {
+                                                     bool zero_acc = true, const int* __restrict__ rmap = nullptr) {
+  static_assert(MAP == kMapNone || (MAP == kMapRows && KCA) || (MAP == kMapK && !KCA && !KCB), "kMapRows: rows of a k-contiguous A; kMapK: both operands row-contiguous");
+  constexpr int MAPB = MAP == kMapK ? kMapK : kMapNone;
   // colsum (row-contiguous A only, i.e. the weight-gradient form dW = dY^T X): colsum[m] += sum_k A[k][m] over this tile's k
   // range, added with float atomics -- the bias gradient rides in the product that reads dY anyway (round 6: 62 colsum
   // launches per TransformerAM step, one per LF-MMI step).  The caller passes it to the tiles of ONE column block only.
@@ -218,8 +250,8 @@ __device__ __forceinline__ void tile_mainloop_bf16x3(const float* __restrict__ A
                         (n0 + BN <= N || KCB || ((N & 3) == 0 && N >= 4));
   const float* pa[2]; const float* pb[2];
   int64_t stepA = 0, stepB = 0;
-  xslab_pointers<KCA, TILES>(pma, A, lda, m0, kbeg, M, pa, &stepA);
-  xslab_pointers<KCB, TILES>(pmb, B, ldb, n0, kbeg, N, pb, &stepB);
+  xslab_pointers<KCA, TILES, MAP>(pma, A, lda, m0, kbeg, M, pa, &stepA, rmap);
+  xslab_pointers<KCB, TILES, MAPB>(pmb, B, ldb, n0, kbeg, N, pb, &stepB, rmap);
   // per-lane operand slots of this wave's MFMA tiles (k-group kq of step 0)
   int sa[TILES], sb[TILES];
 #pragma unroll
@@ -292,6 +324,25 @@ __device__ __forceinline__ void tile_mainloop_bf16x3(const float* __restrict__ A
   };
   if (interior) {
     const int nk_fast = (K - kbeg) / XBK;
+    if constexpr (MAP == kMapK) {
+      // (as in tile_mainloop: every fetch first issues the loads of the NEXT fetch's two map entries -- k and k + 1 of this thread,
+      // the same for both operands -- and forms its own pointers from the entries the fetch before it loaded)
+      int mk[2];
+#pragma unroll
+      for (int h = 0; h < 2; ++h) mk[h] = nk_fast > 0 ? rmap[kbeg + pma.k[h]] : 0;
+      pipeline(nk_fast, [&](int ks, float4 (&xa)[2], float4 (&xb)[2]) {
+        int nm[2];
+        const int kn = kbeg + min(ks + 1, nk_fast - 1) * XBK;
+#pragma unroll
+        for (int h = 0; h < 2; ++h) nm[h] = rmap[kn + pma.k[h]];
+#pragma unroll
+        for (int h = 0; h < 2; ++h) xa[h] = *reinterpret_cast<const float4*>(pa[h] + (int64_t)mk[h] * lda);
+#pragma unroll
+        for (int h = 0; h < 2; ++h) xb[h] = *reinterpret_cast<const float4*>(pb[h] + (int64_t)mk[h] * ldb);
+#pragma unroll
+        for (int h = 0; h < 2; ++h) mk[h] = nm[h];
+      });
+    } else
     pipeline(nk_fast, [&](int ks, float4 (&xa)[2], float4 (&xb)[2]) {
 #ifdef PK2_X3_DBG_NOLOAD        // (bottleneck hunt: every slab re-reads slab 0 -- L1 hits)
       ks = 0;
@@ -302,8 +353,8 @@ __device__ __forceinline__ void tile_mainloop_bf16x3(const float* __restrict__ A
       for (int h = 0; h < 2; ++h) xb[h] = *reinterpret_cast<const float4*>(pb[h] + ks * stepB);
     });
     if (nk > nk_fast) {
-      xload_general<KCA, TILES>(pma, A, lda, m0, kbeg + nk_fast * XBK, M, K, vecA, ra[0]);
-      xload_general<KCB, TILES>(pmb, B, ldb, n0, kbeg + nk_fast * XBK, N, K, vecB, rb[0]);
+      xload_general<KCA, TILES, MAP>(pma, A, lda, m0, kbeg + nk_fast * XBK, M, K, vecA, ra[0], rmap);
+      xload_general<KCB, TILES, MAPB>(pmb, B, ldb, n0, kbeg + nk_fast * XBK, N, K, vecB, rb[0], rmap);
       store_a(As[0], ra[0]);
       xstore<KCB, TILES>(pmb, Bs[0], rb[0]);
       lds_barrier();
@@ -312,8 +363,8 @@ __device__ __forceinline__ void tile_mainloop_bf16x3(const float* __restrict__ A
     }
   } else {
     pipeline(nk, [&](int ks, float4 (&xa)[2], float4 (&xb)[2]) {
-      xload_general<KCA, TILES>(pma, A, lda, m0, kbeg + ks * XBK, M, K, vecA, xa);
-      xload_general<KCB, TILES>(pmb, B, ldb, n0, kbeg + ks * XBK, N, K, vecB, xb);
+      xload_general<KCA, TILES, MAP>(pma, A, lda, m0, kbeg + ks * XBK, M, K, vecA, xa, rmap);
+      xload_general<KCB, TILES, MAPB>(pmb, B, ldb, n0, kbeg + ks * XBK, N, K, vecB, xb, rmap);
     });
   }
   if constexpr (!KCA) {

@@ -34,10 +34,12 @@ struct GemmBatch { int n1; int64_t sA0, sA1, sB0, sB1, sC0, sC1; int ksplit, kle
 #endif
 // Epilogue of a block tile: the wave's TILES x TILES accumulators (C/D layout of the 32x32 MFMA: col = lane & 31,
 // row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)) -> C rows m0 + wm.., columns n0 + wn..
-template <int TILES>
+// RMAP (pk2_gemm_f32_rows): row m of the product is stored to row rmap[m] of C (M = the number of mapped rows).
+template <int TILES, bool RMAP = false>
 __device__ __forceinline__ void gemm_store(const f32x16 (&acc)[TILES][TILES], int M, int N, float alpha, float beta, float* __restrict__ C,
                                            int64_t ldc, const float* __restrict__ bias, int m0, int n0, int wm, int wn, bool atomic,
-                                           int act = 0, const float* __restrict__ gate = nullptr, int64_t ldg = 0) {
+                                           int act = 0, const float* __restrict__ gate = nullptr, int64_t ldg = 0,
+                                           const int* __restrict__ rmap = nullptr) {
   const int lane = threadIdx.x & 63;
   const int col_l = lane & 31, row_h = 4 * (lane >> 5);
 #pragma unroll
@@ -50,6 +52,8 @@ __device__ __forceinline__ void gemm_store(const f32x16 (&acc)[TILES][TILES], in
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const int gr = m0 + wm + i * 32 + (r & 3) + 8 * (r >> 2) + row_h;
+          if constexpr (RMAP) { if (gr < M) atomicAdd(C + (int64_t)rmap[gr] * ldc + gc, alpha * acc[i][j][r]); }
+          else
           if (gr < M) atomicAdd(C + (int64_t)gr * ldc + gc, alpha * acc[i][j][r]);
         }
         continue;
@@ -58,6 +62,14 @@ __device__ __forceinline__ void gemm_store(const f32x16 (&acc)[TILES][TILES], in
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int gr = m0 + wm + i * 32 + (r & 3) + 8 * (r >> 2) + row_h;
+        if constexpr (RMAP) {
+          if (gr < M) {
+            float* o = C + (int64_t)rmap[gr] * ldc + gc;
+            float v = alpha * acc[i][j][r] + bv;
+            if (beta != 0.f) v += beta * (*o);
+            *o = v;
+          }
+        } else
         if (gr < M) {
           float* o = C + (int64_t)gr * ldc + gc;
           float v = alpha * acc[i][j][r] + bv;
@@ -79,12 +91,14 @@ constexpr size_t gemm_smem_bytes() {
   return 2 * sizeof(float) * BK * (size_t)(Geo<TILES>::template ld<!TA>() + Geo<TILES>::template ld<TB>());
 }
 
-template <bool TA, bool TB, int TILES, bool X3, bool SEG = false>
+template <bool TA, bool TB, int TILES, bool X3, bool SEG = false, int MAP = kMapNone>
 __device__ __forceinline__ void gemm_block(void* smem, int M, int N, int K, int kbeg, float alpha, const float* __restrict__ A, int64_t lda,
                                            const float* __restrict__ B, int64_t ldb, float beta, float* __restrict__ C,
                                            int64_t ldc, const float* __restrict__ bias, bool vecA, bool vecB, int m0, int n0,
                                            bool atomic, float* colsum = nullptr, int act = 0, const float* __restrict__ gate = nullptr,
-                                           int64_t ldg = 0, int nseg = 1, int64_t segA = 0, int64_t segB = 0) {
+                                           int64_t ldg = 0, int nseg = 1, int64_t segA = 0, int64_t segB = 0,
+                                           const int* __restrict__ rmap = nullptr) {
+  static_assert(MAP == kMapNone || !SEG, "a mapped product has one segment");
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int wm = (w >> 1) * 32 * TILES, wn = (w & 1) * 32 * TILES;
 
@@ -100,6 +114,8 @@ __device__ __forceinline__ void gemm_block(void* smem, int M, int N, int K, int 
     // SEG (pk2_gemm_f32_seg): the segments' products one behind the other into the same accumulators (each main loop ends behind a
     // barrier).  A template parameter, not a run-time branch: with both forms in ONE kernel every ordinary product ran slower (CE
     // step 19.0 -> 19.8 ms, LF-MMI 11.59 -> 11.73, same job twice: the second copy of the main loop changes the register allocation).
+    if constexpr (MAP != kMapNone) tile_mainloop_bf16x3<!TA, TB, TILES, MAP>(A, lda, B, ldb, m0, n0, kbeg, K, M, N, vecA, vecB, Ax, Bx, acc, n0 == 0 ? colsum : nullptr, true, rmap);
+    else
     if constexpr (!SEG) tile_mainloop_bf16x3<!TA, TB, TILES>(A, lda, B, ldb, m0, n0, kbeg, K, M, N, vecA, vecB, Ax, Bx, acc, n0 == 0 ? colsum : nullptr);
     else
       for (int sg = 0; sg < nseg; ++sg)
@@ -110,6 +126,8 @@ __device__ __forceinline__ void gemm_block(void* smem, int M, int N, int K, int 
     typedef float (*StB)[BK * LDB];
     StA As = reinterpret_cast<StA>(smem);
     StB Bs = reinterpret_cast<StB>(reinterpret_cast<float*>(smem) + 2 * BK * LDA);
+    if constexpr (MAP != kMapNone) tile_mainloop<!TA, TB, TILES, MAP>(A, lda, B, ldb, m0, n0, kbeg, K, M, N, vecA, vecB, As, Bs, acc, true, rmap);
+    else
     if constexpr (!SEG) tile_mainloop<!TA, TB, TILES>(A, lda, B, ldb, m0, n0, kbeg, K, M, N, vecA, vecB, As, Bs, acc);
     else
       for (int sg = 0; sg < nseg; ++sg)
@@ -118,6 +136,8 @@ __device__ __forceinline__ void gemm_block(void* smem, int M, int N, int K, int 
 #ifdef PK2_GEMM_PROFILE
   const long long gp_t1 = wall_clock64();
 #endif
+  if constexpr (MAP == kMapRows) gemm_store<TILES, true>(acc, M, N, alpha, beta, C, ldc, bias, m0, n0, wm, wn, atomic, 0, nullptr, 0, rmap);
+  else
   gemm_store<TILES>(acc, M, N, alpha, beta, C, ldc, bias, m0, n0, wm, wn, atomic, act, gate, ldg);
 #ifdef PK2_GEMM_PROFILE
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -189,6 +209,101 @@ __global__ void __launch_bounds__(kGemmThreads, X3 ? PK2_GEMMX_WAVES : 3) gemm_f
   }
 }
 
+// Row-mapped products (pk2_gemm_f32_rows, pk2_gemm_f32_tn_colsum_rows).  `rmap[0..Mv)` lists, in ascending order, the rows of a
+// time-major [T B, .] matrix that hold real frames.  Kernels of their own: the unmapped kernels above keep their code.
+//   kMapRows  C[rmap[m], :] = alpha A[rmap[m], :] op(B) + beta C[rmap[m], :] + bias   (A row-major; M = Mv rows of tiles)
+//   kMapK     C += alpha A[rmap[k], :]^T B[rmap[k], :]                                  (A, B row-major; K = Mv)
+// blockIdx.z = K slice (ksplit > 1: float atomics into a C that holds beta C + bias in the mapped rows already).
+template <bool TA, bool TB, int TILES, bool X3, int MAP>
+__global__ void __launch_bounds__(kGemmThreads, X3 ? PK2_GEMMX_WAVES : 3) gemm_f32_rows_kernel(int M, int N, int K, float alpha,
+                                                                const float* __restrict__ A, int64_t lda,
+                                                                const float* __restrict__ B, int64_t ldb,
+                                                                float beta, float* __restrict__ C, int64_t ldc,
+                                                                const float* __restrict__ bias, bool vecA, bool vecB,
+                                                                int ksplit, int klen, float* __restrict__ colsum,
+                                                                const int* __restrict__ rmap) {
+  int kbeg = 0;
+  if (ksplit > 1) {
+    kbeg = blockIdx.z * klen;
+    K = min(K, kbeg + klen);
+  }
+  __shared__ __attribute__((aligned(16))) char smem[gemm_smem_bytes<TA, TB, TILES, X3>()];
+  gemm_block<TA, TB, TILES, X3, false, MAP>(smem, M, N, K, kbeg, alpha, A, lda, B, ldb, beta, C, ldc, bias, vecA, vecB,
+                                            blockIdx.y * Geo<TILES>::BMN, blockIdx.x * Geo<TILES>::BMN, ksplit > 1, colsum, 0, nullptr, 0,
+                                            1, 0, 0, rmap);
+}
+
+// (the row bands of gemm_f32_bands_kernel over the mapped rows)
+template <bool TB, bool X3>
+__global__ void __launch_bounds__(kGemmThreads, X3 ? PK2_GEMMX_WAVES : 3) gemm_f32_rows_bands_kernel(int M, int N, int K, float alpha,
+                                                                         const float* __restrict__ A, int64_t lda,
+                                                                         const float* __restrict__ B, int64_t ldb,
+                                                                         float beta, float* __restrict__ C, int64_t ldc,
+                                                                         const float* __restrict__ bias, bool vecA,
+                                                                         bool vecB, int nbig, int big_cols, int m_split,
+                                                                         int small_cols, const int* __restrict__ rmap) {
+  const int b = blockIdx.x;
+  __shared__ __attribute__((aligned(16))) char smem[std::max(gemm_smem_bytes<false, TB, 2, X3>(), gemm_smem_bytes<false, TB, 1, X3>())];
+  if (b < nbig) {
+    gemm_block<false, TB, 2, X3, false, kMapRows>(smem, M, N, K, 0, alpha, A, lda, B, ldb, beta, C, ldc, bias, vecA, vecB, (b / big_cols) * 128,
+                                                  (b % big_cols) * 128, false, nullptr, 0, nullptr, 0, 1, 0, 0, rmap);
+  } else {
+    const int s = b - nbig;
+    gemm_block<false, TB, 1, X3, false, kMapRows>(smem, M, N, K, 0, alpha, A, lda, B, ldb, beta, C, ldc, bias, vecA, vecB,
+                                                  m_split + (s / small_cols) * 64, (s % small_cols) * 64, false, nullptr, 0, nullptr, 0, 1,
+                                                  0, 0, rmap);
+  }
+}
+
+// C[rmap[m], :] = beta * C[rmap[m], :] + bias ahead of a split-K row-mapped product.
+__global__ void __launch_bounds__(256) gemm_prescale_rows_kernel(int M, int N, float beta, float* __restrict__ C, int64_t ldc,
+                                                                 const float* __restrict__ bias, const int* __restrict__ rmap) {
+  const int n = blockIdx.x * 256 + threadIdx.x;
+  if (n >= N) return;
+  const float bv = bias ? bias[n] : 0.f;
+  for (int m = blockIdx.y; m < M; m += gridDim.y) {
+    float* o = C + (int64_t)rmap[m] * ldc + n;
+    *o = beta == 0.f ? bv : beta * (*o) + bv;
+  }
+}
+
+// out[n] += sum_m A[rmap[m]][n]: colsum_kernel over the mapped rows (the f32 arithmetic's bias gradient).
+__global__ void __launch_bounds__(256) colsum_rows_kernel(const float* __restrict__ A, int64_t lda, int M, int N, int rows_per_block,
+                                                          float* __restrict__ out, const int* __restrict__ rmap) {
+  __shared__ float red[4][64];
+  const int n = blockIdx.x * 64 + (threadIdx.x & 63);
+  const int part = threadIdx.x >> 6;
+  const int m0 = blockIdx.y * rows_per_block, m1 = min(M, m0 + rows_per_block);
+  float acc = 0.f;
+  if (n < N)
+    for (int m = m0 + part; m < m1; m += 4) acc += A[(int64_t)rmap[m] * lda + n];
+  red[part][threadIdx.x & 63] = acc;
+  __syncthreads();
+  if (part == 0 && n < N)
+    atomicAdd(out + n, (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]));
+}
+
+// X[rows[i], 0..N) = 0 for i < n: the padded rows of a row-mapped product's result, without a fill of the whole matrix.
+// PACK: out[i, 0..N) = X[rows[i], 0..N) instead -- the valid rows gathered into a dense matrix.  One row per blockIdx.y pass.
+template <bool PACK>
+__global__ void __launch_bounds__(256) rows_zero_or_pack_kernel(float* __restrict__ X, int64_t ldx, int N, const int* __restrict__ rows,
+                                                                int n, float* __restrict__ out, int64_t ldo, bool vec) {
+  for (int i = blockIdx.y; i < n; i += gridDim.y) {
+    float* x = X + (int64_t)rows[i] * ldx;
+    if (vec) {        // (N, ldx, ldo multiples of four and 16-byte aligned bases: pk2_rows_zero / pk2_rows_pack)
+      for (int c = (blockIdx.x * 256 + threadIdx.x) * 4; c < N; c += gridDim.x * 1024) {
+        if (PACK) *reinterpret_cast<float4*>(out + (int64_t)i * ldo + c) = *reinterpret_cast<const float4*>(x + c);
+        else *reinterpret_cast<float4*>(x + c) = make_float4(0.f, 0.f, 0.f, 0.f);
+      }
+    } else {
+      for (int c = blockIdx.x * 256 + threadIdx.x; c < N; c += gridDim.x * 256) {
+        if (PACK) out[(int64_t)i * ldo + c] = x[c];
+        else x[c] = 0.f;
+      }
+    }
+  }
+}
+
 // C = beta * C + bias ahead of a split-K product (blockIdx.z = batch entry).
 __global__ void __launch_bounds__(256) gemm_prescale_kernel(int M, int N, float beta, float* __restrict__ C,
                                                             int64_t ldc, const float* __restrict__ bias, GemmBatch bt) {
@@ -254,7 +369,9 @@ extern "C" int pk2_gemm_get_arith(void) { return gemm_arith(); }
 #endif
 static int gemm_launch(int transa, int transb, int M, int N, int K, float alpha, const float* A, int64_t lda,
                        const float* B, int64_t ldb, float beta, float* C, int64_t ldc, const float* bias,
-                       int n0, const GemmBatch& bt_in, bool aligned_strides, hipStream_t stream) {
+                       int n0, const GemmBatch& bt_in, bool aligned_strides, hipStream_t stream,
+                       const int* rmap = nullptr, int map = kMapNone) {
+  // (map: a row-mapped product -- M (kMapRows) or K (kMapK) counts the mapped rows, and every choice below is made for that count)
   GemmBatch bt = bt_in;
   const bool x3 = gemm_arith() == 1;
   const bool vecA = aligned_strides && (reinterpret_cast<uintptr_t>(A) & 15) == 0 && (lda & 3) == 0;
@@ -292,8 +409,26 @@ static int gemm_launch(int transa, int transb, int M, int N, int K, float alpha,
   // summation-order noise of 1e-7 cannot flip anything).  PK2_GEMM_SPLIT_FWD=1 restores the round-5 behaviour.
   static const bool split_fwd = [] { const char* e = getenv("PK2_GEMM_SPLIT_FWD"); return e && atoi(e) == 1; }();
   const bool forward_form = !transa && transb && !split_fwd;
-  if (!forward_form && bt.act == 0 && bt.nseg == 1 && (big_tiles <= 256 || (split_mid && transa && !transb && big_tiles < 512)) && K >= deep_k && (!fsplit || atoi(fsplit) != 1)) {
+  // Row-mapped products of 64 .. 511 tiles (the output layer over the valid rows of a minibatch: dX 11-15 x 8 tiles over K = 6080,
+  // dW 48 x 8 tiles over K = Mv = 1400-1900): the rules below were measured on the unmapped shapes and miss these -- dW at
+  // K = 1413 < 2048 fell to unsliced 64x64 tiles (220 us where the unmapped product over 2276 rows takes 190), dX got
+  // ceil(768 / tiles) = 7-8 slices = 1.5 rounds of the 512 workgroup slots (146-189 us against 128-178 unmapped).  Here the
+  // slice count is the SMALLEST that fills whole rounds of the 512 slots to 90 % (else the best-filling one), slices of at
+  // least PK2_GEMM_MIN_KSLICE k's.  Figures: DESIGN.md 4.2l, profiles/out_rows.txt.  PK2_GEMM_ROWS_SLICES=0 restores the rules below.
+  static const bool rows_slices = [] { const char* e = getenv("PK2_GEMM_ROWS_SLICES"); return !(e && atoi(e) == 0); }();
+  const bool rows_rule = map != kMapNone && rows_slices && !forward_form && !fsplit && !force && big_tiles >= 64 && big_tiles < 512 && K >= 1024;
+  if (rows_rule || (!forward_form && bt.act == 0 && bt.nseg == 1 && (big_tiles <= 256 || (split_mid && transa && !transb && big_tiles < 512)) && K >= deep_k && (!fsplit || atoi(fsplit) != 1))) {
     int ks = (int)std::min<int64_t>((768 + big_tiles - 1) / big_tiles, K / PK2_GEMM_MIN_KSLICE);
+    if (rows_rule) {
+      double best = -1.0;
+      ks = 1;
+      for (int c = 1; c <= std::min(16, K / PK2_GEMM_MIN_KSLICE); ++c) {
+        const int64_t n = big_tiles * c;
+        const double eff = (double)n / (double)((n + 511) / 512 * 512);
+        if (eff >= 0.9) { ks = c; break; }
+        if (eff > best) { best = eff; ks = c; }
+      }
+    } else
     if (big_tiles > 256) {
       // between one and two tiles per CU: the slice count that fills whole rounds of the 512 workgroup slots best (368 tiles:
       // 3 slices leave the last round 28 % idle; measured 2598 us with 3, 2246 with 4, 1998 with 8, 1902 with 16 slices)
@@ -309,7 +444,10 @@ static int gemm_launch(int transa, int transb, int M, int N, int K, float alpha,
       tiles = 2;
       bt.klen = ((K + ks - 1) / ks + BK - 1) / BK * BK;
       bt.ksplit = (K + bt.klen - 1) / bt.klen;
-      if (beta != 1.f || bias)
+      if ((beta != 1.f || bias) && map == kMapRows)
+        hipLaunchKernelGGL(gemm_prescale_rows_kernel, dim3((N + 255) / 256, std::min(M, 256)), dim3(256), 0, stream, M, N, beta, C, ldc,
+                           bias, rmap);
+      else if (beta != 1.f || bias)
         hipLaunchKernelGGL(gemm_prescale_kernel, dim3((N + 255) / 256, std::min(M, 256), n0 * bt.n1), dim3(256), 0,
                            stream, M, N, beta, C, ldc, bias, bt);
     }
@@ -326,6 +464,22 @@ static int gemm_launch(int transa, int transb, int M, int N, int K, float alpha,
 #define PK2_GEMM_SEG_T(TB, T, X)                                                                                  \
   hipLaunchKernelGGL((gemm_f32_kernel<false, TB, T, X, true>), grid, block, 0, stream, m_rows, N, K, alpha, Ap, lda, B, ldb, \
                      beta, Cp, ldc, bias, vecA, vecB, bt)
+    if (map != kMapNone) {   // (never batched, one segment, no activation: the entries see to it; m_off = 0)
+#define PK2_GEMM_ROWS_T(TA, TB, T, X, MP)                                                                                  \
+  hipLaunchKernelGGL((gemm_f32_rows_kernel<TA, TB, T, X, MP>), grid, block, 0, stream, m_rows, N, K, alpha, A, lda, B, ldb, \
+                     beta, C, ldc, bias, vecA, vecB, bt.ksplit, bt.klen, bt.colsum, rmap)
+#define PK2_GEMM_ROWS(TA, TB, MP)                                                                                      \
+  do {                                                                                                                 \
+    if (t == 2) { if (x3) PK2_GEMM_ROWS_T(TA, TB, 2, true, MP); else PK2_GEMM_ROWS_T(TA, TB, 2, false, MP); }          \
+    else        { if (x3) PK2_GEMM_ROWS_T(TA, TB, 1, true, MP); else PK2_GEMM_ROWS_T(TA, TB, 1, false, MP); }          \
+  } while (0)
+      if (map == kMapK) PK2_GEMM_ROWS(true, false, kMapK);
+      else if (transb) PK2_GEMM_ROWS(false, true, kMapRows);
+      else PK2_GEMM_ROWS(false, false, kMapRows);
+#undef PK2_GEMM_ROWS
+#undef PK2_GEMM_ROWS_T
+      return;
+    }
     if (bt.nseg > 1) {       // (A row-major only: pk2_gemm_f32_seg)
       if (transb) { if (t == 2) { if (x3) PK2_GEMM_SEG_T(true, 2, true); else PK2_GEMM_SEG_T(true, 2, false); }
                     else        { if (x3) PK2_GEMM_SEG_T(true, 1, true); else PK2_GEMM_SEG_T(true, 1, false); } }
@@ -367,6 +521,24 @@ static int gemm_launch(int transa, int transb, int M, int N, int K, float alpha,
     }
     if (best_r < R) {
       static const bool one_launch = [] { const char* e = getenv("PK2_GEMM_BANDS_ONE"); return !(e && atoi(e) == 0); }();
+      if (best_r > 0 && map == kMapRows) {
+        const int m_split = best_r * 128, small_rows = (M - m_split + 63) / 64;
+        const int nbig = best_r * Cn;
+        dim3 grid(nbig + small_rows * Cs), block(kGemmThreads);
+#define PK2_GEMM_RBANDS(TB, X)                                                                                                  \
+  hipLaunchKernelGGL((gemm_f32_rows_bands_kernel<TB, X>), grid, block, 0, stream, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc, \
+                     bias, vecA, vecB, nbig, Cn, m_split, Cs, rmap)
+        if (transb) { if (x3) PK2_GEMM_RBANDS(true, true); else PK2_GEMM_RBANDS(true, false); }
+        else        { if (x3) PK2_GEMM_RBANDS(false, true); else PK2_GEMM_RBANDS(false, false); }
+#undef PK2_GEMM_RBANDS
+        PK2_LAUNCH_CHECK();
+        return PK2_OK;
+      }
+      if (map != kMapNone) {      // (all rows on 64x64 tiles, or a k-mapped product: one plain launch)
+        launch(best_r > 0 ? 2 : 1, 0, M);
+        PK2_LAUNCH_CHECK();
+        return PK2_OK;
+      }
       if (best_r > 0 && one_launch) {
         const int m_split = best_r * 128, small_rows = (M - m_split + 63) / 64;
         const int nbig = best_r * Cn;
@@ -454,6 +626,68 @@ extern "C" int pk2_gemm_f32_tn_colsum(int32_t M, int32_t N, int32_t K, float alp
   int rc = gemm_launch(1, 0, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc, nullptr, 1, bt, true, static_cast<hipStream_t>(stream_));
   if (rc || fuse) return rc;
   return pk2_colsum_f32(A, lda, K, M, 1.0f, colsum, stream_);
+}
+
+// Row-mapped forms.  rmap[0..Mv): ascending row indices < M_total of a row-major matrix (the rows of a time-major [T B, .]
+// minibatch that hold real frames).  A null map or Mv == M_total is today's entry, unchanged.
+//   pk2_gemm_f32_rows:  C[rmap[m], :] = alpha A[rmap[m], :] op(B) + beta C[rmap[m], :] + bias for m < Mv; no other row of A is read,
+//   no other row of C written.  A is row-major [M_total, K] (no transa).  Tiles, bands and K slices are chosen for M = Mv.
+extern "C" int pk2_gemm_f32_rows(int32_t transb, int32_t M_total, int32_t N, int32_t K, float alpha, const float* A, int64_t lda,
+                                 const float* B, int64_t ldb, float beta, float* C, int64_t ldc, const float* bias,
+                                 const int32_t* rmap, int32_t Mv, void* stream_) {
+  if (!rmap || Mv == M_total) return pk2_gemm_f32(0, transb, M_total, N, K, alpha, A, lda, B, ldb, beta, C, ldc, bias, stream_);
+  PK2_REQUIRE(A && B && C && N > 0 && K > 0 && Mv > 0 && Mv < M_total, "gemm_f32_rows: bad args");
+  GemmBatch bt{1, 0, 0, 0, 0, 0, 0, 1, 0};
+  return gemm_launch(0, transb, Mv, N, K, alpha, A, lda, B, ldb, beta, C, ldc, bias, 1, bt, true, static_cast<hipStream_t>(stream_),
+                     rmap, kMapRows);
+}
+
+//   pk2_gemm_f32_tn_colsum_rows:  C = alpha sum_{k < Kv} A[rmap[k], :]^T B[rmap[k], :] + beta C, colsum[m] += sum_{k < Kv} A[rmap[k]][m]
+//   (A [K_total, M], B [K_total, N] row-major).  The vector path needs what the unmapped one needs -- 16-byte aligned bases, lda
+//   and ldb multiples of four (a mapped row starts at base + rmap[k] ld: aligned whenever row 0 is), and for an edge tile M / N
+//   a multiple of four (its column offset is clamped to M - 4 / N - 4 as before; the map touches the k term only).
+extern "C" int pk2_gemm_f32_tn_colsum_rows(int32_t M, int32_t N, int32_t K_total, float alpha, const float* A, int64_t lda,
+                                           const float* B, int64_t ldb, float beta, float* C, int64_t ldc, float* colsum,
+                                           const int32_t* rmap, int32_t Kv, void* stream_) {
+  if (!rmap || Kv == K_total) return pk2_gemm_f32_tn_colsum(M, N, K_total, alpha, A, lda, B, ldb, beta, C, ldc, colsum, stream_);
+  PK2_REQUIRE(A && B && C && colsum && M > 0 && N > 0 && Kv > 0 && Kv < K_total, "gemm_f32_tn_colsum_rows: bad args");
+  GemmBatch bt{1, 0, 0, 0, 0, 0, 0, 1, 0};
+  const bool fuse = gemm_arith() == 1;
+  if (fuse) bt.colsum = colsum;
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  int rc = gemm_launch(1, 0, M, N, Kv, alpha, A, lda, B, ldb, beta, C, ldc, nullptr, 1, bt, true, stream, rmap, kMapK);
+  if (rc || fuse) return rc;
+  const int col_blocks = (M + 63) / 64;
+  const int splits = std::max(1, std::min((Kv + 63) / 64, 1024 / col_blocks));
+  const int rows_per_block = (Kv + splits - 1) / splits;
+  hipLaunchKernelGGL(colsum_rows_kernel, dim3(col_blocks, (Kv + rows_per_block - 1) / rows_per_block), dim3(256), 0, stream, A, lda, Kv,
+                     M, rows_per_block, colsum, rmap);
+  PK2_LAUNCH_CHECK();
+  return PK2_OK;
+}
+
+// X[rows[i], 0..N) = 0 for i < n (the padded rows of a row-mapped product's result; no fill of the whole matrix).
+extern "C" int pk2_rows_zero(float* X, int64_t ldx, int32_t N, const int32_t* rows, int32_t n, void* stream_) {
+  PK2_REQUIRE(X && rows && N > 0 && n >= 0 && ldx >= N, "rows_zero: bad args");
+  if (n == 0) return PK2_OK;
+  const bool vec = (N & 3) == 0 && (ldx & 3) == 0 && (reinterpret_cast<uintptr_t>(X) & 15) == 0;
+  const int per = vec ? 1024 : 256;
+  hipLaunchKernelGGL((rows_zero_or_pack_kernel<false>), dim3(std::min((N + per - 1) / per, 64), std::min(n, 4096)), dim3(256), 0,
+                     static_cast<hipStream_t>(stream_), X, ldx, N, rows, n, (float*)nullptr, (int64_t)0, vec);
+  PK2_LAUNCH_CHECK();
+  return PK2_OK;
+}
+
+// out[i, 0..N) = X[rows[i], 0..N) for i < n: the valid rows gathered into a dense matrix (the packed form of the weight gradient).
+extern "C" int pk2_rows_pack(const float* X, int64_t ldx, int32_t N, const int32_t* rows, int32_t n, float* out, int64_t ldo,
+                             void* stream_) {
+  PK2_REQUIRE(X && rows && out && N > 0 && n > 0 && ldx >= N && ldo >= N, "rows_pack: bad args");
+  const bool vec = (N & 3) == 0 && (ldx & 3) == 0 && (ldo & 3) == 0 && ((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(out)) & 15) == 0;
+  const int per = vec ? 1024 : 256;
+  hipLaunchKernelGGL((rows_zero_or_pack_kernel<true>), dim3(std::min((N + per - 1) / per, 64), std::min(n, 4096)), dim3(256), 0,
+                     static_cast<hipStream_t>(stream_), const_cast<float*>(X), ldx, N, rows, n, out, ldo, vec);
+  PK2_LAUNCH_CHECK();
+  return PK2_OK;
 }
 
 extern "C" int pk2_gemm_f32_batched(int32_t transa, int32_t transb, int32_t M, int32_t N, int32_t K, float alpha,

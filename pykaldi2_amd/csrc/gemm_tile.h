@@ -36,9 +36,14 @@ template <int TILES> struct Geo {
 //   KCONTIG: element (r, k) at base[r*ld + k]  -> thread owns float4 along k of 2 rows
 //  !KCONTIG: element (r, k) at base[k*ld + r]  -> thread owns float4 along r of 2 k's
 // Out-of-range elements read as 0.  `vec` = base/ld allow aligned float4 loads.
-template <bool KCONTIG, int TILES>
+// MAP (row-mapped products, pk2_gemm_f32_rows / pk2_gemm_f32_tn_colsum_rows): the memory row of the operand's row-major image is
+// looked up in `rmap` -- kMapRows: element (r, k) of a k-contiguous operand at base[rmap[r] ld + k]; kMapK: element (r, k) of
+// a row-contiguous operand at base[rmap[k] ld + r].  The bounds R / K are those of the MAPPED index, tested before the lookup.
+constexpr int kMapNone = 0, kMapRows = 1, kMapK = 2;
+template <bool KCONTIG, int TILES, int MAP = kMapNone>
 __device__ __forceinline__ void load_slab(const float* __restrict__ base, int64_t ld, int r0, int k0,
-                                          int R, int K, bool vec, float4 (&reg)[TILES]) {
+                                          int R, int K, bool vec, float4 (&reg)[TILES], const int* __restrict__ rmap = nullptr) {
+  static_assert(MAP == kMapNone || (MAP == kMapRows && KCONTIG) || (MAP == kMapK && !KCONTIG), "which operand layout a map applies to");
   const int tid = threadIdx.x;
 #pragma unroll
   for (int h = 0; h < TILES; ++h) {
@@ -47,6 +52,31 @@ __device__ __forceinline__ void load_slab(const float* __restrict__ base, int64_
     else         { k = tid / Geo<TILES>::LPK + h * (kGemmThreads / Geo<TILES>::LPK); r = (tid % Geo<TILES>::LPK) * 4; }
     const int gr = r0 + r, gk = k0 + k;
     float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    if constexpr (MAP == kMapRows) {
+      if (gr < R) {
+        const float* p = base + (int64_t)rmap[gr] * ld + gk;
+        if (vec && gk + 3 < K) {
+          v = *reinterpret_cast<const float4*>(p);
+        } else {
+          if (gk + 0 < K) v.x = p[0];
+          if (gk + 1 < K) v.y = p[1];
+          if (gk + 2 < K) v.z = p[2];
+          if (gk + 3 < K) v.w = p[3];
+        }
+      }
+    } else if constexpr (MAP == kMapK) {
+      if (gk < K) {
+        const float* p = base + (int64_t)rmap[gk] * ld + gr;
+        if (vec && gr + 3 < R) {
+          v = *reinterpret_cast<const float4*>(p);
+        } else {
+          if (gr + 0 < R) v.x = p[0];
+          if (gr + 1 < R) v.y = p[1];
+          if (gr + 2 < R) v.z = p[2];
+          if (gr + 3 < R) v.w = p[3];
+        }
+      }
+    } else
     if (KCONTIG) {
       if (gr < R) {
         const float* p = base + (int64_t)gr * ld + gk;
@@ -88,14 +118,18 @@ __device__ __forceinline__ void load_slab(const float* __restrict__ base, int64_
 // stores.  (Until round 4 edge tiles went through the general loader: on R = 2356 frames the last row band of 64x64 tiles
 // ran its main loop 4.6 x as long as the interior ones -- 60 us against 13 in the profile build -- and every product with
 // M = frames waited for it: 2356 x 512 x 512 took 33 us of which the interior tiles needed 15.)
-template <bool KCONTIG, int TILES>
+// (ROWMAP: the clamped row index goes through the map -- a k-contiguous operand only; the clamp is to the last MAPPED row.
+// For a k-mapped product (kMapK) the pointers are formed WITHOUT the k term: column offsets only, see tile_mainloop.)
+template <bool KCONTIG, int TILES, bool ROWMAP = false>
 __device__ __forceinline__ void slab_pointers(const float* __restrict__ base, int64_t ld, int r0, int k0, int R,
-                                              const float* (&ptr)[TILES], int64_t* step) {
+                                              const float* (&ptr)[TILES], int64_t* step, const int* __restrict__ rmap = nullptr) {
   const int tid = threadIdx.x;
 #pragma unroll
   for (int h = 0; h < TILES; ++h) {
     if (KCONTIG) {
       const int r = (tid >> 2) + h * 64, k = (tid & 3) * 4;
+      if constexpr (ROWMAP) ptr[h] = base + (int64_t)rmap[min(r0 + r, R - 1)] * ld + k0 + k;
+      else
       ptr[h] = base + (int64_t)min(r0 + r, R - 1) * ld + k0 + k;
     } else {
       const int k = tid / Geo<TILES>::LPK + h * (kGemmThreads / Geo<TILES>::LPK), r = (tid % Geo<TILES>::LPK) * 4;
@@ -141,12 +175,14 @@ __device__ __forceinline__ void static_for(F&& f) {
 // (64 TILES) x (64 TILES) tile of 256 threads (4 waves, 2 x 2; wave w owns rows 32 TILES (w / 2).., columns 32 TILES (w % 2)..).
 // KCA / KCB: the operand is k-contiguous in memory (element (r, k) at base[r ld + k]) or row-contiguous (base[k ld + r]).
 // As / Bs: two LDS buffers of BK x Geo<TILES>::ld<KC?>() floats each.  Ends behind a barrier (the buffers are free).
-template <bool KCA, bool KCB, int TILES>
+template <bool KCA, bool KCB, int TILES, int MAP = kMapNone>
 __device__ __forceinline__ void tile_mainloop(const float* __restrict__ A, int64_t lda, const float* __restrict__ B, int64_t ldb,
                                               int m0, int n0, int kbeg, int K, int M, int N, bool vecA, bool vecB,
                                               float (*As)[BK * Geo<TILES>::template ld<KCA>()],
                                               float (*Bs)[BK * Geo<TILES>::template ld<KCB>()],
-                                              f32x16 (&acc)[TILES][TILES], bool zero_acc = true) {
+                                              f32x16 (&acc)[TILES][TILES], bool zero_acc = true, const int* __restrict__ rmap = nullptr) {
+  static_assert(MAP == kMapNone || (MAP == kMapRows && KCA) || (MAP == kMapK && !KCA && !KCB), "kMapRows: rows of a k-contiguous A; kMapK: both operands row-contiguous");
+  constexpr int MAPA = MAP, MAPB = MAP == kMapK ? kMapK : kMapNone;
   constexpr int BM = Geo<TILES>::BMN, BN = Geo<TILES>::BMN;
   constexpr int LDA = Geo<TILES>::template ld<KCA>(), LDB = Geo<TILES>::template ld<KCB>();
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -186,8 +222,22 @@ __device__ __forceinline__ void tile_mainloop(const float* __restrict__ A, int64
                         (n0 + BN <= N || KCB || ((N & 3) == 0 && N >= 4));
   const float* pa[TILES]; const float* pb[TILES];
   int64_t stepA = 0, stepB = 0;
+  if constexpr (MAP == kMapK) {       // column offsets only: the slab's memory rows come from the map, slab by slab
+    slab_pointers<KCA, TILES>(A, lda, m0, 0, M, pa, &stepA);
+    slab_pointers<KCB, TILES>(B, ldb, n0, 0, N, pb, &stepB);
+#pragma unroll
+    for (int h = 0; h < TILES; ++h) {
+      const int k = threadIdx.x / Geo<TILES>::LPK + h * (kGemmThreads / Geo<TILES>::LPK);
+      pa[h] -= (int64_t)k * lda;
+      pb[h] -= (int64_t)k * ldb;
+    }
+  } else if constexpr (MAP == kMapRows) {
+    slab_pointers<KCA, TILES, true>(A, lda, m0, kbeg, M, pa, &stepA, rmap);
+    slab_pointers<KCB, TILES>(B, ldb, n0, kbeg, N, pb, &stepB);
+  } else {
   slab_pointers<KCA, TILES>(A, lda, m0, kbeg, M, pa, &stepA);
   slab_pointers<KCB, TILES>(B, ldb, n0, kbeg, N, pb, &stepB);
+  }
 #ifndef PK2_GEMM_HOIST
 #define PK2_GEMM_HOIST 8        // k-pairs whose operand reads are issued together ahead of their MFMAs (64x64 tiles)
 #endif
@@ -257,13 +307,40 @@ __device__ __forceinline__ void tile_mainloop(const float* __restrict__ A, int64
   };
   if (interior) {
     const int nk_fast = (K - kbeg) / BK;        // slabs that lie wholly inside K
+    if constexpr (MAP == kMapK) {
+      // The memory rows of a slab are no longer affine in the slab index.  The pipeline fetches slabs 0, 1, 2, ... in order
+      // (clamped to the last), so each fetch first issues the loads of the NEXT fetch's map entries and then forms its own
+      // pointers from the entries the fetch before it loaded: the wait for those entries lets this fetch's predecessor's
+      // data loads stay in flight (they were issued behind them), i.e. with two register stages nothing is lost.  Both
+      // operands are row-contiguous with the same thread -> k assignment, so one set of entries serves both.
+      int mk[TILES];
+#pragma unroll
+      for (int h = 0; h < TILES; ++h) mk[h] = nk_fast > 0 ? rmap[kbeg + threadIdx.x / Geo<TILES>::LPK + h * (kGemmThreads / Geo<TILES>::LPK)] : 0;
+      pipeline(nk_fast, [&](int ks, float4 (&xa)[TILES], float4 (&xb)[TILES]) {
+        int nm[TILES];
+        const int kn = kbeg + min(ks + 1, nk_fast - 1) * BK + threadIdx.x / Geo<TILES>::LPK;
+#pragma unroll
+        for (int h = 0; h < TILES; ++h) nm[h] = rmap[kn + h * (kGemmThreads / Geo<TILES>::LPK)];
+#pragma unroll
+        for (int h = 0; h < TILES; ++h) xa[h] = *reinterpret_cast<const float4*>(pa[h] + (int64_t)mk[h] * lda);
+#pragma unroll
+        for (int h = 0; h < TILES; ++h) xb[h] = *reinterpret_cast<const float4*>(pb[h] + (int64_t)mk[h] * ldb);
+#pragma unroll
+        for (int h = 0; h < TILES; ++h) mk[h] = nm[h];
+      });
+    } else
     pipeline(nk_fast, [&](int ks, float4 (&xa)[TILES], float4 (&xb)[TILES]) {
       load_slab_fast<TILES>(pa, ks * stepA, xa);
       load_slab_fast<TILES>(pb, ks * stepB, xb);
     });
     if (nk > nk_fast) {     // the partial last slab (its LDS buffers are free: the loop ends behind a barrier)
+      if constexpr (MAP != kMapNone) {
+        load_slab<KCA, TILES, MAPA>(A, lda, m0, kbeg + nk_fast * BK, M, K, vecA, ra[0], rmap);
+        load_slab<KCB, TILES, MAPB>(B, ldb, n0, kbeg + nk_fast * BK, N, K, vecB, rb[0], rmap);
+      } else {
       load_slab<KCA, TILES>(A, lda, m0, kbeg + nk_fast * BK, M, K, vecA, ra[0]);
       load_slab<KCB, TILES>(B, ldb, n0, kbeg + nk_fast * BK, N, K, vecB, rb[0]);
+      }
       store_slab<KCA, TILES>(As[0], ra[0]);
       store_slab<KCB, TILES>(Bs[0], rb[0]);
       lds_barrier();
@@ -271,6 +348,12 @@ __device__ __forceinline__ void tile_mainloop(const float* __restrict__ A, int64
       lds_barrier();        // (stream-K: the next piece of this workgroup reuses the buffers)
     }
   } else {
+    if constexpr (MAP != kMapNone)
+      pipeline(nk, [&](int ks, float4 (&xa)[TILES], float4 (&xb)[TILES]) {
+        load_slab<KCA, TILES, MAPA>(A, lda, m0, kbeg + ks * BK, M, K, vecA, xa, rmap);
+        load_slab<KCB, TILES, MAPB>(B, ldb, n0, kbeg + ks * BK, N, K, vecB, xb, rmap);
+      });
+    else
     pipeline(nk, [&](int ks, float4 (&xa)[TILES], float4 (&xb)[TILES]) {
       load_slab<KCA, TILES>(A, lda, m0, kbeg + ks * BK, M, K, vecA, xa);
       load_slab<KCB, TILES>(B, ldb, n0, kbeg + ks * BK, N, K, vecB, xb);

@@ -84,7 +84,17 @@ class FbankExtractor:
     def pad_roll_subsample(feats, row_off, frames, shift=0, subsample=1, time_major=False):
         """Zero-pad to max(frames), torch.roll by `shift` along time, keep every `subsample`-th frame
         (reference bin/train_chain.py:251-255; with subsample=1, shift=0 it is SeqDataloader's padding,
-        data/dataloader.py:96-103).  Returns [N, T', 80] or [T', N, 80]."""
+        data/dataloader.py:96-103).  Returns [N, T', 80] or [T', N, 80].
+
+        The returned tensor object carries ``pk2_lengths``: per utterance the number of leading rows of T' that can hold
+        a real frame, ``row_lengths(frames, shift, subsample)`` -- what LSTMAM.forward_time_major reads when it is given no
+        lengths.  It is an attribute of this Python object only: any torch operation on the tensor returns one without it."""
+        x = FbankExtractor._pad_roll_subsample(feats, row_off, frames, shift, subsample, time_major)
+        x.pk2_lengths = row_lengths(frames, shift, subsample)
+        return x
+
+    @staticmethod
+    def _pad_roll_subsample(feats, row_off, frames, shift, subsample, time_major):
         n = len(frames)
         max_t = int(max(frames))
         out_t = (max_t - 1) // subsample + 1
@@ -94,6 +104,17 @@ class FbankExtractor:
                                                      int(subsample), _lib.ptr(x), out_t, 1 if time_major else 0,
                                                      _lib.stream_ptr(feats.device)))
         return x
+
+
+def row_lengths(frames, shift=0, subsample=1):
+    """Per utterance, how many leading rows of pad_roll_subsample's result can hold a real frame: frame j of an utterance
+    of f frames lands at time j + shift of the padded, rolled sequence, of which every `subsample`-th time is kept, so
+    the rows beyond ceil((f + max(shift, 0)) / subsample) hold padding.  (The few frames a roll wraps around -- the first
+    -shift frames reappear at the END of the padded length -- lie in a shorter utterance's padding and are not counted: no
+    loss reads them.)  For shift <= 0 this is ceil(f / subsample), the frame count of the utterance's chain supervision
+    (frames_per_sequence), which rolls nothing: never less than the rows a loss reads.  Capped at the result's T'."""
+    out_t = (int(max(frames)) - 1) // subsample + 1
+    return tuple(min(out_t, -(-(int(f) + max(int(shift), 0)) // subsample)) for f in frames)
 
 
 def utt2seg(feats, seg_len, seg_shift):

@@ -71,11 +71,49 @@ class _LinearParams(nn.Module):
         nn.init.uniform_(self.bias, -bound, bound)
 
 
+_row_map_cache = {}
+
+
+def row_map_host(lengths, T, B):
+    """(perm, Mv): perm is an int32 array of all T * B row indices of a time-major [T * B, .] matrix -- first the Mv rows
+    t * B + b with t < lengths[b] (the frames that are not padding) in ascending order, then the padded rows in ascending
+    order.  perm[:Mv] is the row map of pk2_gemm_f32_rows / pk2_gemm_f32_tn_colsum_rows, perm[Mv:] what pk2_rows_zero clears."""
+    import numpy as np
+    lens = np.asarray(lengths, dtype=np.int64)
+    if lens.shape != (B,) or (lens < 0).any() or (lens > T).any():
+        raise ValueError("lengths: one frame count in [0, T] per sequence (B = %d, T = %d): %r" % (B, T, list(lengths)))
+    valid = (np.arange(T)[:, None] < lens[None, :]).reshape(-1)
+    return np.concatenate([np.flatnonzero(valid), np.flatnonzero(~valid)]).astype(np.int32), int(valid.sum())
+
+
+def _row_map(lengths, T, B, dev):
+    """The device copy of row_map_host: the host array is built once per (lengths, T, B) and kept in pinned memory (a
+    training run draws its minibatch lengths from a few thousand values of T and the bench from four); every step copies
+    it non-blocking (4 T B bytes: 9 KB for the bench minibatch) in front of the forward's kernels.  (map, Mv) or None when
+    nothing is padded."""
+    key = (tuple(int(v) for v in lengths), T, B)
+    hit = _row_map_cache.get(key)
+    if hit is None:
+        if len(_row_map_cache) >= 4096:
+            _row_map_cache.clear()
+        perm, mv = row_map_host(key[0], T, B)
+        hit = _row_map_cache[key] = (torch.from_numpy(perm).pin_memory(), mv)
+    host, mv = hit
+    if mv == T * B or mv == 0:
+        return None
+    return host.to(dev, non_blocking=True), mv
+
+
+def _p32(t, off_ints=0):
+    return ctypes.c_void_p(t.data_ptr() + 4 * off_ints)
+
+
 class _LstmAmFunction(torch.autograd.Function):
-    """x_tm [T,B,Din] (time-major) -> logits_tm [T,B,P]."""
+    """x_tm [T,B,Din] (time-major) -> logits_tm [T,B,P].  lengths (or None): frames per sequence -- the output layer's
+    three products then run over the rows t * B + b, t < lengths[b], only (LSTMAM.forward_time_major)."""
 
     @staticmethod
-    def forward(ctx, x_tm, model, *params):
+    def forward(ctx, x_tm, model, lengths, *params):
         m = model
         T, B, Din = x_tm.shape
         H, D, Lr = m.hidden_size, m.num_dirs, m.num_layers
@@ -119,8 +157,18 @@ class _LstmAmFunction(torch.autograd.Function):
                 seeds.append(None)
         P = m.output_size
         logits = torch.empty(T, B, P, device=dev, dtype=torch.float32)
-        _gemm(0, 1, rows, P, D * H, _p(inp), D * H, _p(m.output_layer.weight), D * H, _p(logits), P,
-              bias=_p(m.output_layer.bias))
+        # the output layer is the one part of a BLSTM whose padded rows nobody reads (the layers below need them: the reverse
+        # direction starts inside the padding): with lengths its product runs over the valid rows, the others are set to 0
+        rm = _row_map(lengths, T, B, dev) if lengths is not None and os.environ.get("PK2_OUT_ROWS", "1") != "0" else None
+        if rm is not None:
+            rmap, mv = rm
+            _lib.check(L.pk2_gemm_f32_rows(1, rows, P, D * H, 1.0, _p(inp), D * H, _p(m.output_layer.weight), D * H, 0.0,
+                                           _p(logits), P, _p(m.output_layer.bias), _p32(rmap), mv, sp))
+            _lib.check(L.pk2_rows_zero(_p(logits), P, P, _p32(rmap, mv), rows - mv, sp))
+        else:
+            _gemm(0, 1, rows, P, D * H, _p(inp), D * H, _p(m.output_layer.weight), D * H, _p(logits), P,
+                  bias=_p(m.output_layer.bias))
+        ctx.row_map = rm
         ctx.model = m
         ctx.saved = saved
         ctx.seeds = seeds
@@ -165,12 +213,33 @@ class _LstmAmFunction(torch.autograd.Function):
         # output layer: dy = dlogits W (critical path), dW = dlogits^T y, db = colsum(dlogits)
         gw, gb = views["output_layer.weight"], views["output_layer.bias"]
         dy = torch.empty(T, B, D * H, device=dev, dtype=torch.float32)
-        _gemm(0, 0, rows, D * H, P, _p(dlogits), P, _p(m.output_layer.weight), D * H, _p(dy), D * H)
+        rm = ctx.row_map
+        if rm is not None:
+            # rows of dlogits beyond a sequence's length are not read: dy is exactly 0 there, as it is for the zero rows a
+            # loss writes (the backward recurrences below run over every row)
+            rmap, mv = rm
+            _lib.check(L.pk2_gemm_f32_rows(0, rows, D * H, P, 1.0, _p(dlogits), P, _p(m.output_layer.weight), D * H, 0.0,
+                                           _p(dy), D * H, None, _p32(rmap), mv, sp))
+            _lib.check(L.pk2_rows_zero(_p(dy), D * H, D * H, _p32(rmap, mv), rows - mv, sp))
+        else:
+            _gemm(0, 0, rows, D * H, P, _p(dlogits), P, _p(m.output_layer.weight), D * H, _p(dy), D * H)
 
         def out_grads():
             # weight and bias gradient in one launch (round 6: the column sums ride in the product's operand loader)
-            _lib.check(L.pk2_gemm_f32_tn_colsum(P, D * H, rows, 1.0, _p(dlogits), P, _p(y_last), D * H, 1.0, _p(gw), D * H, _p(gb),
-                                                _lib.stream_ptr()))
+            if rm is not None and os.environ.get("PK2_OUT_ROWS_WGRAD", "map") == "pack":
+                # (the measured alternative, DESIGN 4.2l: gather the valid rows, then today's product over K = Mv)
+                dl_p = torch.empty(mv, P, device=dev, dtype=torch.float32)
+                y_p = torch.empty(mv, D * H, device=dev, dtype=torch.float32)
+                _lib.check(L.pk2_rows_pack(_p(dlogits), P, P, _p32(rmap), mv, _p(dl_p), P, _lib.stream_ptr()))
+                _lib.check(L.pk2_rows_pack(_p(y_last), D * H, D * H, _p32(rmap), mv, _p(y_p), D * H, _lib.stream_ptr()))
+                _lib.check(L.pk2_gemm_f32_tn_colsum(P, D * H, mv, 1.0, _p(dl_p), P, _p(y_p), D * H, 1.0, _p(gw), D * H, _p(gb),
+                                                    _lib.stream_ptr()))
+            elif rm is not None:
+                _lib.check(L.pk2_gemm_f32_tn_colsum_rows(P, D * H, rows, 1.0, _p(dlogits), P, _p(y_last), D * H, 1.0, _p(gw),
+                                                         D * H, _p(gb), _p32(rmap), mv, _lib.stream_ptr()))
+            else:
+                _lib.check(L.pk2_gemm_f32_tn_colsum(P, D * H, rows, 1.0, _p(dlogits), P, _p(y_last), D * H, 1.0, _p(gw), D * H,
+                                                    _p(gb), _lib.stream_ptr()))
             m._bucket_ready("output_layer")
         on_side(out_grads, dlogits, y_last)
         scratch = torch.empty(L.pk2_lstm_bwd_scratch_floats(B, H, D), device=dev, dtype=torch.float32)
@@ -243,7 +312,7 @@ class _LstmAmFunction(torch.autograd.Function):
             if p.grad is None or p.grad.data_ptr() != v.data_ptr():
                 p.grad = v
         ctx.saved = None
-        return (dx, None) + (None,) * len(m._param_names)
+        return (dx, None, None) + (None,) * len(m._param_names)
 
 
 class LSTMAM(nn.Module):
@@ -356,8 +425,23 @@ class LSTMAM(nn.Module):
             self._bucket_hook(name, self._gflat[lo:hi])
 
     # ---- forward ---------------------------------------------------------------------
-    def forward_time_major(self, x_tm):
-        """x_tm [T,B,D] -> logits [T,B,P] (time-major, the kernels' native layout)."""
+    def forward_time_major(self, x_tm, lengths=None):
+        """x_tm [T,B,D] -> logits [T,B,P] (time-major, the kernels' native layout).
+
+        lengths: frames per sequence (B integers in [0, T]), or None.  Taken from the argument first, else from the
+        attribute ``pk2_lengths`` of the tensor object x_tm (FbankExtractor.pad_roll_subsample records it there), else every
+        row is computed as before.  With lengths the output layer and its three gradient products run over the rows
+        t < lengths[b] only:  logits[t, b] is 0 for t >= lengths[b] (not W y + bias), and the rows of the logits' gradient
+        beyond a sequence's length are IGNORED (treated as zero, whatever they hold).  The LSTM layers themselves still run
+        over all T frames of every sequence, as nn.LSTM does on a padded batch, so the valid logits are what they are
+        without lengths.  A caller whose loss reads logits of padded frames passes no lengths and an untagged tensor
+        (``x_tm.detach()`` or any torch operation drops the attribute).  PK2_OUT_ROWS=0 (read per call) ignores lengths."""
+        if lengths is None:
+            lengths = getattr(x_tm, "pk2_lengths", None)
+        if lengths is not None:
+            lengths = tuple(int(v) for v in lengths)
+            if len(lengths) != x_tm.shape[1] or min(lengths) < 0 or max(lengths) > x_tm.shape[0]:
+                raise ValueError("lengths: one frame count in [0, T] per sequence, got %r for x_tm %r" % (lengths, tuple(x_tm.shape)))
         _lib.require_gpu()
         assert x_tm.is_cuda and x_tm.dtype == torch.float32
         self._ensure_flat()
@@ -366,7 +450,7 @@ class LSTMAM(nn.Module):
             in_size = self.input_size if l == 0 else H * D
             assert (4 * H * in_size) % 64 == 0 and (4 * H * H) % 64 == 0 and (4 * H) % 64 == 0
         params = [p for _, p in self.named_parameters()]
-        return _LstmAmFunction.apply(x_tm, self, *params)
+        return _LstmAmFunction.apply(x_tm, self, lengths, *params)
 
     def forward(self, data):
         """data [B,T,D] -> logits [B,T,P], contiguous like the reference's (callers do
