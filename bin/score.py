@@ -1,0 +1,138 @@
+#!/usr/bin/env python
+"""Scores a compact-lattice archive against reference transcripts -- the last step of the reference's recipes
+(example/*/local/score*.sh: lattice-scale | lattice-add-penalty | lattice-best-path or lattice-mbr-decode for every LM
+weight and word insertion penalty, then utt_wer.py), running on libpk2hip.so: every (lattice, setting) pair of a batch is
+decoded in one launch (pykaldi2_amd.score), the word errors are counted on the device.
+
+  python bin/score.py -lat_file exp/se/lat.ark -words_txt exp/tri/graph/words.txt -ref_text data/dev/text \
+      -out_dir exp/se/scoring [-min_lmwt 7 -max_lmwt 17 -word_ins_penalty 0.0,0.5,1.0] [-decode_mbr]
+
+Writes hyp_<LMWT>.<wip>.txt (key, then words) and result_<LMWT>_<wip> (utt_wer.py's three lines per utterance: reco:, ref:,
+`<key> err: E ref_len: L`; with -decode_mbr a fourth line `conf: <key> c1 c2 ...`) per setting and prints
+`best: LMWT=.. wip=.. errors=.. ref_words=.. WER=..%` last: the lowest error count, ties to the first setting of the sweep.
+<NOISE> and <SPOKEN_NOISE> are removed from the references and <UNK> from the hypotheses (score_opencss.sh).  Lattices
+without a reference are reported and skipped; a reference without a lattice counts all its words as errors."""
+import argparse
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from pykaldi2_amd import kaldi_io, score  # noqa: E402
+
+REF_FILTER = ("<NOISE>", "<SPOKEN_NOISE>")
+HYP_FILTER = ("<UNK>",)
+
+
+def read_words_txt(path):
+    table = {}
+    with open(path) as f:
+        for line in f:
+            parts = line.split()
+            if len(parts) == 2:
+                table[int(parts[1])] = parts[0]
+    return table
+
+
+def read_text(path):
+    refs = {}
+    with open(path) as f:
+        for line in f:
+            parts = line.split()
+            if parts:
+                refs[parts[0]] = [w for w in parts[1:] if w not in REF_FILTER]
+    return refs
+
+
+def main():
+    parser = argparse.ArgumentParser()
+    parser.add_argument("-lat_file", required=True, help="binary compact-lattice archive (bin/latgen.py -out_file)")
+    parser.add_argument("-words_txt", required=True, help="the graph directory's words.txt")
+    parser.add_argument("-ref_text", required=True, help="Kaldi text: key, then the reference words")
+    parser.add_argument("-out_dir", required=True)
+    parser.add_argument("-min_lmwt", default=7, type=int)
+    parser.add_argument("-max_lmwt", default=17, type=int)
+    parser.add_argument("-word_ins_penalty", default="0.0,0.5,1.0")
+    parser.add_argument("-decode_mbr", action="store_true", help="minimum Bayes risk decoding with word confidences")
+    parser.add_argument("-batch_size", default=32, type=int, help="lattices per device batch")
+    args = parser.parse_args()
+
+    symbols = read_words_txt(args.words_txt)
+    refs = read_text(args.ref_text)
+    wips = [float(x) for x in args.word_ins_penalty.split(",") if x.strip()]
+    settings = score.sweep(args.min_lmwt, args.max_lmwt, wips)
+    G = len(settings)
+    os.makedirs(args.out_dir, exist_ok=True)
+    # word <-> integer for the error count: the symbol table's ids, new ids for reference words it does not hold
+    ids = {s: i for i, s in symbols.items()}
+    next_id = max(list(symbols) + [0]) + 1
+
+    def word_id(w):
+        nonlocal next_id
+        if w not in ids:
+            ids[w] = next_id
+            next_id += 1
+        return ids[w]
+
+    hyps = [dict() for _ in range(G)]      # per setting: key -> (words, confidences)
+    seen, batch = set(), []
+
+    def flush():
+        if not batch:
+            return
+        wl = score.WordLatticeBatch([lat for _, lat in batch], "cuda", names=[k for k, _ in batch])
+        for g0 in range(0, G, score.MAX_SETTINGS):
+            part = settings[g0:g0 + score.MAX_SETTINGS]
+            if args.decode_mbr:
+                res = wl.mbr(part, decode_mbr=True)
+            else:
+                res = [[dict(words=w, conf=None) for w, _ in row] for row in wl.best_path(part)]
+            for (key, _), row in zip(batch, res):
+                for g, rec in enumerate(row):
+                    keep = [i for i, w in enumerate(rec["words"]) if symbols.get(w, str(w)) not in HYP_FILTER]
+                    hyps[g0 + g][key] = ([symbols.get(rec["words"][i], str(rec["words"][i])) for i in keep],
+                                         None if rec["conf"] is None else [float(rec["conf"][i]) for i in keep])
+        del batch[:]
+
+    for key, lat in kaldi_io.read_compact_lattice_ark(args.lat_file):
+        if key not in refs:
+            print("no reference for %s: skipped" % key)
+            continue
+        seen.add(key)
+        batch.append((key, lat))
+        if len(batch) >= args.batch_size:
+            flush()
+    flush()
+    missing = [k for k in refs if k not in seen]
+    for k in missing:
+        print("no lattice for %s: its %d reference words count as errors" % (k, len(refs[k])))
+    keys = [k for k in refs if k in seen]
+    ref_words = sum(len(r) for r in refs.values())
+    best = None
+    for g, st in enumerate(settings):
+        lmwt, wip = st[3]
+        hw = [hyps[g][k][0] for k in keys]
+        nz = [i for i, k in enumerate(keys) if hw[i]]           # an empty hypothesis costs len(ref), as utt_wer.py counts
+        errs = {k: len(refs[k]) for k in keys}
+        if nz:
+            d = score.edit_distance([[word_id(w) for w in hw[i]] for i in nz], [[word_id(w) for w in refs[keys[i]]] for i in nz])
+            for i, e in zip(nz, d):
+                errs[keys[i]] = int(e)
+        total = sum(errs.values()) + sum(len(refs[k]) for k in missing)
+        with open(os.path.join(args.out_dir, "hyp_%d.%s.txt" % (lmwt, wip)), "w") as f:
+            for k in keys:
+                f.write(" ".join([k] + hyps[g][k][0]) + "\n")
+        with open(os.path.join(args.out_dir, "result_%d_%s" % (lmwt, wip)), "w") as f:
+            for k in keys:
+                f.write("reco: %s %s\n" % (k, " ".join(hyps[g][k][0])))
+                f.write("ref: %s %s\n" % (k, " ".join(refs[k])))
+                f.write("%s err: %d ref_len: %d\n" % (k, errs[k], len(refs[k])))
+                if args.decode_mbr:
+                    f.write("conf: %s %s\n" % (k, " ".join("%.4f" % c for c in hyps[g][k][1])))
+        if best is None or total < best[0]:
+            best = (total, lmwt, wip)
+    print("best: LMWT=%d wip=%s errors=%d ref_words=%d WER=%.2f%%" % (best[1], best[2], best[0], ref_words,
+                                                                      100.0 * best[0] / max(1, ref_words)))
+
+
+if __name__ == "__main__":
+    main()

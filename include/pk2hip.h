@@ -758,6 +758,64 @@ int pk2_perm_align(const float* const* masks, const float* cov, const float* log
                    float* const* out_masks, float* out_cov, float* out_log_alpha, int32_t* perm, float* margin, void* stream);
 
 /* ------------------------------------------------------------------ *
+ * Lattice scoring (csrc/lattice_score.hip): what the reference's example/.../local/score.sh hand to Kaldi
+ * (lattice-scale | lattice-add-penalty | lattice-best-path, lattice-mbr-decode, utt_wer.py), for a grid of
+ * (lattice, setting) pairs per call.  A setting is three doubles (lm, am, wip): cost_a = lm graph_a + am acoustic_a +
+ * wip [word_a != 0] in float64; `settings` is a HOST array of G x 3, G in 1 .. PK2_WORDLAT_MAX_SETTINGS.
+ *
+ * pk2_wordlat_create uploads N packed word lattices (all arguments HOST arrays; pykaldi2_amd/score.py: pack_lattice).
+ * Per lattice: states 0..S-1 ordered by (level, id), level = longest arc count from the start, 0 = start, S-1 = the only
+ * end; arcs sorted by (destination, original index).  state_off, arc_off (N + 1): offsets into the concatenated arrays;
+ * level_off_off: offsets of the per-lattice level_off (depth + 2 entries: the state range of every level);
+ * word_off_off: offsets of word_off (W + 1 entries; word_ids holds W entries per lattice, at word_off_off[n] - n).
+ * src, dst, word (LOCAL id 0..W-1, 0 = epsilon, ascending with the word id), graph, acoustic: per arc; in_off, out_off
+ * (S + 1 per lattice, at state_off[n] + n): CSR by destination (arcs are contiguous) and by source over out_idx (arc
+ * indices, ascending); word_arcs: the arcs of every local word, ascending.  Every index is validated on the host; a
+ * malformed lattice is PK2_ERR_INVALID.  The row capacity of a lattice is min(PK2_WORDLAT_MAX_POSITIONS, 2 depth + 1).
+ *
+ * Results are indexed by pair = (n - first) * G + g.  Failures of a pair are reported in status[pair] (0 ok, 1 not
+ * converged, 2 capacity, 3 empty or failed), never through the return code.  Null pointers, G outside
+ * 1 .. PK2_WORDLAT_MAX_SETTINGS, bins outside 0 .. PK2_WORDLAT_MAX_BINS, max_iter < 1, a non-finite scale, a range outside the
+ * batch, strides below what the range needs and a short workspace return PK2_ERR_INVALID before the device is touched.
+ * work: device memory of pk2_wordlat_workspace_bytes(h, first, count, G, bins) bytes (bins = -1: best path only; 0 for
+ * arguments the entries would refuse).  No floating-point atomics, fixed summation orders: the same bits from run to
+ * run and in a batch as in a single call.
+ *
+ * pk2_wordlat_best_path: alpha (log-add in incoming-arc order), arc posteriors, the tropical best path (a later arc
+ * replaces an earlier one only on <).  words (pairs x word_stride, word_stride >= depth of every lattice of the range),
+ * nwords, cost, alpha_end, status: device, per pair.  post (optional): p_a at G * (arc_off[n] - arc_off[first]) + g * A_n;
+ * backpointer (optional): the best incoming arc of every state, at G * (state_off[n] - state_off[first]) + g * S_n.
+ *
+ * pk2_wordlat_mbr: minimum Bayes risk decoding (Xu, Povey, Mangu, Zhu 2011; DESIGN.md 7.13 fixes the arithmetic), started
+ * from the best path, at most max_iter E-steps; decode_mbr = 0: one E-step on the best path and no update.  words, conf
+ * (pairs x word_stride, word_stride >= (capacity - 1) / 2), nwords, risk, iterations, status per pair.  bins > 0: bin_n
+ * per pair and bin_word / bin_post (pairs x bin_stride x bins, bin_stride >= capacity): for every position whose top
+ * entry is not epsilon the `bins` highest (word, posterior) pairs, word -1 where the lattice has fewer words.
+ *
+ * pk2_edit_distance_batch: Levenshtein distance with unit costs of n pairs, one wavefront each; hyp / ref: device int32
+ * labels, hyp_off / ref_off: device int64 (n + 1); out[i] = -1 for a reference beyond PK2_WORDLAT_MAX_POSITIONS labels.
+ * ------------------------------------------------------------------ */
+#define PK2_WORDLAT_MAX_SETTINGS 64
+#define PK2_WORDLAT_MAX_POSITIONS 1023
+#define PK2_WORDLAT_MAX_BINS 8
+int pk2_wordlat_create(int32_t N, const int64_t* state_off, const int64_t* arc_off, const int64_t* level_off_off,
+                       const int64_t* word_off_off, const int32_t* src, const int32_t* dst, const int32_t* word,
+                       const float* graph, const float* acoustic, const int32_t* in_off, const int32_t* out_off,
+                       const int32_t* out_idx, const int32_t* level_off, const int32_t* word_ids, const int32_t* word_off,
+                       const int32_t* word_arcs, void* stream, void** out);
+int pk2_wordlat_destroy(void* h);
+size_t pk2_wordlat_workspace_bytes(const void* h, int32_t first, int32_t count, int32_t G, int32_t bins);
+int pk2_wordlat_best_path(const void* h, int32_t first, int32_t count, const double* settings, int32_t G, void* work,
+                          size_t work_bytes, int32_t* words, int32_t word_stride, int32_t* nwords, double* cost, double* alpha_end,
+                          double* post, int32_t* backpointer, int32_t* status, void* stream);
+int pk2_wordlat_mbr(const void* h, int32_t first, int32_t count, const double* settings, int32_t G, int32_t decode_mbr,
+                    int32_t max_iter, int32_t bins, void* work, size_t work_bytes, int32_t* words, double* conf,
+                    int32_t word_stride, int32_t* nwords, double* risk, int32_t* iterations, int32_t* status, int32_t* bin_n,
+                    int32_t* bin_word, double* bin_post, int32_t bin_stride, void* stream);
+int pk2_edit_distance_batch(const int32_t* hyp, const int64_t* hyp_off, const int32_t* ref, const int64_t* ref_off, int32_t n,
+                            int32_t* out, void* stream);
+
+/* ------------------------------------------------------------------ *
  * Fused log-softmax + NLL + gradient. Replaces nn.CrossEntropyLoss
  * (ignore_index=-100; reduction mean: reference bin/train_ce.py:134,189;
  * reduction sum: bin/train_se.py:214,235).

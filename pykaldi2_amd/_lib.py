@@ -233,6 +233,13 @@ SIGNATURES = {
     "pk2_perm_align_workspace_bytes": (_sz, [_vp, _i32, _i32, _i32]),
     "pk2_perm_align": (C.c_int, [C.POINTER(_vp), _vp, _vp, C.POINTER(_i32), _i32, _i32, _i32, _i32, _i32, _i32, _vp, _sz,
                                  C.POINTER(_vp), _vp, _vp, _vp, _vp, _vp]),
+    "pk2_wordlat_create": (C.c_int, [_i32] + [_vp] * 17 + [C.POINTER(_vp)]),
+    "pk2_wordlat_destroy": (C.c_int, [_vp]),
+    "pk2_wordlat_workspace_bytes": (_sz, [_vp, _i32, _i32, _i32, _i32]),
+    "pk2_wordlat_best_path": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _vp, _sz, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pk2_wordlat_mbr": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _sz, _vp, _vp, _i32, _vp, _vp, _vp, _vp,
+                                  _vp, _vp, _vp, _i32, _vp]),
+    "pk2_edit_distance_batch": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _vp, _vp]),
     "pk2_softmax_ce_fwd_bwd": (C.c_int, [_vp, _i64, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _i64, _vp, _vp]),
     "pk2_softmax_ce_fwd_bwd_mean": (C.c_int, [_vp, _i64, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _i64, _vp]),
     "pk2_scale_inplace_ratio": (C.c_int, [_vp, _i64, _vp, _vp, _vp]),

@@ -24,6 +24,7 @@
 #include <cmath>
 #include <cstdlib>
 
+#include "lattice_edit.h"
 #include "lattice_internal.h"
 #include "persist_guard.h"
 
@@ -36,7 +37,6 @@ constexpr int kNbWaves = kNbThreads / 64;
 constexpr int kNbSlots = 4;            // candidate slots per lane of a merge pass: 256 per wavefront
 constexpr int kNbMaxPaths = 64;
 constexpr int kNbLds = 150 * 1024;     // LDS of nb_kbest: merge lists, then the grouping of a frame's links
-constexpr int kEdChunks = 16;          // Levenshtein: supervision of at most 64 * 16 - 1 labels
 constexpr uint64_t kNbHash0 = 1469598103934665603ull;
 
 __host__ __device__ __forceinline__ uint64_t nb_hash_step(uint64_t h, int32_t label) {
@@ -428,8 +428,7 @@ struct MweParams {
   const LatUtt* utt;
 };
 
-// Levenshtein distance (unit costs) of hypothesis m and the supervision: rows = hypothesis labels, the row of DP values
-// over the supervision positions j = 0..b held by the lanes (j = 64 c + lane), the insertion chain as a prefix minimum.
+// Levenshtein distance (unit costs) of hypothesis m and the supervision (lattice_edit.h).
 __global__ void __launch_bounds__(64) mwe_edit(MweParams p) {
   const int n = blockIdx.y, m = blockIdx.x, lane = threadIdx.x;
   if (!p.ok[n] || m >= p.num_hyp[n]) return;
@@ -438,39 +437,7 @@ __global__ void __launch_bounds__(64) mwe_edit(MweParams p) {
   if (a < 0 || b < 0 || b > 64 * kEdChunks - 1) { if (lane == 0) p.ek[(int64_t)n * p.K + m] = -1; return; }
   const int32_t* x = p.path_labels + pk * p.label_cap;
   const int32_t* y = p.sup + (int64_t)n * p.sup_stride;
-  const int nc = b / 64 + 1;
-  int prev[kEdChunks], ylab[kEdChunks];
-#pragma unroll
-  for (int c = 0; c < kEdChunks; ++c) {
-    const int j = 64 * c + lane;
-    prev[c] = j;
-    ylab[c] = (c < nc && j >= 1 && j <= b) ? y[j - 1] : 0;
-  }
-  for (int i = 1; i <= a; ++i) {
-    const int xi = x[i - 1];
-    int carry_old = 0, carry_min = 0x3FFFFFFF;
-#pragma unroll
-    for (int c = 0; c < kEdChunks; ++c) {
-      if (c < nc) {
-        const int j = 64 * c + lane;
-        const int up = prev[c];
-        int diag = __shfl_up(up, 1, 64);
-        if (lane == 0) diag = carry_old;
-        const int tmp = j == 0 ? i : min(up + 1, diag + (xi != ylab[c] ? 1 : 0));
-        int v = tmp - j;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) { const int u = __shfl_up(v, o, 64); if (lane >= o) v = min(v, u); }
-        v = min(v, carry_min);
-        carry_old = __shfl(up, 63, 64);
-        carry_min = __shfl(v, 63, 64);
-        prev[c] = v + j;
-      }
-    }
-  }
-  int e = 0;
-#pragma unroll
-  for (int c = 0; c < kEdChunks; ++c) if (c == b / 64) e = prev[c];
-  e = __shfl(e, b % 64, 64);
+  const int e = edit_wave(x, a, y, b, lane);
   if (lane == 0) p.ek[(int64_t)n * p.K + m] = e;
 }
 
