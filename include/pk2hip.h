@@ -816,6 +816,49 @@ int pk2_edit_distance_batch(const int32_t* hyp, const int64_t* hyp_off, const in
                             int32_t* out, void* stream);
 
 /* ------------------------------------------------------------------ *
+ * N-gram LM rescoring of word lattices (csrc/lattice_lmrescore.hip): what the reference's
+ * local/lmrescore_const_arpa.sh hands to Kaldi (lattice-lmrescore | lattice-lmrescore-const-arpa) -- the composition of a
+ * packed word lattice with a deterministic backoff LM, one workgroup per lattice.
+ *
+ * pk2_ngram_create uploads the trie of pykaldi2_amd/ngram.py (all arguments HOST arrays).  N nodes: node 0 = the empty
+ * history, then the unigrams in ascending word id, then the order-k n-grams sorted by (parent node, word); order_off
+ * (order + 2): the node range of every order (order_off[0] = 0, order_off[1] = 1).  Per node: word, cost = -ln p, backoff =
+ * -ln bo (0 where absent), child_begin (N + 1: the children of node i are child_begin[i] .. child_begin[i + 1]),
+ * bo_link (the longest proper suffix that is a node), next_state (the longest suffix of at most order - 1 words with
+ * children, or 0).  start: the LM state after <s>; eos: the word id of </s>.  Validated on the host before the upload:
+ * child ranges monotone and inside the next order, words ascending inside a child range, bo_link to a strictly lower
+ * order, next_state and start a node with children or 0, finite weights, a unigram for eos; otherwise PK2_ERR_INVALID.
+ *
+ * pk2_wordlat_lmrescore composes the lattices first .. first + count - 1 of a pk2_wordlat_create batch with the LM:
+ * states = the reachable pairs (packed state s, LM node h) numbered in ascending (s, h), arcs in ascending (destination
+ * pair, input arc, source pair); an arc along input arc a from (s, h): into the end state cost = final(h), target
+ * (S - 1, 0); another epsilon cost 0, target (n_a, h); a word arc (cost, h') = arc(h, lm_word[word_a]), target
+ * (n_a, h'); new graph cost = float32(float64(graph_a) + scale * cost) with separate roundings.  lm_word: DEVICE array laid
+ * out like word_ids of the whole batch: the LM's word id of every local word (a word without a unigram: status 3).
+ * Lattice i of the range has room for (int64)(expand * S_i) states and (int64)(expand * A_i) arcs, its share of the
+ * output arrays starts at the sum of the rooms before it.  out_nstates, out_narcs, status: device, per lattice;
+ * states: the pair of every output state; arcs: per output arc its end points, the global word id, the input arc
+ * (orig) and the two costs.  status: 0 ok, 2 the room is short (nothing is written outside
+ * the lattice's share, its counts are 0), 3 empty or failed.  Null pointers, a non-finite scale, expand <= 0, a range
+ * outside the batch, state_room / arc_room (elements) or work_bytes below what the range needs return PK2_ERR_INVALID
+ * before the device is touched.  States of at most 64 candidate arcs are sorted by one wavefront, up to
+ * PK2_LMRESCORE_SORT_LDS by the workgroup in LDS, above that in the workspace.
+ * ------------------------------------------------------------------ */
+#define PK2_NGRAM_MAX_ORDER 8
+#define PK2_LMRESCORE_SORT_LDS 4096
+typedef struct { int32_t s, h; } pk2_lm_state;                                   /* packed input state, LM node */
+typedef struct { int32_t src, dst, word, orig; float graph, acoustic; } pk2_lm_arc;
+int pk2_ngram_create(int32_t N, int32_t order, const int32_t* order_off, const int32_t* word, const float* cost,
+                     const float* backoff, const int32_t* child_begin, const int32_t* bo_link, const int32_t* next_state,
+                     int32_t start, int32_t eos, void* stream, void** out);
+int pk2_ngram_destroy(void* h);
+size_t pk2_wordlat_lmrescore_workspace_bytes(const void* h, int32_t first, int32_t count, double expand);
+int pk2_wordlat_lmrescore(const void* h_lat, int32_t first, int32_t count, const void* h_lm, const int32_t* lm_word,
+                          double scale, double expand, void* work, size_t work_bytes, int32_t* out_nstates,
+                          int32_t* out_narcs, pk2_lm_state* states, size_t state_room, pk2_lm_arc* arcs, size_t arc_room,
+                          int32_t* status, void* stream);
+
+/* ------------------------------------------------------------------ *
  * Fused log-softmax + NLL + gradient. Replaces nn.CrossEntropyLoss
  * (ignore_index=-100; reduction mean: reference bin/train_ce.py:134,189;
  * reduction sum: bin/train_se.py:214,235).

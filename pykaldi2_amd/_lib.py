@@ -240,6 +240,11 @@ SIGNATURES = {
     "pk2_wordlat_mbr": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _sz, _vp, _vp, _i32, _vp, _vp, _vp, _vp,
                                   _vp, _vp, _vp, _i32, _vp]),
     "pk2_edit_distance_batch": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _vp, _vp]),
+    "pk2_ngram_create": (C.c_int, [_i32, _i32] + [_vp] * 7 + [_i32, _i32, _vp, C.POINTER(_vp)]),
+    "pk2_ngram_destroy": (C.c_int, [_vp]),
+    "pk2_wordlat_lmrescore_workspace_bytes": (_sz, [_vp, _i32, _i32, C.c_double]),
+    "pk2_wordlat_lmrescore": (C.c_int, [_vp, _i32, _i32, _vp, _vp, C.c_double, C.c_double, _vp, _sz, _vp, _vp, _vp, _sz, _vp, _sz,
+                                        _vp, _vp]),
     "pk2_softmax_ce_fwd_bwd": (C.c_int, [_vp, _i64, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _i64, _vp, _vp]),
     "pk2_softmax_ce_fwd_bwd_mean": (C.c_int, [_vp, _i64, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _i64, _vp]),
     "pk2_scale_inplace_ratio": (C.c_int, [_vp, _i64, _vp, _vp, _vp]),

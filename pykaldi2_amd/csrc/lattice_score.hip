@@ -16,6 +16,7 @@
 
 #include "common.h"
 #include "lattice_edit.h"
+#include "wordlat.h"
 
 #pragma clang fp contract(off)
 
@@ -28,16 +29,6 @@ constexpr int kWsPostThreads = 1024;
 constexpr int kWsMaxGroups = kWsThreads / 16;   // lane groups of a workgroup at the smallest group width
 constexpr double kWsDelta = 1e-5;      // l'(w) = 1 + delta for a word on an arc that the hypothesis does not consume
 constexpr double kWsTau = 1e-9;        // tie rule: match, then deletion, then insertion
-
-struct WordLat {
-  int N = 0;
-  std::vector<int64_t> state_off, arc_off, level_off_off, word_off_off, post_pre, mbr_pre, pe_pre;
-  std::vector<int32_t> depth, cap;
-  void* blob = nullptr;
-  const int64_t *d_state_off, *d_arc_off, *d_level_off_off, *d_word_off_off, *d_post_pre, *d_mbr_pre, *d_pe_pre;
-  const int32_t *d_src, *d_dst, *d_word, *d_in_off, *d_out_off, *d_out_idx, *d_level_off, *d_word_ids, *d_word_off, *d_word_arcs;
-  const float *d_graph, *d_acoustic;
-};
 
 struct WsParams {
   const int64_t *state_off, *arc_off, *level_off_off, *word_off_off, *post_pre, *mbr_pre, *pe_pre;

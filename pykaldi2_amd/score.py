@@ -6,6 +6,12 @@ lattice-mbr-decode, utt_wer.py).  Packing is numpy on the host; the kernels are 
     batch = WordLatticeBatch([lat0, lat1, ...], "cuda")        # dicts of compact_lattice / determinize_lattice / an archive
     for (words, cost) in batch.best_path(sweep())[0]: ...
     rec = batch.mbr(sweep(), decode_mbr=True)[0][0]             # words, conf, risk, iterations, status
+
+N-gram LM rescoring (csrc/lattice_lmrescore.hip, pykaldi2_amd.ngram): the composition of the lattices with a
+backoff LM, what local/lmrescore_const_arpa.sh hands to Kaldi's lattice-lmrescore and lattice-lmrescore-const-arpa.
+
+    lats = rescore_lm(lats, [(old_lm, -1.0), (new_lm, 1.0)])    # raw lattice dicts; fold_finals(lat) for CompactLatticeWriter
+    new = batch.rescore_lm(new_lm, 1.0)                         # a WordLatticeBatch again
 """
 import ctypes as C
 
@@ -17,6 +23,7 @@ from . import _lib
 MAX_SETTINGS = 64        # PK2_WORDLAT_MAX_SETTINGS
 MAX_POSITIONS = 1023     # PK2_WORDLAT_MAX_POSITIONS
 MAX_BINS = 8             # PK2_WORDLAT_MAX_BINS
+LMRESCORE_SORT_LDS = 4096  # PK2_LMRESCORE_SORT_LDS: candidate arcs of one state the rescoring kernel sorts in LDS
 _DEBUG_GUARD = False     # tests: NaN / sentinel poisoned buffers with checked guard padding around every device buffer
 _GUARD = 64
 
@@ -216,6 +223,8 @@ class WordLatticeBatch:
             raise ValueError("WordLatticeBatch: no lattices")
         names = list(names) if names is not None else [str(i) for i in range(len(lattices))]
         self.packed = [p if isinstance(p, PackedLattice) else pack_lattice(p, names[i]) for i, p in enumerate(lattices)]
+        self.names = names
+        self.source = [None if isinstance(p, PackedLattice) else p for p in lattices]
         self.device = torch.device(device)
         _lib.require_gpu()
         P = self.packed
@@ -246,6 +255,11 @@ class WordLatticeBatch:
         h, self._h = getattr(self, "_h", None), None
         if h:
             _lib.lib().pk2_wordlat_destroy(h)
+
+    def rescore_lm(self, lm, scale=1.0, expand=8, max_expand=64):
+        """This batch composed with an n-gram LM (ngram.NgramLM) at `scale`: a new WordLatticeBatch; the composed dicts
+        are its .source."""
+        return WordLatticeBatch(_rescore_batch(self, lm, float(scale), expand, max_expand), self.device, names=self.names)
 
     # ---- launches cut to the workspace budget ----
     def _chunks(self, G, bins, workspace_mb):
@@ -361,6 +375,187 @@ class WordLatticeBatch:
                         row.append(r)
                     res.append(row)
         return res
+
+
+# ---- n-gram LM rescoring (csrc/lattice_lmrescore.hip) ----
+_LM_STATE = np.dtype([("s", np.int32), ("h", np.int32)])
+_LM_ARC = np.dtype([("src", np.int32), ("dst", np.int32), ("word", np.int32), ("orig", np.int32), ("graph", np.float32),
+                    ("acoustic", np.float32)])
+
+
+def _lm_words(batch, lm):
+    """The LM's word id of every local word of the batch (laid out like word_ids): the word itself, `unk` for a word the LM
+    has no unigram for when it was loaded with one, otherwise ValueError naming the word id and the lattice."""
+    uni = lm.word[1:int(lm.order_off[2])]
+    out = []
+    for i, p in enumerate(batch.packed):
+        w = p.word_ids.astype(np.int32).copy()
+        missing = ~np.isin(w, uni)
+        missing[0] = False
+        if missing.any():
+            if lm.unk_id is None:
+                raise ValueError("lattice %s: word id %d has no unigram in the LM (load it with unk= to map such words)"
+                                 % (batch.names[i], int(w[missing][0])))
+            w[missing] = lm.unk_id
+        out.append(w)
+    return np.ascontiguousarray(np.concatenate(out))
+
+
+def _lmrescore_launch(batch, first, count, lm, lm_word_dev, scale, expand):
+    """One pk2_wordlat_lmrescore call -> [(status, states, arcs) per lattice] (host structured arrays)."""
+    L, dev, H = _lib.lib(), batch.device, batch._host
+    rooms = [(int(expand * p.S), int(expand * p.A)) for p in batch.packed[first:first + count]]
+    nS, nA = sum(r[0] for r in rooms), sum(r[1] for r in rooms)
+    ws_bytes = int(L.pk2_wordlat_lmrescore_workspace_bytes(batch._h, first, count, float(expand)))
+    if ws_bytes == 0:
+        raise ValueError("rescore_lm: expand=%r gives a lattice more than 2^29 states or arcs" % (expand,))
+    B = _Bufs(dev)
+    work = B(ws_bytes // 8 + 1, torch.float64)
+    ons, ona, status = B(count, torch.int32), B(count, torch.int32), B(count, torch.int32)
+    states, arcs = B(2 * nS, torch.int32), B(6 * nA, torch.int32)
+    _lib.check(L.pk2_wordlat_lmrescore(batch._h, first, count, lm.handle(dev), _lib.ptr(lm_word_dev), float(scale), float(expand),
+                                       _lib.ptr(work), ws_bytes, _lib.ptr(ons), _lib.ptr(ona), _lib.ptr(states), nS,
+                                       _lib.ptr(arcs), nA, _lib.ptr(status), _lib.stream_ptr(dev)))
+    hs, ha, hst, hns, hna = (x.cpu().numpy() for x in (states, arcs, status, ons, ona))
+    B.check()
+    hs, ha = hs.view(_LM_STATE), ha.view(_LM_ARC)
+    out, so, ao = [], 0, 0
+    for i, (rs, ra) in enumerate(rooms):
+        ok = hst[i] == 0
+        out.append((int(hst[i]), hs[so:so + hns[i]].copy() if ok else None, ha[ao:ao + hna[i]].copy() if ok else None))
+        so, ao = so + rs, ao + ra
+    return out
+
+
+def _strings(lat):
+    """(transition-id string per arc, per state's final weight) of any accepted lattice form; None where the form has none."""
+    if lat is None:
+        return None, None
+    if "arcs" in lat and "finals" in lat:
+        return [list(a[4][2]) for a in lat["arcs"]], [list(f[2]) for f in lat["finals"]]
+    n = int(lat["num_states"])
+    if "tid_off" in lat:
+        to, ti = np.asarray(lat["tid_off"]), np.asarray(lat["tids"])
+        fo, fi = np.asarray(lat["final_tid_off"]), np.asarray(lat["final_tids"])
+        return ([[int(x) for x in ti[to[a]:to[a + 1]]] for a in range(to.size - 1)],
+                [[int(x) for x in fi[fo[s]:fo[s + 1]]] for s in range(n)])
+    if "tid" in lat:
+        return [[int(x)] if int(x) > 0 else [] for x in lat["tid"]], [[] for _ in range(n)]
+    return None, None
+
+
+def _composed_dict(p, src_lat, states, arcs):
+    """The kernel's output as a raw lattice dict (the form pack_lattice accepts) with orig_arc = the packed input arc;
+    `input_arc` follows it back to src_lat (an arc index, or number of arcs + rank of the final state for the arc that a
+    final weight became) and the transition-id strings are copied along it."""
+    n = states.shape[0]
+    final = np.full(n, np.inf, np.float32)
+    final[n - 1] = 0.0
+    orig = arcs["orig"].astype(np.int64)
+    d = dict(num_states=n, start=0, src=arcs["src"].copy(), dst=arcs["dst"].copy(), word=arcs["word"].copy(),
+             graph=arcs["graph"].copy(), acoustic=arcs["acoustic"].copy(), final=final, orig_arc=orig,
+             state_s=states["s"].copy(), state_h=states["h"].copy(), input_arc=np.asarray(p.orig_arc, np.int64)[orig])
+    astr, fstr = _strings(src_lat)
+    if astr is not None:
+        fin_states = np.flatnonzero(np.isfinite(_lattice_arcs(src_lat, "?")[7]))
+        nA = len(astr)
+        strs = [astr[k] if k < nA else fstr[fin_states[k - nA]] for k in d["input_arc"]]
+        d["tid_off"] = np.concatenate([[0], np.cumsum([len(s) for s in strs])]).astype(np.int64)
+        d["tids"] = np.asarray([x for s in strs for x in s], np.int32)
+        d["final_acoustic"] = np.zeros(n, np.float32)
+        d["final_tid_off"] = np.zeros(n + 1, np.int64)
+        d["final_tids"] = np.zeros(0, np.int32)
+    return d
+
+
+def fold_finals(lat):
+    """A composed lattice (single end state with final weight 0) in the form CompactLatticeWriter and Kaldi expect: the arcs
+    into the end state become the final weights of their source states (graph, acoustic and transition-id string of the
+    arc) and the end state is dropped.  orig_arc / input_arc are kept for the arcs; final_orig_arc / final_input_arc hold
+    those of the arcs that became final weights (-1 elsewhere)."""
+    n = int(lat["num_states"])
+    end = n - 1
+    fin = np.asarray(lat["final"], np.float32)
+    if n < 2 or fin[end] != 0 or np.isfinite(fin[:end]).any() or (np.asarray(lat["src"]) == end).any():
+        raise ValueError("fold_finals: not a composed lattice (the last state must be the only final one, weight 0, no arc out)")
+    dst = np.asarray(lat["dst"])
+    to_end = dst == end
+    keep, fa = np.flatnonzero(~to_end), np.flatnonzero(to_end)
+    fs = np.asarray(lat["src"])[fa]
+    if np.unique(fs).size != fs.size:
+        raise ValueError("fold_finals: a state with two arcs into the end state")
+    out = dict(num_states=end, start=int(lat["start"]))
+    for k in ("src", "dst", "word", "graph", "acoustic"):
+        out[k] = np.asarray(lat[k])[keep].copy()
+    final, final_ac = np.full(end, np.inf, np.float32), np.zeros(end, np.float32)
+    final[fs], final_ac[fs] = np.asarray(lat["graph"])[fa], np.asarray(lat["acoustic"])[fa]
+    out["final"], out["final_acoustic"] = final, final_ac
+    for k in ("orig_arc", "input_arc"):
+        if k in lat:
+            out[k] = np.asarray(lat[k])[keep].copy()
+            f = np.full(end, -1, np.int64)
+            f[fs] = np.asarray(lat[k])[fa]
+            out["final_" + k] = f
+    to = np.asarray(lat["tid_off"]) if "tid_off" in lat else np.zeros(dst.size + 1, np.int64)
+    ti = np.asarray(lat["tids"]) if "tid_off" in lat else np.zeros(0, np.int32)
+    strs = [ti[to[a]:to[a + 1]] for a in keep]
+    out["tid_off"] = np.concatenate([[0], np.cumsum([len(s) for s in strs])]).astype(np.int64)
+    out["tids"] = np.concatenate(strs + [np.zeros(0, np.int32)]).astype(np.int32)
+    fstr = [np.zeros(0, np.int32)] * end
+    for a, s in zip(fa, fs):
+        fstr[s] = ti[to[a]:to[a + 1]]
+    out["final_tid_off"] = np.concatenate([[0], np.cumsum([len(s) for s in fstr])]).astype(np.int64)
+    out["final_tids"] = np.concatenate(fstr + [np.zeros(0, np.int32)]).astype(np.int32)
+    return out
+
+
+def _follow(prev, lat):
+    """input_arc of `lat`, composed from the folded lattice `prev`, taken back to the lattice `prev` was composed from."""
+    fin = np.flatnonzero(np.isfinite(np.asarray(prev["final"], np.float32)))
+    back = np.concatenate([np.asarray(prev["input_arc"], np.int64), np.asarray(prev["final_input_arc"], np.int64)[fin]])
+    lat["input_arc"] = back[lat["input_arc"]]
+
+
+def _rescore_batch(batch, lm, scale, expand, max_expand):
+    """The composed dict of every lattice of the batch; a lattice whose room was short is run again alone with twice the
+    room, up to max_expand."""
+    if not np.isfinite(scale):
+        raise ValueError("rescore_lm: the LM scale must be finite, got %r" % (scale,))
+    if not (np.isfinite(expand) and np.isfinite(max_expand) and 0 < expand <= max_expand):
+        raise ValueError("rescore_lm: need 0 < expand <= max_expand, got %r, %r" % (expand, max_expand))
+    dev = batch.device
+    with torch.cuda.device(dev):
+        lm_word_dev = _lib.h2d(_lm_words(batch, lm), dev)
+        res = _lmrescore_launch(batch, 0, len(batch), lm, lm_word_dev, scale, expand)
+        for i, p in enumerate(batch.packed):
+            e = expand
+            while res[i][0] == 2:
+                e *= 2
+                if e > max_expand:
+                    raise ValueError("lattice %s (%d states, %d arcs): the lattice composed with the LM does not fit %g times "
+                                     "its size (max_expand)" % (batch.names[i], p.S, p.A, max_expand))
+                res[i] = _lmrescore_launch(batch, i, 1, lm, lm_word_dev, scale, e)[0]
+            if res[i][0] != 0:
+                raise _lib.Pk2Error("lattice %s: LM rescoring failed with status %d" % (batch.names[i], res[i][0]))
+    return [_composed_dict(p, batch.source[i], res[i][1], res[i][2]) for i, p in enumerate(batch.packed)]
+
+
+def rescore_lm(lattices, lms, device="cuda", expand=8, max_expand=64, names=None):
+    """Composes every lattice with the LMs of lms = [(NgramLM, scale), ...] one after the other: [(old, -1.0), (new, 1.0)]
+    takes the first-pass LM out and puts a larger one in (the recipes' lmrescore_const_arpa.sh).  Returns the composed
+    lattices as raw dicts (single end state with final weight 0, `orig_arc` = the packed arc of the last composition's
+    input, `input_arc` = the arc of the caller's lattice); fold_finals() turns one into the form of the archive writer.
+    No determinisation follows (Kaldi determinises again; a determinised input stays deterministic on words)."""
+    if len(lms) == 0:
+        raise ValueError("rescore_lm: no LM")
+    cur = list(lattices)
+    for k, (lm, scale) in enumerate(lms):
+        out = _rescore_batch(WordLatticeBatch(cur, device, names=names), lm, float(scale), expand, max_expand)
+        if k > 0:
+            for prev, lat in zip(cur, out):
+                _follow(prev, lat)
+        cur = [fold_finals(d) for d in out] if k + 1 < len(lms) else out
+    return cur
 
 
 def edit_distance(hyps, refs, device="cuda"):
