@@ -5,13 +5,16 @@ weight and word insertion penalty, then utt_wer.py), running on libpk2hip.so: ev
 decoded in one launch (pykaldi2_amd.score), the word errors are counted on the device.
 
   python bin/score.py -lat_file exp/se/lat.ark -words_txt exp/tri/graph/words.txt -ref_text data/dev/text \
-      -out_dir exp/se/scoring [-min_lmwt 7 -max_lmwt 17 -word_ins_penalty 0.0,0.5,1.0] [-decode_mbr]
+      -out_dir exp/se/scoring [-min_lmwt 7 -max_lmwt 17 -word_ins_penalty 0.0,0.5,1.0] [-decode_mbr] [-ctm -frame_shift 0.03]
 
 Writes hyp_<LMWT>.<wip>.txt (key, then words) and result_<LMWT>_<wip> (utt_wer.py's three lines per utterance: reco:, ref:,
 `<key> err: E ref_len: L`; with -decode_mbr a fourth line `conf: <key> c1 c2 ...`) per setting and prints
 `best: LMWT=.. wip=.. errors=.. ref_words=.. WER=..%` last: the lowest error count, ties to the first setting of the sweep.
 <NOISE> and <SPOKEN_NOISE> are removed from the references and <UNK> from the hypotheses (score_opencss.sh).  Lattices
-without a reference are reported and skipped; a reference without a lattice counts all its words as errors."""
+without a reference are reported and skipped; a reference without a lattice counts all its words as errors.
+-ctm adds ctm_<LMWT>_<wip> per setting (score_sclite.sh's lattice-to-ctm-conf): `<key> 1 <begin> <duration> <word> <confidence>`
+in seconds, keys in archive order, the times of the lattice's own word arcs (no word-boundary alignment) -- of the MBR
+hypothesis with -decode_mbr, otherwise of the best path with its confidences (--decode-mbr=false)."""
 import argparse
 import os
 import sys
@@ -53,6 +56,8 @@ def main():
     parser.add_argument("-max_lmwt", default=17, type=int)
     parser.add_argument("-word_ins_penalty", default="0.0,0.5,1.0")
     parser.add_argument("-decode_mbr", action="store_true", help="minimum Bayes risk decoding with word confidences")
+    parser.add_argument("-ctm", action="store_true", help="also write ctm_<LMWT>_<wip>: word times and confidences")
+    parser.add_argument("-frame_shift", default=0.01, type=float, help="seconds per frame (0.03 for a chain model)")
     parser.add_argument("-batch_size", default=32, type=int, help="lattices per device batch")
     args = parser.parse_args()
 
@@ -74,7 +79,8 @@ def main():
         return ids[w]
 
     hyps = [dict() for _ in range(G)]      # per setting: key -> (words, confidences)
-    seen, batch = set(), []
+    ctm = [dict() for _ in range(G)]       # per setting: key -> CTM lines
+    seen, batch, order = set(), [], []
 
     def flush():
         if not batch:
@@ -82,10 +88,15 @@ def main():
         wl = score.WordLatticeBatch([lat for _, lat in batch], "cuda", names=[k for k, _ in batch])
         for g0 in range(0, G, score.MAX_SETTINGS):
             part = settings[g0:g0 + score.MAX_SETTINGS]
+            timed = wl.mbr(part, decode_mbr=args.decode_mbr, times=True) if args.ctm else None
             if args.decode_mbr:
-                res = wl.mbr(part, decode_mbr=True)
+                res = timed if args.ctm else wl.mbr(part, decode_mbr=True)
             else:
                 res = [[dict(words=w, conf=None) for w, _ in row] for row in wl.best_path(part)]
+            if args.ctm:
+                for (key, _), row in zip(batch, timed):
+                    for g, rec in enumerate(row):
+                        ctm[g0 + g][key] = score.ctm_lines(key, rec, symbols, args.frame_shift, drop=HYP_FILTER)
             for (key, _), row in zip(batch, res):
                 for g, rec in enumerate(row):
                     keep = [i for i, w in enumerate(rec["words"]) if symbols.get(w, str(w)) not in HYP_FILTER]
@@ -98,6 +109,7 @@ def main():
             print("no reference for %s: skipped" % key)
             continue
         seen.add(key)
+        order.append(key)
         batch.append((key, lat))
         if len(batch) >= args.batch_size:
             flush()
@@ -128,6 +140,10 @@ def main():
                 f.write("%s err: %d ref_len: %d\n" % (k, errs[k], len(refs[k])))
                 if args.decode_mbr:
                     f.write("conf: %s %s\n" % (k, " ".join("%.4f" % c for c in hyps[g][k][1])))
+        if args.ctm:
+            with open(os.path.join(args.out_dir, "ctm_%d_%s" % (lmwt, wip)), "w") as f:
+                for k in order:
+                    f.write("".join(line + "\n" for line in ctm[g][k]))
         if best is None or total < best[0]:
             best = (total, lmwt, wip)
     print("best: LMWT=%d wip=%s errors=%d ref_words=%d WER=%.2f%%" % (best[1], best[2], best[0], ref_words,

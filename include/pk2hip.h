@@ -792,6 +792,18 @@ int pk2_perm_align(const float* const* masks, const float* cov, const float* log
  * per pair and bin_word / bin_post (pairs x bin_stride x bins, bin_stride >= capacity): for every position whose top
  * entry is not epsilon the `bins` highest (word, posterior) pairs, word -1 where the lattice has fewer words.
  *
+ * Word times.  pk2_wordlat_set_times takes the frame at which every packed state is reached (HOST int32,
+ * laid out like state_off: state_off[N] entries), checks on the host that every lattice starts at frame 0 and that no
+ * arc has a negative length (PK2_ERR_INVALID otherwise) and uploads it once for the batch.  pk2_wordlat_mbr_times is
+ * pk2_wordlat_mbr -- the same words, confidences, risk, iterations, status and bins, bit for bit -- followed by the time
+ * statistics of the last E-step: times (pairs x word_stride x 2): (begin, end) of every hypothesis word in frames,
+ * TB / gamma and TE / gamma with TB(q)[w] = sum over the arcs of w of [dec_a(q) = 1] t(s_a) b_a(q) and TE with t(n_a),
+ * (-1, -1) where gamma <= 0; bin_times (pairs x bin_stride x bins x 2, with bins > 0): the same for every bin entry,
+ * (-1, -1) for epsilon and for absent entries; path_times (pairs x path_stride x 2, path_stride >= depth of every
+ * lattice of the range): (t(s_a), t(n_a)) of the word arcs of the best path, the rows behind them (-1, -1).  work:
+ * pk2_wordlat_times_workspace_bytes(h, first, count, G, bins) bytes.  A batch without uploaded times, null outputs and a
+ * short path_stride or workspace are refused before the device is touched.
+ *
  * pk2_edit_distance_batch: Levenshtein distance with unit costs of n pairs, one wavefront each; hyp / ref: device int32
  * labels, hyp_off / ref_off: device int64 (n + 1); out[i] = -1 for a reference beyond PK2_WORDLAT_MAX_POSITIONS labels.
  * ------------------------------------------------------------------ */
@@ -812,6 +824,13 @@ int pk2_wordlat_mbr(const void* h, int32_t first, int32_t count, const double* s
                     int32_t max_iter, int32_t bins, void* work, size_t work_bytes, int32_t* words, double* conf,
                     int32_t word_stride, int32_t* nwords, double* risk, int32_t* iterations, int32_t* status, int32_t* bin_n,
                     int32_t* bin_word, double* bin_post, int32_t bin_stride, void* stream);
+int pk2_wordlat_set_times(void* h, const int32_t* state_time);
+size_t pk2_wordlat_times_workspace_bytes(const void* h, int32_t first, int32_t count, int32_t G, int32_t bins);
+int pk2_wordlat_mbr_times(const void* h, int32_t first, int32_t count, const double* settings, int32_t G, int32_t decode_mbr,
+                          int32_t max_iter, int32_t bins, void* work, size_t work_bytes, int32_t* words, double* conf,
+                          int32_t word_stride, int32_t* nwords, double* risk, int32_t* iterations, int32_t* status,
+                          int32_t* bin_n, int32_t* bin_word, double* bin_post, int32_t bin_stride, double* times,
+                          double* bin_times, int32_t* path_times, int32_t path_stride, void* stream);
 int pk2_edit_distance_batch(const int32_t* hyp, const int64_t* hyp_off, const int32_t* ref, const int64_t* ref_off, int32_t n,
                             int32_t* out, void* stream);
 

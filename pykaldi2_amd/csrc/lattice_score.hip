@@ -460,6 +460,123 @@ __global__ void __launch_bounds__(kWsThreads) ws_mbr_kernel(WsParams p) {
   }
 }
 
+// ---- word times ----
+struct WsTimes {
+  const int32_t* state_time;   // frame of every state, laid out like state_off
+  int64_t base;                // words of `work` in front of the times area: the MBR workspace of the launch
+  double* times; double* bin_times; int32_t* path_times; int32_t path_stride;
+};
+
+// Words of the times area per pair: [TB 64 x Pe | TE 64 x Pe | wanted W + 1 (int32, one word each for a simple prefix)]
+__host__ __device__ inline int64_t ws_times_words(int64_t W, int64_t Pe) { return 2 * kWsMaxGroups * Pe + (W + 1); }
+
+// After ws_mbr_kernel, on the workspace it leaves behind (A, B, gamma, topw of the last E-step; bp and best of
+// ws_post_kernel): TB(q)[w] = sum over the arcs of w of [dec_a(q) = 1] t(s_a) b_a(q), TE with t(n_a), for the words the
+// record reports; begin = TB / gamma, end = TE / gamma.  One lane group per wanted word, the arcs of the word in the order
+// and with the group widths of the statistics pass; the lane that owns q keeps TB(q), TE(q) in its group's row and
+// divides.  Thread 0 walks the back-pointers for the best path's own arc times.
+__global__ void __launch_bounds__(kWsThreads) ws_times_kernel(WsParams p, WsTimes x) {
+  __shared__ int32_t r[kWsThreads];
+  __shared__ int32_t bidx[kWsThreads];
+  __shared__ unsigned char decs[kWsWaves * kWsThreads];
+  __shared__ int32_t wave_tot[kWsWaves];
+  const int pair = blockIdx.x, li = pair / p.G, g = pair % p.G, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const WsView L = ws_view(p, li, g);
+  const int l = p.first + li, P = L.P, kk = p.kk;
+  const int32_t* T = x.state_time + p.state_off[l];
+  const int m0 = L.best[0];
+  // ---- the best path's word arcs; the rows behind them are (-1, -1) ----
+  int32_t* pt = x.path_times + 2 * (int64_t)pair * x.path_stride;
+  for (int k = max(m0, 0) + tid; k < x.path_stride; k += kWsThreads) { pt[2 * k] = -1; pt[2 * k + 1] = -1; }
+  if (tid == 0 && m0 > 0) {
+    int i = m0;
+    for (int s = L.S - 1, guard = 0; s > 0 && guard < L.S; ++guard) {
+      const int a = L.bp[s];
+      if (L.word[a] != 0 && i > 0) {
+        --i;
+        if (i < x.path_stride) { pt[2 * i] = T[L.src[a]]; pt[2 * i + 1] = T[L.dst[a]]; }
+      }
+      s = L.src[a];
+    }
+  }
+  if (m0 < 0 || 2 * m0 + 1 > L.cap) return;      // ws_mbr_kernel ran no E-step
+  // ---- the hypothesis of the last E-step, from the words it reported ----
+  const int m = max(0, min(p.nwords[pair], (L.cap - 1) / 2)), Q = 2 * m + 1;
+  const int64_t Pe = (P + 1) & ~1;
+  double* tw = p.work + x.base + (int64_t)p.G * (2 * kWsMaxGroups * (p.pe_pre[l] - p.pe_pre[p.first]) +
+                                                 (p.word_off_off[l] - p.word_off_off[p.first])) +
+               (int64_t)g * ws_times_words(L.W, Pe);
+  int32_t* want = reinterpret_cast<int32_t*>(tw + 2 * kWsMaxGroups * Pe);
+  r[tid] = 0;
+  bidx[tid] = -1;
+  for (int w = tid; w < L.W; w += kWsThreads) want[w] = 0;
+  __syncthreads();
+  if (tid < m) {
+    const int gid = p.words[(int64_t)pair * p.word_stride + tid];
+    int lo = 0, hi = L.W - 1;
+    while (lo < hi) { const int mid = (lo + hi) >> 1; if (L.word_ids[mid] < gid) lo = mid + 1; else hi = mid; }
+    r[2 * (tid + 1)] = lo;
+    want[lo] = 1;
+    x.times[2 * ((int64_t)pair * p.word_stride + tid)] = -1.0;
+    x.times[2 * ((int64_t)pair * p.word_stride + tid) + 1] = -1.0;
+  }
+  // ---- the bins: position q is reported when its best word is not epsilon, at the rank ws_mbr_kernel gave it ----
+  if (p.bins > 0) {
+    const bool flag = tid >= 1 && tid <= Q && L.topw[(int64_t)tid * kk] > 0;
+    const unsigned long long mask = __ballot(flag);
+    if (lane == 0) wave_tot[wave] = __popcll(mask);
+    __syncthreads();
+    int idx = __popcll(mask & ((1ull << lane) - 1ull));
+    for (int w2 = 0; w2 < wave; ++w2) idx += wave_tot[w2];
+    if (flag && idx < p.bin_stride) {
+      bidx[tid] = idx;
+      for (int t = 0; t < p.bins; ++t) {
+        const int w = L.topw[(int64_t)tid * kk + t];
+        if (w > 0) want[w] = 1;
+        const int64_t o = 2 * (((int64_t)pair * p.bin_stride + idx) * p.bins + t);
+        x.bin_times[o] = -1.0; x.bin_times[o + 1] = -1.0;
+      }
+    }
+  }
+  __syncthreads();
+  // ---- the wanted words ----
+  const int wd = Q + 1 <= 16 ? 16 : (Q + 1 <= 32 ? 32 : 64), sub = tid & (wd - 1), grp = tid / wd, ngrp = kWsThreads / wd;
+  const int gnc = Q / wd + 1;
+  unsigned char* decw = decs + grp * (kWsThreads / 64) * wd;
+  double* TBg = tw + (int64_t)grp * P;
+  double* TEg = tw + (int64_t)(kWsMaxGroups + grp) * P;
+  for (int w = 1 + grp; w < L.W; w += ngrp) {
+    if (!want[w]) continue;
+    for (int c = 0; c < gnc; ++c) { const int q = wd * c + sub; if (q <= Q) { TBg[q] = 0.0; TEg[q] = 0.0; } }
+    for (int k = L.word_off[w]; k < L.word_off[w + 1]; ++k) {
+      const int a = L.word_arcs[k];
+      const double ts = (double)T[L.src[a]], tn = (double)T[L.dst[a]];
+      ws_arc_back(L.Am + (int64_t)L.src[a] * P, L.Bm + (int64_t)L.dst[a] * P, r, Q, sub, wd, w, L.post[a], decw,
+                  [&](int q, bool valid, int d, int dn, double b, double bn) {
+                    if (valid && q >= 1 && d == 1) { TBg[q] += ts * b; TEg[q] += tn * b; }
+                  });
+    }
+    for (int c = 0; c < gnc; ++c) {
+      const int q = wd * c + sub;
+      if (q < 1 || q > Q) continue;
+      const double gm = L.gamma[(int64_t)w * P + q];
+      const double tb = gm > 0.0 ? TBg[q] / gm : -1.0, te = gm > 0.0 ? TEg[q] / gm : -1.0;
+      if (r[q] == w) {
+        const int64_t o = 2 * ((int64_t)pair * p.word_stride + (q / 2 - 1));
+        x.times[o] = tb; x.times[o + 1] = te;
+      }
+      const int idx = bidx[q];
+      if (idx >= 0) {
+        for (int t = 0; t < p.bins; ++t) {
+          if (L.topw[(int64_t)q * kk + t] != w) continue;
+          const int64_t o = 2 * (((int64_t)pair * p.bin_stride + idx) * p.bins + t);
+          x.bin_times[o] = tb; x.bin_times[o + 1] = te;
+        }
+      }
+    }
+  }
+}
+
 __global__ void __launch_bounds__(64) ws_edit_kernel(const int32_t* hyp, const int64_t* hyp_off, const int32_t* ref,
                                                      const int64_t* ref_off, int32_t* out) {
   const int n = blockIdx.x, lane = threadIdx.x;
@@ -488,6 +605,12 @@ size_t ws_bytes(const WordLat* h, int first, int count, int G, int bins) {
     w += (h->mbr_pre[first + count] - h->mbr_pre[first]) + 3 * kk * (h->pe_pre[first + count] - h->pe_pre[first]) / 2;
   }
   return (size_t)(w * G) * 8;
+}
+
+size_t ws_times_bytes(const WordLat* h, int first, int count, int G, int bins) {
+  const int64_t w = 2 * kWsMaxGroups * (h->pe_pre[first + count] - h->pe_pre[first]) +
+                    (h->word_off_off[first + count] - h->word_off_off[first]);
+  return ws_bytes(h, first, count, G, bins) + (size_t)(w * G) * 8;
 }
 
 bool ws_range_ok(const WordLat* h, int first, int count) {
@@ -562,6 +685,7 @@ extern "C" int pk2_wordlat_create(int32_t N, const int64_t* state_off, const int
         if (wa[k] < 0 || wa[k] >= A || w_[wa[k]] != w || (k > wo[w] && wa[k] <= wa[k - 1])) { bad = "word arc list"; break; }
     const int64_t cap = std::min<int64_t>(PK2_WORDLAT_MAX_POSITIONS, 2 * D + 1), P = cap + 1;
     h->depth[l] = (int32_t)D; h->cap[l] = (int32_t)cap;
+    h->h_src.insert(h->h_src.end(), s_, s_ + A); h->h_dst.insert(h->h_dst.end(), d_, d_ + A);
     h->post_pre[l + 1] = h->post_pre[l] + ws_post_words(S, A, D);
     h->mbr_pre[l + 1] = h->mbr_pre[l] + ws_mbr_words(S, W, P);
     h->pe_pre[l + 1] = h->pe_pre[l] + ((P + 1) & ~(int64_t)1);
@@ -612,6 +736,7 @@ extern "C" int pk2_wordlat_create(int32_t N, const int64_t* state_off, const int
 extern "C" int pk2_wordlat_destroy(void* handle) {
   WordLat* h = static_cast<WordLat*>(handle);
   if (!h) return PK2_OK;
+  if (h->d_state_time) (void)hipFree(h->d_state_time);
   if (h->blob) PK2_HIP(hipFree(h->blob));
   delete h;
   return PK2_OK;
@@ -677,6 +802,63 @@ extern "C" int pk2_wordlat_mbr(const void* handle, int32_t first, int32_t count,
   hipLaunchKernelGGL(ws_post_kernel, dim3(count * G), dim3(kWsPostThreads), 0, st, p);
   PK2_LAUNCH_CHECK();
   hipLaunchKernelGGL(ws_mbr_kernel, dim3(count * G), dim3(kWsThreads), 0, st, p);
+  PK2_LAUNCH_CHECK();
+  return PK2_OK;
+}
+
+extern "C" int pk2_wordlat_set_times(void* handle, const int32_t* state_time) {
+  WordLat* h = static_cast<WordLat*>(handle);
+  PK2_REQUIRE(h && state_time, "wordlat_set_times: null pointer");
+  PK2_REQUIRE(h->N >= 1, "wordlat_set_times: not a batch of pk2_wordlat_create");
+  for (int l = 0; l < h->N; ++l) {
+    const int32_t* t = state_time + h->state_off[l];
+    PK2_REQUIRE(t[0] == 0, "wordlat_set_times: lattice %d starts at frame %d, not 0", l, t[0]);
+    for (int64_t a = h->arc_off[l]; a < h->arc_off[l + 1]; ++a)
+      PK2_REQUIRE(t[h->h_dst[a]] >= t[h->h_src[a]], "wordlat_set_times: lattice %d, arc %lld has the negative length %d", l,
+                  (long long)(a - h->arc_off[l]), t[h->h_dst[a]] - t[h->h_src[a]]);
+  }
+  const size_t bytes = 4 * (size_t)h->state_off[h->N];
+  if (!h->d_state_time) PK2_HIP(hipMalloc(reinterpret_cast<void**>(&h->d_state_time), bytes));
+  PK2_HIP(hipMemcpy(h->d_state_time, state_time, bytes, hipMemcpyHostToDevice));
+  return PK2_OK;
+}
+
+extern "C" size_t pk2_wordlat_times_workspace_bytes(const void* handle, int32_t first, int32_t count, int32_t G, int32_t bins) {
+  const WordLat* h = static_cast<const WordLat*>(handle);
+  if (!ws_range_ok(h, first, count) || G < 1 || G > PK2_WORDLAT_MAX_SETTINGS || bins < 0 || bins > PK2_WORDLAT_MAX_BINS) return 0;
+  return ws_times_bytes(h, first, count, G, bins);
+}
+
+extern "C" int pk2_wordlat_mbr_times(const void* handle, int32_t first, int32_t count, const double* settings, int32_t G,
+                                     int32_t decode_mbr, int32_t max_iter, int32_t bins, void* work, size_t work_bytes,
+                                     int32_t* words, double* conf, int32_t word_stride, int32_t* nwords, double* risk,
+                                     int32_t* iterations, int32_t* status, int32_t* bin_n, int32_t* bin_word, double* bin_post,
+                                     int32_t bin_stride, double* times, double* bin_times, int32_t* path_times,
+                                     int32_t path_stride, void* stream) {
+  const WordLat* h = static_cast<const WordLat*>(handle);
+  PK2_REQUIRE(h && times && path_times, "wordlat_mbr_times: null pointer");
+  PK2_REQUIRE(h->d_state_time, "wordlat_mbr_times: no state times (pk2_wordlat_set_times comes first)");
+  PK2_REQUIRE(bins >= 0 && bins <= PK2_WORDLAT_MAX_BINS, "wordlat_mbr_times: bins %d (0..%d)", bins, PK2_WORDLAT_MAX_BINS);
+  PK2_REQUIRE(bins == 0 || bin_times, "wordlat_mbr_times: null pointer for the bin times");
+  PK2_REQUIRE(G >= 1 && G <= PK2_WORDLAT_MAX_SETTINGS, "wordlat_mbr_times: %d settings (1..%d)", G, PK2_WORDLAT_MAX_SETTINGS);
+  PK2_REQUIRE(ws_range_ok(h, first, count), "wordlat_mbr_times: lattices %d..%d of %d", first, first + count, h->N);
+  for (int l = first; l < first + count; ++l)
+    PK2_REQUIRE(path_stride >= h->depth[l], "wordlat_mbr_times: path_stride %d below the depth %d of lattice %d", path_stride,
+                h->depth[l], l);
+  PK2_REQUIRE(work_bytes >= ws_times_bytes(h, first, count, G, bins), "wordlat_mbr_times: workspace of %zu bytes, need %zu",
+              work_bytes, ws_times_bytes(h, first, count, G, bins));
+  // the remaining arguments are pk2_wordlat_mbr's and are checked there, before its first launch
+  const int rc = pk2_wordlat_mbr(handle, first, count, settings, G, decode_mbr, max_iter, bins, work, work_bytes, words, conf,
+                                 word_stride, nwords, risk, iterations, status, bin_n, bin_word, bin_post, bin_stride, stream);
+  if (rc != PK2_OK) return rc;
+  WsParams p;
+  ws_fill(h, p, first, count, settings, G, true, bins);
+  p.work = static_cast<double*>(work);
+  p.words = words; p.word_stride = word_stride; p.nwords = nwords; p.bin_stride = bin_stride;
+  WsTimes x;
+  x.state_time = h->d_state_time; x.base = (int64_t)(ws_bytes(h, first, count, G, bins) / 8);
+  x.times = times; x.bin_times = bin_times; x.path_times = path_times; x.path_stride = path_stride;
+  hipLaunchKernelGGL(ws_times_kernel, dim3(count * G), dim3(kWsThreads), 0, static_cast<hipStream_t>(stream), p, x);
   PK2_LAUNCH_CHECK();
   return PK2_OK;
 }

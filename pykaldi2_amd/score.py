@@ -6,6 +6,8 @@ lattice-mbr-decode, utt_wer.py).  Packing is numpy on the host; the kernels are 
     batch = WordLatticeBatch([lat0, lat1, ...], "cuda")        # dicts of compact_lattice / determinize_lattice / an archive
     for (words, cost) in batch.best_path(sweep())[0]: ...
     rec = batch.mbr(sweep(), decode_mbr=True)[0][0]             # words, conf, risk, iterations, status
+    rec = batch.mbr(sweep(), times=True)[0][0]                  # + times, path_times (frames)
+    lines = ctm_lines("utt1", rec, symbols, frame_shift=0.03)   # "<key> 1 <begin> <duration> <word> <confidence>"
 
 N-gram LM rescoring (csrc/lattice_lmrescore.hip, pykaldi2_amd.ngram): the composition of the lattices with a
 backoff LM, what local/lmrescore_const_arpa.sh hands to Kaldi's lattice-lmrescore and lattice-lmrescore-const-arpa.
@@ -54,9 +56,10 @@ class PackedLattice:
     id): 0 = start, S-1 = the single end; arcs sorted by (destination, original index): in_off is the CSR by destination,
     out_off / out_idx the CSR by source (arc indices ascending); level_off the state range of every level; word = local
     id (0 = epsilon, ascending word id <-> ascending local id), word_ids the global ids, word_off / word_arcs the arcs of
-    every local word (ascending)."""
+    every local word (ascending); arc_len the length in frames of every arc's transition-id string (None for a lattice
+    form without strings), read only by state_times."""
     __slots__ = ("S", "A", "W", "depth", "cap", "src", "dst", "word", "graph", "acoustic", "in_off", "out_off", "out_idx",
-                 "level_off", "word_ids", "word_off", "word_arcs", "orig_arc")
+                 "level_off", "word_ids", "word_off", "word_arcs", "orig_arc", "arc_len")
 
 
 def _lattice_arcs(lat, name):
@@ -91,6 +94,91 @@ def _lattice_arcs(lat, name):
     if not (np.isfinite(g).all() and np.isfinite(c).all()):
         raise ValueError("lattice %s: non-finite arc cost" % name)
     return n, int(lat["start"]), src, dst, word, g, c, fg, fc
+
+
+def _string_lengths(lat):
+    """(length of the transition-id string of every input arc, of every state's final weight) as int64 arrays; None for a
+    form without strings or with string arrays that do not fit its arcs."""
+    if "arcs" in lat and "finals" in lat:
+        return (np.fromiter((len(a[4][2]) for a in lat["arcs"]), np.int64, len(lat["arcs"])),
+                np.fromiter((len(f[2]) for f in lat["finals"]), np.int64, len(lat["finals"])))
+    n, A = int(lat["num_states"]), np.asarray(lat["src"]).size
+    if "tid_off" in lat and "final_tid_off" in lat:
+        al, fl = np.diff(np.asarray(lat["tid_off"], np.int64)), np.diff(np.asarray(lat["final_tid_off"], np.int64))
+    elif "tid" in lat:
+        al, fl = (np.asarray(lat["tid"]).reshape(-1) > 0).astype(np.int64), np.zeros(n, np.int64)
+    else:
+        return None
+    return (al, fl) if al.size == A and fl.size == n else None
+
+
+def _packed_arc_len(P, lat, fg):
+    """The string length of every packed arc: the arcs that packing made of the finals (orig_arc >= number of arcs, in
+    state order) carry the final weight's string."""
+    lens = _string_lengths(lat)
+    if lens is None:
+        return None
+    both = np.concatenate([lens[0], lens[1][np.flatnonzero(np.isfinite(fg))]])
+    return np.ascontiguousarray(both[P.orig_arc].astype(np.int64))
+
+
+def state_times(P, lat=None, name="?"):
+    """The frame at which every packed state is reached (int32, P.S entries): t(0) = 0, t(n) = t(s_a) + len_a for every
+    incoming arc a of n, with len_a the length of the arc's transition-id string.  The incoming arcs must agree (Kaldi's
+    CompactLatticeStateTimes asserts the same; ValueError naming the lattice, the state and the two frames); only the end
+    state takes the maximum, the utterance length.  `lat` is the dict P was packed from (None: the lengths P carries)."""
+    lens = P.arc_len if lat is None else _packed_arc_len(P, lat, _lattice_arcs(lat, name)[7])
+    if lens is None:
+        raise ValueError("lattice %s: no transition-id strings (tid_off / tid / archive strings), so no times" % name)
+    t = np.zeros(P.S, np.int64)
+    for lev in range(1, P.depth + 1):
+        s0, s1 = int(P.level_off[lev]), int(P.level_off[lev + 1])
+        a0, a1 = int(P.in_off[s0]), int(P.in_off[s1])
+        cand = t[P.src[a0:a1]] + lens[a0:a1]
+        off = P.in_off[s0:s1].astype(np.int64) - a0
+        hi, lo = np.maximum.reduceat(cand, off), np.minimum.reduceat(cand, off)
+        bad = np.flatnonzero(hi != lo)
+        if bad.size and s0 + int(bad[0]) != P.S - 1:
+            raise ValueError("lattice %s: state %d is reached at frame %d and at frame %d: the transition-id strings of its "
+                             "incoming arcs disagree" % (name, s0 + int(bad[0]), int(lo[bad[0]]), int(hi[bad[0]])))
+        t[s0:s1] = hi
+    if t[-1] >= 2 ** 31:
+        raise ValueError("lattice %s: %d frames" % (name, int(t[-1])))
+    return t.astype(np.int32)
+
+
+def fix_word_times(times):
+    """Kaldi's clean-up of one-best word times on a copy of `times` (rows of (begin, end), float64), left to right: a word
+    that begins before its predecessor ends meets it half way (and the predecessor's begin stays <= its end); afterwards
+    no word ends before it begins.  Rows of -1 (no time) are left alone and skipped as neighbours."""
+    t = np.array(times, np.float64).reshape(-1, 2)
+    prev = -1
+    for i in range(t.shape[0]):
+        if t[i, 0] < 0:
+            continue
+        if prev >= 0 and t[i, 0] < t[prev, 1]:
+            m = 0.5 * (t[i, 0] + t[prev, 1])
+            t[prev, 1] = t[i, 0] = m
+            t[prev, 0] = min(t[prev, 0], t[prev, 1])
+        prev = i
+    ok = t[:, 0] >= 0
+    t[ok, 1] = np.maximum(t[ok, 1], t[ok, 0])
+    return t
+
+
+def ctm_lines(key, rec, symbols, frame_shift=0.01, channel="1", drop=("<UNK>",)):
+    """The CTM lines of a record of mbr(times=True): "<key> <channel> <begin> <duration> <word> <confidence>", seconds with
+    three decimals from fix_word_times(rec["times"]); symbols: word id -> symbol.  Symbols in `drop` and words without a
+    time are left out."""
+    t = fix_word_times(rec["times"])
+    out = []
+    for i, w in enumerate(rec["words"]):
+        sym = symbols.get(w, str(w))
+        if sym in drop or t[i, 0] < 0:
+            continue
+        out.append("%s %s %.3f %.3f %s %.4f" % (key, channel, t[i, 0] * frame_shift, (t[i, 1] - t[i, 0]) * frame_shift, sym,
+                                                float(rec["conf"][i])))
+    return out
 
 
 def _reach(n, start, frm, to):
@@ -177,6 +265,7 @@ def pack_lattice(lat, name="?"):
     P.level_off = np.searchsorted(lv, np.arange(P.depth + 2)).astype(np.int32)
     P.cap = min(MAX_POSITIONS, 2 * P.depth + 1)
     assert P.dst[-1] == P.S - 1 and P.level_off[1] == 1 and P.level_off[-1] - P.level_off[-2] == 1
+    P.arc_len = _packed_arc_len(P, lat, fg)
     return P
 
 
@@ -247,6 +336,19 @@ class WordLatticeBatch:
                 _lib.ptr(H["level_off"]), _lib.ptr(H["word_ids"]), _lib.ptr(H["word_off"]), _lib.ptr(H["word_arcs"]),
                 _lib.stream_ptr(self.device), C.byref(h)))
         self._h = h
+        self.state_time = None      # per lattice, once mbr(times=True) has asked for them
+
+    def _upload_times(self):
+        """State times of every lattice (state_times; its ValueError surfaces here), uploaded once."""
+        if self.state_time is not None:
+            return
+        ts = [state_times(p, None, self.names[i]) for i, p in enumerate(self.packed)]
+        flat = np.ascontiguousarray(np.concatenate(ts).astype(np.int32))
+        if flat.size != int(self._host["state_off"][-1]):
+            raise ValueError("state times: %d entries for %d states" % (flat.size, int(self._host["state_off"][-1])))
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().pk2_wordlat_set_times(self._h, _lib.ptr(flat)))
+        self.state_time = ts
 
     def __len__(self):
         return len(self.packed)
@@ -262,10 +364,11 @@ class WordLatticeBatch:
         return WordLatticeBatch(_rescore_batch(self, lm, float(scale), expand, max_expand), self.device, names=self.names)
 
     # ---- launches cut to the workspace budget ----
-    def _chunks(self, G, bins, workspace_mb):
+    def _chunks(self, G, bins, workspace_mb, times=False):
         budget = int(workspace_mb * (1 << 20))
         L, out, first = _lib.lib(), [], 0
-        one = lambda f, k: int(L.pk2_wordlat_workspace_bytes(self._h, f, k, G, bins))
+        size = L.pk2_wordlat_times_workspace_bytes if times else L.pk2_wordlat_workspace_bytes
+        one = lambda f, k: int(size(self._h, f, k, G, bins))
         while first < len(self.packed):
             count = 1
             if one(first, 1) > budget:
@@ -326,10 +429,14 @@ class WordLatticeBatch:
         PACKED arcs / states (self.packed[n])."""
         return self._run_post(settings, True, workspace_mb)
 
-    def mbr(self, settings, decode_mbr=True, max_iter=10, bins=0, workspace_mb=4096):
+    def mbr(self, settings, decode_mbr=True, max_iter=10, bins=0, workspace_mb=4096, times=False):
         """[[record per setting] per lattice], record = dict(words, conf, risk, iterations, status[, bins]).  status: 0 ok,
         1 not converged within max_iter E-steps, 2 the next hypothesis would not fit the row capacity (in both cases the
-        record is the last E-step's hypothesis with its own statistics), 3 empty or failed."""
+        record is the last E-step's hypothesis with its own statistics), 3 empty or failed.
+        times=True: the records gain `times` (float64 (m, 2): begin and end of every word in frames, raw:
+        fix_word_times cleans them up; -1 without a time), `path_times` (int32 (m0, 2): the best path's own word arcs)
+        and with bins `bin_times` (a (begin, end) per entry of `bins`; (-1, -1) for epsilon).  The state times are
+        computed and uploaded on the first such call; a lattice whose strings disagree raises ValueError there."""
         st = _settings_array(settings)
         if isinstance(max_iter, bool) or int(max_iter) != max_iter or max_iter < 1:
             raise ValueError("max_iter must be an integer >= 1, got %r" % (max_iter,))
@@ -337,27 +444,40 @@ class WordLatticeBatch:
             raise ValueError("bins must be an integer in 0..%d, got %r" % (MAX_BINS, bins))
         bins, max_iter = int(bins), int(max_iter)
         G, L, dev, res = st.shape[0], _lib.lib(), self.device, []
+        if times:
+            self._upload_times()
         with torch.cuda.device(dev):
-            for first, count in self._chunks(G, bins, workspace_mb):
+            for first, count in self._chunks(G, bins, workspace_mb, times):
                 B = _Bufs(dev)
-                ws_bytes = int(L.pk2_wordlat_workspace_bytes(self._h, first, count, G, bins))
+                ws_bytes = int((L.pk2_wordlat_times_workspace_bytes if times else L.pk2_wordlat_workspace_bytes)(
+                    self._h, first, count, G, bins))
                 work = B(ws_bytes // 8 + 1, torch.float64)
                 ps = self.packed[first:first + count]
                 stride = max(1, max((p.cap - 1) // 2 for p in ps))
                 bstride = max(p.cap for p in ps)
+                pstride = max(1, max(p.depth for p in ps))
                 n = count * G
                 words, nw, conf = B(n * stride, torch.int32), B(n, torch.int32), B(n * stride, torch.float64)
                 risk, iters, status = B(n, torch.float64), B(n, torch.int32), B(n, torch.int32)
                 bn = B(n, torch.int32) if bins else None
                 bw = B(n * bstride * bins, torch.int32) if bins else None
                 bv = B(n * bstride * bins, torch.float64) if bins else None
-                _lib.check(L.pk2_wordlat_mbr(self._h, first, count, _lib.ptr(st), G, int(bool(decode_mbr)), max_iter, bins,
-                                             _lib.ptr(work), ws_bytes, _lib.ptr(words), _lib.ptr(conf), stride, _lib.ptr(nw),
-                                             _lib.ptr(risk), _lib.ptr(iters), _lib.ptr(status), _lib.ptr(bn), _lib.ptr(bw),
-                                             _lib.ptr(bv), bstride, _lib.stream_ptr(dev)))
+                args = (self._h, first, count, _lib.ptr(st), G, int(bool(decode_mbr)), max_iter, bins, _lib.ptr(work), ws_bytes,
+                        _lib.ptr(words), _lib.ptr(conf), stride, _lib.ptr(nw), _lib.ptr(risk), _lib.ptr(iters),
+                        _lib.ptr(status), _lib.ptr(bn), _lib.ptr(bw), _lib.ptr(bv), bstride)
+                if times:
+                    tm, pt = B(n * stride * 2, torch.float64), B(n * pstride * 2, torch.int32)
+                    bt = B(n * bstride * bins * 2, torch.float64) if bins else None
+                    _lib.check(L.pk2_wordlat_mbr_times(*args, _lib.ptr(tm), _lib.ptr(bt), _lib.ptr(pt), pstride,
+                                                       _lib.stream_ptr(dev)))
+                else:
+                    _lib.check(L.pk2_wordlat_mbr(*args, _lib.stream_ptr(dev)))
                 hw, hn, hc, hr, hi, hs = (t.cpu().numpy() for t in (words, nw, conf, risk, iters, status))
                 if bins:
                     hbn, hbw, hbv = bn.cpu().numpy(), bw.cpu().numpy(), bv.cpu().numpy()
+                if times:
+                    htm, hpt = tm.cpu().numpy().reshape(-1, 2), pt.cpu().numpy().reshape(-1, 2)
+                    hbt = bt.cpu().numpy().reshape(-1, 2) if bins else None
                 B.check()
                 for i in range(count):
                     row = []
@@ -372,6 +492,13 @@ class WordLatticeBatch:
                             o = k * bstride * bins
                             r["bins"] = [[(int(hbw[o + j * bins + t]), float(hbv[o + j * bins + t])) for t in range(bins)
                                           if hbw[o + j * bins + t] >= 0] for j in range(nb)]
+                            if times:
+                                r["bin_times"] = [[(float(hbt[o + j * bins + t, 0]), float(hbt[o + j * bins + t, 1]))
+                                                   for t in range(bins) if hbw[o + j * bins + t] >= 0] for j in range(nb)]
+                        if times:
+                            r["times"] = htm[k * stride:k * stride + m].copy()
+                            path = hpt[k * pstride:(k + 1) * pstride]
+                            r["path_times"] = path[:int((path[:, 0] >= 0).sum())].copy()
                         row.append(r)
                     res.append(row)
         return res
