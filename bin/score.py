@@ -5,7 +5,8 @@ weight and word insertion penalty, then utt_wer.py), running on libpk2hip.so: ev
 decoded in one launch (pykaldi2_amd.score), the word errors are counted on the device.
 
   python bin/score.py -lat_file exp/se/lat.ark -words_txt exp/tri/graph/words.txt -ref_text data/dev/text \
-      -out_dir exp/se/scoring [-min_lmwt 7 -max_lmwt 17 -word_ins_penalty 0.0,0.5,1.0] [-decode_mbr] [-ctm -frame_shift 0.03]
+      -out_dir exp/se/scoring [-min_lmwt 7 -max_lmwt 17 -word_ins_penalty 0.0,0.5,1.0] [-decode_mbr] [-ctm -frame_shift 0.03] \
+      [-oracle]
 
 Writes hyp_<LMWT>.<wip>.txt (key, then words) and result_<LMWT>_<wip> (utt_wer.py's three lines per utterance: reco:, ref:,
 `<key> err: E ref_len: L`; with -decode_mbr a fourth line `conf: <key> c1 c2 ...`) per setting and prints
@@ -14,7 +15,11 @@ Writes hyp_<LMWT>.<wip>.txt (key, then words) and result_<LMWT>_<wip> (utt_wer.p
 without a reference are reported and skipped; a reference without a lattice counts all its words as errors.
 -ctm adds ctm_<LMWT>_<wip> per setting (score_sclite.sh's lattice-to-ctm-conf): `<key> 1 <begin> <duration> <word> <confidence>`
 in seconds, keys in archive order, the times of the lattice's own word arcs (no word-boundary alignment) -- of the MBR
-hypothesis with -decode_mbr, otherwise of the best path with its confidences (--decode-mbr=false)."""
+hypothesis with -decode_mbr, otherwise of the best path with its confidences (--decode-mbr=false).
+-oracle adds what lattice-oracle and lattice-depth report: oracle.txt (key, then the words of the lattice path closest to the
+reference), result_oracle (reco: / ref: / err: as above and `<key> ins: I del: D sub: S`) and, before the `best:` line,
+`oracle: errors=E ref_words=N WER=x.xx% ins=I del=D sub=S depth=d.dd` -- the floor under every result_* file; <UNK> arcs
+cost nothing, as <UNK> is dropped from the hypotheses; depth = arc-frames over frames of all lattices."""
 import argparse
 import os
 import sys
@@ -58,6 +63,7 @@ def main():
     parser.add_argument("-decode_mbr", action="store_true", help="minimum Bayes risk decoding with word confidences")
     parser.add_argument("-ctm", action="store_true", help="also write ctm_<LMWT>_<wip>: word times and confidences")
     parser.add_argument("-frame_shift", default=0.01, type=float, help="seconds per frame (0.03 for a chain model)")
+    parser.add_argument("-oracle", action="store_true", help="also write oracle.txt / result_oracle: the lattice oracle WER")
     parser.add_argument("-batch_size", default=32, type=int, help="lattices per device batch")
     args = parser.parse_args()
 
@@ -80,6 +86,9 @@ def main():
 
     hyps = [dict() for _ in range(G)]      # per setting: key -> (words, confidences)
     ctm = [dict() for _ in range(G)]       # per setting: key -> CTM lines
+    oracle = {}                            # key -> record of WordLatticeBatch.oracle
+    depth = [0, 0]                         # arc-frames, frames over all lattices
+    skip = [i for i, s in symbols.items() if s in HYP_FILTER]
     seen, batch, order = set(), [], []
 
     def flush():
@@ -102,6 +111,14 @@ def main():
                     keep = [i for i, w in enumerate(rec["words"]) if symbols.get(w, str(w)) not in HYP_FILTER]
                     hyps[g0 + g][key] = ([symbols.get(rec["words"][i], str(rec["words"][i])) for i in keep],
                                          None if rec["conf"] is None else [float(rec["conf"][i]) for i in keep])
+        if args.oracle:
+            for (key, _), rec in zip(batch, wl.oracle([[word_id(w) for w in refs[k]] for k, _ in batch], skip_words=skip)):
+                oracle[key] = rec
+            for P in wl.packed:
+                d = score.lattice_depth(P)
+                if d is not None:
+                    depth[0] += d[0]
+                    depth[1] += d[1]
         del batch[:]
 
     for key, lat in kaldi_io.read_compact_lattice_ark(args.lat_file):
@@ -146,6 +163,24 @@ def main():
                     f.write("".join(line + "\n" for line in ctm[g][k]))
         if best is None or total < best[0]:
             best = (total, lmwt, wip)
+    if args.oracle:
+        tot = dict(errors=sum(len(refs[k]) for k in missing), ins=0, dele=sum(len(refs[k]) for k in missing), sub=0)
+        with open(os.path.join(args.out_dir, "oracle.txt"), "w") as fh, open(os.path.join(args.out_dir, "result_oracle"), "w") as fr:
+            for k in keys:
+                rec = oracle[k]
+                if rec["status"] != 0:       # a reference beyond the kernel's capacity: all its words count, as for a missing lattice
+                    rec = dict(errors=len(refs[k]), ins=0, dele=len(refs[k]), sub=0, words=[])
+                words = [symbols.get(w, str(w)) for w in rec["words"]]
+                fh.write(" ".join([k] + words) + "\n")
+                fr.write("reco: %s %s\n" % (k, " ".join(words)))
+                fr.write("ref: %s %s\n" % (k, " ".join(refs[k])))
+                fr.write("%s err: %d ref_len: %d\n" % (k, rec["errors"], len(refs[k])))
+                fr.write("%s ins: %d del: %d sub: %d\n" % (k, rec["ins"], rec["dele"], rec["sub"]))
+                for f in tot:
+                    tot[f] += rec[f]
+        print("oracle: errors=%d ref_words=%d WER=%.2f%% ins=%d del=%d sub=%d%s"
+              % (tot["errors"], ref_words, 100.0 * tot["errors"] / max(1, ref_words), tot["ins"], tot["dele"], tot["sub"],
+                 " depth=%.2f" % (depth[0] / depth[1]) if depth[1] > 0 else ""))
     print("best: LMWT=%d wip=%s errors=%d ref_words=%d WER=%.2f%%" % (best[1], best[2], best[0], ref_words,
                                                                       100.0 * best[0] / max(1, ref_words)))
 

@@ -835,6 +835,37 @@ int pk2_edit_distance_batch(const int32_t* hyp, const int64_t* hyp_off, const in
                             int32_t* out, void* stream);
 
 /* ------------------------------------------------------------------ *
+ * Lattice oracle (csrc/lattice_oracle.hip): Kaldi's lattice-oracle on a pk2_wordlat_create batch -- the
+ * smallest edit distance (unit costs) between a reference and any path of the lattice, the path that reaches it and its
+ * insertions, deletions and substitutions; one workgroup per lattice, integers only, no settings.
+ *
+ * arc_label: DEVICE int32 laid out like arc_off of the whole batch: 0 for an arc that costs nothing (epsilon, or a word
+ * the caller wants skipped), otherwise the arc's local word id.  ref: DEVICE int32, the references of the range in the
+ * lattices' LOCAL word ids, -1 for a word a lattice does not contain (it never matches); ref_off (DEVICE) and ref_off_host
+ * (HOST), count + 1 entries each and equal: the reference of lattice first + i is ref[ref_off[i] .. ref_off[i + 1]).
+ *   D[0][j] = j;  C[n][j] = min over the incoming arcs a = (s -> n) of  label_a == 0: D[s][j];  otherwise
+ *   min(D[s][j] + 1, D[s][j-1] + (label_a != ref[j-1]));  D[n][j] = min over k <= j of C[n][k] + (j - k);
+ *   errors = D[S-1][R].
+ * The path is walked back from (S-1, R): at (n, j) the incoming arcs of n in ascending index, for each first the diagonal
+ * step, then the free step, then the insertion; the first arc that fits is taken, and if none fits the step is a deletion
+ * to (n, j-1).  Outputs per lattice of the range (device): errors; counts (3: insertions, deletions, substitutions, their
+ * sum = errors); words (word_stride per lattice: the GLOBAL ids of the path's labels != 0, the rest -1) and nwords; path
+ * (path_stride per lattice: the packed arc indices of the path, the rest -1) and npath; status: 0 ok, 2 a reference of
+ * more than PK2_WORDLAT_MAX_POSITIONS words (errors -1, words and path all -1, nothing else written), 3 failed (the same;
+ * device offsets that disagree with ref_off_host end here and write nothing to the workspace).
+ * work: device memory of pk2_wordlat_oracle_workspace_bytes(h, first, count, ref_off_host) bytes (0 for arguments the
+ * entry would refuse): per lattice (S + 64) x (R + 1) + 2 depth int32.  Null pointers, a range outside the batch, a
+ * negative or decreasing ref_off_host, word_stride or path_stride below the depth of a lattice of the range and a short
+ * or misaligned workspace return PK2_ERR_INVALID before the device is touched.  The same bytes for a lattice alone, in a
+ * batch and in any split of the batch into calls.
+ * ------------------------------------------------------------------ */
+size_t pk2_wordlat_oracle_workspace_bytes(const void* h, int32_t first, int32_t count, const int64_t* ref_off);
+int pk2_wordlat_oracle(const void* h, int32_t first, int32_t count, const int32_t* arc_label, const int32_t* ref,
+                       const int64_t* ref_off, const int64_t* ref_off_host, void* work, size_t work_bytes, int32_t* errors,
+                       int32_t* counts, int32_t* words, int32_t word_stride, int32_t* nwords, int32_t* path,
+                       int32_t path_stride, int32_t* npath, int32_t* status, void* stream);
+
+/* ------------------------------------------------------------------ *
  * N-gram LM rescoring of word lattices (csrc/lattice_lmrescore.hip): what the reference's
  * local/lmrescore_const_arpa.sh hands to Kaldi (lattice-lmrescore | lattice-lmrescore-const-arpa) -- the composition of a
  * packed word lattice with a deterministic backoff LM, one workgroup per lattice.

@@ -244,6 +244,9 @@ SIGNATURES = {
     "pk2_wordlat_mbr_times": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _sz, _vp, _vp, _i32, _vp, _vp, _vp,
                                         _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _vp]),
     "pk2_edit_distance_batch": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _vp, _vp]),
+    "pk2_wordlat_oracle_workspace_bytes": (_sz, [_vp, _i32, _i32, _vp]),
+    "pk2_wordlat_oracle": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _vp,
+                                     _vp, _vp]),
     "pk2_ngram_create": (C.c_int, [_i32, _i32] + [_vp] * 7 + [_i32, _i32, _vp, C.POINTER(_vp)]),
     "pk2_ngram_destroy": (C.c_int, [_vp]),
     "pk2_wordlat_lmrescore_workspace_bytes": (_sz, [_vp, _i32, _i32, C.c_double]),

@@ -8,6 +8,8 @@ lattice-mbr-decode, utt_wer.py).  Packing is numpy on the host; the kernels are 
     rec = batch.mbr(sweep(), decode_mbr=True)[0][0]             # words, conf, risk, iterations, status
     rec = batch.mbr(sweep(), times=True)[0][0]                  # + times, path_times (frames)
     lines = ctm_lines("utt1", rec, symbols, frame_shift=0.03)   # "<key> 1 <begin> <duration> <word> <confidence>"
+    rec = batch.oracle(refs, skip_words=(unk_id,))[0]          # lattice-oracle: errors, ins, dele, sub, words, arcs (7.16)
+    arc_frames, frames = lattice_depth(batch.packed[0])         # lattice-depth = arc_frames / frames
 
 N-gram LM rescoring (csrc/lattice_lmrescore.hip, pykaldi2_amd.ngram): the composition of the lattices with a
 backoff LM, what local/lmrescore_const_arpa.sh hands to Kaldi's lattice-lmrescore and lattice-lmrescore-const-arpa.
@@ -337,6 +339,7 @@ class WordLatticeBatch:
                 _lib.stream_ptr(self.device), C.byref(h)))
         self._h = h
         self.state_time = None      # per lattice, once mbr(times=True) has asked for them
+        self._labels = {}           # oracle(): the device arc labels per set of skipped words
 
     def _upload_times(self):
         """State times of every lattice (state_times; its ValueError surfaces here), uploaded once."""
@@ -502,6 +505,99 @@ class WordLatticeBatch:
                         row.append(r)
                     res.append(row)
         return res
+
+    # ---- lattice oracle (csrc/lattice_oracle.hip) ----
+    def _arc_labels(self, skip_words):
+        """arc_label of the whole batch on the device: the local word id of every packed arc, 0 for epsilon and for the
+        words of skip_words (global ids); cached per skip set."""
+        key = tuple(sorted({int(w) for w in skip_words}))
+        if key not in self._labels:
+            skip = np.asarray(key, np.int64)
+            lab = [np.where(np.isin(p.word_ids, skip)[p.word], 0, p.word) for p in self.packed]
+            self._labels[key] = _lib.h2d(np.ascontiguousarray(np.concatenate(lab).astype(np.int32)), self.device)
+        return self._labels[key]
+
+    def _oracle_chunks(self, ref_off, workspace_mb):
+        budget = int(workspace_mb * (1 << 20))
+        L, out, first = _lib.lib(), [], 0
+        one = lambda f, k: int(L.pk2_wordlat_oracle_workspace_bytes(self._h, f, k, _lib.ptr(ref_off[f:f + k + 1])))
+        while first < len(self.packed):
+            count = 1
+            if one(first, 1) > budget:
+                p = self.packed[first]
+                raise ValueError("lattice %d (%d states, depth %d) needs %d bytes of workspace for a reference of %d words: "
+                                 "more than workspace_mb=%d" % (first, p.S, p.depth, one(first, 1),
+                                                                int(ref_off[first + 1] - ref_off[first]), workspace_mb))
+            while first + count < len(self.packed) and one(first, count + 1) <= budget:
+                count += 1
+            out.append((first, count))
+            first += count
+        return out
+
+    def oracle(self, refs, skip_words=(), workspace_mb=4096):
+        """Kaldi's lattice-oracle: [dict(errors, ins, dele, sub, words, arcs, status) per lattice] for refs = one sequence
+        of global word ids per lattice.  errors = the smallest edit distance between the reference and any path of the
+        lattice = ins + dele + sub; words = that path's words (global ids), arcs = its arcs as indices into the input
+        lattice's arcs (the arcs packing made of the final weights are left out).  Arcs of the words in skip_words (global
+        ids) cost nothing and are left out of `words`; a reference word in that set never matches.  status: 0 ok, 2 a
+        reference of more than MAX_POSITIONS words (errors -1, nothing else).  Ties between paths and edit types are
+        broken by the rule of tests/oracle_ref.py."""
+        if len(refs) != len(self.packed):
+            raise ValueError("oracle: %d references for %d lattices" % (len(refs), len(self.packed)))
+        local = []
+        for i, (p, r) in enumerate(zip(self.packed, refs)):
+            r = np.asarray(r, np.int64).reshape(-1)
+            if r.size and r.min() <= 0:
+                raise ValueError("lattice %s: reference word %d (word ids start at 1)" % (self.names[i], int(r.min())))
+            k = np.minimum(np.searchsorted(p.word_ids, r), p.W - 1)
+            local.append(np.where(p.word_ids[k] == r, k, -1).astype(np.int32))
+        ref_off = np.concatenate([[0], np.cumsum([r.size for r in local])]).astype(np.int64)
+        flat = np.ascontiguousarray(np.concatenate(local + [np.full(1, -1, np.int32)]))
+        L, dev, res = _lib.lib(), self.device, []
+        with torch.cuda.device(dev):
+            labels = self._arc_labels(skip_words)
+            ref_dev = _lib.h2d(flat, dev)
+            for first, count in self._oracle_chunks(ref_off, workspace_mb):
+                B = _Bufs(dev)
+                off_host = np.ascontiguousarray(ref_off[first:first + count + 1])
+                off_dev = _lib.h2d(off_host, dev)
+                ws_bytes = int(L.pk2_wordlat_oracle_workspace_bytes(self._h, first, count, _lib.ptr(off_host)))
+                work = B(ws_bytes // 8 + 1, torch.float64)
+                stride = max(1, max(p.depth for p in self.packed[first:first + count]))
+                errors, counts, status = B(count, torch.int32), B(3 * count, torch.int32), B(count, torch.int32)
+                words, nw = B(count * stride, torch.int32), B(count, torch.int32)
+                path, npath = B(count * stride, torch.int32), B(count, torch.int32)
+                _lib.check(L.pk2_wordlat_oracle(self._h, first, count, _lib.ptr(labels), _lib.ptr(ref_dev), _lib.ptr(off_dev),
+                                                _lib.ptr(off_host), _lib.ptr(work), ws_bytes, _lib.ptr(errors), _lib.ptr(counts),
+                                                _lib.ptr(words), stride, _lib.ptr(nw), _lib.ptr(path), stride, _lib.ptr(npath),
+                                                _lib.ptr(status), _lib.stream_ptr(dev)))
+                he, hc, hs, hw, hn, hp, hm = (t.cpu().numpy() for t in (errors, counts, status, words, nw, path, npath))
+                B.check()
+                for i in range(count):
+                    p = self.packed[first + i]
+                    if hs[i] == 3:
+                        raise _lib.Pk2Error("lattice %s: the oracle walk failed" % self.names[first + i])
+                    ok = hs[i] == 0
+                    pa = hp[i * stride:i * stride + hm[i]] if ok else hp[:0]
+                    res.append(dict(errors=int(he[i]), ins=int(hc[3 * i]) if ok else 0, dele=int(hc[3 * i + 1]) if ok else 0,
+                                    sub=int(hc[3 * i + 2]) if ok else 0,
+                                    words=[int(x) for x in hw[i * stride:i * stride + hn[i]]] if ok else [],
+                                    arcs=[int(p.orig_arc[a]) for a in pa if p.dst[a] != p.S - 1],
+                                    packed_arcs=[int(a) for a in pa], status=int(hs[i])))
+        return res
+
+
+def lattice_depth(P):
+    """(sum of the arcs' lengths in frames, frames of the utterance) of a packed lattice -- their ratio is Kaldi's
+    lattice-depth, the average number of arcs that cross a frame; None for a lattice form without transition-id strings."""
+    if P.arc_len is None:
+        return None
+    return int(P.arc_len.sum()), int(state_times(P)[-1])
+
+
+def oracle_wer(batch_results, refs):
+    """(errors, reference words) over the records of WordLatticeBatch.oracle."""
+    return sum(r["errors"] for r in batch_results), sum(len(r) for r in refs)
 
 
 # ---- n-gram LM rescoring (DESIGN.md 7.14; csrc/lattice_lmrescore.hip) ----
