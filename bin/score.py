@@ -6,7 +6,7 @@ decoded in one launch (pykaldi2_amd.score), the word errors are counted on the d
 
   python bin/score.py -lat_file exp/se/lat.ark -words_txt exp/tri/graph/words.txt -ref_text data/dev/text \
       -out_dir exp/se/scoring [-min_lmwt 7 -max_lmwt 17 -word_ins_penalty 0.0,0.5,1.0] [-decode_mbr] [-ctm -frame_shift 0.03] \
-      [-oracle]
+      [-oracle] [-combine exp/tf/lat.ark[,exp/x/lat.ark,...] [-lat_weights 0.6:0.4]]
 
 Writes hyp_<LMWT>.<wip>.txt (key, then words) and result_<LMWT>_<wip> (utt_wer.py's three lines per utterance: reco:, ref:,
 `<key> err: E ref_len: L`; with -decode_mbr a fourth line `conf: <key> c1 c2 ...`) per setting and prints
@@ -19,7 +19,12 @@ hypothesis with -decode_mbr, otherwise of the best path with its confidences (--
 -oracle adds what lattice-oracle and lattice-depth report: oracle.txt (key, then the words of the lattice path closest to the
 reference), result_oracle (reco: / ref: / err: as above and `<key> ins: I del: D sub: S`) and, before the `best:` line,
 `oracle: errors=E ref_words=N WER=x.xx% ins=I del=D sub=S depth=d.dd` -- the floor under every result_* file; <UNK> arcs
-cost nothing, as <UNK> is dropped from the hypotheses; depth = arc-frames over frames of all lattices."""
+cost nothing, as <UNK> is dropped from the hypotheses; depth = arc-frames over frames of all lattices.
+-combine adds the lattices that other systems made of the same utterances (score_combine.sh: lattice-combine
+--lat-weights=w1:w2:.. | lattice-mbr-decode): every utterance of -lat_file is decoded by minimum Bayes risk over the weighted
+union of its lattices (pykaldi2_amd.score.CombinedBatch; equal weights without -lat_weights, the first weight is -lat_file's).
+A key that another archive lacks is reported and combined from the systems that have it.  The output files are those of
+-decode_mbr; -ctm and -oracle are not available with it."""
 import argparse
 import os
 import sys
@@ -64,8 +69,21 @@ def main():
     parser.add_argument("-ctm", action="store_true", help="also write ctm_<LMWT>_<wip>: word times and confidences")
     parser.add_argument("-frame_shift", default=0.01, type=float, help="seconds per frame (0.03 for a chain model)")
     parser.add_argument("-oracle", action="store_true", help="also write oracle.txt / result_oracle: the lattice oracle WER")
+    parser.add_argument("-combine", default="", help="comma-separated archives of further systems: MBR system combination")
+    parser.add_argument("-lat_weights", default="", help="w1:w2:... for -lat_file and the archives of -combine (default: equal)")
     parser.add_argument("-batch_size", default=32, type=int, help="lattices per device batch")
     args = parser.parse_args()
+    others = [x for x in args.combine.split(",") if x.strip()]
+    if others:
+        for flag in ("ctm", "oracle"):
+            if getattr(args, flag):
+                parser.error("-%s is not available with -combine" % flag)
+        args.decode_mbr = True
+    elif args.lat_weights:
+        parser.error("-lat_weights needs -combine")
+    lat_weights = [float(x) for x in args.lat_weights.split(":") if x.strip()] or None
+    if lat_weights is not None and len(lat_weights) != 1 + len(others):
+        parser.error("-lat_weights: %d weights for %d systems" % (len(lat_weights), 1 + len(others)))
 
     symbols = read_words_txt(args.words_txt)
     refs = read_text(args.ref_text)
@@ -90,9 +108,25 @@ def main():
     depth = [0, 0]                         # arc-frames, frames over all lattices
     skip = [i for i, s in symbols.items() if s in HYP_FILTER]
     seen, batch, order = set(), [], []
+    extra = [dict(kaldi_io.read_compact_lattice_ark(path)) for path in others]     # the other systems' lattices by key
 
     def flush():
         if not batch:
+            return
+        if others:
+            for path, table in zip(others, extra):
+                for key, _ in batch:
+                    if key not in table:
+                        print("no lattice for %s in %s: combined from the other systems" % (key, path))
+            cb = score.CombinedBatch([[lat for _, lat in batch]] + [[table.get(k) for k, _ in batch] for table in extra], "cuda",
+                                     names=[k for k, _ in batch], weights=lat_weights)
+            for g0 in range(0, G, score.MAX_SETTINGS):
+                for (key, _), row in zip(batch, cb.mbr(settings[g0:g0 + score.MAX_SETTINGS])):
+                    for g, rec in enumerate(row):
+                        keep = [i for i, w in enumerate(rec["words"]) if symbols.get(w, str(w)) not in HYP_FILTER]
+                        hyps[g0 + g][key] = ([symbols.get(rec["words"][i], str(rec["words"][i])) for i in keep],
+                                             [float(rec["conf"][i]) for i in keep])
+            del batch[:]
             return
         wl = score.WordLatticeBatch([lat for _, lat in batch], "cuda", names=[k for k, _ in batch])
         for g0 in range(0, G, score.MAX_SETTINGS):

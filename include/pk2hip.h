@@ -835,6 +835,41 @@ int pk2_edit_distance_batch(const int32_t* hyp, const int64_t* hyp_off, const in
                             int32_t* out, void* stream);
 
 /* ------------------------------------------------------------------ *
+ * MBR system combination (csrc/lattice_combine.hip): the reference's score_combine.sh (lattice-combine |
+ * lattice-mbr-decode) on a pk2_wordlat_create batch whose lattices are stored group by group, a group = the lattices that
+ * K systems (1 .. PK2_WORDLAT_MAX_SYSTEMS) made of one utterance.  The union's path distribution is sum_k wn_k P_k with
+ * P_k the path posterior of system k under the setting; no union lattice is built: every system runs the E-step of
+ * pk2_wordlat_mbr on its own lattice and the statistics are added with the weights, in ascending k.
+ *
+ * pk2_wordlat_set_groups (all arguments HOST arrays, uploaded once): group_off (NG + 1) the lattice range of every group;
+ * wn, log_wn (N): the normalised weight of every lattice within its group (positive, adding up to 1 per group) and its
+ * logarithm -- both are passed so that the device and a restatement use the same numbers; uvoc_off (NG + 1), uvoc: the
+ * ascending union of the group's word ids, 0 first; map: for every lattice, in batch order, one entry per word of its
+ * group's vocabulary: the lattice's LOCAL id of that word, or W (its number of local words) for a word it does not have.
+ * Everything is validated on the host (PK2_ERR_INVALID).  The row capacity of a group is
+ * min(PK2_WORDLAT_MAX_POSITIONS, 2 max depth + 1); every system's rows have that size.
+ *
+ * pk2_wordlat_combine decodes the groups first_group .. first_group + group_count - 1 under G settings; results are indexed
+ * by pair = (group - first_group) * G + g and are those of pk2_wordlat_mbr (words, conf: pairs x word_stride, word_stride >=
+ * (capacity - 1) / 2 of every group; bins: bin_stride >= capacity) plus system[pair]: the system (index within the group)
+ * whose best path was the first hypothesis -- the one minimising v_k(end) + alpha_k(end) - log wn_k, a later system on <
+ * only; -1 with status 3.  status: 0 ok, 1 not converged within max_iter E-steps, 2 capacity, 3 a system of the group has no
+ * finite alpha(end).  max_iter in 1 .. PK2_WORDLAT_COMBINE_MAX_ITER: 2 max_iter + 2 launches are enqueued, nothing is read
+ * back.  work: device memory of pk2_wordlat_combine_workspace_bytes(h, first_group, group_count, G, bins) bytes (0 for
+ * arguments the entry would refuse).  The same bits from run to run, for a group in a batch as alone, and for a group of
+ * one system as pk2_wordlat_mbr of that lattice.
+ * ------------------------------------------------------------------ */
+#define PK2_WORDLAT_MAX_SYSTEMS 8
+#define PK2_WORDLAT_COMBINE_MAX_ITER 100
+int pk2_wordlat_set_groups(void* h, int32_t NG, const int32_t* group_off, const double* wn, const double* log_wn,
+                           const int64_t* uvoc_off, const int32_t* uvoc, const int32_t* map);
+size_t pk2_wordlat_combine_workspace_bytes(const void* h, int32_t first_group, int32_t group_count, int32_t G, int32_t bins);
+int pk2_wordlat_combine(const void* h, int32_t first_group, int32_t group_count, const double* settings, int32_t G,
+                        int32_t decode_mbr, int32_t max_iter, int32_t bins, void* work, size_t work_bytes, int32_t* words,
+                        double* conf, int32_t word_stride, int32_t* nwords, double* risk, int32_t* iterations, int32_t* status,
+                        int32_t* system, int32_t* bin_n, int32_t* bin_word, double* bin_post, int32_t bin_stride, void* stream);
+
+/* ------------------------------------------------------------------ *
  * Lattice oracle (csrc/lattice_oracle.hip): Kaldi's lattice-oracle on a pk2_wordlat_create batch -- the
  * smallest edit distance (unit costs) between a reference and any path of the lattice, the path that reaches it and its
  * insertions, deletions and substitutions; one workgroup per lattice, integers only, no settings.

@@ -244,6 +244,10 @@ SIGNATURES = {
     "pk2_wordlat_mbr_times": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _sz, _vp, _vp, _i32, _vp, _vp, _vp,
                                         _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _vp]),
     "pk2_edit_distance_batch": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _vp, _vp]),
+    "pk2_wordlat_set_groups": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pk2_wordlat_combine_workspace_bytes": (_sz, [_vp, _i32, _i32, _i32, _i32]),
+    "pk2_wordlat_combine": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _sz, _vp, _vp, _i32, _vp, _vp, _vp,
+                                      _vp, _vp, _vp, _vp, _vp, _i32, _vp]),
     "pk2_wordlat_oracle_workspace_bytes": (_sz, [_vp, _i32, _i32, _vp]),
     "pk2_wordlat_oracle": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _vp,
                                      _vp, _vp]),

@@ -18,6 +18,18 @@ struct WordLat {
   // frame at which every state is reached, laid out like state_off (a device allocation of its own, null until set)
   std::vector<int32_t> h_src, h_dst;
   int32_t* d_state_time = nullptr;
+  // system combination (pk2_wordlat_set_groups, lattice_combine.hip): the lattices are stored group by
+  // group (one group = the systems' lattices of one utterance).  Host copies for validation and workspace sizes, one
+  // device allocation of its own (null until set).  est_pre: words of E-step workspace in front of every lattice, rows
+  // sized by its GROUP's capacity; grp_pre / gpe_pre: words of Gamma and state, and even row lengths, in front of every group.
+  std::vector<int32_t> h_word_ids;      // laid out like d_word_ids
+  int NG = 0;
+  std::vector<int32_t> group_off, gcap;
+  std::vector<int64_t> est_pre, grp_pre, gpe_pre;
+  void* gblob = nullptr;
+  const int32_t *d_group_off, *d_lat_group, *d_gcap, *d_uvoc, *d_map;
+  const double *d_wn, *d_logwn;
+  const int64_t *d_uvoc_off, *d_map_off, *d_est_pre, *d_grp_pre, *d_gpe_pre;
 };
 
 }  // namespace pk2

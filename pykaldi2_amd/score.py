@@ -16,6 +16,12 @@ backoff LM, what local/lmrescore_const_arpa.sh hands to Kaldi's lattice-lmrescor
 
     lats = rescore_lm(lats, [(old_lm, -1.0), (new_lm, 1.0)])    # raw lattice dicts; fold_finals(lat) for CompactLatticeWriter
     new = batch.rescore_lm(new_lm, 1.0)                         # a WordLatticeBatch again
+
+MBR system combination (csrc/lattice_combine.hip): the recipes' score_combine.sh, lattice-combine followed by
+lattice-mbr-decode, without building the union lattice.
+
+    recs = combine([lats_blstm, lats_transformer], sweep(), weights=[0.6, 0.4])   # [[record per setting] per utterance]
+    cb = CombinedBatch([sysA, sysB, sysC]); cb.mbr(sweep(), bins=3); cb.best_path(sweep())
 """
 import ctypes as C
 
@@ -585,6 +591,172 @@ class WordLatticeBatch:
                                     arcs=[int(p.orig_arc[a]) for a in pa if p.dst[a] != p.S - 1],
                                     packed_arcs=[int(a) for a in pa], status=int(hs[i])))
         return res
+
+
+# ---- MBR system combination (csrc/lattice_combine.hip) ----
+MAX_SYSTEMS = 8           # PK2_WORDLAT_MAX_SYSTEMS
+COMBINE_MAX_ITER = 100    # PK2_WORDLAT_COMBINE_MAX_ITER
+
+
+def pack_groups(groups, weights):
+    """The host side of a combination, no device needed: groups = [[PackedLattice per present system] per utterance],
+    weights = the raw weights of the same systems.  Returns dict(group_off, wn, log_wn, uvoc_off, uvoc, map, cap) in the
+    layout of pk2_wordlat_set_groups plus `vocab` (the ascending union of every group's word ids, 0 first) and `maps` (per
+    lattice: union local id -> the lattice's local id, W for a word it does not have)."""
+    group_off, wn, vocab, maps, cap = [0], [], [], [], []
+    for ps, ws in zip(groups, weights):
+        w = np.asarray(ws, np.float64).reshape(-1)
+        if not 1 <= len(ps) <= MAX_SYSTEMS or w.size != len(ps):
+            raise ValueError("a group holds 1..%d lattices with one weight each, got %d and %d" % (MAX_SYSTEMS, len(ps), w.size))
+        if not (np.isfinite(w).all() and (w > 0).all()):
+            raise ValueError("the weights must be positive and finite, got %r" % (list(ws),))
+        wn.append(w / w.sum())
+        u = np.unique(np.concatenate([p.word_ids for p in ps])).astype(np.int32)
+        vocab.append(u)
+        for p in ps:
+            k = np.minimum(np.searchsorted(p.word_ids, u), p.W - 1)
+            maps.append(np.where(p.word_ids[k] == u, k, p.W).astype(np.int32))
+        cap.append(min(MAX_POSITIONS, 2 * max(p.depth for p in ps) + 1))
+        group_off.append(group_off[-1] + len(ps))
+    wn = np.ascontiguousarray(np.concatenate(wn))
+    return dict(group_off=np.asarray(group_off, np.int32), wn=wn, log_wn=np.log(wn),
+                uvoc_off=np.concatenate([[0], np.cumsum([v.size for v in vocab])]).astype(np.int64),
+                uvoc=np.ascontiguousarray(np.concatenate(vocab)), map=np.ascontiguousarray(np.concatenate(maps)),
+                cap=cap, vocab=vocab, maps=maps)
+
+
+class CombinedBatch:
+    """The lattices that K systems made of the same utterances, for minimum Bayes risk decoding of their weighted union --
+    the recipes' score_combine.sh (lattice-combine --lat-weights | lattice-mbr-decode).  systems = K lists, one entry per
+    utterance: a lattice dict, a PackedLattice, or None where the system has no lattice for it (the weights are then
+    renormalised over the systems that have one).  No union lattice is built: DESIGN.md 7.17."""
+
+    def __init__(self, systems, device="cuda", names=None, weights=None):
+        systems = [list(s) for s in systems]
+        K = len(systems)
+        if not 1 <= K <= MAX_SYSTEMS:
+            raise ValueError("CombinedBatch: %d systems (1..%d)" % (K, MAX_SYSTEMS))
+        U = len(systems[0])
+        if U == 0 or any(len(s) != U for s in systems):
+            raise ValueError("CombinedBatch: every system needs one entry per utterance (None for a missing lattice)")
+        weights = [1.0] * K if weights is None else [float(w) for w in weights]
+        if len(weights) != K:
+            raise ValueError("CombinedBatch: %d weights for %d systems" % (len(weights), K))
+        if not all(np.isfinite(w) and w > 0 for w in weights):
+            raise ValueError("CombinedBatch: the weights must be positive and finite, got %r" % (weights,))
+        self.names = list(names) if names is not None else [str(i) for i in range(U)]
+        self.present = [[k for k in range(K) if systems[k][u] is not None] for u in range(U)]
+        for u, pr in enumerate(self.present):
+            if not pr:
+                raise ValueError("CombinedBatch: utterance %s has a lattice in no system" % self.names[u])
+        flat = [systems[k][u] for u in range(U) for k in self.present[u]]
+        flat_names = ["%s[%d]" % (self.names[u], k) for u in range(U) for k in self.present[u]]
+        self.batch = WordLatticeBatch(flat, device, names=flat_names)
+        self.device, self.weights, self.K = self.batch.device, weights, K
+        off = np.concatenate([[0], np.cumsum([len(pr) for pr in self.present])])
+        self.groups = [self.batch.packed[off[u]:off[u + 1]] for u in range(U)]
+        self.host = pack_groups(self.groups, [[weights[k] for k in pr] for pr in self.present])
+        H = self.host
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().pk2_wordlat_set_groups(self.batch._h, U, _lib.ptr(H["group_off"]), _lib.ptr(H["wn"]),
+                                                          _lib.ptr(H["log_wn"]), _lib.ptr(H["uvoc_off"]), _lib.ptr(H["uvoc"]),
+                                                          _lib.ptr(H["map"])))
+
+    def __len__(self):
+        return len(self.groups)
+
+    def _chunks(self, G, bins, workspace_mb):
+        budget = int(workspace_mb * (1 << 20))
+        L, out, first = _lib.lib(), [], 0
+        one = lambda f, k: int(L.pk2_wordlat_combine_workspace_bytes(self.batch._h, f, k, G, bins))
+        while first < len(self.groups):
+            count = 1
+            if one(first, 1) > budget:
+                raise ValueError("utterance %s (%d systems) needs %d bytes of workspace for %d settings: more than "
+                                 "workspace_mb=%d" % (self.names[first], len(self.groups[first]), one(first, 1), G, workspace_mb))
+            while first + count < len(self.groups) and one(first, count + 1) <= budget:
+                count += 1
+            out.append((first, count))
+            first += count
+        return out
+
+    def mbr(self, settings, decode_mbr=True, max_iter=10, bins=0, workspace_mb=4096, times=False):
+        """[[record per setting] per utterance]: the records of WordLatticeBatch.mbr (words, conf, risk, iterations,
+        status[, bins]) of the weighted union plus `system`: the system whose best path was the first hypothesis (-1 with
+        status 3: a system of the utterance has no path).  Launches are cut to the workspace budget by whole utterances."""
+        if times:
+            raise ValueError("CombinedBatch.mbr: word times of a combination are not built (times=True)")
+        st = _settings_array(settings)
+        if isinstance(max_iter, bool) or int(max_iter) != max_iter or not 1 <= max_iter <= COMBINE_MAX_ITER:
+            raise ValueError("max_iter must be an integer in 1..%d, got %r" % (COMBINE_MAX_ITER, max_iter))
+        if isinstance(bins, bool) or int(bins) != bins or not 0 <= bins <= MAX_BINS:
+            raise ValueError("bins must be an integer in 0..%d, got %r" % (MAX_BINS, bins))
+        bins, max_iter = int(bins), int(max_iter)
+        G, L, dev, res = st.shape[0], _lib.lib(), self.device, []
+        with torch.cuda.device(dev):
+            for first, count in self._chunks(G, bins, workspace_mb):
+                B = _Bufs(dev)
+                ws_bytes = int(L.pk2_wordlat_combine_workspace_bytes(self.batch._h, first, count, G, bins))
+                work = B(ws_bytes // 8 + 1, torch.float64)
+                caps = self.host["cap"][first:first + count]
+                stride, bstride, n = max(1, max((c - 1) // 2 for c in caps)), max(caps), count * G
+                words, nw, conf = B(n * stride, torch.int32), B(n, torch.int32), B(n * stride, torch.float64)
+                risk, iters, status, system = B(n, torch.float64), B(n, torch.int32), B(n, torch.int32), B(n, torch.int32)
+                bn = B(n, torch.int32) if bins else None
+                bw = B(n * bstride * bins, torch.int32) if bins else None
+                bv = B(n * bstride * bins, torch.float64) if bins else None
+                _lib.check(L.pk2_wordlat_combine(self.batch._h, first, count, _lib.ptr(st), G, int(bool(decode_mbr)), max_iter,
+                                                 bins, _lib.ptr(work), ws_bytes, _lib.ptr(words), _lib.ptr(conf), stride,
+                                                 _lib.ptr(nw), _lib.ptr(risk), _lib.ptr(iters), _lib.ptr(status),
+                                                 _lib.ptr(system), _lib.ptr(bn), _lib.ptr(bw), _lib.ptr(bv), bstride,
+                                                 _lib.stream_ptr(dev)))
+                hw, hn, hc, hr, hi, hs, hy = (t.cpu().numpy() for t in (words, nw, conf, risk, iters, status, system))
+                if bins:
+                    hbn, hbw, hbv = bn.cpu().numpy(), bw.cpu().numpy(), bv.cpu().numpy()
+                B.check()
+                for i in range(count):
+                    row = []
+                    for g_ in range(G):
+                        k = i * G + g_
+                        m = int(hn[k]) if hs[k] != 3 else 0
+                        r = dict(words=[int(x) for x in hw[k * stride:k * stride + m]],
+                                 conf=hc[k * stride:k * stride + m].copy(), risk=float(hr[k]), iterations=int(hi[k]),
+                                 status=int(hs[k]), system=self.present[first + i][int(hy[k])] if hy[k] >= 0 else -1)
+                        if bins:
+                            nb = int(hbn[k]) if hs[k] != 3 else 0
+                            o = k * bstride * bins
+                            r["bins"] = [[(int(hbw[o + j * bins + t]), float(hbv[o + j * bins + t])) for t in range(bins)
+                                          if hbw[o + j * bins + t] >= 0] for j in range(nb)]
+                        row.append(r)
+                    res.append(row)
+        return res
+
+    def best_path(self, settings, workspace_mb=4096):
+        """[[(words, cost, system) per setting] per utterance]: the path of the highest normalised weight in the union, on the
+        host from the systems' own best paths: the system minimising cost_k + alpha_k(end) - log wn_k (a later one on <
+        only), its words and the cost of its path in its own lattice; ([], inf, -1) where a system has no path."""
+        per, res, l = self.batch._run_post(settings, False, workspace_mb), [], 0
+        for u, pr in enumerate(self.present):
+            row = []
+            for g_ in range(len(per[0])):
+                pick, bs = -1, 0.0
+                for j in range(len(pr)):
+                    r = per[l + j][g_]
+                    if r["status"] != 0:
+                        pick = -1
+                        break
+                    s = (r["cost"] + r["alpha_end"]) - float(self.host["log_wn"][l + j])
+                    if pick < 0 or s < bs:
+                        pick, bs = j, s
+                row.append((per[l + pick][g_]["words"], per[l + pick][g_]["cost"], pr[pick]) if pick >= 0 else ([], float("inf"), -1))
+            res.append(row)
+            l += len(pr)
+        return res
+
+
+def combine(systems, settings, weights=None, device="cuda", names=None, **kw):
+    """CombinedBatch(systems, device, names, weights).mbr(settings, **kw) in one call."""
+    return CombinedBatch(systems, device, names=names, weights=weights).mbr(settings, **kw)
 
 
 def lattice_depth(P):

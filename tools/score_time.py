@@ -21,11 +21,11 @@ import mbr_ref  # noqa: E402
 from pykaldi2_amd import lattice, score, synth  # noqa: E402
 
 
-def lattices(num=8, P=120, words=200, seed=5):
+def lattices(num=8, P=120, words=200, seed=5, beam=13.0, lattice_beam=6.0):
     g = synth.decoding_graph_arcs(words, P, seed=seed, max_phones=3)
     tm = synth.transition_model_arrays(P)
     rec = lattice.MappedLatticeFasterRecognizer(lattice.TransitionModel.from_arrays(tm), g, 0.1,
-                                                lattice.LatticeFasterDecoderOptions(beam=13.0, lattice_beam=6.0))
+                                                lattice.LatticeFasterDecoderOptions(beam=beam, lattice_beam=lattice_beam))
     rng = np.random.default_rng(seed)
     lens = [int(x) for x in rng.integers(150, 400, num)]
     ll = np.zeros((num, max(lens), P), np.float32)
