@@ -6,7 +6,8 @@ decoded in one launch (pykaldi2_amd.score), the word errors are counted on the d
 
   python bin/score.py -lat_file exp/se/lat.ark -words_txt exp/tri/graph/words.txt -ref_text data/dev/text \
       -out_dir exp/se/scoring [-min_lmwt 7 -max_lmwt 17 -word_ins_penalty 0.0,0.5,1.0] [-decode_mbr] [-ctm -frame_shift 0.03] \
-      [-oracle] [-combine exp/tf/lat.ark[,exp/x/lat.ark,...] [-lat_weights 0.6:0.4]]
+      [-oracle] [-combine exp/tf/lat.ark[,exp/x/lat.ark,...] [-lat_weights 0.6:0.4]] \
+      [-ctm -word_boundary lang/phones/word_boundary.int -model exp/tri/final.mdl [-phone_ctm]]
 
 Writes hyp_<LMWT>.<wip>.txt (key, then words) and result_<LMWT>_<wip> (utt_wer.py's three lines per utterance: reco:, ref:,
 `<key> err: E ref_len: L`; with -decode_mbr a fourth line `conf: <key> c1 c2 ...`) per setting and prints
@@ -14,7 +15,7 @@ Writes hyp_<LMWT>.<wip>.txt (key, then words) and result_<LMWT>_<wip> (utt_wer.p
 <NOISE> and <SPOKEN_NOISE> are removed from the references and <UNK> from the hypotheses (score_opencss.sh).  Lattices
 without a reference are reported and skipped; a reference without a lattice counts all its words as errors.
 -ctm adds ctm_<LMWT>_<wip> per setting (score_sclite.sh's lattice-to-ctm-conf): `<key> 1 <begin> <duration> <word> <confidence>`
-in seconds, keys in archive order, the times of the lattice's own word arcs (no word-boundary alignment) -- of the MBR
+in seconds, keys in archive order, the times of the lattice's own word arcs (-word_boundary aligns them) -- of the MBR
 hypothesis with -decode_mbr, otherwise of the best path with its confidences (--decode-mbr=false).
 -oracle adds what lattice-oracle and lattice-depth report: oracle.txt (key, then the words of the lattice path closest to the
 reference), result_oracle (reco: / ref: / err: as above and `<key> ins: I del: D sub: S`) and, before the `best:` line,
@@ -24,13 +25,21 @@ cost nothing, as <UNK> is dropped from the hypotheses; depth = arc-frames over f
 --lat-weights=w1:w2:.. | lattice-mbr-decode): every utterance of -lat_file is decoded by minimum Bayes risk over the weighted
 union of its lattices (pykaldi2_amd.score.CombinedBatch; equal weights without -lat_weights, the first weight is -lat_file's).
 A key that another archive lacks is reported and combined from the systems that have it.  The output files are those of
--decode_mbr; -ctm and -oracle are not available with it."""
+-decode_mbr; -ctm and -oracle are not available with it.
+-word_boundary with -model (and -ctm, without -decode_mbr) is score_ctm.sh's lattice-1best | lattice-align-words | nbest-to-ctm:
+the ctm_* files carry every word's own begin and end, found by cutting the best path's transition-id string into phones and
+grouping them by word_boundary.int (pykaldi2_amd.score.WordLatticeBatch.align_words); the confidences stay as they are.  A
+path whose string is not a sequence of whole words keeps its arcs' times; `aligned: P of Q pairs, fallback: F` counts them.
+-phone_ctm adds phone_ctm_<LMWT>_<wip> (lattice-align-phones): `<key> 1 <begin> <duration> <phone-id>`.  An MBR or combined
+hypothesis is not a path, so -word_boundary is refused with -decode_mbr and -combine."""
 import argparse
 import os
 import sys
 
+import numpy as np
+
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from pykaldi2_amd import kaldi_io, score  # noqa: E402
+from pykaldi2_amd import kaldi_io, lattice, score  # noqa: E402
 
 REF_FILTER = ("<NOISE>", "<SPOKEN_NOISE>")
 HYP_FILTER = ("<UNK>",)
@@ -71,9 +80,23 @@ def main():
     parser.add_argument("-oracle", action="store_true", help="also write oracle.txt / result_oracle: the lattice oracle WER")
     parser.add_argument("-combine", default="", help="comma-separated archives of further systems: MBR system combination")
     parser.add_argument("-lat_weights", default="", help="w1:w2:... for -lat_file and the archives of -combine (default: equal)")
+    parser.add_argument("-word_boundary", default="", help="phones/word_boundary.int: align the CTM times to the words' own phones")
+    parser.add_argument("-model", default="", help="final.mdl (or its text form), for -word_boundary")
+    parser.add_argument("-phone_ctm", action="store_true", help="with -word_boundary: also write phone_ctm_<LMWT>_<wip>")
     parser.add_argument("-batch_size", default=32, type=int, help="lattices per device batch")
     args = parser.parse_args()
     others = [x for x in args.combine.split(",") if x.strip()]
+    if args.word_boundary:
+        if args.decode_mbr:
+            parser.error("-word_boundary is not available with -decode_mbr: an MBR hypothesis is not a path of the lattice")
+        if others:
+            parser.error("-word_boundary is not available with -combine: a combined hypothesis is not a path of a lattice")
+        if not args.model:
+            parser.error("-word_boundary needs -model (final.mdl)")
+        if not args.ctm:
+            parser.error("-word_boundary needs -ctm")
+    elif args.model or args.phone_ctm:
+        parser.error("-model and -phone_ctm need -word_boundary")
     if others:
         for flag in ("ctm", "oracle"):
             if getattr(args, flag):
@@ -85,6 +108,8 @@ def main():
     if lat_weights is not None and len(lat_weights) != 1 + len(others):
         parser.error("-lat_weights: %d weights for %d systems" % (len(lat_weights), 1 + len(others)))
 
+    boundary = score.WordBoundary.read(args.word_boundary) if args.word_boundary else None
+    trans_model = lattice.TransitionModel.read(args.model) if args.word_boundary else None
     symbols = read_words_txt(args.words_txt)
     refs = read_text(args.ref_text)
     wips = [float(x) for x in args.word_ins_penalty.split(",") if x.strip()]
@@ -104,6 +129,8 @@ def main():
 
     hyps = [dict() for _ in range(G)]      # per setting: key -> (words, confidences)
     ctm = [dict() for _ in range(G)]       # per setting: key -> CTM lines
+    phone_ctm = [dict() for _ in range(G)]  # per setting: key -> phone CTM lines (-phone_ctm)
+    aligned = [0, 0, 0]                    # -word_boundary: pairs aligned, pairs, pairs that kept their arcs' times
     oracle = {}                            # key -> record of WordLatticeBatch.oracle
     depth = [0, 0]                         # arc-frames, frames over all lattices
     skip = [i for i, s in symbols.items() if s in HYP_FILTER]
@@ -131,12 +158,24 @@ def main():
         wl = score.WordLatticeBatch([lat for _, lat in batch], "cuda", names=[k for k, _ in batch])
         for g0 in range(0, G, score.MAX_SETTINGS):
             part = settings[g0:g0 + score.MAX_SETTINGS]
-            timed = wl.mbr(part, decode_mbr=args.decode_mbr, times=True) if args.ctm else None
+            timed = wl.mbr(part, decode_mbr=args.decode_mbr, times=True) if args.ctm and boundary is None else None
             if args.decode_mbr:
                 res = timed if args.ctm else wl.mbr(part, decode_mbr=True)
             else:
                 res = [[dict(words=w, conf=None) for w, _ in row] for row in wl.best_path(part)]
-            if args.ctm:
+            if boundary is not None:
+                for (key, _), row, crow in zip(batch, wl.align_words(part, trans_model, boundary, phones=args.phone_ctm),
+                                               wl.mbr(part, decode_mbr=False)):
+                    for g, (rec, crec) in enumerate(zip(row, crow)):
+                        conf = crec["conf"] if crec["words"] == rec["words"] else np.ones(len(rec["words"]))
+                        ctm[g0 + g][key] = score.ctm_lines(key, dict(rec, conf=conf), symbols, args.frame_shift, drop=HYP_FILTER)
+                        aligned[0] += rec["status"] == 0
+                        aligned[1] += 1
+                        aligned[2] += rec["status"] == 1
+                        if args.phone_ctm:
+                            phone_ctm[g0 + g][key] = ["%s 1 %.3f %.3f %d" % (key, b * args.frame_shift, d * args.frame_shift, p)
+                                                      for p, b, d in rec["phones"].tolist()]
+            elif args.ctm:
                 for (key, _), row in zip(batch, timed):
                     for g, rec in enumerate(row):
                         ctm[g0 + g][key] = score.ctm_lines(key, rec, symbols, args.frame_shift, drop=HYP_FILTER)
@@ -195,8 +234,14 @@ def main():
             with open(os.path.join(args.out_dir, "ctm_%d_%s" % (lmwt, wip)), "w") as f:
                 for k in order:
                     f.write("".join(line + "\n" for line in ctm[g][k]))
+        if args.phone_ctm:
+            with open(os.path.join(args.out_dir, "phone_ctm_%d_%s" % (lmwt, wip)), "w") as f:
+                for k in order:
+                    f.write("".join(line + "\n" for line in phone_ctm[g][k]))
         if best is None or total < best[0]:
             best = (total, lmwt, wip)
+    if boundary is not None:
+        print("aligned: %d of %d pairs, fallback: %d" % tuple(aligned))
     if args.oracle:
         tot = dict(errors=sum(len(refs[k]) for k in missing), ins=0, dele=sum(len(refs[k]) for k in missing), sub=0)
         with open(os.path.join(args.out_dir, "oracle.txt"), "w") as fh, open(os.path.join(args.out_dir, "result_oracle"), "w") as fr:

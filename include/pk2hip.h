@@ -901,6 +901,57 @@ int pk2_wordlat_oracle(const void* h, int32_t first, int32_t count, const int32_
                        int32_t path_stride, int32_t* npath, int32_t* status, void* stream);
 
 /* ------------------------------------------------------------------ *
+ * Word-boundary alignment of best-path word times (csrc/lattice_align_words.hip): what the recipes'
+ * `lattice-1best | lattice-align-words word_boundary.int final.mdl | nbest-to-ctm` (and lattice-align-phones) print, for
+ * every (lattice, setting) pair of a pk2_wordlat_best_path call; one workgroup per pair, integers only.
+ *
+ * pk2_wordlat_set_strings gives a pk2_wordlat_create batch the transition-id string of every packed arc: tid_off (HOST
+ * int64, arc_off[N] + 1 entries, laid out like arc_off: the string of arc a of lattice n is tids[tid_off[arc_off[n] + a] ..
+ * tid_off[arc_off[n] + a + 1])) and tids (HOST int32).  Offsets that do not start at 0 or decrease and a transition-id
+ * below 1 are PK2_ERR_INVALID.  It records the largest transition-id and per lattice its frame capacity -- the longest
+ * start -> end path in frames (below 2^30), pk2_wordlat_frame_capacity copies them to a HOST int32[N] -- and uploads once;
+ * a second call is refused.
+ *
+ * pk2_wordalign_model_create holds the tables on the device: tid_tstate, tid_phone, tid_flags as pk2_split_to_phones takes
+ * them (num_tids + 1 entries, entry 0 unused; bit 0 self-loop, bit 1 transition to the final HMM state) and phone_cat
+ * (uint8, num_phones entries indexed by phone: 0 nonword, 1 begin, 2 end, 3 internal, 4 singleton, 255 no entry; a phone
+ * >= num_phones has no entry).
+ *
+ * pk2_wordlat_align_words: backpointer and bp_status are the DEVICE outputs `backpointer` and `status` of a
+ * pk2_wordlat_best_path call on the same range with the same G, in the same stream.  Per pair = (n - first) * G + g:
+ *   the path's arcs follow the back-pointers from the end state; its string is the concatenation of their strings, an
+ *   arc begins at the sum of the lengths before it.  path_times (pairs x word_stride x 2): (begin, begin + length) of the
+ *   j-th arc with a word label, the rows behind them (-1, -1).
+ *   phones (optional; pairs x phone_stride x 3: phone, begin, duration) and nphones: exactly pk2_split_to_phones on the
+ *   path's string; its *ok = 0 sets bit 1 of reason.
+ *   tokens (pairs x token_stride x 4: label, begin, duration, kind) and ntokens: with c_k the category of phone k, phone k
+ *   starts a token when k = 0, c_k is nonword, singleton or begin, or c_{k-1} is nonword, singleton or end.  kind 0: a
+ *   silence (one nonword phone); 1: a word (one singleton phone, or begin internal* end); 2: partial (anything else; bit 2
+ *   of reason).  label: the path's j-th word label on the j-th token of kind 1 or 2, otherwise 0.
+ *   word_times (pairs x word_stride x 2): (begin, end) of the j-th token of kind 1 or 2; rows behind the words (-1, -1).
+ *   status 0 when reason = 0; reason bit 4: the number of such tokens differs from the number of word labels; bit 8: a
+ *   phone without a category.  status 1 otherwise: word_times is then a copy of path_times.  status 3: bp_status != 0 or a
+ *   back-pointer that is not an arc into its state; nothing but (-1, -1) rows and zero counts is written.
+ * word_stride >= the depth of every lattice of the range; token_stride, phone_stride >= its frame capacity.  work: device
+ * memory of pk2_wordlat_align_workspace_bytes(h, first, count, G) bytes (0 for arguments the entry would refuse), per pair
+ * 3 depth + 4 capacity int32.  Null pointers (phones may be null), a batch without strings, a largest transition-id above
+ * the model's num_tids, G outside 1 .. PK2_WORDLAT_MAX_SETTINGS, a range outside the batch, short strides and a short or
+ * misaligned workspace return PK2_ERR_INVALID before the device is touched; failures of a pair go to status.  The same
+ * bits for a lattice alone, in a batch and in any split of the batch into calls.
+ * ------------------------------------------------------------------ */
+int pk2_wordlat_set_strings(void* h, const int64_t* tid_off, const int32_t* tids);
+int pk2_wordlat_frame_capacity(const void* h, int32_t* out);
+int pk2_wordalign_model_create(int32_t num_tids, const int32_t* tid_tstate, const int32_t* tid_phone, const uint8_t* tid_flags,
+                               int32_t num_phones, const uint8_t* phone_cat, void* stream, void** out);
+int pk2_wordalign_model_destroy(void* model);
+size_t pk2_wordlat_align_workspace_bytes(const void* h, int32_t first, int32_t count, int32_t G);
+int pk2_wordlat_align_words(const void* h, const void* model, int32_t first, int32_t count, int32_t G,
+                            const int32_t* backpointer, const int32_t* bp_status, void* work, size_t work_bytes,
+                            int32_t* path_times, int32_t* word_times, int32_t word_stride, int32_t* tokens, int32_t* ntokens,
+                            int32_t token_stride, int32_t* phones, int32_t* nphones, int32_t phone_stride, int32_t* status,
+                            int32_t* reason, void* stream);
+
+/* ------------------------------------------------------------------ *
  * N-gram LM rescoring of word lattices (csrc/lattice_lmrescore.hip): what the reference's
  * local/lmrescore_const_arpa.sh hands to Kaldi (lattice-lmrescore | lattice-lmrescore-const-arpa) -- the composition of a
  * packed word lattice with a deterministic backoff LM, one workgroup per lattice.

@@ -251,6 +251,13 @@ SIGNATURES = {
     "pk2_wordlat_oracle_workspace_bytes": (_sz, [_vp, _i32, _i32, _vp]),
     "pk2_wordlat_oracle": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _vp,
                                      _vp, _vp]),
+    "pk2_wordlat_set_strings": (C.c_int, [_vp, _vp, _vp]),
+    "pk2_wordlat_frame_capacity": (C.c_int, [_vp, _vp]),
+    "pk2_wordalign_model_create": (C.c_int, [_i32, _vp, _vp, _vp, _i32, _vp, _vp, C.POINTER(_vp)]),
+    "pk2_wordalign_model_destroy": (C.c_int, [_vp]),
+    "pk2_wordlat_align_workspace_bytes": (_sz, [_vp, _i32, _i32, _i32]),
+    "pk2_wordlat_align_words": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _sz, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _vp,
+                                          _i32, _vp, _vp, _vp]),
     "pk2_ngram_create": (C.c_int, [_i32, _i32] + [_vp] * 7 + [_i32, _i32, _vp, C.POINTER(_vp)]),
     "pk2_ngram_destroy": (C.c_int, [_vp]),
     "pk2_wordlat_lmrescore_workspace_bytes": (_sz, [_vp, _i32, _i32, C.c_double]),

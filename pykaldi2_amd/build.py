@@ -33,6 +33,7 @@ FILE_FLAGS = {"lattice_decode.hip": ["-ffp-contract=off"], "lattice_decode_frame
               "lattice_score.hip": ["-ffp-contract=off"], "lattice_lmrescore.hip": ["-ffp-contract=off"],
               "lattice_combine.hip": ["-ffp-contract=off"],
               "lattice_oracle.hip": ["-ffp-contract=off"],        # integers only; the flag of its siblings, for uniformity
+              "lattice_align_words.hip": ["-ffp-contract=off"],   # integers only, likewise
               # ng_chains<true> (graph in LDS) and ng_chains<false> (global memory) are one source, but under =fast the
               # backend fused `mysum += h` with the product that made h in one of them only: the beta rows of the two
               # routes differed in the last bit, and so did a small utterance's posteriors with and without a large

@@ -458,6 +458,7 @@ extern "C" int pk2_wordlat_destroy(void* handle) {
   if (!h) return PK2_OK;
   if (h->d_state_time) (void)hipFree(h->d_state_time);
   if (h->gblob) (void)hipFree(h->gblob);
+  if (h->sblob) (void)hipFree(h->sblob);
   if (h->blob) PK2_HIP(hipFree(h->blob));
   delete h;
   return PK2_OK;

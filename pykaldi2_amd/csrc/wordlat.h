@@ -18,6 +18,15 @@ struct WordLat {
   // frame at which every state is reached, laid out like state_off (a device allocation of its own, null until set)
   std::vector<int32_t> h_src, h_dst;
   int32_t* d_state_time = nullptr;
+  // word-boundary alignment (pk2_wordlat_set_strings, lattice_align_words.hip): the transition-id string of
+  // every packed arc (offsets laid out like arc_off), per lattice the longest start -> end path in frames and the words of
+  // alignment workspace in front of it; one device allocation of its own (null until set)
+  std::vector<int32_t> fcap;
+  std::vector<int64_t> align_pre;
+  int32_t max_tid = 0;
+  void* sblob = nullptr;
+  const int64_t *d_tid_off = nullptr, *d_align_pre = nullptr;
+  const int32_t *d_tids = nullptr, *d_fcap = nullptr;
   // system combination (pk2_wordlat_set_groups, lattice_combine.hip): the lattices are stored group by
   // group (one group = the systems' lattices of one utterance).  Host copies for validation and workspace sizes, one
   // device allocation of its own (null until set).  est_pre: words of E-step workspace in front of every lattice, rows

@@ -10,6 +10,8 @@ lattice-mbr-decode, utt_wer.py).  Packing is numpy on the host; the kernels are 
     lines = ctm_lines("utt1", rec, symbols, frame_shift=0.03)   # "<key> 1 <begin> <duration> <word> <confidence>"
     rec = batch.oracle(refs, skip_words=(unk_id,))[0]          # lattice-oracle: errors, ins, dele, sub, words, arcs (7.16)
     arc_frames, frames = lattice_depth(batch.packed[0])         # lattice-depth = arc_frames / frames
+    rec = batch.align_words(sweep(), trans_model, WordBoundary.read("phones/word_boundary.int"))[0][0]   # DESIGN.md 7.18:
+    #   words, cost, times (int32: every word's own begin and end), silences, path_times, status, reason[, phones]
 
 N-gram LM rescoring (csrc/lattice_lmrescore.hip, pykaldi2_amd.ngram): the composition of the lattices with a
 backoff LM, what local/lmrescore_const_arpa.sh hands to Kaldi's lattice-lmrescore and lattice-lmrescore-const-arpa.
@@ -33,6 +35,7 @@ from . import _lib
 MAX_SETTINGS = 64        # PK2_WORDLAT_MAX_SETTINGS
 MAX_POSITIONS = 1023     # PK2_WORDLAT_MAX_POSITIONS
 MAX_BINS = 8             # PK2_WORDLAT_MAX_BINS
+ALIGN_CHUNK = 256        # kWaThreads: frames (and phones) the word-alignment kernel takes per pass
 LMRESCORE_SORT_LDS = 4096  # PK2_LMRESCORE_SORT_LDS: candidate arcs of one state the rescoring kernel sorts in LDS
 _DEBUG_GUARD = False     # tests: NaN / sentinel poisoned buffers with checked guard padding around every device buffer
 _GUARD = 64
@@ -174,11 +177,13 @@ def fix_word_times(times):
     return t
 
 
-def ctm_lines(key, rec, symbols, frame_shift=0.01, channel="1", drop=("<UNK>",)):
+def ctm_lines(key, rec, symbols, frame_shift=0.01, channel="1", drop=("<UNK>",), times_key="times"):
     """The CTM lines of a record of mbr(times=True): "<key> <channel> <begin> <duration> <word> <confidence>", seconds with
     three decimals from fix_word_times(rec["times"]); symbols: word id -> symbol.  Symbols in `drop` and words without a
-    time are left out."""
-    t = fix_word_times(rec["times"])
+    time are left out.  times_key names the record's entry to print; integer times (align_words: every word's own begin
+    and end, which cannot overlap) are printed as they are, without fix_word_times."""
+    t = np.asarray(rec[times_key])
+    t = t.reshape(-1, 2).astype(np.float64) if np.issubdtype(t.dtype, np.integer) else fix_word_times(t)
     out = []
     for i, w in enumerate(rec["words"]):
         sym = symbols.get(w, str(w))
@@ -187,6 +192,76 @@ def ctm_lines(key, rec, symbols, frame_shift=0.01, channel="1", drop=("<UNK>",))
         out.append("%s %s %.3f %.3f %s %.4f" % (key, channel, t[i, 0] * frame_shift, (t[i, 1] - t[i, 0]) * frame_shift, sym,
                                                 float(rec["conf"][i])))
     return out
+
+
+WORD_BOUNDARY_CATEGORIES = {"nonword": 0, "begin": 1, "end": 2, "internal": 3, "singleton": 4}
+
+
+class WordBoundary:
+    """Kaldi's phones/word_boundary.int as a table: .table[phone] (uint8) = 0 nonword, 1 begin, 2 end, 3 internal,
+    4 singleton, 255 for a phone without an entry.  WordBoundary({phone: category}) or WordBoundary.read(path)."""
+
+    def __init__(self, mapping):
+        items = [(int(p), c) for p, c in dict(mapping).items()]
+        for p, c in items:
+            if p < 0 or (c not in WORD_BOUNDARY_CATEGORIES and c not in WORD_BOUNDARY_CATEGORIES.values()):
+                raise ValueError("word boundary: phone %r with category %r" % (p, c))
+        self.table = np.full(max([p for p, _ in items] + [0]) + 1, 255, np.uint8)
+        for p, c in items:
+            self.table[p] = WORD_BOUNDARY_CATEGORIES.get(c, c)
+
+    @classmethod
+    def read(cls, path):
+        mapping = {}
+        with open(path) as f:
+            for n, line in enumerate(f, start=1):
+                parts = line.split()
+                if not parts:
+                    continue
+                ok = len(parts) == 2 and parts[0].isdigit() and parts[1] in WORD_BOUNDARY_CATEGORIES
+                if not ok or int(parts[0]) in mapping:
+                    raise ValueError("%s, line %d: expected `<phone-id> nonword|begin|end|internal|singleton`, one line per "
+                                     "phone, got %r" % (path, n, line.rstrip("\n")))
+                mapping[int(parts[0])] = parts[1]
+        return cls(mapping)
+
+    def category(self, phone):
+        return int(self.table[phone]) if 0 <= phone < self.table.size else 255
+
+
+def packed_strings(P, lat, name="?"):
+    """(offsets int64 (P.A + 1), transition-ids int32) of the packed arcs of P, which was packed from the dict `lat`: the
+    arcs that packing made of the finals (orig_arc >= number of arcs, in state order) carry the final weight's string; the
+    one-tid form counts as strings of length 0 or 1.  ValueError for a lattice form without strings."""
+    if _string_lengths(lat) is None:
+        raise ValueError("lattice %s: no transition-id strings (tid_off / tid / archive strings), so no times" % name)
+    astr, fstr = _strings(lat)
+    fin = np.flatnonzero(np.isfinite(_lattice_arcs(lat, name)[7]))
+    both = astr + [fstr[s] for s in fin]
+    strs = [both[k] for k in P.orig_arc]
+    off = np.concatenate([[0], np.cumsum([len(x) for x in strs])]).astype(np.int64)
+    return off, np.asarray([t for x in strs for t in x], np.int32).reshape(-1)
+
+
+class _AlignModel:
+    """The device tables of pk2_wordalign_model_create for one (transition model, word boundary) pair."""
+
+    def __init__(self, trans_model, word_boundary, device):
+        if trans_model.tid2tstate is None or trans_model.tid_flags is None:
+            raise ValueError("the transition model carries no topology (read it from final.mdl)")
+        self.refs = (trans_model, word_boundary)
+        h = C.c_void_p()
+        cat = np.ascontiguousarray(word_boundary.table, np.uint8)
+        with torch.cuda.device(device):
+            _lib.check(_lib.lib().pk2_wordalign_model_create(
+                trans_model.num_transition_ids(), _lib.ptr(trans_model.tid2tstate), _lib.ptr(trans_model.tid2phone),
+                _lib.ptr(trans_model.tid_flags), cat.size, _lib.ptr(cat), _lib.stream_ptr(device), C.byref(h)))
+        self.h = h
+
+    def __del__(self):
+        h, self.h = getattr(self, "h", None), None
+        if h:
+            _lib.lib().pk2_wordalign_model_destroy(h)
 
 
 def _reach(n, start, frm, to):
@@ -346,6 +421,8 @@ class WordLatticeBatch:
         self._h = h
         self.state_time = None      # per lattice, once mbr(times=True) has asked for them
         self._labels = {}           # oracle(): the device arc labels per set of skipped words
+        self.strings = self.frame_cap = None    # per lattice, once align_words has asked for them
+        self._align_models = {}
 
     def _upload_times(self):
         """State times of every lattice (state_times; its ValueError surfaces here), uploaded once."""
@@ -508,6 +585,107 @@ class WordLatticeBatch:
                             r["times"] = htm[k * stride:k * stride + m].copy()
                             path = hpt[k * pstride:(k + 1) * pstride]
                             r["path_times"] = path[:int((path[:, 0] >= 0).sum())].copy()
+                        row.append(r)
+                    res.append(row)
+        return res
+
+    # ---- word-boundary alignment (csrc/lattice_align_words.hip) ----
+    def _upload_strings(self):
+        """The transition-id strings of the packed arcs (packed_strings; its ValueError surfaces here), built and uploaded
+        the first time an alignment is asked for."""
+        if self.frame_cap is not None:
+            return
+        offs, tids = [], []
+        for i, p in enumerate(self.packed):
+            if self.source[i] is None:
+                raise ValueError("lattice %s: no transition-id strings (tid_off / tid / archive strings), so no times"
+                                 % self.names[i])
+            o, t = packed_strings(p, self.source[i], self.names[i])
+            offs.append(o)
+            tids.append(t)
+        base = np.concatenate([[0], np.cumsum([t.size for t in tids])]).astype(np.int64)
+        off = np.ascontiguousarray(np.concatenate([o[:-1] + base[i] for i, o in enumerate(offs)] + [base[-1:]]).astype(np.int64))
+        flat = np.ascontiguousarray(np.concatenate(tids + [np.zeros(1, np.int32)]).astype(np.int32))
+        cap = np.zeros(len(self.packed), np.int32)
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.lib().pk2_wordlat_set_strings(self._h, _lib.ptr(off), _lib.ptr(flat)))
+            _lib.check(_lib.lib().pk2_wordlat_frame_capacity(self._h, _lib.ptr(cap)))
+        self.strings = [(o, t) for o, t in zip(offs, tids)]
+        self.frame_cap = [int(c) for c in cap]
+
+    def _align_chunks(self, G, workspace_mb):
+        budget = int(workspace_mb * (1 << 20))
+        L, out, first = _lib.lib(), [], 0
+        one = lambda f, k: int(L.pk2_wordlat_workspace_bytes(self._h, f, k, G, -1)) + \
+            int(L.pk2_wordlat_align_workspace_bytes(self._h, f, k, G))
+        while first < len(self.packed):
+            count = 1
+            if one(first, 1) > budget:
+                raise ValueError("lattice %d needs %d bytes of workspace for %d settings: more than workspace_mb=%d"
+                                 % (first, one(first, 1), G, workspace_mb))
+            while first + count < len(self.packed) and one(first, count + 1) <= budget:
+                count += 1
+            out.append((first, count))
+            first += count
+        return out
+
+    def align_words(self, settings, trans_model, word_boundary, phones=False, workspace_mb=4096):
+        """[[record per setting] per lattice]: the best path with every word's own begin and end frame, what the recipes'
+        lattice-1best | lattice-align-words | nbest-to-ctm print.  record = dict(words, cost, times (int32
+        (m, 2)), silences (int32 (k, 2)), path_times (int32 (m, 2): the word arcs' own times), status, reason[, phones
+        (int32 (n, 3): phone, begin, duration)]).  status 0: aligned; 1: the path's string is not a sequence of whole words
+        with one label each (reason: 1 SplitToPhones not ok, 2 a partial word, 4 words and labels differ in number, 8 a phone
+        without a category): times = path_times, silences empty; 3: no best path, everything empty.  trans_model must carry
+        the topology (TransitionModel.read / from_topology), word_boundary is a WordBoundary."""
+        st = _settings_array(settings)
+        key = (id(trans_model), id(word_boundary))
+        if key not in self._align_models:
+            self._align_models[key] = _AlignModel(trans_model, word_boundary, self.device)
+        model = self._align_models[key]
+        self._upload_strings()
+        G, L, dev, H, res = st.shape[0], _lib.lib(), self.device, self._host, []
+        with torch.cuda.device(dev):
+            for first, count in self._align_chunks(G, workspace_mb):
+                B = _Bufs(dev)
+                ws_bytes = int(L.pk2_wordlat_workspace_bytes(self._h, first, count, G, -1))
+                aw_bytes = int(L.pk2_wordlat_align_workspace_bytes(self._h, first, count, G))
+                work, awork = B(ws_bytes // 8 + 1, torch.float64), B(aw_bytes // 8 + 1, torch.float64)
+                ps = self.packed[first:first + count]
+                stride = max(1, max(p.depth for p in ps))
+                fstride = max(1, max(self.frame_cap[first:first + count]))
+                nS = int(H["state_off"][first + count] - H["state_off"][first])
+                n = count * G
+                words, nw = B(n * stride, torch.int32), B(n, torch.int32)
+                cost, aend, bstat = B(n, torch.float64), B(n, torch.float64), B(n, torch.int32)
+                bp = B(G * nS, torch.int32)
+                pt, wt = B(n * stride * 2, torch.int32), B(n * stride * 2, torch.int32)
+                tok, ntok = B(n * fstride * 4, torch.int32), B(n, torch.int32)
+                pho = B(n * fstride * 3, torch.int32) if phones else None
+                nph, status, reason = B(n, torch.int32), B(n, torch.int32), B(n, torch.int32)
+                _lib.check(L.pk2_wordlat_best_path(self._h, first, count, _lib.ptr(st), G, _lib.ptr(work), ws_bytes,
+                                                   _lib.ptr(words), stride, _lib.ptr(nw), _lib.ptr(cost), _lib.ptr(aend),
+                                                   None, _lib.ptr(bp), _lib.ptr(bstat), _lib.stream_ptr(dev)))
+                _lib.check(L.pk2_wordlat_align_words(self._h, model.h, first, count, G, _lib.ptr(bp), _lib.ptr(bstat),
+                                                     _lib.ptr(awork), aw_bytes, _lib.ptr(pt), _lib.ptr(wt), stride, _lib.ptr(tok),
+                                                     _lib.ptr(ntok), fstride, _lib.ptr(pho), _lib.ptr(nph), fstride,
+                                                     _lib.ptr(status), _lib.ptr(reason), _lib.stream_ptr(dev)))
+                hw, hn, hc, hs, hr, hnt, hnp = (t.cpu().numpy() for t in (words, nw, cost, status, reason, ntok, nph))
+                hpt, hwt = pt.cpu().numpy().reshape(n, stride, 2), wt.cpu().numpy().reshape(n, stride, 2)
+                htok = tok.cpu().numpy().reshape(n, fstride, 4)
+                hpho = pho.cpu().numpy().reshape(n, fstride, 3) if phones else None
+                B.check()
+                for i in range(count):
+                    row = []
+                    for g_ in range(G):
+                        k = i * G + g_
+                        m = int(hn[k]) if hs[k] != 3 else 0
+                        r = dict(words=[int(x) for x in hw[k * stride:k * stride + m]], cost=float(hc[k]),
+                                 times=hwt[k, :m].copy(), path_times=hpt[k, :m].copy(), status=int(hs[k]), reason=int(hr[k]))
+                        t = htok[k, :int(hnt[k])] if hs[k] == 0 else htok[k, :0]
+                        sil = t[t[:, 3] == 0]
+                        r["silences"] = np.stack([sil[:, 1], sil[:, 1] + sil[:, 2]], axis=1).astype(np.int32)
+                        if phones:
+                            r["phones"] = hpho[k, :int(hnp[k]) if hs[k] != 3 else 0].copy()
                         row.append(r)
                     res.append(row)
         return res

@@ -229,6 +229,16 @@ def transition_model_arrays(num_pdfs):
     return dict(tid2pdf=tid2pdf, tid2phone=tid2phone, num_phones=num_phones, silence_phones=[1])
 
 
+def transition_model_topology(num_pdfs):
+    """The model of transition_model_arrays with its topology (lattice.TransitionModel.from_topology: the same transition-ids,
+    plus transition-states and self-loop / final flags), for splitting an alignment into phones."""
+    from .lattice import TransitionModel
+    num_phones = num_pdfs // 3
+    entry = [(s, s, [s, s + 1]) for s in range(3)] + [(-1, -1, [])]
+    tuples = [(p, s, 3 * (p - 1) + s, 3 * (p - 1) + s) for p in range(1, num_phones + 1) for s in range(3)]
+    return TransitionModel.from_topology({p: 0 for p in range(1, num_phones + 1)}, [entry], tuples)
+
+
 def decoding_graph_arcs(num_words=2000, num_pdfs=5768, seed=0, max_phones=5):
     """Synthetic HCLG-shaped decoding graph: a word loop over `num_words` pronunciations of 2..max_phones
     phones, every phone 3 HMM states with a self-loop and a forward arc (ilabels = transition-ids of
