@@ -41,6 +41,11 @@ def parse_config(argv=None, arch="blstm"):
         parser.add_argument("-ff_size", default=2048, type=int, help="the size of feed-forward layer")
         parser.add_argument("-nlayers", default=6, type=int, help="the number of layers")
         parser.add_argument("-look_ahead", default=-1, type=int, help="the number of frames to look ahead")
+        parser.add_argument("-left_context", default=-1, type=int, help="the number of frames to look back (-1: all)")
+        parser.add_argument("-chunk", default=1, type=int,
+                            help="chunk-wise attention: a frame sees its chunk, -left_context frames before and -look_ahead after it")
+        parser.add_argument("-band", action="store_true",
+                            help="describe the context as a band (the banded attention kernels) even for -look_ahead alone")
     else:
         parser.add_argument("-data_path", default='', type=str, help="path of data files")
     parser.add_argument("-seed_model", default='', help="the seed nerual network model")
@@ -107,7 +112,7 @@ def main(arch="blstm"):
     if arch == "transformer":     # reference bin/train_transformer_se.py:128
         model = transformer.TransformerAM(mc["feat_dim"], args.dim_model, args.nheads, args.ff_size, args.nlayers,
                                           args.dropout, P).to(dev)
-        forward = lambda m, x, frames: transformer.padded_forward(m, x, frames, args.look_ahead)   # noqa: E731
+        forward = lambda m, x, frames: transformer.padded_forward(m, x, frames, args.look_ahead, args.left_context, args.chunk, args.band)   # noqa: E731
     else:
         model = lstm.LSTMAM(mc["feat_dim"], P, mc["hidden_size"], mc["num_layers"], mc["dropout"], True).to(dev)
     if args.seed_model:

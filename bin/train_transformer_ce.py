@@ -47,6 +47,11 @@ def parse_config(argv=None):
     parser.add_argument("-ff_size", default=2048, type=int, help="the size of feed-forward layer")
     parser.add_argument("-nlayers", default=6, type=int, help="the number of layers")
     parser.add_argument("-look_ahead", default=-1, type=int, help="the number of frames to look ahead")
+    parser.add_argument("-left_context", default=-1, type=int, help="the number of frames to look back (-1: all)")
+    parser.add_argument("-chunk", default=1, type=int,
+                        help="chunk-wise attention: a frame sees its chunk, -left_context frames before and -look_ahead after it")
+    parser.add_argument("-band", action="store_true",
+                        help="describe the context as a band (the banded attention kernels) even for -look_ahead alone")
     parser.add_argument('-print_freq', default=100, type=int, metavar='N', help='print frequency (default: 100)')
     parser.add_argument('-hvd', default=True, type=bool, help="whether to use horovod for training")
     parser.add_argument('-synthetic', action='store_true', help='seeded synthetic utterances')
@@ -139,7 +144,7 @@ def run_train_epoch(model, optimizer, criterion, source, fb, epoch, config, args
         if spec is not None:
             feats = spec(feats, row_off, frames)
         x = fb.pad_roll_subsample(feats, row_off, frames, shift=0, subsample=1, time_major=True)     # [Tmax, N, 80]
-        prediction = transformer.padded_forward(model, x, frames, args.look_ahead)                    # [N, Tmax, P]
+        prediction = transformer.padded_forward(model, x, frames, args.look_ahead, args.left_context, args.chunk, args.band)                    # [N, Tmax, P]
         N, Tmax = prediction.shape[0], prediction.shape[1]
         y = np.full((N, Tmax), -100, np.int64)          # SeqDataloader pads the labels with -100 (data/dataloader.py:94-136)
         for n, lab in enumerate(batch["y"]):

@@ -1227,6 +1227,21 @@ int pk2_attention_bwd(const float* qkv, const float* ctx, const float* dctx, con
 int pk2_attention_bwd_part(int32_t parts, const float* qkv, const float* ctx, const float* dctx, const float* lse, int32_t T,
                            int32_t B, int32_t H, int32_t head_dim, float scale, const float* src_mask,
                            const uint8_t* key_padding, float dropout_p, uint64_t seed, float* dqkv, float* dsum, void* stream);
+/* The same attention over a context band instead of an additive [T][T] mask (csrc/attention_band.hip): with
+ * c(q) = q / chunk * chunk, query q sees key k iff k < T, key k is not padded, (left < 0 or k >= c(q) - left) and
+ * (right < 0 or k <= c(q) + chunk - 1 + right).  chunk = 1 is a sliding window, (-1, n, 1) the look-ahead mask
+ * tril(diagonal = n), (-1, -1, 1) no restriction, chunk > 1 chunk-wise attention: a query sees its own chunk, `left` frames
+ * before it and `right` frames after it.  Everything else is pk2_attention_fwd / _bwd's contract: layouts, lse (-inf, and
+ * ctx = 0, for a query with no visible key), the dropout draws of the dense form for the same seed, backward by
+ * recomputation, every element of dqkv written, dsum scratch, head sizes 64 and 128.  Only the (query tile, key tile)
+ * pairs the band reaches are multiplied, and no mask is read.  PK2_ERR_INVALID for left or right < -1, chunk < 1, a null
+ * pointer or another head size. */
+int pk2_attention_band_fwd(const float* qkv, int32_t T, int32_t B, int32_t H, int32_t head_dim, float scale,
+                           int32_t left, int32_t right, int32_t chunk, const uint8_t* key_padding,
+                           float dropout_p, uint64_t seed, float* ctx, float* lse, void* stream);
+int pk2_attention_band_bwd(const float* qkv, const float* ctx, const float* dctx, const float* lse, int32_t T, int32_t B,
+                           int32_t H, int32_t head_dim, float scale, int32_t left, int32_t right, int32_t chunk,
+                           const uint8_t* key_padding, float dropout_p, uint64_t seed, float* dqkv, float* dsum, void* stream);
 int pk2_relu_fwd(float* x, int64_t n, void* stream);                 /* in place */
 int pk2_relu_bwd(const float* y, float* dy, int64_t n, void* stream); /* dy <- dy * (y > 0) */
 int pk2_add_inplace(float* a, const float* b, int64_t n, void* stream);

@@ -38,7 +38,9 @@ FILE_FLAGS = {"lattice_decode.hip": ["-ffp-contract=off"], "lattice_decode_frame
               # backend fused `mysum += h` with the product that made h in one of them only: the beta rows of the two
               # routes differed in the last bit, and so did a small utterance's posteriors with and without a large
               # neighbour in its batch.  =on fuses inside a statement only, the same way in every instantiation.
-              "chain_num_graph.hip": ["-ffp-contract=on"]}
+              "chain_num_graph.hip": ["-ffp-contract=on"],
+              # no packed-f32 arithmetic (v_pk_fma_f32 and its kin) in the banded attention kernels: plain f32 VALU only
+              "attention_band.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 # experiment builds: PK2_FILE_FLAGS="gemm_f32.hip:-mllvm,-align-loops=64;..." adds flags to single sources
 for _spec in os.environ.get("PK2_FILE_FLAGS", "").split(";"):
     if ":" in _spec:

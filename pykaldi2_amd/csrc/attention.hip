@@ -393,7 +393,7 @@ __global__ void __launch_bounds__(64 * kAWaves) attn_bwd_dkv_kernel(AttnParams p
 
 using namespace pk2;
 
-static int attn_fill(AttnParams* p, int32_t T, int32_t B, int32_t H, int32_t head_dim, float scale, const float* src_mask,
+int pk2::attn_fill(AttnParams* p, int32_t T, int32_t B, int32_t H, int32_t head_dim, float scale, const float* src_mask,
                      const uint8_t* key_pad, float dropout_p, uint64_t seed) {
   PK2_REQUIRE(T > 0 && B > 0 && H > 0 && (int64_t)B * H <= 65535, "attention: bad sizes");
   PK2_REQUIRE(head_dim == kAD || head_dim == 128, "attention: the fused kernels serve head sizes %d and 128 (got %d)", kAD, head_dim);

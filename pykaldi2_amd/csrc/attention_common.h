@@ -21,6 +21,10 @@ struct AttnParams {
   uint32_t keep_threshold; float keep_scale; uint64_t seed; int dropout;
 };
 
+// The checks and the fields every attention entry shares: sizes, head size, dropout, PK2_ATTN_SKIP_PAD (attention.hip)
+int attn_fill(AttnParams* p, int32_t T, int32_t B, int32_t H, int32_t head_dim, float scale, const float* src_mask,
+              const uint8_t* key_pad, float dropout_p, uint64_t seed);
+
 // head size 128 (attention128.hip): the launches behind pk2_attention_fwd / pk2_attention_bwd, same grid as head size 64
 void attn128_launch_fwd(const AttnParams& p, hipStream_t stream);
 void attn128_launch_bwd(const AttnParams& p, int parts, hipStream_t stream);      // parts: bit 0 dQ, bit 1 dK / dV

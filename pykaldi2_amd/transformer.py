@@ -16,6 +16,7 @@ softmax, LayerNorm(+residual), ReLU, counter-based dropout -- all HIP kernels of
 the fused kernel of csrc/attention.hip (head size 64, the reference model's 512 / 8) or csrc/attention128.hip (head size
 128, the command lines' default 512 / 4): scores never reach HBM, backward by recomputation.  `attention_is_fused` says
 which head sizes take it (PK2_ATTN_FUSED); every other one takes the batched-GEMM form with the scores in HBM.
+A `BandMask` as src_mask (left context, look-ahead, chunk) takes the banded kernels of csrc/attention_band.hip instead.
 """
 import copy
 import math
@@ -116,6 +117,33 @@ def attention_is_fused(head_dim):
     return head_dim in (FUSED_HEAD_SIZES if mode == "all" else DEFAULT_FUSED_HEAD_SIZES)
 
 
+class BandMask:
+    """Which keys a query may see, as three integers instead of a [T, T] mask: with c(q) = q // chunk * chunk, query q
+    sees key k iff (left < 0 or k >= c(q) - left) and (right < 0 or k <= c(q) + chunk - 1 + right).  chunk = 1 is a
+    sliding window, BandMask(-1, n) the look-ahead mask tril(diagonal=n), chunk > 1 chunk-wise attention (a query sees
+    its own chunk, `left` frames before it and `right` frames after it).  As TransformerAM's src_mask it selects the
+    banded attention kernels (csrc/attention_band.hip), which multiply only the tiles the band reaches and read no mask."""
+
+    def __init__(self, left=-1, right=-1, chunk=1):
+        if left < -1 or right < -1 or chunk < 1:
+            raise ValueError("BandMask: left >= -1, right >= -1, chunk >= 1 (got %r, %r, %r)" % (left, right, chunk))
+        self.left, self.right, self.chunk = int(left), int(right), int(chunk)
+
+    def __repr__(self):
+        return "BandMask(left=%d, right=%d, chunk=%d)" % (self.left, self.right, self.chunk)
+
+    def dense(self, T):
+        """The equivalent additive mask: [T, T] float32, 0 where query (row) sees key (column), -inf elsewhere."""
+        c = (torch.arange(T) // self.chunk * self.chunk)[:, None]
+        k = torch.arange(T)[None, :]
+        seen = torch.ones(T, T, dtype=torch.bool)
+        if self.left >= 0:
+            seen &= k >= c - self.left
+        if self.right >= 0:
+            seen &= k <= c + self.chunk - 1 + self.right
+        return torch.zeros(T, T).masked_fill(~seen, float("-inf"))
+
+
 def _attention_bwd_unfused(L, sp, new, s, qkv, dcx, dqkv, T, B, C, H, d, drop):
     """Batched-GEMM form: dP = dctx V^T ; dV = Pd^T dctx ; dS = softmax'(P, dP) ; dQ = a dS K ; dK = a dS^T Q."""
     dP = new(B * H, T, T)
@@ -148,6 +176,8 @@ class _TransformerFunction(torch.autograd.Function):
         drop = m.dropout if m.training else 0.0
         fused = attention_is_fused(d)
         ctx.fused, ctx.masks = fused, (src_mask, key_pad)
+        band = src_mask if isinstance(src_mask, BandMask) else None      # (TransformerAM.forward passes one to the fused form only)
+        assert band is None or fused
         fuse_relu, fuse_conv = _fuse_relu(), _fuse_conv()
 
         def new_padded(rows, cols):
@@ -177,7 +207,12 @@ class _TransformerFunction(torch.autograd.Function):
             s["seed_attn"] = _seed() if drop > 0 else None
             cx = new(R, C)
             Pm = Pd = lse = None
-            if fused:
+            if fused and band is not None:
+                lse = new(B * H, T)
+                _lib.check(L.pk2_attention_band_fwd(_p(qkv), T, B, H, d, 1.0 / math.sqrt(d), band.left, band.right, band.chunk,
+                                                    _p(key_pad) if key_pad is not None else None, float(drop),
+                                                    s["seed_attn"] or 0, _p(cx), _p(lse), sp))
+            elif fused:
                 lse = new(B * H, T)
                 _lib.check(L.pk2_attention_fwd(_p(qkv), T, B, H, d, 1.0 / math.sqrt(d),
                                                _p(src_mask) if src_mask is not None else None,
@@ -384,7 +419,13 @@ class _TransformerFunction(torch.autograd.Function):
             # attention: dP = dctx V^T ; dV = Pd^T dctx ; dS = softmax'(P, dP) ; dQ = a dS K ; dK = a dS^T Q
             qkv = s["qkv"]
             dqkv = new(R, 3 * C)
-            if ctx.fused:
+            if ctx.fused and isinstance(ctx.masks[0], BandMask):
+                band, key_pad = ctx.masks
+                _lib.check(L.pk2_attention_band_bwd(_p(qkv), _p(s["cx"]), _p(dcx), _p(s["lse"]), T, B, H, d, 1.0 / math.sqrt(d),
+                                                    band.left, band.right, band.chunk,
+                                                    _p(key_pad) if key_pad is not None else None, float(drop),
+                                                    s["seed_attn"] or 0, _p(dqkv), _p(new(B * H, T)), sp))
+            elif ctx.fused:
                 src_mask, key_pad = ctx.masks
                 _lib.check(L.pk2_attention_bwd(_p(qkv), _p(s["cx"]), _p(dcx), _p(s["lse"]), T, B, H, d, 1.0 / math.sqrt(d),
                                                _p(src_mask) if src_mask is not None else None,
@@ -493,8 +534,9 @@ class TransformerAM(nn.Module):
         return {n: gflat[o:o + c].view(params[n].shape) for n, (o, c) in self._layout.items()}
 
     def forward(self, data, src_mask=None, src_key_padding_mask=None):
-        """data [T,B,D]; src_mask [T,T] additive float (-inf = blocked) or None; src_key_padding_mask [B,T] bool,
-        True = padding (reference bin/train_transformer_se.py:245-257)."""
+        """data [T,B,D]; src_mask [T,T] additive float (-inf = blocked), a BandMask or None; src_key_padding_mask [B,T]
+        bool, True = padding (reference bin/train_transformer_se.py:245-257).  A BandMask runs the banded kernels where the
+        fused kernels would have run a dense mask (attention_is_fused), and as its dense(T) mask everywhere else."""
         _lib.require_gpu()
         assert data.is_cuda and data.dtype == torch.float32 and data.dim() == 3
         self._ensure_flat()
@@ -502,23 +544,32 @@ class TransformerAM(nn.Module):
         if src_key_padding_mask is not None:
             kp = _mask_to_device(src_key_padding_mask, data.device, torch.uint8)
         sm = None
-        if src_mask is not None:
+        if isinstance(src_mask, BandMask):
+            if attention_is_fused(self.dim_model // self.nheads):
+                sm = src_mask
+            else:
+                sm = _mask_to_device(src_mask.dense(data.shape[0]), data.device, torch.float32)
+        elif src_mask is not None:
             sm = _mask_to_device(src_mask, data.device, torch.float32)
         params = [q for q, _ in self._plist]     # named_parameters() order (_ensure_flat)
         return _TransformerFunction.apply(data, self, sm, kp, *params)
 
 
-def padded_forward(model, x, frames, look_ahead=-1):
+def padded_forward(model, x, frames, look_ahead=-1, left_context=-1, chunk=1, band=False):
     """The masks of reference bin/train_transformer_se.py:242-257 (= train_transformer_ce.py:188-201) around one
     forward: x [T, B, D] time-major, zero-padded; frames[b] valid frames of utterance b.  key_padding_mask is True
-    on padding; with look_ahead > -1 frame t may attend to frames <= t + look_ahead.  Returns [B, T, P] (a
-    transposed view of the model's [T, B, P] output)."""
+    on padding; with look_ahead > -1 frame t may attend to frames <= t + look_ahead.  left_context > -1, chunk > 1 or
+    band=True describe the context as BandMask(left_context, look_ahead, chunk) instead of a [T, T] mask (the banded
+    kernels); with none of them the dense mask is built as before.  Returns [B, T, P] (a transposed view of the model's
+    [T, B, P] output)."""
     T, B = x.shape[0], x.shape[1]
     kpm = torch.ones(B, T, dtype=torch.bool)
     for b, n in enumerate(frames):
         kpm[b, :int(n)] = False
     src_mask = None
-    if look_ahead > -1:
+    if left_context > -1 or chunk > 1 or band:
+        src_mask = BandMask(left_context, look_ahead, chunk)
+    elif look_ahead > -1:
         keep = torch.tril(torch.ones(T, T), diagonal=look_ahead)
         src_mask = torch.zeros(T, T).masked_fill(keep == 0, float("-inf"))
     return model(x, src_mask, kpm).transpose(0, 1)
