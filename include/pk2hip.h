@@ -312,6 +312,31 @@ int pk2_chain_objf_and_deriv_graph_op(const pk2_den_graph* g, const float* logit
                                       size_t workspace_bytes, float grad_scale, float* objf_sum, void* stream);
 
 /* ------------------------------------------------------------------ *
+ * Connectionist temporal classification: loss and gradient of a minibatch from unnormalised logits in three launches
+ * (csrc/ctc.hip; torch.nn.functional.ctc_loss after log_softmax, and its backward).  With y_t = softmax(x[t, .])
+ * and the extended sequence blank, l_1, blank, .., l_L, blank:  loss = -log p(l | x),
+ *   grad[t, k] = w * (y_t(k) - sum_{s: ext_s = k} P(state s at frame t | l, x)).
+ * packed: int32 descriptor, the same words on the host and (packed_dev) on the device.  8 words per utterance
+ *   {frames T, labels L, status, lab, ord, weight w (f32 bits), 0, 0},  lab / ord: word offsets into the descriptor of
+ *   labels i32[L] and of {label positions 0..L-1 sorted by (label, position) i32[L], the labels in that order i32[L]};
+ *   status = PK2_CTC_OK, or PK2_CTC_NO_PATH when T < max(1, L + #{i: l_i = l_{i+1}}).  The host copy is checked in full
+ *   (PK2_ERR_INVALID; more than PK2_CTC_MAX_LABELS labels: PK2_ERR_LIMIT) before anything is launched.
+ * ------------------------------------------------------------------ */
+#define PK2_CTC_OK 0
+#define PK2_CTC_NO_PATH 2      /* no alignment of that many frames: loss 0, gradient rows 0 */
+#define PK2_CTC_NUMERIC 3      /* a frame's scale came out 0 or non-finite (logits outside the supported range): the same zeros */
+#define PK2_CTC_MAX_LABELS 4095
+size_t pk2_ctc_workspace_bytes(const int32_t* packed, int32_t num_utts);
+/* logits / grad: device f32, frame t of utterance n at [n * seq_stride + t * frame_stride], num_classes columns; logits rows
+ * t >= T_n are not read, ALL Tpad rows of grad are written (zeros for t >= T_n and when the status is not 0).  loss f64[N],
+ * status i32[N]: device.  workspace: device, 256-byte aligned, pk2_ctc_workspace_bytes().  The result is bit-reproducible
+ * and an utterance's part of it does not depend on the other utterances of the call. */
+int pk2_ctc_loss_and_grad(const int32_t* packed, const int32_t* packed_dev, int64_t packed_words, int32_t num_utts, const float* logits,
+                          int64_t seq_stride, int64_t frame_stride, int32_t Tpad, int32_t num_classes, int32_t blank, float* grad,
+                          int64_t grad_seq_stride, int64_t grad_frame_stride, double* loss, int32_t* status, void* workspace,
+                          size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------ *
  * Reverberation + additive noise of one utterance (single channel), device arrays throughout.
  * Replaces the numpy arithmetic of the reference's dynamic data simulation: Distorter.apply_rir /
  * Distorter.add_noise (reference simulation/_distorter.py:86-154) as _Simulator.simulate uses them for one

@@ -40,7 +40,11 @@ FILE_FLAGS = {"lattice_decode.hip": ["-ffp-contract=off"], "lattice_decode_frame
               # neighbour in its batch.  =on fuses inside a statement only, the same way in every instantiation.
               "chain_num_graph.hip": ["-ffp-contract=on"],
               # no packed-f32 arithmetic (v_pk_fma_f32 and its kin) in the banded attention kernels: plain f32 VALU only
-              "attention_band.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+              "attention_band.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+              # ctc_rows and ctc_grad both form y = exp(x - m) / Z and must round it alike, and an utterance's chains must
+              # not depend on what the unrolled pair loop of a longer neighbour made the backend fuse: =on, as above; and
+              # plain f32 VALU only
+              "ctc.hip": ["-ffp-contract=on", "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 # experiment builds: PK2_FILE_FLAGS="gemm_f32.hip:-mllvm,-align-loops=64;..." adds flags to single sources
 for _spec in os.environ.get("PK2_FILE_FLAGS", "").split(";"):
     if ":" in _spec:

@@ -23,7 +23,7 @@ import os
 import torch
 from torch.autograd import Function
 
-from . import _lib, chain, lattice
+from . import _lib, chain, ctc, lattice
 
 
 class ChainObjtiveFunction(Function):
@@ -294,3 +294,60 @@ class TeacherStudentBatch(Function):
     def backward(ctx, grad_out):
         grad, = ctx.saved_tensors
         return None, grad, None, None, None, None, None
+
+
+class CTCFunction(Function):
+    """``CTCFunction.apply(logits, lengths, labels, blank, reduction, zero_infinity, time_major)``: connectionist temporal
+    classification on unnormalised logits [N, T, P] ([T, N, P] with time_major), ctc.ctc_loss_and_grad under autograd.  Forward
+    computes loss and gradient in one library call with the reduction's factors as the per-utterance weights; backward hands
+    the stored gradient on, multiplied by the incoming gradient only when that is not 1 (the CrossEntropyLoss scheme).
+    ctx.per_sequence: float64 loss of every utterance, ctx.status: ctc.CTC_OK / CTC_NO_PATH / CTC_NUMERIC."""
+
+    @staticmethod
+    def forward(ctx, logits, lengths, labels, blank=0, reduction="mean", zero_infinity=True, time_major=False):
+        N = len(labels)
+        w = np.ones(N, np.float32)
+        if reduction == "mean":
+            w = (1.0 / (np.maximum([len(s) for s in labels], 1) * float(N))).astype(np.float32)
+        loss, grad, status = ctc.ctc_loss_and_grad(logits, lengths, labels, blank, w, time_major)
+        if not zero_infinity:      # an utterance without an alignment reports inf; its gradient rows stay 0
+            loss = torch.where(status == ctc.CTC_NO_PATH, torch.full_like(loss, float("inf")), loss)
+        ctx.per_sequence, ctx.status = loss, status
+        ctx.save_for_backward(grad)
+        ctx.utt_dim = None if reduction != "none" else (1 if time_major else 0)
+        ctx.applied = None
+        if reduction == "none":
+            return loss.to(torch.float32)
+        if reduction == "mean":
+            loss = loss * _lib.h2d(w.astype(np.float64), loss.device)
+        return loss.sum().to(torch.float32)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        grad, = ctx.saved_tensors
+        if ctx.utt_dim is not None:      # reduction 'none': one incoming gradient per utterance
+            shape = [1, 1, 1]
+            shape[ctx.utt_dim] = -1
+            return (grad * grad_out.detach().to(torch.float32).view(shape),) + (None,) * 6
+        go = grad_out.detach().to(device=grad.device, dtype=torch.float32).reshape(-1)[:1].contiguous()
+        _lib.check(_lib.lib().pk2_scale_inplace_ratio(_lib.ptr(grad), grad.numel(), _lib.ptr(go),
+                                                      _lib.ptr(ctx.applied) if ctx.applied is not None else None,
+                                                      _lib.stream_ptr(grad.device)))
+        ctx.applied = go
+        return (grad,) + (None,) * 6
+
+
+class CTCLoss(torch.nn.Module):
+    """torch.nn.CTCLoss(blank, reduction, zero_infinity) on UNNORMALISED logits, softmax included, fused into HIP kernels
+    (csrc/ctc.hip): ``CTCLoss()(logits, lengths, labels)`` with logits [N, T, P] ([T, N, P] with time_major=True), lengths
+    the frame counts and labels a list of int sequences.  'mean' divides every loss by its label count (at least 1) and
+    averages over the utterances, 'sum' adds them, 'none' returns them.  zero_infinity (default True, unlike torch): an
+    utterance with fewer frames than labels + repeats counts 0; with False it reports inf and still adds no gradient."""
+
+    def __init__(self, blank=0, reduction="mean", zero_infinity=True, time_major=False):
+        super().__init__()
+        assert reduction in ("mean", "sum", "none")
+        self.blank, self.reduction, self.zero_infinity, self.time_major = blank, reduction, zero_infinity, time_major
+
+    def forward(self, logits, lengths, labels):
+        return CTCFunction.apply(logits, lengths, labels, self.blank, self.reduction, self.zero_infinity, self.time_major)
