@@ -11,7 +11,9 @@ The label files' word transcripts (aux_label) are mapped to the phones of each w
 blank behind them (the last column).  With -synthetic the transcripts are seeded (synth.word_transcript) over the synthetic
 lexicon of train_chain.py -e2e.  Nothing frame-level is read, so data_config speed_perturb / volume_perturb and spec_augment
 with time_warp are all honoured.  A progress line carries the loss per frame and the greedy phone error rate of the minibatch;
-the sweep's totals are printed at its end.  Checkpoints: exp_dir/ctc.model.{epoch}.tar = {'model', 'optimizer', 'epoch'}.
+the sweep's totals are printed at its end.  With -beam N the line and the totals also carry the phone error rate of the prefix
+beam search (ctc.beam_search, csrc/ctc_beam.hip), with -phone_lm ARPA -phones_txt FILE fused with an n-gram LM
+over the phones (-lm_weight, -ins_bonus).  Checkpoints: exp_dir/ctc.model.{epoch}.tar = {'model', 'optimizer', 'epoch'}.
 """
 import argparse
 import json
@@ -24,7 +26,7 @@ import torch as th
 import yaml
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from pykaldi2_amd import augment, beamform, ctc, data, dereverb, fbank, hvd, lstm, ops, optim, score, synth, transformer, utils  # noqa: E402
+from pykaldi2_amd import augment, beamform, ctc, data, dereverb, fbank, hvd, lstm, ngram, ops, optim, score, synth, transformer, utils  # noqa: E402
 
 
 def parse_config(argv=None):
@@ -51,6 +53,12 @@ def parse_config(argv=None):
     parser.add_argument("-dim_model", default=512, type=int, help="(-transformer) the model dimension")
     parser.add_argument("-ff_size", default=2048, type=int, help="(-transformer) the size of feed-forward layer")
     parser.add_argument("-nlayers", default=6, type=int, help="(-transformer) the number of layers")
+    parser.add_argument("-beam", default=0, type=int, help="prefix beam search of this width next to the greedy decoding (0: off)")
+    parser.add_argument("-top_tokens", default=16, type=int, help="(-beam) phones a hypothesis is extended by per frame")
+    parser.add_argument("-phone_lm", help="(-beam) ARPA n-gram LM over the phones, fused into the search")
+    parser.add_argument("-phones_txt", help="(-phone_lm) phones.txt: the LM's symbol table, `phone id` per line")
+    parser.add_argument("-lm_weight", default=1.0, type=float, help="(-phone_lm) weight of the LM cost")
+    parser.add_argument("-ins_bonus", default=0.0, type=float, help="(-phone_lm) bonus per phone of a hypothesis")
     args = parser.parse_args(argv)
     with open(args.config) as f:
         config = yaml.safe_load(f)
@@ -120,6 +128,10 @@ def main():
     transform = None
     if args.transform is not None and os.path.isfile(args.transform):
         transform = fbank.GlobalMeanVarianceNormalization.load(args.transform)
+    args.lm = None
+    if args.beam and args.phone_lm:                           # column p is phone p + 1 of phones.txt (labels = ph - 1)
+        args.lm = ngram.NgramLM.from_arpa(args.phone_lm, words_txt=args.phones_txt)
+    args.lm_ids = np.arange(1, num_phones + 2) if args.lm is not None else None
     criterion = ops.CTCLoss(blank=args.blank, reduction="sum", zero_infinity=True, time_major=not args.transformer)
     fb = fbank.FbankExtractor()
     model.train()
@@ -136,9 +148,11 @@ def run_train_epoch(model, optimizer, criterion, source, fb, epoch, args, dev, t
     batch_time = utils.AverageMeter('Time', ':6.3f')
     losses = utils.AverageMeter('Loss', ':.4e')
     per = utils.AverageMeter('PER', ':.4f')
+    beam_per = utils.AverageMeter('beam_PER', ':.4f')
     grad_norm = utils.AverageMeter('grad_norm', ':.4e')
     n_batches = max(1, int(args.sweep_size * 3600 / (12.3 * args.batch_size)))
-    progress = utils.ProgressMeter(n_batches, batch_time, losses, per, grad_norm, prefix="Epoch: [{}]".format(epoch))
+    meters = [batch_time, losses, per] + ([beam_per] if args.beam else []) + [grad_norm]
+    progress = utils.ProgressMeter(n_batches, *meters, prefix="Epoch: [{}]".format(epoch))
     text_rng = np.random.default_rng(4321 + epoch + hvd.rank())
     spec = args.spec.epoch(hvd.rank(), epoch) if args.spec is not None else None
     sub = args.subsample
@@ -175,13 +189,20 @@ def run_train_epoch(model, optimizer, criterion, source, fb, epoch, args, dev, t
             grad_norm.update(norm.item())
             losses.update(loss.item() / float(np.sum(sub_frames)), int(np.sum(sub_frames)))
             per.update(errs / max(words, 1), words)
+            if args.beam:
+                best = ctc.beam_search(prediction, sub_frames, blank=args.blank, beam=args.beam, top_tokens=args.top_tokens,
+                                       lm=args.lm, lm_weight=args.lm_weight, insertion_bonus=args.ins_bonus, lm_ids=args.lm_ids,
+                                       time_major=not args.transformer)
+                errs, words = score.wer([h[0][0] if h else [] for h in best], labels, device="cpu")
+                beam_per.update(errs / max(words, 1), words)
             batch_time.update(time.time() - end)
             if hvd.rank() == 0:
                 progress.print(i)
         end = time.time()
     if hvd.rank() == 0:
-        print("Epoch {}: loss per frame {:.4f}, greedy phone error rate {:.4f} (over the printed minibatches)".format(
-            epoch, losses.avg, per.avg))
+        beam_txt = ", beam {} phone error rate {:.4f}".format(args.beam, beam_per.avg) if args.beam else ""
+        print("Epoch {}: loss per frame {:.4f}, greedy phone error rate {:.4f}{} (over the printed minibatches)".format(
+            epoch, losses.avg, per.avg, beam_txt))
 
 
 if __name__ == '__main__':

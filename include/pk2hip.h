@@ -337,6 +337,33 @@ int pk2_ctc_loss_and_grad(const int32_t* packed, const int32_t* packed_dev, int6
                           size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------ *
+ * CTC prefix beam search with optional shallow fusion of a backoff n-gram LM over the tokens (csrc/ctc_beam.hip, DESIGN.md
+ * 7.20), two launches: ctcb_rows (softmax statistics and the top_tokens non-blank columns of every frame) and ctcb_search
+ * (one workgroup per utterance, all frames).  A hypothesis is a blank-free prefix l with the masses pb(l), pnb(l) of the
+ * alignments that end in blank / in a non-blank; per frame every l stays, is extended by the frame's top_tokens columns
+ * (an extension that is itself in the beam is merged into it), and the `beam` largest pb + pnb survive.  With an LM an
+ * extension by column c is weighted exp(-lm_weight * cost(lm_ids[c] | LM state of l) + insertion_bonus), and with lm_eos
+ * the final score log(pb + pnb) gets -lm_weight * cost(</s> | state).  Every non-blank column must have a unigram in the
+ * LM (the caller checks that: the kernels give a failed lookup the weight 0).
+ * ------------------------------------------------------------------ */
+#define PK2_CTC_BEAM_MAX 128
+#define PK2_CTC_BEAM_MAX_TOKENS 32
+size_t pk2_ctc_beam_workspace_bytes(int32_t num_utts, int32_t T, int32_t num_classes, int32_t beam, int32_t top_tokens);
+/* lengths: N frame counts in [0, T], the same on the host and (lengths_dev) on the device.  logits as for the loss; rows
+ * t >= T_n are not read.  top_tokens is clamped to num_classes - 1.  lm: a pk2_ngram_create handle or NULL; lm_ids: device
+ * i32[num_classes] column -> LM word id, or NULL for the identity (only with an LM).  Outputs, device: out_tokens
+ * i32[N][beam][T] (hypothesis r of utterance n left-aligned, -1 behind it), out_lens i32[N][beam] (-1: unused slot),
+ * out_scores f64[N][beam] in non-increasing order (-inf: unused), out_status i32[N] (PK2_CTC_OK, or PK2_CTC_NUMERIC when
+ * the best total of a frame was 0 or not finite: all slots unused).  beam outside 1..PK2_CTC_BEAM_MAX or top_tokens outside
+ * 1..PK2_CTC_BEAM_MAX_TOKENS: PK2_ERR_LIMIT; anything else wrong: PK2_ERR_INVALID, before any launch.  workspace: device,
+ * 256-byte aligned.  Bit-reproducible; an utterance's result does not depend on the other utterances of the call. */
+int pk2_ctc_beam_search(const int32_t* lengths, const int32_t* lengths_dev, int32_t num_utts, const float* logits, int64_t seq_stride,
+                        int64_t frame_stride, int32_t T, int32_t num_classes, int32_t blank, int32_t beam, int32_t top_tokens,
+                        const void* lm, const int32_t* lm_ids, double lm_weight, double insertion_bonus, int32_t lm_eos,
+                        int32_t* out_tokens, int32_t* out_lens, double* out_scores, int32_t* out_status, void* workspace,
+                        size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------ *
  * Reverberation + additive noise of one utterance (single channel), device arrays throughout.
  * Replaces the numpy arithmetic of the reference's dynamic data simulation: Distorter.apply_rir /
  * Distorter.add_noise (reference simulation/_distorter.py:86-154) as _Simulator.simulate uses them for one

@@ -44,7 +44,10 @@ FILE_FLAGS = {"lattice_decode.hip": ["-ffp-contract=off"], "lattice_decode_frame
               # ctc_rows and ctc_grad both form y = exp(x - m) / Z and must round it alike, and an utterance's chains must
               # not depend on what the unrolled pair loop of a longer neighbour made the backend fuse: =on, as above; and
               # plain f32 VALU only
-              "ctc.hip": ["-ffp-contract=on", "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+              "ctc.hip": ["-ffp-contract=on", "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+              # the masses round like the float64 restatement's separate operations, and ctcb_rows and ctcb_search form
+              # y = exp(x - m) / Z alike; plain f32 VALU only
+              "ctc_beam.hip": ["-ffp-contract=off", "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 # experiment builds: PK2_FILE_FLAGS="gemm_f32.hip:-mllvm,-align-loops=64;..." adds flags to single sources
 for _spec in os.environ.get("PK2_FILE_FLAGS", "").split(";"):
     if ":" in _spec:

@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "common.h"
+#include "ngram_dev.h"
 #include "wordlat.h"
 
 #pragma clang fp contract(off)
@@ -30,13 +31,6 @@ constexpr int kLrThreads = 1024;
 constexpr int kLrWaves = kLrThreads / 64;
 static_assert((PK2_LMRESCORE_SORT_LDS & (PK2_LMRESCORE_SORT_LDS - 1)) == 0 && PK2_LMRESCORE_SORT_LDS >= 128, "bitonic sort: a power of two");
 constexpr int64_t kLrMaxRoom = (int64_t)1 << 29;     // states / arcs of one composed lattice
-
-struct NgramDev {
-  int32_t N = 0, order = 0, start = 0, eos = 0;
-  void* blob = nullptr;
-  const int32_t *d_word, *d_child, *d_bo, *d_next;
-  const float *d_cost, *d_backoff;
-};
 
 struct LrParams {
   const int64_t *state_off, *arc_off, *level_off_off, *word_off_off;

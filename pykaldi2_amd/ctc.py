@@ -2,6 +2,7 @@
 
     loss, grad, status = ctc.ctc_loss_and_grad(logits, lengths, labels, blank=0)
     hyps = ctc.greedy_decode(logits, lengths, blank=0)
+    nbest = ctc.beam_search(logits, lengths, nbest=4, beam=16, top_tokens=16, lm=phone_lm, lm_weight=0.5)
 
 ops.CTCLoss is the autograd form.  The logits are UNNORMALISED network outputs (log-probabilities are the special case whose
 rows have log-sum-exp 0): softmax, loss and gradient are one library call of three launches, bit-reproducible.
@@ -18,6 +19,7 @@ from .chain import _workspace
 
 CTC_OK, CTC_NO_PATH, CTC_NUMERIC = 0, 2, 3      # PK2_CTC_OK / PK2_CTC_NO_PATH / PK2_CTC_NUMERIC
 MAX_LABELS = 4095                               # PK2_CTC_MAX_LABELS
+MAX_BEAM, MAX_TOP_TOKENS = 128, 32              # PK2_CTC_BEAM_MAX / PK2_CTC_BEAM_MAX_TOKENS
 
 
 def pack(lengths, labels, num_frames, num_classes, blank=0, weights=None):
@@ -83,6 +85,76 @@ def ctc_loss_and_grad(logits, lengths, labels, blank=0, weights=None, time_major
                                        _lib.ptr(ws), ws.numel(), _lib.stream_ptr(x.device)))
     loss._pk2_keepalive = (host, dev)      # the pinned block until the stream has consumed it
     return loss, g, status
+
+
+def _beam_args(lengths, N, T, P, blank, beam, top_tokens, lm, lm_ids):
+    """The host checks of beam_search_raw (ValueError before anything is launched): (lengths int32 [N], lm_ids int32 [P] or None)."""
+    lengths = np.asarray(lengths, dtype=np.int64).reshape(-1)
+    if lengths.shape[0] != N or (N and (lengths.min() < 0 or lengths.max() > T)):
+        raise ValueError("ctc: %d lengths for %d utterances of at most %d frames" % (lengths.shape[0], N, T))
+    if N < 1 or P < 2 or not 0 <= blank < P:
+        raise ValueError("ctc: %d utterances, blank %d of %d columns" % (N, blank, P))
+    if isinstance(beam, bool) or int(beam) != beam or not 1 <= beam <= MAX_BEAM:
+        raise ValueError("ctc: beam %r outside 1..%d" % (beam, MAX_BEAM))
+    if isinstance(top_tokens, bool) or int(top_tokens) != top_tokens or not 1 <= top_tokens <= MAX_TOP_TOKENS:
+        raise ValueError("ctc: top_tokens %r outside 1..%d" % (top_tokens, MAX_TOP_TOKENS))
+    if lm is None:
+        if lm_ids is not None:
+            raise ValueError("ctc: lm_ids without an LM")
+        return lengths.astype(np.int32), None
+    ids = np.arange(P, dtype=np.int64) if lm_ids is None else np.asarray(lm_ids, dtype=np.int64).reshape(-1)
+    if ids.shape[0] != P:
+        raise ValueError("ctc: lm_ids has %d entries for %d columns" % (ids.shape[0], P))
+    unigrams = lm.word[int(lm.child_begin[0]):int(lm.child_begin[1])]
+    missing = [c for c in np.flatnonzero(~np.isin(ids, unigrams)).tolist() if c != blank]
+    if missing:
+        raise ValueError("ctc: column %d (LM word id %d) has no unigram in the LM" % (missing[0], ids[missing[0]]))
+    return lengths.astype(np.int32), (None if lm_ids is None else np.where(np.arange(P) == blank, 0, ids).astype(np.int32))
+
+
+def beam_search_raw(logits, lengths, blank=0, beam=16, top_tokens=16, lm=None, lm_weight=1.0, insertion_bonus=0.0, lm_ids=None,
+                    lm_eos=True, time_major=False):
+    """CTC prefix beam search on the device (csrc/ctc_beam.hip), two launches, nothing read back.
+
+    logits, lengths, time_major: as for ctc_loss_and_grad (served in place, rows past a length are not read).  Per frame a
+    hypothesis stays or is extended by the top_tokens non-blank columns of the largest logit (clamped to P - 1); extensions
+    that meet a hypothesis of the beam are merged into it; the `beam` (1..128) most probable survive.  lm: an ngram.NgramLM
+    over the TOKENS (lm_ids: int [P], column -> LM word id, default the identity; every non-blank column needs a unigram):
+    an extension by c is weighted exp(-lm_weight * cost(c | history) + insertion_bonus), and with lm_eos the final score
+    gets -lm_weight * cost(</s> | history).
+    Returns device tensors (tokens int32 [N, beam, T] left-aligned with -1 behind, lens int32 [N, beam] with -1 for unused
+    slots, scores float64 [N, beam] = log(pb + pnb) (+ the </s> term), non-increasing, -inf for unused slots, status int32
+    [N]): status 3 (CTC_NUMERIC) = a frame's best total was 0 or not finite, all slots unused; the others are unaffected."""
+    if logits.dim() != 3 or logits.dtype != torch.float32 or logits.stride(2) != 1:
+        raise ValueError("ctc: logits must be float32 [N, T, P] with a unit column stride")
+    x = logits.detach().transpose(0, 1) if time_major else logits.detach()
+    N, T, P = x.shape
+    host, ids = _beam_args(lengths, N, T, P, blank, beam, top_tokens, lm, lm_ids)
+    _lib.require_gpu()
+    L = _lib.lib()
+    host = torch.from_numpy(host).pin_memory()
+    dev = host.to(x.device, non_blocking=True)
+    ids_dev = None if ids is None else torch.from_numpy(ids).to(x.device)
+    ws = _workspace(x.device, L.pk2_ctc_beam_workspace_bytes(N, T, P, int(beam), int(top_tokens)))
+    tokens = torch.empty((N, int(beam), T), dtype=torch.int32, device=x.device)
+    lens = torch.empty((N, int(beam)), dtype=torch.int32, device=x.device)
+    scores = torch.empty((N, int(beam)), dtype=torch.float64, device=x.device)
+    status = torch.empty(N, dtype=torch.int32, device=x.device)
+    _lib.check(L.pk2_ctc_beam_search(_lib.ptr(host), _lib.ptr(dev), N, _lib.ptr(x), x.stride(0), x.stride(1), T, P, int(blank), int(beam),
+                                     int(top_tokens), lm.handle(x.device) if lm is not None else None, _lib.ptr(ids_dev),
+                                     float(lm_weight), float(insertion_bonus), int(bool(lm_eos)), _lib.ptr(tokens), _lib.ptr(lens),
+                                     _lib.ptr(scores), _lib.ptr(status), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(x.device)))
+    scores._pk2_keepalive = (host, dev, ids_dev, lm)      # until the stream has consumed them
+    return tokens, lens, scores, status
+
+
+def beam_search(logits, lengths, nbest=1, **kw):
+    """beam_search_raw and ONE copy to the host: per utterance a list of at most nbest (token list, score), best first."""
+    tokens, lens, scores, _ = beam_search_raw(logits, lengths, **kw)
+    N, B, T = tokens.shape
+    flat = torch.cat([tokens.reshape(N, -1).double(), lens.double(), scores], dim=1).cpu().numpy()      # (int32 is exact in float64)
+    tok, ln, sc = flat[:, :B * T].reshape(N, B, T).astype(np.int64), flat[:, B * T:B * T + B].astype(np.int64), flat[:, B * T + B:]
+    return [[(tok[n, r, :ln[n, r]].tolist(), float(sc[n, r])) for r in range(min(nbest, B)) if ln[n, r] >= 0] for n in range(N)]
 
 
 def greedy_decode(logits, lengths, blank=0, time_major=False):
