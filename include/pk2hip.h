@@ -364,6 +364,47 @@ int pk2_ctc_beam_search(const int32_t* lengths, const int32_t* lengths_dev, int3
                         size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------ *
+ * Transducer (RNN-T) loss and gradient with an additive joint, the [T][U+1][V] joint never stored (csrc/transducer.hip,
+ * DESIGN.md 7.21; k2's rnnt_loss_simple).  Utterance n has T_n >= 1 frames and U_n >= 0 labels, none the blank b.  With
+ * z[t,u,.] = am[t,.] + lm[u,.], y = softmax(z), py[t,u] = log y[t,u,b] (t -> t+1), px[t,u] = log y[t,u,l_{u+1}] (u -> u+1):
+ *   alpha[0,0] = 0, alpha[t,u] = logadd(alpha[t-1,u] + py[t-1,u], alpha[t,u-1] + px[t,u-1]),
+ *   loss = -(alpha[T-1,U] + py[T-1,U]),   occ_y / occ_x: the posteriors of the two moves out of (t,u), gamma their sum,
+ *   grad_am[t,v] = w (sum_u gamma[t,u] y[t,u,v] - [v = b] sum_u occ_y[t,u] - sum_{u: l_{u+1} = v} occ_x[t,u]),
+ *   grad_lm[u,v] = w (sum_t gamma[t,u] y[t,u,v] - [v = b] sum_t occ_y[t,u] - [v = l_{u+1}] sum_t occ_x[t,u]).
+ * packed: the int32 descriptor of pk2_ctc_loss_and_grad, 8 words per utterance {frames T, labels U, status = 0, lab, ord,
+ *   weight w (f32 bits), 0, 0} and the same label arrays; the host copy is checked in full (PK2_ERR_INVALID; more than
+ *   PK2_TRANSDUCER_MAX_LABELS labels: PK2_ERR_LIMIT) before anything is launched.  Every utterance has an alignment, so
+ *   there is no status 2.  Supported range: row spread of am (max - min over the columns) plus row spread of lm <= 60.
+ * ------------------------------------------------------------------ */
+#define PK2_TRANSDUCER_OK 0
+#define PK2_TRANSDUCER_NUMERIC 3      /* a normaliser or the total came out 0 or non-finite: loss 0, gradient rows 0 */
+/* A lane of the lattice kernel owns ONE grid column u = 0..U (its state is a float64 in the log domain, its exchange one
+ * shift), and a workgroup has at most 1024 lanes: U + 1 <= 1024. */
+#define PK2_TRANSDUCER_MAX_LABELS 1023
+/* O(T U + T + U) per utterance: no term in num_classes (the argument is there so that a caller can see that). */
+size_t pk2_transducer_workspace_bytes(const int32_t* packed, int32_t num_utts, int32_t num_classes);
+/* am / grad_am: device f32, frame t of utterance n at [n * am_seq_stride + t * am_row_stride], Tpad rows; lm / grad_lm:
+ * predictor row u (after u labels) at [n * lm_seq_stride + u * lm_row_stride], Upad1 >= max U_n + 1 rows; num_classes
+ * columns, unit column stride, an utterance's rows within 2^31 floats.  Rows t >= T_n of am and u > U_n of lm are not read;
+ * ALL rows of both gradients are written (zeros there, and when the status is not 0).  loss f64[N], status i32[N]: device.
+ * workspace: device, 256-byte aligned, pk2_transducer_workspace_bytes().  Seven launches on `stream`, nothing is read back;
+ * bit-reproducible, and an utterance's part of the result does not depend on the other utterances of the call. */
+int pk2_transducer_loss_and_grad(const int32_t* packed, const int32_t* packed_dev, int64_t packed_words, int32_t num_utts, const float* am,
+                                 int64_t am_seq_stride, int64_t am_row_stride, int32_t Tpad, const float* lm, int64_t lm_seq_stride,
+                                 int64_t lm_row_stride, int32_t Upad1, int32_t num_classes, int32_t blank, float* grad_am,
+                                 int64_t gam_seq_stride, int64_t gam_row_stride, float* grad_lm, int64_t glm_seq_stride,
+                                 int64_t glm_row_stride, double* loss, int32_t* status, void* workspace, size_t workspace_bytes,
+                                 void* stream);
+/* Greedy decoding of a stateless transducer whose predictor is a table of previous-label rows, one wave per utterance:
+ * prev = blank; at frame t, v* = argmax_v (am[t,v] + table[prev * table_stride + v]) as a float32 sum, ties to the lower
+ * column; the blank moves to frame t + 1, anything else is emitted, becomes prev and stays on the frame, at most
+ * max_symbols per frame.  lengths: N frame counts in [0, T], the same on the host and (lengths_dev) on the device.
+ * out_tokens i32[N][T * max_symbols] left-aligned with -1 behind, out_lens i32[N]: device. */
+int pk2_transducer_greedy(const int32_t* lengths, const int32_t* lengths_dev, int32_t num_utts, const float* am, int64_t seq_stride,
+                          int64_t frame_stride, int32_t T, const float* table, int64_t table_stride, int32_t num_classes, int32_t blank,
+                          int32_t max_symbols, int32_t* out_tokens, int32_t* out_lens, void* stream);
+
+/* ------------------------------------------------------------------ *
  * Reverberation + additive noise of one utterance (single channel), device arrays throughout.
  * Replaces the numpy arithmetic of the reference's dynamic data simulation: Distorter.apply_rir /
  * Distorter.add_noise (reference simulation/_distorter.py:86-154) as _Simulator.simulate uses them for one

@@ -141,6 +141,10 @@ SIGNATURES = {
     "pk2_ctc_beam_workspace_bytes": (_sz, [_i32] * 5),
     "pk2_ctc_beam_search": (C.c_int, [_vp, _vp, _i32, _vp, _i64, _i64] + [_i32] * 5 + [_vp, _vp, C.c_double, C.c_double, _i32] +
                             [_vp] * 5 + [_sz, _vp]),
+    "pk2_transducer_workspace_bytes": (_sz, [_vp, _i32, _i32]),
+    "pk2_transducer_loss_and_grad": (C.c_int, [_vp, _vp, _i64, _i32, _vp, _i64, _i64, _i32, _vp, _i64, _i64, _i32, _i32, _i32,
+                                               _vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _sz, _vp]),
+    "pk2_transducer_greedy": (C.c_int, [_vp, _vp, _i32, _vp, _i64, _i64, _i32, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp]),
     "pk2_decode_graph_create": (C.c_int, [_i32, _i32, _i64, _vp, _vp, _vp, _vp, _vp, C.POINTER(_vp)]),
     "pk2_decode_graph_create_words": (C.c_int, [_i32, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_vp)]),
     "pk2_decode_graph_link_words": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp]),

@@ -23,7 +23,7 @@ import os
 import torch
 from torch.autograd import Function
 
-from . import _lib, chain, ctc, lattice
+from . import _lib, chain, ctc, lattice, transducer
 
 
 class ChainObjtiveFunction(Function):
@@ -351,3 +351,61 @@ class CTCLoss(torch.nn.Module):
 
     def forward(self, logits, lengths, labels):
         return CTCFunction.apply(logits, lengths, labels, self.blank, self.reduction, self.zero_infinity, self.time_major)
+
+
+class TransducerFunction(Function):
+    """``TransducerFunction.apply(am, lm, lengths, labels, blank, reduction, time_major)``: the transducer loss with an additive
+    joint on unnormalised logits am [N, T, V] ([T, N, V] with time_major) and lm [N, U + 1, V],
+    transducer.transducer_loss_and_grad under autograd.  Forward computes the loss and both gradients in one library call
+    with the reduction's factors as the per-utterance weights; backward hands the stored gradients on, multiplied by the
+    incoming gradient only when that is not 1 (the CTCFunction scheme).  ctx.per_sequence: float64 loss of every utterance,
+    ctx.status: transducer.TRANSDUCER_OK / TRANSDUCER_NUMERIC."""
+
+    @staticmethod
+    def forward(ctx, am, lm, lengths, labels, blank=0, reduction="mean", time_major=False):
+        N = len(labels)
+        w = np.ones(N, np.float32)
+        if reduction == "mean":
+            w = (1.0 / (np.maximum([len(s) for s in labels], 1) * float(N))).astype(np.float32)
+        loss, grad_am, grad_lm, status = transducer.transducer_loss_and_grad(am, lm, lengths, labels, blank, w, time_major)
+        ctx.per_sequence, ctx.status = loss, status
+        ctx.save_for_backward(grad_am, grad_lm)
+        ctx.utt_dim = None if reduction != "none" else (1 if time_major else 0)
+        ctx.applied = [None, None]
+        if reduction == "none":
+            return loss.to(torch.float32)
+        if reduction == "mean":
+            loss = loss * _lib.h2d(w.astype(np.float64), loss.device)
+        return loss.sum().to(torch.float32)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        grads = ctx.saved_tensors
+        if ctx.utt_dim is not None:      # reduction 'none': one incoming gradient per utterance
+            go = grad_out.detach().to(torch.float32)
+            shape = [1, 1, 1]
+            shape[ctx.utt_dim] = -1
+            return (grads[0] * go.view(shape), grads[1] * go.view(-1, 1, 1)) + (None,) * 5
+        go = grad_out.detach().to(device=grads[0].device, dtype=torch.float32).reshape(-1)[:1].contiguous()
+        for i, g in enumerate(grads):
+            _lib.check(_lib.lib().pk2_scale_inplace_ratio(_lib.ptr(g), g.numel(), _lib.ptr(go),
+                                                          _lib.ptr(ctx.applied[i]) if ctx.applied[i] is not None else None,
+                                                          _lib.stream_ptr(g.device)))
+            ctx.applied[i] = go
+        return tuple(grads) + (None,) * 5
+
+
+class TransducerLoss(torch.nn.Module):
+    """The transducer (RNN-T) loss with an additive joint on UNNORMALISED logits, fused into HIP kernels that never store the
+    joint (csrc/transducer.hip): ``TransducerLoss()(am, lm, lengths, labels)`` with am [N, T, V] ([T, N, V] with
+    time_major=True), lm [N, U + 1, V] (row u: the predictor after u labels), lengths the frame counts and labels a list of
+    int sequences.  'mean' divides every loss by its label count (at least 1) and averages over the utterances, 'sum' adds
+    them, 'none' returns them."""
+
+    def __init__(self, blank=0, reduction="mean", time_major=False):
+        super().__init__()
+        assert reduction in ("mean", "sum", "none")
+        self.blank, self.reduction, self.time_major = blank, reduction, time_major
+
+    def forward(self, am, lm, lengths, labels):
+        return TransducerFunction.apply(am, lm, lengths, labels, self.blank, self.reduction, self.time_major)
