@@ -12,7 +12,14 @@ table of previous-label rows, lm[n, u, :] = table[prev_u] with prev_0 the blank'
 indexing; the joint is the sum am[t] + lm[u].  The table has a small Adam of its own (its gradient is all-reduced with
 hvd.allreduce_), optim.Adam owns the encoder's flat buffer.  A progress line carries the loss per frame and the phone error
 rate of the greedy decoding (transducer.greedy_decode); the sweep's totals are printed at its end.  Checkpoints:
-exp_dir/transducer.model.{epoch}.tar = {'model', 'table', 'optimizer', 'table_optimizer', 'epoch'}.
+exp_dir/transducer.model.{epoch}.tar = {'model', 'table', 'joiner', 'optimizer', 'table_optimizer', 'epoch'}.
+
+With -joiner J the additive loss becomes the first of two stages (k2's pruned recipe): it also returns, per
+frame, the band of -prune_range predictor rows that its occupancies favour.  Three small torch.nn.Linear layers (V -> J on the
+encoder's logits, V -> J on the table rows, J -> V behind the join) make a nonlinear joiner that ops.PrunedJoin evaluates on
+that band only and ops.PrunedTransducerLoss scores (csrc/transducer_pruned.hip); the loss is simple_scale * simple + pruned.
+The layers are trained by the table's optimiser and their gradients all-reduced as the table's is.  The printed greedy phone
+error rate stays that of the ADDITIVE head: decoding through the joiner is not built.
 """
 import argparse
 import json
@@ -54,6 +61,10 @@ def parse_config(argv=None):
     parser.add_argument("-nlayers", default=6, type=int, help="(-transformer) the number of layers")
     parser.add_argument("-table_lr", type=float, default=1e-2, help="learning rate of the predictor table's optimiser")
     parser.add_argument("-max_symbols", default=8, type=int, help="phones the greedy decoding may emit per frame")
+    parser.add_argument("-joiner", default=0, type=int, metavar='J', help="train a nonlinear joiner of width J on the pruned band "
+                        "(the second stage); the printed error rate stays the additive head's, decoding through the joiner is not built")
+    parser.add_argument("-prune_range", default=5, type=int, metavar='S', help="(-joiner) predictor rows per frame in the band")
+    parser.add_argument("-simple_scale", default=0.5, type=float, metavar='X', help="(-joiner) the loss is X * simple + pruned")
     args = parser.parse_args(argv)
     with open(args.config) as f:
         config = yaml.safe_load(f)
@@ -118,7 +129,14 @@ def main():
     table = th.zeros(num_phones + 1, num_phones + 1, device=dev, requires_grad=True)      # the predictor: row = previous label
     if args.seed_model and "table" in th.load(args.seed_model, map_location="cpu"):
         table.data.copy_(th.load(args.seed_model, map_location="cpu")["table"])
-    table_optimizer = th.optim.Adam([table], lr=args.table_lr)
+    joiner = None
+    if args.joiner:      # (made only on request: a seeded run without it draws the same random numbers as before)
+        joiner = th.nn.ModuleDict({"enc": th.nn.Linear(num_phones + 1, args.joiner), "pred": th.nn.Linear(num_phones + 1, args.joiner),
+                                   "out": th.nn.Linear(args.joiner, num_phones + 1)}).to(dev)
+        if args.seed_model and th.load(args.seed_model, map_location="cpu").get("joiner"):
+            joiner.load_state_dict(th.load(args.seed_model, map_location="cpu")["joiner"])
+        hvd.broadcast_parameters(joiner.state_dict(), root_rank=0)
+    table_optimizer = th.optim.Adam([table] + (list(joiner.parameters()) if joiner else []), lr=args.table_lr)
     optimizer = optim.Adam(model, lr=args.lr, amsgrad=True)
     hvd.broadcast_parameters({"table": table.data}, root_rank=0)
     hvd.broadcast_parameters(model.state_dict(), root_rank=0)
@@ -128,20 +146,23 @@ def main():
     transform = None
     if args.transform is not None and os.path.isfile(args.transform):
         transform = fbank.GlobalMeanVarianceNormalization.load(args.transform)
-    criterion = ops.TransducerLoss(blank=args.blank, reduction="sum", time_major=not args.transformer)
+    criterion = ops.TransducerLoss(blank=args.blank, reduction="sum", time_major=not args.transformer,
+                                   prune_range=args.prune_range if joiner else None)
+    args.pruned = ops.PrunedTransducerLoss(blank=args.blank, reduction="sum")
     fb = fbank.FbankExtractor()
     model.train()
     for epoch in range(args.num_epochs):
-        run_train_epoch(model, table, optimizer, table_optimizer, criterion, source, fb, epoch, args, dev, transform)
+        run_train_epoch(model, table, joiner, optimizer, table_optimizer, criterion, source, fb, epoch, args, dev, transform)
         hvd.finish()
         if hvd.rank() == 0 and args.exp_dir:
             th.save({'model': model.state_dict(), 'table': table.detach().cpu(), 'optimizer': optimizer.state_dict(),
+                     'joiner': joiner.state_dict() if joiner else None,
                      'table_optimizer': table_optimizer.state_dict(), 'epoch': epoch},
                     args.exp_dir + '/transducer.model.' + str(epoch) + '.tar')
     hvd.shutdown()
 
 
-def run_train_epoch(model, table, optimizer, table_optimizer, criterion, source, fb, epoch, args, dev, transform):
+def run_train_epoch(model, table, joiner, optimizer, table_optimizer, criterion, source, fb, epoch, args, dev, transform):
     batch_time = utils.AverageMeter('Time', ':6.3f')
     losses = utils.AverageMeter('Loss', ':.4e')
     per = utils.AverageMeter('PER', ':.4f')
@@ -171,11 +192,21 @@ def run_train_epoch(model, table, optimizer, table_optimizer, criterion, source,
             prediction = model.forward_time_major(x)                           # [Tmax, N, P]
         umax = max(len(lab) for lab in labels)
         prev = th.tensor([[args.blank] + lab + [args.blank] * (umax - len(lab)) for lab in labels], device=dev)
-        loss = criterion(prediction, table[prev], sub_frames, labels)      # lm [N, umax + 1, V]
+        lm = table[prev]                                                   # [N, umax + 1, V]
+        if joiner is None:
+            loss = criterion(prediction, lm, sub_frames, labels)
+        else:      # the additive loss picks the band, the joiner is evaluated and scored on it
+            simple, begin = criterion(prediction, lm, sub_frames, labels)
+            am = prediction if args.transformer else prediction.transpose(0, 1)      # [N, Tmax, V]
+            h = ops.PrunedJoin.apply(joiner["enc"](am), joiner["pred"](lm), begin, sub_frames, [len(lab) for lab in labels],
+                                     args.prune_range)
+            loss = args.simple_scale * simple + args.pruned(joiner["out"](h), begin, sub_frames, labels)
         optimizer.zero_grad()
         table_optimizer.zero_grad()
         loss.backward()
         hvd.allreduce_(table.grad)
+        for q in (joiner.parameters() if joiner else ()):
+            hvd.allreduce_(q.grad)
         table_optimizer.step()
         step = n_batches * epoch + i + 1
         lr = utils.noam_decay(step, args.warmup_steps, args.lr)

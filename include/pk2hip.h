@@ -405,6 +405,50 @@ int pk2_transducer_greedy(const int32_t* lengths, const int32_t* lengths_dev, in
                           int32_t max_symbols, int32_t* out_tokens, int32_t* out_lens, void* stream);
 
 /* ------------------------------------------------------------------ *
+ * The pruned transducer loss (csrc/transducer_pruned.hip; k2's rnnt_loss_pruned): the second stage.  The
+ * first stage's occupancies give, per frame t, the first begin[t] of the S = prune_range predictor rows that matter; a
+ * joiner is evaluated on that band only and the loss taken on its logits [N][T][S][V], cell (t, s) being u = begin[t] + s.
+ * ------------------------------------------------------------------ */
+#define PK2_TRANSDUCER_RANGES 2       /* begin[0] != 0, a step outside [0, S-1], begin[T-1] + S - 1 < U or a negative entry */
+#define PK2_TRANSDUCER_MAX_PRUNE_RANGE 32
+/* Rows of fewer columns than this are served by 16 lanes each (four rows a wave), longer ones by a whole wave. */
+#define PK2_TRANSDUCER_PRUNED_SHORT_ROWS 256
+/* The follow-on of pk2_transducer_loss_and_grad: called on the SAME stream, with the same descriptor, the status it wrote and
+ * the workspace it left, before anything else uses that workspace.  gamma f32 [N][Tpad][Upad1] = occ_x + occ_y (0 past T_n /
+ * U_n and for a status-3 utterance), begin i32 [N][Tpad] (0 past T_n).  With Bmax = max(0, U + 1 - S), all scans backwards:
+ *   win[t,s] = sum_{u=s}^{min(s+S-1,U)} gamma[t,u]   in float64, ascending u, every window on its own
+ *   raw[t]   = argmax_{0<=s<=Bmax} win[t,s] (ties: lowest s), clamped into [max(0, Bmax - (S-1)(T-1-t)), min(Bmax, (S-1) t)]
+ *   b[t]     = min_{t'>=t} raw[t'],   begin[t] = max_{t'>=t} (b[t'] - (S-1)(t'-t)).
+ * 2 <= S <= 32; an utterance with Bmax > (S-1)(T-1) cannot be covered: PK2_ERR_INVALID.  One launch. */
+int pk2_transducer_ranges(const int32_t* packed, const int32_t* packed_dev, int64_t packed_words, int32_t num_utts, int32_t prune_range,
+                          int32_t Tpad, int32_t Upad1, const int32_t* status, const void* workspace, size_t workspace_bytes,
+                          int32_t* begin, float* gamma, void* stream);
+/* O(N Tpad S): no term in num_classes. */
+size_t pk2_transducer_pruned_workspace_bytes(int32_t num_utts, int32_t Tpad, int32_t prune_range, int32_t num_classes);
+/* logits: device f32, row (n, t, s) at [n * seq_stride + t * frame_stride + s * band_stride], unit column stride, unnormalised,
+ * any numeric range; begin: device i32 [N][Tpad] dense, VALIDATED ON THE DEVICE before it is used as an index (status 2: loss 0,
+ * gradient 0, the other utterances untouched); grad: dense f32 [N][Tpad][S][V], every row written (zeros for t >= T_n, u > U_n
+ * and any status but 0).  packed: the descriptor of pk2_transducer_loss_and_grad (the sorted label arrays are not read).
+ * Status 3: a row's maximum or the total is not finite.  Three launches on `stream`, nothing read back, bit-reproducible, an
+ * utterance's part of the result independent of the other utterances. */
+int pk2_transducer_pruned_loss_and_grad(const int32_t* packed, const int32_t* packed_dev, int64_t packed_words, int32_t num_utts,
+                                        const float* logits, int64_t seq_stride, int64_t frame_stride, int64_t band_stride, int32_t Tpad,
+                                        int32_t prune_range, int32_t num_classes, int32_t blank, const int32_t* begin, float* grad,
+                                        double* loss, int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
+/* The banded join h[n,t,s,:] = tanh(enc[n,t,:] + pred[n,begin[t]+s,:]) (the plain sum with use_tanh = 0), zeros for t >= T_n and
+ * for begin[t] + s outside [0, U_n].  lens: i32 [N][2] = {T_n, U_n}, the same on the host and (lens_dev) on the device.
+ * enc [N][Tpad][dim], pred [N][Upad1][dim] by strides (unit column stride); h dense f32 [N][Tpad][S][dim].  One launch. */
+int pk2_transducer_join(const int32_t* lens, const int32_t* lens_dev, int32_t num_utts, const float* enc, int64_t enc_seq_stride,
+                        int64_t enc_row_stride, const float* pred, int64_t pred_seq_stride, int64_t pred_row_stride, const int32_t* begin,
+                        int32_t Tpad, int32_t Upad1, int32_t prune_range, int32_t dim, int32_t use_tanh, float* h, void* stream);
+/* d_enc[t,:] = sum_s dh (1 - h^2) in ascending s; d_pred[u,:] = sum_t dh[t, u - begin[t], :] (1 - h^2) over the frames whose
+ * band holds u, in ascending t, by the workgroup that owns the row: no atomics.  All of dh, h, d_enc [N][Tpad][dim] and d_pred
+ * [N][Upad1][dim] dense; rows past T_n / U_n are zeros.  One launch. */
+int pk2_transducer_join_backward(const int32_t* lens, const int32_t* lens_dev, int32_t num_utts, const float* dh, const float* h,
+                                 const int32_t* begin, int32_t Tpad, int32_t Upad1, int32_t prune_range, int32_t dim, int32_t use_tanh,
+                                 float* d_enc, float* d_pred, void* stream);
+
+/* ------------------------------------------------------------------ *
  * Reverberation + additive noise of one utterance (single channel), device arrays throughout.
  * Replaces the numpy arithmetic of the reference's dynamic data simulation: Distorter.apply_rir /
  * Distorter.add_noise (reference simulation/_distorter.py:86-154) as _Simulator.simulate uses them for one

@@ -145,6 +145,12 @@ SIGNATURES = {
     "pk2_transducer_loss_and_grad": (C.c_int, [_vp, _vp, _i64, _i32, _vp, _i64, _i64, _i32, _vp, _i64, _i64, _i32, _i32, _i32,
                                                _vp, _i64, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _sz, _vp]),
     "pk2_transducer_greedy": (C.c_int, [_vp, _vp, _i32, _vp, _i64, _i64, _i32, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "pk2_transducer_ranges": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _sz, _vp, _vp, _vp]),
+    "pk2_transducer_pruned_workspace_bytes": (_sz, [_i32] * 4),
+    "pk2_transducer_pruned_loss_and_grad": (C.c_int, [_vp, _vp, _i64, _i32, _vp, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _vp, _vp,
+                                                      _vp, _vp, _vp, _sz, _vp]),
+    "pk2_transducer_join": (C.c_int, [_vp, _vp, _i32, _vp, _i64, _i64, _vp, _i64, _i64, _vp] + [_i32] * 5 + [_vp, _vp]),
+    "pk2_transducer_join_backward": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _vp] + [_i32] * 5 + [_vp, _vp, _vp]),
     "pk2_decode_graph_create": (C.c_int, [_i32, _i32, _i64, _vp, _vp, _vp, _vp, _vp, C.POINTER(_vp)]),
     "pk2_decode_graph_create_words": (C.c_int, [_i32, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_vp)]),
     "pk2_decode_graph_link_words": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp]),

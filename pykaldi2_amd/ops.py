@@ -354,7 +354,7 @@ class CTCLoss(torch.nn.Module):
 
 
 class TransducerFunction(Function):
-    """``TransducerFunction.apply(am, lm, lengths, labels, blank, reduction, time_major)``: the transducer loss with an additive
+    """``TransducerFunction.apply(am, lm, lengths, labels, blank, reduction, time_major, prune_range)``: the transducer loss with an additive
     joint on unnormalised logits am [N, T, V] ([T, N, V] with time_major) and lm [N, U + 1, V],
     transducer.transducer_loss_and_grad under autograd.  Forward computes the loss and both gradients in one library call
     with the reduction's factors as the per-utterance weights; backward hands the stored gradients on, multiplied by the
@@ -362,16 +362,81 @@ class TransducerFunction(Function):
     ctx.status: transducer.TRANSDUCER_OK / TRANSDUCER_NUMERIC."""
 
     @staticmethod
-    def forward(ctx, am, lm, lengths, labels, blank=0, reduction="mean", time_major=False):
+    def forward(ctx, am, lm, lengths, labels, blank=0, reduction="mean", time_major=False, prune_range=None):
         N = len(labels)
         w = np.ones(N, np.float32)
         if reduction == "mean":
             w = (1.0 / (np.maximum([len(s) for s in labels], 1) * float(N))).astype(np.float32)
-        loss, grad_am, grad_lm, status = transducer.transducer_loss_and_grad(am, lm, lengths, labels, blank, w, time_major)
+        begin = None
+        if prune_range is None:
+            loss, grad_am, grad_lm, status = transducer.transducer_loss_and_grad(am, lm, lengths, labels, blank, w, time_major)
+        else:
+            loss, grad_am, grad_lm, status, begin, _ = transducer.loss_grad_and_ranges(am, lm, lengths, labels, prune_range, blank, w,
+                                                                                      time_major)
+            ctx.mark_non_differentiable(begin)
         ctx.per_sequence, ctx.status = loss, status
         ctx.save_for_backward(grad_am, grad_lm)
         ctx.utt_dim = None if reduction != "none" else (1 if time_major else 0)
         ctx.applied = [None, None]
+        if reduction == "none":
+            out = loss.to(torch.float32)
+        else:
+            if reduction == "mean":
+                loss = loss * _lib.h2d(w.astype(np.float64), loss.device)
+            out = loss.sum().to(torch.float32)
+        return out if begin is None else (out, begin)
+
+    @staticmethod
+    def backward(ctx, grad_out, *unused):
+        grads = ctx.saved_tensors
+        if ctx.utt_dim is not None:      # reduction 'none': one incoming gradient per utterance
+            go = grad_out.detach().to(torch.float32)
+            shape = [1, 1, 1]
+            shape[ctx.utt_dim] = -1
+            return (grads[0] * go.view(shape), grads[1] * go.view(-1, 1, 1)) + (None,) * 6
+        go = grad_out.detach().to(device=grads[0].device, dtype=torch.float32).reshape(-1)[:1].contiguous()
+        for i, g in enumerate(grads):
+            _lib.check(_lib.lib().pk2_scale_inplace_ratio(_lib.ptr(g), g.numel(), _lib.ptr(go),
+                                                          _lib.ptr(ctx.applied[i]) if ctx.applied[i] is not None else None,
+                                                          _lib.stream_ptr(g.device)))
+            ctx.applied[i] = go
+        return tuple(grads) + (None,) * 6
+
+
+class TransducerLoss(torch.nn.Module):
+    """The transducer (RNN-T) loss with an additive joint on UNNORMALISED logits, fused into HIP kernels that never store the
+    joint (csrc/transducer.hip): ``TransducerLoss()(am, lm, lengths, labels)`` with am [N, T, V] ([T, N, V] with
+    time_major=True), lm [N, U + 1, V] (row u: the predictor after u labels), lengths the frame counts and labels a list of
+    int sequences.  'mean' divides every loss by its label count (at least 1) and averages over the utterances, 'sum' adds
+    them, 'none' returns them.  With prune_range=S the call returns (loss, begin): begin int32 [N, T], not differentiable, the
+    pruning ranges of transducer.loss_grad_and_ranges for PrunedJoin and PrunedTransducerLoss."""
+
+    def __init__(self, blank=0, reduction="mean", time_major=False, prune_range=None):
+        super().__init__()
+        assert reduction in ("mean", "sum", "none")
+        self.blank, self.reduction, self.time_major, self.prune_range = blank, reduction, time_major, prune_range
+
+    def forward(self, am, lm, lengths, labels):
+        return TransducerFunction.apply(am, lm, lengths, labels, self.blank, self.reduction, self.time_major, self.prune_range)
+
+
+class PrunedTransducerFunction(Function):
+    """``PrunedTransducerFunction.apply(logits, begin, lengths, labels, blank, reduction)``: the transducer loss on the 4-D logits
+    [N, T, S, V] of a joiner evaluated on the band begin, transducer.pruned_loss_and_grad under autograd (the
+    TransducerFunction scheme).  ctx.per_sequence: float64 loss of every utterance, ctx.status: transducer.TRANSDUCER_OK /
+    TRANSDUCER_RANGES / TRANSDUCER_NUMERIC."""
+
+    @staticmethod
+    def forward(ctx, logits, begin, lengths, labels, blank=0, reduction="mean"):
+        N = len(labels)
+        w = np.ones(N, np.float32)
+        if reduction == "mean":
+            w = (1.0 / (np.maximum([len(s) for s in labels], 1) * float(N))).astype(np.float32)
+        loss, grad, status = transducer.pruned_loss_and_grad(logits, begin, lengths, labels, blank, w)
+        ctx.per_sequence, ctx.status = loss, status
+        ctx.save_for_backward(grad)
+        ctx.per_utt = reduction == "none"
+        ctx.applied = None
         if reduction == "none":
             return loss.to(torch.float32)
         if reduction == "mean":
@@ -380,32 +445,46 @@ class TransducerFunction(Function):
 
     @staticmethod
     def backward(ctx, grad_out):
-        grads = ctx.saved_tensors
-        if ctx.utt_dim is not None:      # reduction 'none': one incoming gradient per utterance
-            go = grad_out.detach().to(torch.float32)
-            shape = [1, 1, 1]
-            shape[ctx.utt_dim] = -1
-            return (grads[0] * go.view(shape), grads[1] * go.view(-1, 1, 1)) + (None,) * 5
-        go = grad_out.detach().to(device=grads[0].device, dtype=torch.float32).reshape(-1)[:1].contiguous()
-        for i, g in enumerate(grads):
-            _lib.check(_lib.lib().pk2_scale_inplace_ratio(_lib.ptr(g), g.numel(), _lib.ptr(go),
-                                                          _lib.ptr(ctx.applied[i]) if ctx.applied[i] is not None else None,
-                                                          _lib.stream_ptr(g.device)))
-            ctx.applied[i] = go
-        return tuple(grads) + (None,) * 5
+        grad, = ctx.saved_tensors
+        if ctx.per_utt:      # reduction 'none': one incoming gradient per utterance
+            return (grad * grad_out.detach().to(torch.float32).view(-1, 1, 1, 1),) + (None,) * 5
+        go = grad_out.detach().to(device=grad.device, dtype=torch.float32).reshape(-1)[:1].contiguous()
+        _lib.check(_lib.lib().pk2_scale_inplace_ratio(_lib.ptr(grad), grad.numel(), _lib.ptr(go),
+                                                      _lib.ptr(ctx.applied) if ctx.applied is not None else None,
+                                                      _lib.stream_ptr(grad.device)))
+        ctx.applied = go
+        return (grad,) + (None,) * 5
 
 
-class TransducerLoss(torch.nn.Module):
-    """The transducer (RNN-T) loss with an additive joint on UNNORMALISED logits, fused into HIP kernels that never store the
-    joint (csrc/transducer.hip): ``TransducerLoss()(am, lm, lengths, labels)`` with am [N, T, V] ([T, N, V] with
-    time_major=True), lm [N, U + 1, V] (row u: the predictor after u labels), lengths the frame counts and labels a list of
-    int sequences.  'mean' divides every loss by its label count (at least 1) and averages over the utterances, 'sum' adds
-    them, 'none' returns them."""
+class PrunedTransducerLoss(torch.nn.Module):
+    """The pruned transducer loss (k2's rnnt_loss_pruned) on the UNNORMALISED 4-D logits of a joiner, log-softmax included, in
+    HIP (csrc/transducer_pruned.hip): ``PrunedTransducerLoss()(logits, begin, lengths, labels)`` with logits [N, T, S, V],
+    row (t, s) for frame t and predictor row begin[t] + s, begin int32 [N, T] from TransducerLoss(prune_range=S).  The
+    reductions are TransducerLoss's."""
 
-    def __init__(self, blank=0, reduction="mean", time_major=False):
+    def __init__(self, blank=0, reduction="mean"):
         super().__init__()
         assert reduction in ("mean", "sum", "none")
-        self.blank, self.reduction, self.time_major = blank, reduction, time_major
+        self.blank, self.reduction = blank, reduction
 
-    def forward(self, am, lm, lengths, labels):
-        return TransducerFunction.apply(am, lm, lengths, labels, self.blank, self.reduction, self.time_major)
+    def forward(self, logits, begin, lengths, labels):
+        return PrunedTransducerFunction.apply(logits, begin, lengths, labels, self.blank, self.reduction)
+
+
+class PrunedJoin(Function):
+    """``PrunedJoin.apply(enc, pred, begin, lengths, label_counts, S, tanh=True)``: h[n, t, s, :] = tanh(enc[n, t, :] +
+    pred[n, begin[t] + s, :]) as [N, T, S, J], transducer.join_pruned under autograd: one launch forward, one backward, the
+    gathered copies of enc and pred never made."""
+
+    @staticmethod
+    def forward(ctx, enc, pred, begin, lengths, label_counts, S, tanh=True):
+        h = transducer.join_pruned(enc, pred, begin, lengths, label_counts, S, tanh)
+        ctx.save_for_backward(h, begin)
+        ctx.args = (list(lengths), list(label_counts), pred.shape[1], tanh)
+        return h
+
+    @staticmethod
+    def backward(ctx, dh):
+        h, begin = ctx.saved_tensors
+        d_enc, d_pred = transducer.join_pruned_backward(dh, h, begin, *ctx.args)
+        return (d_enc, d_pred) + (None,) * 5
