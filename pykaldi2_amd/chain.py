@@ -103,6 +103,9 @@ class DenominatorGraph:
             _lib.check(_lib.lib().pk2_den_graph_debug_persist2_table(self._h, which, _lib.ptr(info), None, None, None))
             pl[name + "_table"] = (int(info[0]), int(info[1]))
             pl[name + "_direct_arcs"] = int(info[3])
+            # the row epilogue of that direction: 1 = batched, 0 = row by row (PK2_DP2_EPI=0 when the graph
+            # was created, an ordering with streamed pieces, or more than two rows per thread), -1 = no persistent layout
+            pl[name + "_epilogue"] = int(_lib.lib().pk2_den_graph_persist2_epilogue(self._h, which))
         return pl
 
     def debug_persist2_table(self, which):

@@ -53,6 +53,7 @@ struct DenPersist2Params {
   const float* pi_pos;          // pi at the forward ordering's vector positions (fwd_direct)
   short task_seq[kMaxTasks];
   unsigned char task_dir[kMaxTasks];
+  int epi;                      // the batched row epilogue (run_fwd2 / run_bwd2 <., ., ., EPI>; pk2_den_graph::p2_epi) in the orderings without streamed pieces
 };
 typedef __attribute__((address_space(4))) const DenPersist2Params CParams2;
 typedef __attribute__((address_space(4))) const DevPersist2 CDev2;
@@ -674,6 +675,49 @@ __device__ __forceinline__ float row_val(const Lds2& L, uint64_t cmask, int q) {
   return v;
 }
 
+// The batched row epilogue (EPI).  row_val() above costs a thread two DEPENDENT LDS round trips per row (the
+// 16-bit maps, then the sums they point at) and two more per wave carry that ANY lane of its wave owns (the carry's row, then
+// the carry), entry after entry: 8 - 12 round trips per frame on the bench graph, for a handful of additions.  What the maps
+// and the carries' rows say never changes during a task, so it is read once, in front of the frame loop: per entry the LDS
+// byte addresses of its first row's sum of pass A, of pass B and of the first carry that belongs to it (`zero`: the address
+// of a word that holds 0, where there is none).  A frame issues all reads of all entries back to back and waits once.
+// Further carries of that row and the further rows of a state with several (multi-entry graphs) go through row_val() with
+// `rest`, the carries no first row has taken -- usually none, and then no lane of the wave enters those loops.
+template <int PSPT>
+struct EpiRegs {
+  uint32_t a[PSPT], b[PSPT], c[PSPT];
+  uint64_t rest;
+  __device__ __forceinline__ void init(const Lds2& L, uint64_t cmask, const int (&row)[PSPT], uint32_t zero) {
+    rest = cmask;
+#pragma unroll
+    for (int i = 0; i < PSPT; ++i) {
+      a[i] = b[i] = c[i] = zero;
+      const int q = row[i];
+      if (q < 0) continue;
+      const int ra = L.mapA[q], rb = L.mapB[q];
+      if (ra >= 0) a[i] = lds_addr(L.accA + ra);
+      if (rb >= 0) b[i] = lds_addr(L.accB + rb);
+      uint64_t m = rest;
+      while (m) {
+        const int k = __builtin_ctzll(m);
+        m &= m - 1;
+        if (L.wcrow[k] == q) { c[i] = lds_addr(L.wcarry + k); rest &= ~(1ull << k); break; }
+      }
+    }
+  }
+};
+template <int PSPT> struct NoEpi { };
+// The carries in `rest` that belong to row q (row_val's loop).
+__device__ __forceinline__ float rest_carries(const Lds2& L, uint64_t rest, int q, float v) {
+  uint64_t m = rest;
+  while (m) {
+    const int k = __builtin_ctzll(m);
+    m &= m - 1;
+    if (L.wcrow[k] == q) v += L.wcarry[k];
+  }
+  return v;
+}
+
 template <int NW>
 __device__ __forceinline__ void block_sum2(float& u, float& v, float* red) {
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -706,7 +750,7 @@ __device__ __forceinline__ void load_frame_regs(CDev2& o, int rank, FrameRegs& r
 }
 
 // alpha recursion of sequence g (T frames).
-template <bool STREAM, int PSPT, bool DIRECT>
+template <bool STREAM, int PSPT, bool DIRECT, bool EPI>
 __device__ __noinline__ void run_fwd2(CParams2* pp_, DenPersistCtl* ctl_, DenPersistCtl::Team* team_,
                                       unsigned* nbar, int g_, int T_, int rank_, float* ring_, float* pring_) {
   CParams2* pp = uni(pp_);
@@ -759,6 +803,7 @@ __device__ __noinline__ void run_fwd2(CParams2* pp_, DenPersistCtl* ctl_, DenPer
   }
   // own words of the three frame slots start as "not yet written"
   if (tid < 3 * kPWords) st_agent(pring + ((tid / kPWords) * kPR + rank) * kPWords + tid % kPWords, __uint_as_float(kRingSentinel));
+  if constexpr (EPI) { if (tid == 0) L.tot[3] = 0.f; }      // (the word the batched epilogue reads where a row has no entry)
   if (!team_barrier(ctl, team, nbar, L.abort)) return;
   uint64_t cmask = 0;
   for (int k = 0; k < kSegs * kPW; ++k) {
@@ -767,6 +812,20 @@ __device__ __noinline__ void run_fwd2(CParams2* pp_, DenPersistCtl* ctl_, DenPer
 #pragma unroll
     for (int i = 0; i < PSPT; ++i) mine = mine || (st_ok[i] && q >= st_lo[i] && q < st_hi[i]);
     if (q >= 0 && mine) cmask |= 1ull << k;
+  }
+  // EPI: the first row of every own state (bench graph: its only one) by precomputed addresses, its leak term in a register
+  static_assert(!(EPI && STREAM), "the batched epilogue is for the orderings without streamed pieces");
+  typename std::conditional<EPI, EpiRegs<PSPT>, NoEpi<PSPT>>::type ep;
+  int e_q[PSPT]; float e_lk[PSPT]; uint32_t e_x[PSPT];
+  if constexpr (EPI) {
+    const uint32_t zero = lds_addr(L.tot + 3);
+#pragma unroll
+    for (int i = 0; i < PSPT; ++i) {
+      e_q[i] = st_ok[i] && st_hi[i] > st_lo[i] ? st_lo[i] : -1;
+      e_lk[i] = e_q[i] >= 0 ? L.leak[e_q[i]] : 0.f;
+      e_x[i] = e_q[i] >= 0 ? lds_addr(L.xown + e_q[i]) : zero;
+    }
+    ep.init(L, cmask, e_q, zero);
   }
 
   const size_t f0 = (size_t)g * (d.Tmax + 1);
@@ -868,13 +927,56 @@ __device__ __noinline__ void run_fwd2(CParams2* pp_, DenPersistCtl* ctl_, DenPer
       if (publish) prefetch(t + 1);
     }, publish);
     DP_TL(0, 4);
-    if constexpr (STREAM) lds_only_barrier(); else __syncthreads();      // (the row sums are in LDS; a streaming frame has piece loads in flight)
+    DP_WB();
+    // (EPI: the barrier orders LDS only, as in a streaming frame -- the next frame's x prefetch stays in flight behind it)
+    if constexpr (STREAM || EPI) lds_only_barrier(); else __syncthreads();      // (the row sums are in LDS; a streaming frame has piece loads in flight)
+    DP_WE();
+    DP_T(10);
     if (rank == 0 && tid == 0) G(d.asum)[f0 + t] = as;
     const float lk = d.leaky * as, inv_as = 1.0f / as;
     // rows are virtual states (dst, pdf); a thread per real state sums its rows and adds the peeled self-loop.  First
     // only what the other workgroups wait for: the ring entries, then (once they are in L2) the partial sum.
     gfloat* ring_n = ring + (size_t)((t + 1) & 1) * p.rpad;
     float outv[PSPT], loopv[PSPT], loc = 0.f, unused = 0.f;
+    if constexpr (EPI) {
+      float ra[PSPT], rb[PSPT], rc[PSPT], rx[PSPT], v0[PSPT];
+#pragma unroll
+      for (int i = 0; i < PSPT; ++i) { ra[i] = lds_load(ep.a[i]); rb[i] = lds_load(ep.b[i]); rc[i] = lds_load(ep.c[i]); rx[i] = lds_load(e_x[i]); }
+      DP_LANDED();
+      DP_T(11);
+#pragma unroll
+      for (int i = 0; i < PSPT; ++i) {
+        // (a state without a row: every address is the zero word's, q = -1 matches no direct arc -- v0 = 0)
+        float rv = (ra[i] + rb[i]) + rc[i];
+        if (ep.rest) rv = rest_carries(L, ep.rest, e_q[i], rv);
+        if constexpr (DIRECT) rv = dr.add_to(e_q[i], rv);
+        v0[i] = (rv + lk * e_lk[i]) * rx[i] * inv_as;
+        float sum = v0[i];
+        if (st_ok[i]) {
+          for (int q = st_lo[i] + 1; q < st_hi[i]; ++q) {       // (a state entered with several pdfs: its further rows)
+            float rw = row_val<STREAM>(L, ep.rest, q);
+            if constexpr (DIRECT) rw = dr.add_to(q, rw);
+            const float v = (rw + lk * L.leak[q]) * L.xown[q] * inv_as;
+            L.aux[q] = v;
+            sum += v;
+          }
+        }
+        loopv[i] = 0.f;
+        if (st_pl[i] > 0.f) { loopv[i] = (own_a[i] + lk * st_pi[i]) * st_pl[i] * xlr[i] * inv_as; sum += loopv[i]; }
+        outv[i] = sum;
+        own_a[i] = sum;
+        loc += sum;
+      }
+      DP_T(12);
+#pragma unroll
+      for (int i = 0; i < PSPT; ++i) {
+        if (e_q[i] >= 0) L.aux[e_q[i]] = v0[i];      // (kept for the history stores, as below)
+        if (!st_ok[i] || !publish) continue;
+        if constexpr (DIRECT) ring_store(ring_n + st_pos[i], outv[i]);
+        else ring_store(ring_n + g0 + tid + i * kPT, outv[i]);
+      }
+      DP_T(13);
+    } else {
 #pragma unroll
     for (int i = 0; i < PSPT; ++i) {
       outv[i] = 0.f; loopv[i] = 0.f;
@@ -893,6 +995,7 @@ __device__ __noinline__ void run_fwd2(CParams2* pp_, DenPersistCtl* ctl_, DenPer
       outv[i] = sum;
       own_a[i] = sum;          // alpha[t+1] of the own state: the next frame's loop term
       loc += sum;
+    }
     }
     DP_T(5);
     DP_TL(0, 5);
@@ -923,7 +1026,7 @@ __device__ __noinline__ void run_fwd2(CParams2* pp_, DenPersistCtl* ctl_, DenPer
 // (lU alike without pi), and the per-virtual-state weights are constants of the graph (the forward layout's row_leak /
 // row_psum).  So the producer of w[t+1] publishes, WITH its slice, its share of the sums frame t is going to compute: a
 // frame knows c[t] before its first arc, scales its rows as soon as they are summed, and one exchange per frame is left.
-template <bool STREAM, int PSPT, bool DIRECT>
+template <bool STREAM, int PSPT, bool DIRECT, bool EPI>
 __device__ __noinline__ void run_bwd2(CParams2* pp_, DenPersistCtl* ctl_, DenPersistCtl::Team* team_,
                                       unsigned* nbar, int g_, int T_, int rank_, float* ring_, float* pring_) {
   CParams2* pp = uni(pp_);
@@ -974,6 +1077,7 @@ __device__ __noinline__ void run_bwd2(CParams2* pp_, DenPersistCtl* ctl_, DenPer
     for (int r = tid; r < nrows; r += kPT) L.pdfl[r] = (short)p.loop_pdf[row0 + r];
   }
   if (tid < 3 * kPWords) st_agent(pring + ((tid / kPWords) * kPR + rank) * kPWords + tid % kPWords, __uint_as_float(kRingSentinel));
+  if constexpr (EPI) { if (tid == 0) L.tot[3] = 0.f; }      // (run_fwd2)
   if (!team_barrier(ctl, team, nbar, L.abort)) return;
   uint64_t cmask = 0;
   for (int k = 0; k < kSegs * kPW; ++k) {
@@ -982,6 +1086,14 @@ __device__ __noinline__ void run_bwd2(CParams2* pp_, DenPersistCtl* ctl_, DenPer
 #pragma unroll
     for (int i = 0; i < PSPT; ++i) mine = mine || (st_ok[i] && q == tid + i * kPT);
     if (q >= 0 && mine) cmask |= 1ull << k;
+  }
+  static_assert(!(EPI && STREAM), "the batched epilogue is for the orderings without streamed pieces");
+  typename std::conditional<EPI, EpiRegs<PSPT>, NoEpi<PSPT>>::type ep;
+  int e_q[PSPT];
+  if constexpr (EPI) {
+#pragma unroll
+    for (int i = 0; i < PSPT; ++i) e_q[i] = st_ok[i] ? tid + i * kPT : -1;
+    ep.init(L, cmask, e_q, lds_addr(L.tot + 3));
   }
 
   const size_t f0 = (size_t)g * (d.Tmax + 1);
@@ -1091,12 +1203,32 @@ __device__ __noinline__ void run_bwd2(CParams2* pp_, DenPersistCtl* ctl_, DenPer
       if (t >= 2) prefetch(t - 2);          // (xw is free again; xl_next becomes xl_prev at the end of the frame)
     }, publish);
     DP_TL(1, 4);
-    if constexpr (STREAM) lds_only_barrier(); else __syncthreads();
+    DP_WB();
+    if constexpr (STREAM || EPI) lds_only_barrier(); else __syncthreads();      // (EPI: run_fwd2)
+    DP_WE();
+    DP_T(10);
     // rows are source states: btilde'[t, s] = row + peeled loop, then beta-hat[t, s] with the sums received above
     const float cu = lB + d.wu * lU;
     const float inv_c = cu > 0.f ? 1.0f / cu : 0.f;
     const float lkr = d.leaky * lB * inv_c;
     float vs[PSPT];
+    if constexpr (EPI) {
+      float ra[PSPT], rb[PSPT], rc[PSPT];
+#pragma unroll
+      for (int i = 0; i < PSPT; ++i) { ra[i] = lds_load(ep.a[i]); rb[i] = lds_load(ep.b[i]); rc[i] = lds_load(ep.c[i]); }
+      DP_LANDED();
+      DP_T(11);
+#pragma unroll
+      for (int i = 0; i < PSPT; ++i) {
+        float v = (ra[i] + rb[i]) + rc[i];
+        if (ep.rest) v = rest_carries(L, ep.rest, e_q[i], v);
+        if constexpr (DIRECT) v = dr.add_to(e_q[i], v);
+        if (st_pl[i] > 0.f) v += st_pl[i] * xl_cur[i] * bh[i];
+        vs[i] = st_ok[i] ? v : 0.f;
+        bh[i] = st_ok[i] ? v * inv_c + lkr : bh[i];
+      }
+      DP_T(12);
+    } else {
 #pragma unroll
     for (int i = 0; i < PSPT; ++i) {
       vs[i] = 0.f;
@@ -1106,6 +1238,7 @@ __device__ __noinline__ void run_bwd2(CParams2* pp_, DenPersistCtl* ctl_, DenPer
       if (st_pl[i] > 0.f) v += st_pl[i] * xl_cur[i] * bh[i];
       vs[i] = v;
       bh[i] = v * inv_c + lkr;
+    }
     }
     DP_T(5);
     DP_TL(1, 5);
@@ -1187,16 +1320,27 @@ __global__ void __launch_bounds__(kPT) den_persist2_kernel(const DenPersist2Para
     }
     // (PSPT: rows / states / own virtual states a thread handles in the row epilogues -- 2 when no rank has more than
     // 2 * kPT of any of them: the per-state constants then take half the registers)
+    // (three entries per thread since round 4: graphs of 33 - 49 k states have 1025 .. 1536 rows per rank)
+    // EPI (p.epi, the default; PK2_DP2_EPI=0 when the graph is created keeps the earlier epilogue): the batched row epilogue,
+    // in the orderings without streamed pieces and with two entries per thread -- with three or four its addresses are
+    // registers the kernels do not have (scratch 16 -> 72 / 52 -> 168 bytes per lane forward, 132 -> 172 backward), and no
+    // graph of that size has been measured: they keep the row-by-row form
+#define PK2_RUN2(fn, STREAM, DIRECT, EPI)                                                                               \
+  do {                                                                                                                  \
+    if (p.pspt == 2) fn<STREAM, 2, DIRECT, EPI>(pp, ctl, team, &nbar, g, T, rank, ring, pring);                         \
+    else if (p.pspt == 3) fn<STREAM, 3, DIRECT, false>(pp, ctl, team, &nbar, g, T, rank, ring, pring);                  \
+    else fn<STREAM, kPSPT, DIRECT, false>(pp, ctl, team, &nbar, g, T, rank, ring, pring);                               \
+  } while (0)
     if (p.task_dir[k] == 0) {
-      // (three entries per thread since round 4: graphs of 33 - 49 k states have 1025 .. 1536 rows per rank)
-      if (p.fwd_stream) { if (p.pspt == 2) run_fwd2<true, 2, false>(pp, ctl, team, &nbar, g, T, rank, ring, pring); else if (p.pspt == 3) run_fwd2<true, 3, false>(pp, ctl, team, &nbar, g, T, rank, ring, pring); else run_fwd2<true, kPSPT, false>(pp, ctl, team, &nbar, g, T, rank, ring, pring); }
-      else if (p.fwd_direct) { if (p.pspt == 2) run_fwd2<false, 2, true>(pp, ctl, team, &nbar, g, T, rank, ring, pring); else if (p.pspt == 3) run_fwd2<false, 3, true>(pp, ctl, team, &nbar, g, T, rank, ring, pring); else run_fwd2<false, kPSPT, true>(pp, ctl, team, &nbar, g, T, rank, ring, pring); }
-      else { if (p.pspt == 2) run_fwd2<false, 2, false>(pp, ctl, team, &nbar, g, T, rank, ring, pring); else if (p.pspt == 3) run_fwd2<false, 3, false>(pp, ctl, team, &nbar, g, T, rank, ring, pring); else run_fwd2<false, kPSPT, false>(pp, ctl, team, &nbar, g, T, rank, ring, pring); }
+      if (p.fwd_stream) PK2_RUN2(run_fwd2, true, false, false);
+      else if (p.fwd_direct) { if (p.epi) PK2_RUN2(run_fwd2, false, true, true); else PK2_RUN2(run_fwd2, false, true, false); }
+      else { if (p.epi) PK2_RUN2(run_fwd2, false, false, true); else PK2_RUN2(run_fwd2, false, false, false); }
     } else {
-      if (p.bwd_stream) { if (p.pspt == 2) run_bwd2<true, 2, false>(pp, ctl, team, &nbar, g, T, rank, ring, pring); else if (p.pspt == 3) run_bwd2<true, 3, false>(pp, ctl, team, &nbar, g, T, rank, ring, pring); else run_bwd2<true, kPSPT, false>(pp, ctl, team, &nbar, g, T, rank, ring, pring); }
-      else if (p.bwd_direct) { if (p.pspt == 2) run_bwd2<false, 2, true>(pp, ctl, team, &nbar, g, T, rank, ring, pring); else if (p.pspt == 3) run_bwd2<false, 3, true>(pp, ctl, team, &nbar, g, T, rank, ring, pring); else run_bwd2<false, kPSPT, true>(pp, ctl, team, &nbar, g, T, rank, ring, pring); }
-      else { if (p.pspt == 2) run_bwd2<false, 2, false>(pp, ctl, team, &nbar, g, T, rank, ring, pring); else if (p.pspt == 3) run_bwd2<false, 3, false>(pp, ctl, team, &nbar, g, T, rank, ring, pring); else run_bwd2<false, kPSPT, false>(pp, ctl, team, &nbar, g, T, rank, ring, pring); }
+      if (p.bwd_stream) PK2_RUN2(run_bwd2, true, false, false);
+      else if (p.bwd_direct) { if (p.epi) PK2_RUN2(run_bwd2, false, true, true); else PK2_RUN2(run_bwd2, false, true, false); }
+      else { if (p.epi) PK2_RUN2(run_bwd2, false, false, true); else PK2_RUN2(run_bwd2, false, false, false); }
     }
+#undef PK2_RUN2
     __syncthreads();
     if (s_abort) return;
     if (tid == 0 && rank == 0) __hip_atomic_fetch_add(&ctl->done, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1283,6 +1427,7 @@ int den_persist2_launch(pk2_den_graph* g, const DenParams& dp, const float* xv, 
   p.fwd_direct = (!p.fwd_stream && g->h_p2fwd.Rt < g->h_p2fwd.R) ? 1 : 0;
   p.bwd_direct = (!p.bwd_stream && g->h_p2bwd.Rt < g->h_p2bwd.R) ? 1 : 0;
   p.pi_pos = g->d_pi_pos;
+  p.epi = g->p2_epi;
   p.ntasks = den_persist_tasks(lengths_host, N, p.task_seq, p.task_dir);
   sc.ntasks = 0;
   if (p.ntasks == 0) { *ran = true; return PK2_OK; }

@@ -730,6 +730,10 @@ static void build_persist2(pk2_den_graph* g, int64_t A2, const int32_t* arc_v, c
   bool prefix_ok = !getenv("PK2_DEN_ORDER") && !getenv("PK2_DP2_RES") && !getenv("PK2_DP2_TCAP") && !getenv("PK2_DP2_SHARED") &&
                    !getenv("PK2_DP2_ROWARRAYS");
   if (const char* env = getenv("PK2_DP2_TABLE")) prefix_ok = prefix_ok && strcmp(env, "full") != 0;
+  // The row epilogue of the orderings without streamed pieces (chain_den_persist2.hip: EPI): batched unless
+  // PK2_DP2_EPI=0 asks for the earlier row-by-row form (the A/B switch; read here, when the graph is created).
+  g->p2_epi = 1;
+  if (const char* env = getenv("PK2_DP2_EPI")) g->p2_epi = atoi(env) != 0 ? 1 : 0;
   struct ArcSet { int64_t A; const int32_t* key; const int32_t* idx; const float* prob; const float* piprob; };
   struct RowIndex { std::vector<int64_t> ptr, perm; };
   auto index_rows = [](const ArcSet& a, int rows, RowIndex* out) {
@@ -1203,6 +1207,17 @@ extern "C" int pk2_den_graph_debug_persist2(const pk2_den_graph* g, int which, i
   cp(grp_begin, h.grp_begin.data(), h.grp_begin.size() * 4); cp(row_leak, h.row_leak.data(), h.row_leak.size() * 4);
   cp(row_psum, h.row_psum.data(), h.row_psum.size() * 4);
   return PK2_OK;
+}
+
+// Reporting hook: the row epilogue the persistent kernel runs for an ordering -- 1 = batched (chain_den_persist2.hip: EPI),
+// 0 = row by row (PK2_DP2_EPI=0, an ordering with streamed pieces / more than two table chunks, or a graph whose ranks hold
+// more than two rows per thread), -1 = no layout.
+extern "C" int32_t pk2_den_graph_persist2_epilogue(const pk2_den_graph* g, int which) {
+  if (!g || (which != 0 && which != 1)) return -1;
+  const HostPersist2& h = which == 0 ? g->h_p2fwd : g->h_p2bwd;
+  if (!h.ok) return -1;
+  const bool stream = !h.sends.empty() || h.K > 2;
+  return !stream && g->p2_epi && g->p2_cap <= 2 * kPT ? 1 : 0;
 }
 
 // Test / reporting hook: the table prefix of an ordering (chain_internal.h: kDirectDeg).  info[8] = {Rt, R, entries chosen for

@@ -13,11 +13,21 @@ constexpr long long kDenSpinTicks = 1000LL * 1000 * 100;   // 1 s of the 100 MHz
 #ifdef PK2_DP_PROFILE
 // Phase timers of rank 0 / thread 0 (shader clocks, averaged over the frames of a call) and the wall-clock timeline of one
 // frame on every rank.  The counters live in `dp_` (DP_T0 declares it; helper functions receive it by reference).
-struct DpTimers { long long last; unsigned long long acc[10]; int tl_on, tl_dir, tl_rank; };
-static __device__ unsigned long long g_dp_prof[2][10];
-#define DP_T0() DpTimers dp_; dp_.last = clock64(); for (int k_ = 0; k_ < 10; ++k_) dp_.acc[k_] = 0
+// Slots 10 .. 13 take the row epilogue apart (profiles/den_epilogue.txt): 10 = the barrier in front of it, 11 = its LDS reads
+// issued -> landed, 12 = arithmetic, 13 = stores issued; slot 5 keeps what the epilogue spends outside these (the parent's
+// epilogue interleaves reads, arithmetic and stores row by row: all of it is in slot 5).  `wbar`: the same barrier's wait
+// seen by lane 0 of EVERY wave of rank 0 -- the spread over the waves is pass B's imbalance.
+constexpr int kDpSlots = 14;
+struct DpTimers { long long last; unsigned long long acc[kDpSlots]; unsigned long long wbar; long long wb0; int tl_on, tl_dir, tl_rank; };
+static __device__ unsigned long long g_dp_prof[2][kDpSlots];
+static __device__ unsigned long long g_dp_wbar[2][kPW];
+#define DP_T0() DpTimers dp_; dp_.last = clock64(); dp_.wbar = 0; for (int k_ = 0; k_ < kDpSlots; ++k_) dp_.acc[k_] = 0
 #define DP_T(k) do { const long long n_ = clock64(); dp_.acc[k] += (unsigned long long)(n_ - dp_.last); dp_.last = n_; } while (0)
-#define DP_FLUSH(dir) do { if (rank == 0 && threadIdx.x == 0) for (int k_ = 0; k_ < 10; ++k_) atomicAdd(&g_dp_prof[dir][k_], dp_.acc[k_]); } while (0)
+#define DP_WB() do { dp_.wb0 = clock64(); } while (0)
+#define DP_WE() do { dp_.wbar += (unsigned long long)(clock64() - dp_.wb0); } while (0)
+#define DP_LANDED() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
+#define DP_FLUSH(dir) do { if (rank == 0 && threadIdx.x == 0) for (int k_ = 0; k_ < kDpSlots; ++k_) atomicAdd(&g_dp_prof[dir][k_], dp_.acc[k_]); \
+                           if (rank == 0 && (threadIdx.x & 63) == 0) atomicAdd(&g_dp_wbar[dir][threadIdx.x >> 6], dp_.wbar); } while (0)
 static __device__ long long g_dp_tl[2][kPR][8];     // wall-clock (10 ns) timeline of frame 100 of the first sequence, per rank
 #define DP_TL(dir, k) do { if (g == 0 && t == 100 && threadIdx.x == 0) g_dp_tl[dir][rank][k] = wall_clock64(); } while (0)
 #define DP_TLSET(dir) do { dp_.tl_on = (g == 0 && t == 100) ? 1 : 0; dp_.tl_dir = dir; dp_.tl_rank = rank; } while (0)
@@ -32,16 +42,25 @@ static __global__ void dp_prof_print(int frames) {
              g_dp_tl[dir][r][3] - t0, g_dp_tl[dir][r][4] - t0, g_dp_tl[dir][r][5] - t0, g_dp_tl[dir][r][6] - t0);
   }
   for (int dir = 0; dir < 2; ++dir) {
+    const unsigned long long epi = g_dp_prof[dir][5] + g_dp_prof[dir][10] + g_dp_prof[dir][11] + g_dp_prof[dir][12] + g_dp_prof[dir][13];
     printf("den_persist2 %s rank 0 thread 0, shader clocks per frame over %d frames: poll + sync + stage + copies issued %llu | chunk 0 landed + barrier %llu | pass A %llu | chunk 1 landed + barrier %llu | pass B (+ streamed) %llu | barrier + epilogue %llu | wait stores + block sum + publish %llu | history + prefetch %llu | streamed segment 0 %llu | streamed segments 1.. %llu\n",
            dir ? "bwd" : "fwd", frames, g_dp_prof[dir][0] / frames, g_dp_prof[dir][1] / frames, g_dp_prof[dir][2] / frames,
-           g_dp_prof[dir][3] / frames, g_dp_prof[dir][4] / frames, g_dp_prof[dir][5] / frames, g_dp_prof[dir][6] / frames, g_dp_prof[dir][7] / frames, g_dp_prof[dir][8] / frames, g_dp_prof[dir][9] / frames);
-    for (int k = 0; k < 10; ++k) g_dp_prof[dir][k] = 0;
+           g_dp_prof[dir][3] / frames, g_dp_prof[dir][4] / frames, epi / frames, g_dp_prof[dir][6] / frames, g_dp_prof[dir][7] / frames, g_dp_prof[dir][8] / frames, g_dp_prof[dir][9] / frames);
+    printf("den_persist2 %s epilogue taken apart: barrier %llu | LDS reads issued -> landed %llu | arithmetic %llu | stores issued %llu | outside these %llu || the barrier's wait per wave 0..%d:",
+           dir ? "bwd" : "fwd", g_dp_prof[dir][10] / frames, g_dp_prof[dir][11] / frames, g_dp_prof[dir][12] / frames, g_dp_prof[dir][13] / frames,
+           g_dp_prof[dir][5] / frames, kPW - 1);
+    for (int w = 0; w < kPW; ++w) { printf(" %llu", g_dp_wbar[dir][w] / frames); g_dp_wbar[dir][w] = 0; }
+    printf("\n");
+    for (int k = 0; k < kDpSlots; ++k) g_dp_prof[dir][k] = 0;
   }
 }
 #else
 struct DpTimers { };
 #define DP_T0() DpTimers dp_; (void)dp_
 #define DP_T(k) do { } while (0)
+#define DP_WB() do { } while (0)
+#define DP_WE() do { } while (0)
+#define DP_LANDED() do { } while (0)
 #define DP_FLUSH(dir) do { } while (0)
 #define DP_TL(dir, k) do { } while (0)
 #define DP_TLSET(dir) do { } while (0)
