@@ -19,7 +19,11 @@ frame, the band of -prune_range predictor rows that its occupancies favour.  Thr
 encoder's logits, V -> J on the table rows, J -> V behind the join) make a nonlinear joiner that ops.PrunedJoin evaluates on
 that band only and ops.PrunedTransducerLoss scores (csrc/transducer_pruned.hip); the loss is simple_scale * simple + pruned.
 The layers are trained by the table's optimiser and their gradients all-reduced as the table's is.  The printed greedy phone
-error rate stays that of the ADDITIVE head: decoding through the joiner is not built.
+error rate is that of the ADDITIVE head.
+
+With -beam B (and -beam_tokens K) a print step also runs transducer.beam_search (csrc/transducer_beam.hip)
+and prints its phone error rate next to the greedy one: that of the additive head, and with -joiner also the joiner's,
+decoded through the joiner.
 """
 import argparse
 import json
@@ -62,9 +66,12 @@ def parse_config(argv=None):
     parser.add_argument("-table_lr", type=float, default=1e-2, help="learning rate of the predictor table's optimiser")
     parser.add_argument("-max_symbols", default=8, type=int, help="phones the greedy decoding may emit per frame")
     parser.add_argument("-joiner", default=0, type=int, metavar='J', help="train a nonlinear joiner of width J on the pruned band "
-                        "(the second stage); the printed error rate stays the additive head's, decoding through the joiner is not built")
+                        "(the second stage); the greedy error rate stays the additive head's, -beam also decodes through the joiner")
     parser.add_argument("-prune_range", default=5, type=int, metavar='S', help="(-joiner) predictor rows per frame in the band")
     parser.add_argument("-simple_scale", default=0.5, type=float, metavar='X', help="(-joiner) the loss is X * simple + pruned")
+    parser.add_argument("-beam", default=0, type=int, metavar='B', help="also decode the printed minibatches by beam search of width B "
+                        "(at most min(max_symbols, 31) phones per frame) and print its phone error rate")
+    parser.add_argument("-beam_tokens", default=8, type=int, metavar='K', help="(-beam) phones that may extend a hypothesis per round")
     args = parser.parse_args(argv)
     with open(args.config) as f:
         config = yaml.safe_load(f)
@@ -167,8 +174,9 @@ def run_train_epoch(model, table, joiner, optimizer, table_optimizer, criterion,
     losses = utils.AverageMeter('Loss', ':.4e')
     per = utils.AverageMeter('PER', ':.4f')
     grad_norm = utils.AverageMeter('grad_norm', ':.4e')
+    beam_per = {k: utils.AverageMeter(k, ':.4f') for k in (['beamPER'] + (['joinerPER'] if joiner else []) if args.beam else [])}
     n_batches = max(1, int(args.sweep_size * 3600 / (12.3 * args.batch_size)))
-    progress = utils.ProgressMeter(n_batches, batch_time, losses, per, grad_norm, prefix="Epoch: [{}]".format(epoch))
+    progress = utils.ProgressMeter(n_batches, batch_time, losses, per, *beam_per.values(), grad_norm, prefix="Epoch: [{}]".format(epoch))
     text_rng = np.random.default_rng(4321 + epoch + hvd.rank())
     spec = args.spec.epoch(hvd.rank(), epoch) if args.spec is not None else None
     sub = args.subsample
@@ -220,6 +228,17 @@ def run_train_epoch(model, table, joiner, optimizer, table_optimizer, criterion,
             grad_norm.update(norm.item())
             losses.update(loss.item() / float(np.sum(sub_frames)), int(np.sum(sub_frames)))
             per.update(errs / max(words, 1), words)
+            if args.beam:
+                kw = dict(blank=args.blank, beam=args.beam, top_tokens=args.beam_tokens, max_symbols=min(args.max_symbols, transducer.MAX_BEAM_SYMBOLS))
+                found = {'beamPER': transducer.beam_search(prediction, sub_frames, table, time_major=not args.transformer, **kw)}
+                if joiner:
+                    with th.no_grad():
+                        found['joinerPER'] = transducer.beam_search(joiner["enc"](prediction), sub_frames, joiner["pred"](table),
+                                                                    joiner=(joiner["out"].weight, joiner["out"].bias),
+                                                                    time_major=not args.transformer, **kw)
+                for k, nbest in found.items():
+                    errs, words = score.wer([h[0][0] if h else [] for h in nbest], labels, device="cpu")
+                    beam_per[k].update(errs / max(words, 1), words)
             batch_time.update(time.time() - end)
             if hvd.rank() == 0:
                 progress.print(i)
@@ -227,6 +246,8 @@ def run_train_epoch(model, table, joiner, optimizer, table_optimizer, criterion,
     if hvd.rank() == 0:
         print("Epoch {}: loss per frame {:.4f}, greedy phone error rate {:.4f} (over the printed minibatches)".format(
             epoch, losses.avg, per.avg))
+        for k, m in beam_per.items():
+            print("Epoch {}: beam {} phone error rate {:.4f} ({})".format(epoch, args.beam, m.avg, k))
 
 
 if __name__ == '__main__':

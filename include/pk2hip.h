@@ -449,6 +449,40 @@ int pk2_transducer_join_backward(const int32_t* lens, const int32_t* lens_dev, i
                                  float* d_enc, float* d_pred, void* stream);
 
 /* ------------------------------------------------------------------ *
+ * Transducer beam search for a stateless predictor of context 1 (csrc/transducer_beam.hip): time-synchronous,
+ * at most R = max_symbols labels per frame, one launch, one workgroup per utterance over all its frames.  A hypothesis is a
+ * blank-free prefix h with a float64 log-probability; the joint depends on (t, last(h)) only, last(()) = blank.
+ *   A = {(): 0};  for t < T_n:  Out = {};  for r = 0..R:
+ *     lp_h = log_softmax(z(t, last(h)))                    for h in A (float32)
+ *     Out[h] = logadd(Out[h], A[h] + lp_h[blank])          merged by prefix identity, new entries appended in slot order
+ *     if r == R: break
+ *     cand = {h + (c,): A[h] + lp_h[c]}, c the K = min(top_tokens, V - 1) non-blank columns of the largest z (ties: lower column)
+ *     A = the `beam` largest of cand in candidate order (parent slot, then rank); ties: the lower candidate
+ *   A = the `beam` largest of Out in the order they were made; ties: the entry made first
+ * join_dim = 0, the additive head: z(t, p) = x[t, :] + rows[p, :] as a float32 sum (x = am [N][T][V], rows = table [V][V]).
+ * join_dim = J >= 1, the joiner: z(t, p) = tanhf(x[t, :] + rows[p, :]) . w_out^T + b_out on v_mfma_f32_32x32x2_f32 (x = enc
+ * [N][T][J], rows = pred [V][J], w_out [V][J] by w_stride, b_out [V]).
+ * ------------------------------------------------------------------ */
+#define PK2_TRANSDUCER_BEAM_MAX 32          /* a round's hypotheses are the 32 rows of one MFMA tile */
+#define PK2_TRANSDUCER_BEAM_MAX_TOKENS 32
+#define PK2_TRANSDUCER_BEAM_MAX_JOIN 512
+#define PK2_TRANSDUCER_BEAM_MAX_SYMBOLS 31  /* Out holds beam * (R + 1) <= 1024 prefixes, one per thread */
+size_t pk2_transducer_beam_workspace_bytes(int32_t num_utts, int32_t T, int32_t num_classes, int32_t beam, int32_t max_symbols,
+                                           int32_t join_dim);
+/* lengths: N frame counts in [0, T], the same on the host and (lengths_dev) on the device; frame t of utterance n at
+ * x[n * seq_stride + t * frame_stride], unit column stride, rows t >= T_n are not read.  Outputs, device: out_tokens
+ * i32[N][beam][T * max_symbols] (left-aligned, -1 behind), out_lens i32[N][beam] (-1: unused slot), out_scores f64[N][beam]
+ * non-increasing (-inf: unused), out_status i32[N]: PK2_TRANSDUCER_OK, or PK2_TRANSDUCER_NUMERIC when a row's maximum or
+ * normaliser was not finite (all slots unused, the other utterances unaffected).  T_n = 0: the empty prefix with score 0.
+ * beam, top_tokens, max_symbols or join_dim beyond their limits: PK2_ERR_LIMIT; anything else wrong: PK2_ERR_INVALID, before
+ * the launch.  workspace: device, 256-byte aligned.  Bit-reproducible; an utterance's result does not depend on the others. */
+int pk2_transducer_beam_search(const int32_t* lengths, const int32_t* lengths_dev, int32_t num_utts, const float* x, int64_t seq_stride,
+                               int64_t frame_stride, int32_t T, const float* rows, int64_t rows_stride, const float* w_out,
+                               int64_t w_stride, const float* b_out, int32_t join_dim, int32_t num_classes, int32_t blank, int32_t beam,
+                               int32_t top_tokens, int32_t max_symbols, int32_t* out_tokens, int32_t* out_lens, double* out_scores,
+                               int32_t* out_status, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------ *
  * Reverberation + additive noise of one utterance (single channel), device arrays throughout.
  * Replaces the numpy arithmetic of the reference's dynamic data simulation: Distorter.apply_rir /
  * Distorter.add_noise (reference simulation/_distorter.py:86-154) as _Simulator.simulate uses them for one

@@ -152,6 +152,9 @@ SIGNATURES = {
                                                       _vp, _vp, _vp, _sz, _vp]),
     "pk2_transducer_join": (C.c_int, [_vp, _vp, _i32, _vp, _i64, _i64, _vp, _i64, _i64, _vp] + [_i32] * 5 + [_vp, _vp]),
     "pk2_transducer_join_backward": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _vp] + [_i32] * 5 + [_vp, _vp, _vp]),
+    "pk2_transducer_beam_workspace_bytes": (_sz, [_i32] * 6),
+    "pk2_transducer_beam_search": (C.c_int, [_vp, _vp, _i32, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _i64, _vp] + [_i32] * 6 + [_vp] * 5 +
+                                   [_sz, _vp]),
     "pk2_decode_graph_create": (C.c_int, [_i32, _i32, _i64, _vp, _vp, _vp, _vp, _vp, C.POINTER(_vp)]),
     "pk2_decode_graph_create_words": (C.c_int, [_i32, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_vp)]),
     "pk2_decode_graph_link_words": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp]),

@@ -51,7 +51,10 @@ FILE_FLAGS = {"lattice_decode.hip": ["-ffp-contract=off"], "lattice_decode_frame
               # the three instances of td_product stage exp(x - max) alike (=on, as above); plain f32 VALU only
               "transducer.hip": ["-ffp-contract=on", "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
               # the long-row and the short-row instances of tp_rows / tp_grad round a row's terms alike; plain f32 VALU only
-              "transducer_pruned.hip": ["-ffp-contract=on", "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+              "transducer_pruned.hip": ["-ffp-contract=on", "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+              # the scores round like the float64 restatement's separate operations and the row pass forms lp alike in
+              # both joints; plain f32 VALU only
+              "transducer_beam.hip": ["-ffp-contract=off", "-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 # experiment builds: PK2_FILE_FLAGS="gemm_f32.hip:-mllvm,-align-loops=64;..." adds flags to single sources
 for _spec in os.environ.get("PK2_FILE_FLAGS", "").split(";"):
     if ":" in _spec:

@@ -21,6 +21,11 @@ predictor rows per frame only:
     loss, grad, status = transducer.pruned_loss_and_grad(logits, begin, lengths, labels)     # logits [N, T, S, V]
 
 ops.PrunedTransducerLoss is the autograd form of the last.  Its logits have no restriction on their numeric range.
+
+Beam search for either head (csrc/transducer_beam.hip), one launch for all frames:
+
+    nbest = transducer.beam_search(am, lengths, table, nbest=4, blank=0, beam=8)                       # the additive head
+    nbest = transducer.beam_search(enc, lengths, pred, joiner=(w_out, b_out), blank=0, beam=8)       # through the joiner
 """
 import numpy as np
 import torch
@@ -33,6 +38,8 @@ TRANSDUCER_RANGES = 2                         # PK2_TRANSDUCER_RANGES (the prune
 MAX_LABELS = 1023                             # PK2_TRANSDUCER_MAX_LABELS
 MAX_PRUNE_RANGE = 32                          # PK2_TRANSDUCER_MAX_PRUNE_RANGE
 PRUNED_SHORT_ROWS = 256                       # PK2_TRANSDUCER_PRUNED_SHORT_ROWS: below it 16 lanes serve a row, else a wave
+MAX_BEAM, MAX_BEAM_TOKENS = 32, 32            # PK2_TRANSDUCER_BEAM_MAX / PK2_TRANSDUCER_BEAM_MAX_TOKENS
+MAX_BEAM_JOIN, MAX_BEAM_SYMBOLS = 512, 31     # PK2_TRANSDUCER_BEAM_MAX_JOIN / PK2_TRANSDUCER_BEAM_MAX_SYMBOLS
 
 
 def _check_range(S):
@@ -276,3 +283,82 @@ def greedy_decode(am, lengths, table, blank=0, max_symbols=8, time_major=False):
     tokens, lens = greedy_decode_raw(am, lengths, table, blank, max_symbols, time_major)
     flat = torch.cat([tokens, lens[:, None]], dim=1).cpu().numpy()
     return [flat[n, :flat[n, -1]].tolist() for n in range(flat.shape[0])]
+
+
+def _limit(value, hi, name):
+    if isinstance(value, bool) or int(value) != value or not 1 <= value <= hi:
+        raise ValueError("transducer: %s %r outside 1..%d" % (name, value, hi))
+    return int(value)
+
+
+def beam_search_raw(am_or_enc, lengths, table_or_pred, blank=0, beam=4, top_tokens=8, max_symbols=2, joiner=None, time_major=False):
+    """Transducer beam search with a stateless predictor of context 1 on the device (csrc/transducer_beam.hip):
+    one launch, nothing read back.  Time-synchronous; per frame at most max_symbols (1..31) rounds in which every hypothesis
+    moves on with the blank and is extended by the top_tokens (1..32, clamped to V - 1) non-blank columns of its largest
+    logit, the `beam` (1..32) most probable extensions going into the next round; at the frame's end the blank moves, merged
+    by prefix, are cut to the `beam` most probable.  Scores are float64 log-probabilities, the log-softmax float32.
+
+    additive head (joiner=None): am float32 [N, T, V] ([T, N, V] with time_major) and table [V, V], greedy_decode's operands:
+    z(t, prev) = am[t] + table[prev].  joiner=(w_out [V, J], b_out [V]): enc [N, T, J] (the joiner's enc layer applied to the
+    encoder output) and pred [V, J] (its pred layer applied to the table rows): z(t, prev) = tanh(enc[t] + pred[prev]) w_out^T
+    + b_out, J <= 512.  Unit column stride, any other strides (served in place); rows past a length are never read.
+    Returns device tensors (tokens int32 [N, beam, T * max_symbols] left-aligned with -1 behind, lens int32 [N, beam] with -1
+    for unused slots, scores float64 [N, beam] non-increasing with -inf for unused slots, status int32 [N]): status 3
+    (TRANSDUCER_NUMERIC) = a row's maximum or normaliser was not finite, all slots unused; the others are unaffected.  An
+    utterance of 0 frames returns the empty prefix with score 0."""
+    x = am_or_enc
+    if x.dim() != 3 or x.dtype != torch.float32 or x.stride(2) != 1:
+        raise ValueError("transducer: %s must be float32 [N, T, %s] with a unit column stride" % (("enc", "J") if joiner else ("am", "V")))
+    x = x.detach().transpose(0, 1) if time_major else x.detach()
+    N, T, D = x.shape
+    rows = table_or_pred
+    if rows.dim() != 2 or rows.dtype != torch.float32 or rows.stride(1) != 1 or rows.device != x.device or rows.shape[1] != D:
+        raise ValueError("transducer: %s must be float32 [V, %d] with a unit column stride, on the first operand's device"
+                         % ("pred" if joiner else "the table", D))
+    V = rows.shape[0]
+    w = b = None
+    if joiner is None:
+        if V != D:
+            raise ValueError("transducer: the table must be [%d, %d], not %s" % (D, D, tuple(rows.shape)))
+    else:
+        w, b = joiner
+        if D > MAX_BEAM_JOIN:
+            raise ValueError("transducer: joiner width %d beyond %d" % (D, MAX_BEAM_JOIN))
+        if (w.dim() != 2 or tuple(w.shape) != (V, D) or w.dtype != torch.float32 or w.stride(1) != 1 or w.device != x.device or
+                b.dim() != 1 or b.shape[0] != V or b.dtype != torch.float32 or b.device != x.device):
+            raise ValueError("transducer: w_out %s / b_out %s do not go with enc %s and pred %s"
+                             % (tuple(w.shape), tuple(b.shape), tuple(am_or_enc.shape), tuple(rows.shape)))
+        w, b = w.detach(), b.detach().contiguous()
+    beam, top_tokens = _limit(beam, MAX_BEAM, "beam"), _limit(top_tokens, MAX_BEAM_TOKENS, "top_tokens")
+    max_symbols = _limit(max_symbols, MAX_BEAM_SYMBOLS, "max_symbols")
+    lengths = np.asarray(lengths, dtype=np.int64).reshape(-1)
+    if N < 1 or lengths.shape[0] != N or lengths.min() < 0 or lengths.max() > T:
+        raise ValueError("transducer: %d lengths for %d utterances of at most %d frames" % (lengths.shape[0], N, T))
+    if V < 2 or not 0 <= blank < V:
+        raise ValueError("transducer: blank %d of %d columns" % (blank, V))
+    _lib.require_gpu()
+    L = _lib.lib()
+    host = torch.from_numpy(lengths.astype(np.int32)).pin_memory()
+    dev = host.to(x.device, non_blocking=True)
+    rows = rows.detach()
+    J = 0 if joiner is None else D
+    ws = _workspace(x.device, L.pk2_transducer_beam_workspace_bytes(N, T, V, beam, max_symbols, J))
+    tokens = torch.empty((N, beam, T * max_symbols), dtype=torch.int32, device=x.device)
+    lens = torch.empty((N, beam), dtype=torch.int32, device=x.device)
+    scores = torch.empty((N, beam), dtype=torch.float64, device=x.device)
+    status = torch.empty(N, dtype=torch.int32, device=x.device)
+    _lib.check(L.pk2_transducer_beam_search(_lib.ptr(host), _lib.ptr(dev), N, _lib.ptr(x), x.stride(0), x.stride(1), T, _lib.ptr(rows),
+                                            rows.stride(0), _lib.ptr(w), w.stride(0) if J else 0, _lib.ptr(b), J, V, int(blank), beam,
+                                            top_tokens, max_symbols, _lib.ptr(tokens), _lib.ptr(lens), _lib.ptr(scores), _lib.ptr(status),
+                                            _lib.ptr(ws), ws.numel(), _lib.stream_ptr(x.device)))
+    scores._pk2_keepalive = (host, dev, b)      # until the stream has consumed them
+    return tokens, lens, scores, status
+
+
+def beam_search(am_or_enc, lengths, table_or_pred, nbest=1, **kw):
+    """beam_search_raw and ONE copy to the host: per utterance a list of at most nbest (token list, score), best first."""
+    tokens, lens, scores, _ = beam_search_raw(am_or_enc, lengths, table_or_pred, **kw)
+    N, B, T = tokens.shape
+    flat = torch.cat([tokens.reshape(N, -1).double(), lens.double(), scores], dim=1).cpu().numpy()      # (int32 is exact in float64)
+    tok, ln, sc = flat[:, :B * T].reshape(N, B, T).astype(np.int64), flat[:, B * T:B * T + B].astype(np.int64), flat[:, B * T + B:]
+    return [[(tok[n, r, :ln[n, r]].tolist(), float(sc[n, r])) for r in range(min(nbest, B)) if ln[n, r] >= 0] for n in range(N)]
