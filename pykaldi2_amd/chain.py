@@ -104,7 +104,9 @@ class DenominatorGraph:
             pl[name + "_table"] = (int(info[0]), int(info[1]))
             pl[name + "_direct_arcs"] = int(info[3])
             # the row epilogue of that direction: 1 = batched, 0 = row by row (PK2_DP2_EPI=0 when the graph
-            # was created, an ordering with streamed pieces, or more than two rows per thread), -1 = no persistent layout
+            # was created, an ordering with streamed pieces, or more than two rows per thread), -1 = no persistent layout.
+            # (The forward recursion has two batched forms; both report 1 here, and
+            # pk2_den_graph_persist2_epilogue(h, 2) tells them apart: 2 = the default, 1 = PK2_DP2_EPI=1.)
             pl[name + "_epilogue"] = int(_lib.lib().pk2_den_graph_persist2_epilogue(self._h, which))
         return pl
 

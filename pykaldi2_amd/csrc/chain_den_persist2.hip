@@ -53,7 +53,7 @@ struct DenPersist2Params {
   const float* pi_pos;          // pi at the forward ordering's vector positions (fwd_direct)
   short task_seq[kMaxTasks];
   unsigned char task_dir[kMaxTasks];
-  int epi;                      // the batched row epilogue (run_fwd2 / run_bwd2 <., ., ., EPI>; pk2_den_graph::p2_epi) in the orderings without streamed pieces
+  int epi;                      // the batched row epilogue (run_fwd2 / run_bwd2 <., ., ., EPI>; pk2_den_graph::p2_epi: 0, 1 or 2) in the orderings without streamed pieces
 };
 typedef __attribute__((address_space(4))) const DenPersist2Params CParams2;
 typedef __attribute__((address_space(4))) const DevPersist2 CDev2;
@@ -563,6 +563,9 @@ struct DirectRegs {
   }
 };
 struct NoDirect { };
+// `early` (frame_rows): the caller's register arithmetic that needs nothing of this frame but the words of the poll -- it runs
+// between the issue of chunk 0's copies and the wait for them, where the wave has nothing else to do.
+struct NoEarly { __device__ __forceinline__ void operator()() const {} };
 __device__ __forceinline__ void load_direct_regs(CDev2& o, int rank, DirectRegs& d) {
 #pragma unroll
   for (int j = 0; j < kDirect; ++j) {
@@ -574,10 +577,10 @@ __device__ __forceinline__ void load_direct_regs(CDev2& o, int rank, DirectRegs&
     d.val[j] = 0.f;
   }
 }
-template <bool STREAM, bool DIRECT, typename DR, typename ST, typename STAGE>
+template <bool STREAM, bool DIRECT, typename DR, typename ST, typename STAGE, typename EARLY = NoEarly>
 __device__ __forceinline__ void frame_rows(CDev2& o, cgfloat* src, int rank, const RowSpan& rs, const FrameRegs& r,
                                            const DmaPlan& plan, DR& dr, ST& st, const Lds2& L, DpTimers& dp_, STAGE stage,
-                                           bool prime_next = false) {
+                                           bool prime_next = false, EARLY early = EARLY()) {
   static_assert(!(STREAM && DIRECT), "direct arcs exist in the fully resident form only");
   const int tid = threadIdx.x;
   if constexpr (STREAM) {
@@ -587,6 +590,7 @@ __device__ __forceinline__ void frame_rows(CDev2& o, cgfloat* src, int rank, con
     for (int q = rs.uncB + tid; q < rs.ncB; q += kPT) L.accB[q] = 0.f;
   }
   dma_chunk(src, o, 0, L.table);
+  early();
   DP_T(0);
   wait_vm(0);                            // chunk 0 has landed (this wave's part)
   lds_only_barrier();
@@ -749,8 +753,9 @@ __device__ __forceinline__ void load_frame_regs(CDev2& o, int rank, FrameRegs& r
   r.frowA = o.first_row[((size_t)rank * 2 + 0) * kPT + tid]; r.frowB = o.first_row[((size_t)rank * 2 + 1) * kPT + tid];
 }
 
-// alpha recursion of sequence g (T frames).
-template <bool STREAM, int PSPT, bool DIRECT, bool EPI>
+// alpha recursion of sequence g (T frames).  EPI: 0 = the row-by-row epilogue, 1 = the batched one, 2 = the
+// batched one with everything that needs only the frame's alpha sum computed in front of the row-sum barrier (4.1j).
+template <bool STREAM, int PSPT, bool DIRECT, int EPI>
 __device__ __noinline__ void run_fwd2(CParams2* pp_, DenPersistCtl* ctl_, DenPersistCtl::Team* team_,
                                       unsigned* nbar, int g_, int T_, int rank_, float* ring_, float* pring_) {
   CParams2* pp = uni(pp_);
@@ -815,7 +820,7 @@ __device__ __noinline__ void run_fwd2(CParams2* pp_, DenPersistCtl* ctl_, DenPer
   }
   // EPI: the first row of every own state (bench graph: its only one) by precomputed addresses, its leak term in a register
   static_assert(!(EPI && STREAM), "the batched epilogue is for the orderings without streamed pieces");
-  typename std::conditional<EPI, EpiRegs<PSPT>, NoEpi<PSPT>>::type ep;
+  typename std::conditional<EPI != 0, EpiRegs<PSPT>, NoEpi<PSPT>>::type ep;
   int e_q[PSPT]; float e_lk[PSPT]; uint32_t e_x[PSPT];
   if constexpr (EPI) {
     const uint32_t zero = lds_addr(L.tot + 3);
@@ -910,22 +915,55 @@ __device__ __noinline__ void run_fwd2(CParams2* pp_, DenPersistCtl* ctl_, DenPer
       DP_TL(0, 1);
       if (*L.abort) return;
       as = L.tot[0];
-      if (tid == 0) L.abort[8] = 0;        // (word 8 had a reader in the dropped poll-copy experiment; the store stays so that
-                                           //  the kernel's instructions remain the measured ones: take it out with the next re-measurement)
     }
     // the word this rank will publish two frames from now must read "not yet written" by then: reset here, before the
     // copies (no store sits between them and their waits), long before the stores it has to precede
     const bool publish = t + 1 < T;
     if (tid == 0 && publish) st_agent(word_of(pring, t + 2, rank, 0), __uint_as_float(kRingSentinel));
-    frame_rows<STREAM, DIRECT>(o, src, rank, rs, fr, plan, dr, st, L, dp_, [&]() {
+    float lk, inv_as;
+    float outv[PSPT], loopv[PSPT], loc = 0.f, unused = 0.f;
+    // EPI == 2: the direct arcs' selected products, formed in front of the row-sum barrier; the first rows, kept for L.aux
+    float e_dsel[PSPT][kDirect], e_v0[PSPT];
+    auto stage_x = [&]() {
 #pragma unroll
       for (int i = 0; i < PSPT; ++i) {
         const int r = tid + i * kPT;
         if (r < nrows) L.xown[r] = xr[i];
       }
-      if (kLateHistory<STREAM> && t > 0) history(t - 1);
-      if (publish) prefetch(t + 1);
-    }, publish);
+    };
+    if constexpr (EPI == 2) {
+      frame_rows<STREAM, DIRECT>(o, src, rank, rs, fr, plan, dr, st, L, dp_, [&]() {
+        stage_x();
+#pragma unroll
+        for (int i = 0; i < PSPT; ++i) {
+          // (the copies' wait in front of this point covers the direct arcs' loads)
+          if constexpr (DIRECT) {
+#pragma unroll
+            for (int j = 0; j < kDirect; ++j) {
+              e_dsel[i][j] = dr.row[j] == e_q[i] ? dr.prob[j] * dr.val[j] : 0.f;
+              asm volatile("" : "+v"(e_dsel[i][j]));
+            }
+          }
+        }
+        if (kLateHistory<STREAM> && t > 0) history(t - 1);
+        if (publish) prefetch(t + 1);
+      }, publish, [&]() {
+        // (the values are made opaque HERE: left alone, the compiler sinks the arithmetic to its uses behind the barrier)
+        lk = d.leaky * as; inv_as = 1.0f / as;
+        asm volatile("" : "+v"(lk), "+v"(inv_as));
+#pragma unroll
+        for (int i = 0; i < PSPT; ++i) {
+          loopv[i] = st_pl[i] > 0.f ? (own_a[i] + lk * st_pi[i]) * st_pl[i] * xlr[i] * inv_as : 0.f;
+          asm volatile("" : "+v"(loopv[i]));
+        }
+      });
+    } else {
+      frame_rows<STREAM, DIRECT>(o, src, rank, rs, fr, plan, dr, st, L, dp_, [&]() {
+        stage_x();
+        if (kLateHistory<STREAM> && t > 0) history(t - 1);
+        if (publish) prefetch(t + 1);
+      }, publish);
+    }
     DP_TL(0, 4);
     DP_WB();
     // (EPI: the barrier orders LDS only, as in a streaming frame -- the next frame's x prefetch stays in flight behind it)
@@ -933,12 +971,51 @@ __device__ __noinline__ void run_fwd2(CParams2* pp_, DenPersistCtl* ctl_, DenPer
     DP_WE();
     DP_T(10);
     if (rank == 0 && tid == 0) G(d.asum)[f0 + t] = as;
-    const float lk = d.leaky * as, inv_as = 1.0f / as;
+    if constexpr (EPI != 2) { lk = d.leaky * as; inv_as = 1.0f / as; }
     // rows are virtual states (dst, pdf); a thread per real state sums its rows and adds the peeled self-loop.  First
     // only what the other workgroups wait for: the ring entries, then (once they are in L2) the partial sum.
     gfloat* ring_n = ring + (size_t)((t + 1) & 1) * p.rpad;
-    float outv[PSPT], loopv[PSPT], loc = 0.f, unused = 0.f;
-    if constexpr (EPI) {
+    if constexpr (EPI == 2) {
+      float ra[PSPT], rb[PSPT], rc[PSPT], rx[PSPT];
+#pragma unroll
+      for (int i = 0; i < PSPT; ++i) { ra[i] = lds_load(ep.a[i]); rb[i] = lds_load(ep.b[i]); rc[i] = lds_load(ep.c[i]); rx[i] = lds_load(e_x[i]); }
+      DP_LANDED();
+      DP_T(11);
+#pragma unroll
+      for (int i = 0; i < PSPT; ++i) {
+        // (a state without a row: every address is the zero word's, no direct arc matches q = -1 -- v0 = 0)
+        float rv = (ra[i] + rb[i]) + rc[i];
+        if (ep.rest) rv = rest_carries(L, ep.rest, e_q[i], rv);
+        // (the operations and their order are the batched form's: the same bits)
+        if constexpr (DIRECT) {
+#pragma unroll
+          for (int j = 0; j < kDirect; ++j) rv += e_dsel[i][j];
+        }
+        e_v0[i] = (rv + lk * e_lk[i]) * rx[i] * inv_as;
+        float sum = e_v0[i];
+        if (st_ok[i]) {
+          for (int q = st_lo[i] + 1; q < st_hi[i]; ++q) {       // (a state entered with several pdfs: its further rows, row by row)
+            float rw = row_val<STREAM>(L, ep.rest, q);
+            if constexpr (DIRECT) rw = dr.add_to(q, rw);
+            const float v = (rw + lk * L.leak[q]) * L.xown[q] * inv_as;
+            L.aux[q] = v;
+            sum += v;
+          }
+        }
+        sum += loopv[i];
+        outv[i] = sum;
+        own_a[i] = sum;
+        loc += sum;
+      }
+      DP_T(12);
+#pragma unroll
+      for (int i = 0; i < PSPT; ++i) {
+        if (!st_ok[i] || !publish) continue;
+        if constexpr (DIRECT) ring_store(ring_n + st_pos[i], outv[i]);
+        else ring_store(ring_n + g0 + tid + i * kPT, outv[i]);
+      }
+      DP_T(13);
+    } else if constexpr (EPI) {
       float ra[PSPT], rb[PSPT], rc[PSPT], rx[PSPT], v0[PSPT];
 #pragma unroll
       for (int i = 0; i < PSPT; ++i) { ra[i] = lds_load(ep.a[i]); rb[i] = lds_load(ep.b[i]); rc[i] = lds_load(ep.c[i]); rx[i] = lds_load(e_x[i]); }
@@ -1002,6 +1079,11 @@ __device__ __noinline__ void run_fwd2(CParams2* pp_, DenPersistCtl* ctl_, DenPer
     wait_stores();        // this rank's slice of frame t+1 (and the reset above) is in L2 before its partial sum says so
     block_sum2<kPW>(loc, unused, L.red);
     if (tid == 0 && publish) st_agent(word_of(pring, t + 1, rank, 0), loc);
+    if constexpr (EPI == 2) {      // (the finished first rows, for this thread's own history stores: nobody waits for them)
+#pragma unroll
+      for (int i = 0; i < PSPT; ++i)
+        if (e_q[i] >= 0) L.aux[e_q[i]] = e_v0[i];
+    }
     DP_T(6);
     DP_TL(0, 6);
     hist_loc = loc;
@@ -1192,7 +1274,6 @@ __device__ __noinline__ void run_bwd2(CParams2* pp_, DenPersistCtl* ctl_, DenPer
     DP_TL(1, 1);
     if (*L.abort) return;
     const float lB = L.tot[0], lU = L.tot[1];        // sums of btilde'[t, .], known before it is computed
-    if (tid == 0) L.abort[8] = 0;          // (as in run_fwd2: no reader left)
     const bool publish = t > 0;
     // the words this rank will publish two frames from now must read "not yet written" by then: reset here, before the
     // copies, long before the stores they have to precede (the waits of emit cover it)
@@ -1324,17 +1405,25 @@ __global__ void __launch_bounds__(kPT) den_persist2_kernel(const DenPersist2Para
     // EPI (p.epi, the default; PK2_DP2_EPI=0 when the graph is created keeps the earlier epilogue): the batched row epilogue,
     // in the orderings without streamed pieces and with two entries per thread -- with three or four its addresses are
     // registers the kernels do not have (scratch 16 -> 72 / 52 -> 168 bytes per lane forward, 132 -> 172 backward), and no
-    // graph of that size has been measured: they keep the row-by-row form
+    // graph of that size has been measured: they keep the row-by-row form.  p.epi == 2 (the default): the forward recursion's
+    // epilogue with its as-dependent work in front of the row-sum barrier; backward it is the batched form
 #define PK2_RUN2(fn, STREAM, DIRECT, EPI)                                                                               \
   do {                                                                                                                  \
     if (p.pspt == 2) fn<STREAM, 2, DIRECT, EPI>(pp, ctl, team, &nbar, g, T, rank, ring, pring);                         \
-    else if (p.pspt == 3) fn<STREAM, 3, DIRECT, false>(pp, ctl, team, &nbar, g, T, rank, ring, pring);                  \
-    else fn<STREAM, kPSPT, DIRECT, false>(pp, ctl, team, &nbar, g, T, rank, ring, pring);                               \
+    else if (p.pspt == 3) fn<STREAM, 3, DIRECT, 0>(pp, ctl, team, &nbar, g, T, rank, ring, pring);                      \
+    else fn<STREAM, kPSPT, DIRECT, 0>(pp, ctl, team, &nbar, g, T, rank, ring, pring);                                   \
   } while (0)
     if (p.task_dir[k] == 0) {
-      if (p.fwd_stream) PK2_RUN2(run_fwd2, true, false, false);
-      else if (p.fwd_direct) { if (p.epi) PK2_RUN2(run_fwd2, false, true, true); else PK2_RUN2(run_fwd2, false, true, false); }
-      else { if (p.epi) PK2_RUN2(run_fwd2, false, false, true); else PK2_RUN2(run_fwd2, false, false, false); }
+      if (p.fwd_stream) PK2_RUN2(run_fwd2, true, false, 0);
+      else if (p.fwd_direct) {
+        if (p.epi == 2) PK2_RUN2(run_fwd2, false, true, 2);
+        else if (p.epi) PK2_RUN2(run_fwd2, false, true, 1);
+        else PK2_RUN2(run_fwd2, false, true, 0);
+      } else {
+        if (p.epi == 2) PK2_RUN2(run_fwd2, false, false, 2);
+        else if (p.epi) PK2_RUN2(run_fwd2, false, false, 1);
+        else PK2_RUN2(run_fwd2, false, false, 0);
+      }
     } else {
       if (p.bwd_stream) PK2_RUN2(run_bwd2, true, false, false);
       else if (p.bwd_direct) { if (p.epi) PK2_RUN2(run_bwd2, false, true, true); else PK2_RUN2(run_bwd2, false, true, false); }

@@ -731,9 +731,11 @@ static void build_persist2(pk2_den_graph* g, int64_t A2, const int32_t* arc_v, c
                    !getenv("PK2_DP2_ROWARRAYS");
   if (const char* env = getenv("PK2_DP2_TABLE")) prefix_ok = prefix_ok && strcmp(env, "full") != 0;
   // The row epilogue of the orderings without streamed pieces (chain_den_persist2.hip: EPI): batched unless
-  // PK2_DP2_EPI=0 asks for the earlier row-by-row form (the A/B switch; read here, when the graph is created).
-  g->p2_epi = 1;
-  if (const char* env = getenv("PK2_DP2_EPI")) g->p2_epi = atoi(env) != 0 ? 1 : 0;
+  // PK2_DP2_EPI=0 asks for the earlier row-by-row form (the A/B switch; read here, when the graph is created).  Forward it
+  // has two forms: 2 (the default) does what needs only the frame's alpha sum in front of the row-sum barrier (4.1j), 1 is
+  // 4.1i's.
+  g->p2_epi = 2;
+  if (const char* env = getenv("PK2_DP2_EPI")) { const int v = atoi(env); g->p2_epi = v == 0 ? 0 : (v == 2 ? 2 : 1); }
   struct ArcSet { int64_t A; const int32_t* key; const int32_t* idx; const float* prob; const float* piprob; };
   struct RowIndex { std::vector<int64_t> ptr, perm; };
   auto index_rows = [](const ArcSet& a, int rows, RowIndex* out) {
@@ -1211,13 +1213,15 @@ extern "C" int pk2_den_graph_debug_persist2(const pk2_den_graph* g, int which, i
 
 // Reporting hook: the row epilogue the persistent kernel runs for an ordering -- 1 = batched (chain_den_persist2.hip: EPI),
 // 0 = row by row (PK2_DP2_EPI=0, an ordering with streamed pieces / more than two table chunks, or a graph whose ranks hold
-// more than two rows per thread), -1 = no layout.
+// more than two rows per thread), -1 = no layout.  which = 2: the forward ordering again, telling the two batched forms
+// apart -- 2 = the as-dependent work in front of the row-sum barrier, 1 = 4.1i's (PK2_DP2_EPI=1).
 extern "C" int32_t pk2_den_graph_persist2_epilogue(const pk2_den_graph* g, int which) {
-  if (!g || (which != 0 && which != 1)) return -1;
-  const HostPersist2& h = which == 0 ? g->h_p2fwd : g->h_p2bwd;
+  if (!g || which < 0 || which > 2) return -1;
+  const HostPersist2& h = which == 1 ? g->h_p2bwd : g->h_p2fwd;
   if (!h.ok) return -1;
   const bool stream = !h.sends.empty() || h.K > 2;
-  return !stream && g->p2_epi && g->p2_cap <= 2 * kPT ? 1 : 0;
+  if (stream || !g->p2_epi || g->p2_cap > 2 * kPT) return 0;
+  return which == 2 ? g->p2_epi : 1;
 }
 
 // Test / reporting hook: the table prefix of an ordering (chain_internal.h: kDirectDeg).  info[8] = {Rt, R, entries chosen for

@@ -178,7 +178,7 @@ struct pk2_den_graph {
   pk2::HostPersist2 h_p2fwd, h_p2bwd;     // the same two orderings for the persistent kernel (chain_den_persist2.hip)
   pk2::DevPersist2 p2fwd, p2bwd;
   int p2_cap = 0;                         // LDS row buffers of that kernel (rows / groups / own virtual states of a rank)
-  int p2_epi = 1;                         // its batched row epilogue (chain_den_persist2.hip: EPI; 0 with PK2_DP2_EPI=0 at creation)
+  int p2_epi = 2;                         // its batched row epilogue (chain_den_persist2.hip: EPI; PK2_DP2_EPI = 0 / 1 / 2 at creation)
   int p2_rowarrays = 8;                   // LDS arrays of p2_cap floats: 8 with the pdfs the x gather needs, 7 without them
   const int32_t* d_voff = nullptr;
   const int32_t* d_vpdf = nullptr;
