@@ -94,5 +94,28 @@ __device__ __forceinline__ double wave_sum_d(double v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
+__device__ __forceinline__ unsigned long long shfl_xor64(unsigned long long v, int m) {
+  const unsigned lo = __shfl_xor((unsigned)v, m, 64), hi = __shfl_xor((unsigned)(v >> 32), m, 64);
+  return ((unsigned long long)hi << 32) | lo;
+}
+__device__ __forceinline__ unsigned wave_scan(unsigned v, int lane) {      // inclusive
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) { const unsigned w = __shfl_up(v, o, 64); if (lane >= o) v += w; }
+  return v;
+}
+
+// A workgroup barrier behind which every thread sees the global memory the others wrote ahead of it.
+__device__ __forceinline__ void block_sync_global() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+  __syncthreads();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+}
+
+__device__ __forceinline__ double log_add(double a, double b) {
+  const double m = fmax(a, b);
+  if (!(m > -INFINITY)) return m;      // both -inf (or NaN).  A NaN next to a finite operand comes out NaN below: the losses
+                                       // show it in log p; the beam search's scores are finite or -inf (its row pass sees to it)
+  return m + log1p(exp(-fabs(a - b)));
+}
 
 }  // namespace pk2

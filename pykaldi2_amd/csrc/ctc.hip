@@ -76,12 +76,6 @@ __device__ inline size_t ctc_base(const CtcDesc* desc, int n) {
   return o;
 }
 
-__device__ __forceinline__ void block_sync_global() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-  __syncthreads();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-}
-
 // ---- ctc_rows: grid (blocks, N), a wave per frame.
 __global__ __launch_bounds__(256) void ctc_rows(const int32_t* __restrict__ pk, const float* __restrict__ x, int64_t seq_stride,
                                                 int64_t frame_stride, int32_t P, int32_t blank, float* __restrict__ ws) {
@@ -234,7 +228,7 @@ __global__ __launch_bounds__(kThreads) void ctc_chains(const int32_t* __restrict
       __syncthreads();
     }
     // log p = sum_{t < T-1} log z_t + log(the two final states of the last stored row) - 2 L log theta
-    block_sync_global();
+    pk2::block_sync_global();
     double acc = 0.0;
     for (int t = tx; t < T - 1; t += kThreads) acc += log(zs[t]);
     acc = pk2::wave_sum_d(acc);

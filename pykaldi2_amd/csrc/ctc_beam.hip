@@ -19,17 +19,20 @@
 //                  1 a thread per slot j finds the slot of its parent and the rank of its last token: redir[i][k] = j [1]
 //                  2 the nb K extensions over all threads, one LM lookup each; a redirected one goes to mval[j]       [1]
 //                  3 a thread per slot: the stay candidate, plus mval[j]                                              [1]
-//                  4 radix select of the beam-th largest total on the bits of the positive doubles, 8 bits a pass from
-//                    the top, LDS integer histogram; it stops at the first pass whose bin is taken whole           [2 a pass]
-//                  5 one packed scan (greater | equal) in candidate order gives every survivor its slot; the survivors
-//                    are written to the other beam buffer times 2^-e, e the exponent of the best total (exact; the
-//                    integer sum of the e is the log scale), new prefixes write (parent node, token) to the table   [2]
+//                  4 beam_select (beam_dev.h) with up to 5 candidates a thread: radix select of the beam-th largest
+//                    total on the bits of the positive doubles, 8 bits a pass from the top, LDS integer histogram; it
+//                    stops at the first pass whose bin is taken whole                                           [2 a pass]
+//                    then one packed scan (greater | equal) in candidate order gives every survivor its slot          [1]
+//                  5 the survivors are written to the other beam buffer times 2^-e, e the exponent of the best total
+//                    (exact; the integer sum of the e is the log scale), new prefixes write (parent node, token) to
+//                    the table                                                                                        [1]
 //                The next compact row is loaded at the top of the frame and stored ahead of its last barrier.  The tail
-//                takes log once per slot, adds the </s> cost, ranks the finals by counting and walks the back-pointers.
+//                takes log once per slot and adds the </s> cost; beam_tail (beam_dev.h) ranks the finals by counting
+//                and walks the back-pointers.  The LM lookup is ngram_arc (ngram_dev.h).
 #include <algorithm>
 #include <cmath>
 
-#include "common.h"
+#include "beam_dev.h"
 #include "ngram_dev.h"
 
 #pragma clang fp contract(off)
@@ -37,10 +40,8 @@
 namespace pk2 {
 namespace {
 
-typedef unsigned long long u64;
-
-constexpr int kThreads = 1024;
-constexpr int kWaves = kThreads / 64;
+constexpr int kThreads = kBeamThreads;
+constexpr int kWaves = kBeamWaves;
 constexpr int kMaxCand = PK2_CTC_BEAM_MAX * (PK2_CTC_BEAM_MAX_TOKENS + 1);      // 4224
 constexpr int kMaxCpt = (kMaxCand + kThreads - 1) / kThreads;                    // 5 candidates per thread at the limits
 constexpr int kRowHead = 4;
@@ -54,8 +55,8 @@ struct CbParams {
   const float* x;
   int64_t ss, fs;
   int32_t Tpad, P, blank, B, K;
-  const int32_t *n_word, *n_child, *n_bo, *n_next, *lm_ids;
-  const float *n_cost, *n_backoff;
+  NgramTrie lm;
+  const int32_t* lm_ids;
   int32_t lm_start, lm_eos, has_lm, use_eos;
   double lm_weight, bonus;
   float* rows;
@@ -79,27 +80,6 @@ __host__ __device__ inline CbLds cb_lds(size_t B, size_t K) {
   l.row = take(8 * cb_row_words(K));                                                              // [2][row words]
   l.bytes = o;
   return l;
-}
-
-__device__ __forceinline__ u64 cb_shfl_xor64(u64 v, int m) {
-  const unsigned lo = __shfl_xor((unsigned)v, m, 64), hi = __shfl_xor((unsigned)(v >> 32), m, 64);
-  return ((u64)hi << 32) | lo;
-}
-__device__ __forceinline__ u64 cb_wave_max64(u64 v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) { const u64 w = cb_shfl_xor64(v, o); v = w > v ? w : v; }
-  return v;
-}
-__device__ __forceinline__ unsigned cb_wave_scan(unsigned v, int lane) {      // inclusive
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) { const unsigned w = __shfl_up(v, o, 64); if (lane >= o) v += w; }
-  return v;
-}
-
-// (logit, column) as one key: a larger logit is a larger key, and of equal logits the lower column
-__device__ __forceinline__ u64 cb_key(float v, int col) {
-  const unsigned b = __float_as_uint(v), u = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-  return ((u64)u << 32) | (0xFFFFFFFFu - (unsigned)col);
 }
 
 // ---- ctcb_rows: grid (blocks, N), a wave per frame.
@@ -144,7 +124,7 @@ __global__ __launch_bounds__(256) void ctcb_rows(const int32_t* __restrict__ len
     for (int k = 0; k < K; ++k) {
       u64 best = 0;
       auto consider = [&](float v, int col) {
-        const u64 key = cb_key(v, col);
+        const u64 key = beam_key(v, col);
         if (col != blank && key < prev && key > best) best = key;
       };
       for (int v = lane; v < nvec; v += 64) {
@@ -153,9 +133,9 @@ __global__ __launch_bounds__(256) void ctcb_rows(const int32_t* __restrict__ len
         consider(q.x, c); consider(q.y, c + 1); consider(q.z, c + 2); consider(q.w, c + 3);
       }
       if (mine >= 0) consider(row[mine], mine);
-      best = cb_wave_max64(best);
+      best = wave_max64(best);
       prev = best;
-      int col = (int)(0xFFFFFFFFu - (unsigned)best);
+      int col = beam_key_col(best);
       if (col < 0 || col >= P) col = blank;      // (K <= P - 1 columns exist: not taken)
       if (lane == 0) {
         out[kRowHead + 2 * k] = __int_as_float(col);
@@ -165,49 +145,13 @@ __global__ __launch_bounds__(256) void ctcb_rows(const int32_t* __restrict__ len
   }
 }
 
-// cost and next state of word w from LM state h: the float64 sum of float32 trie entries along the backoff chain, as
-// lr_lm_arc of lattice_lmrescore.hip; false if w has no unigram
-__device__ __forceinline__ bool cb_lm_arc(const CbParams& p, int h, int w, double& cost, int& next) {
-  double acc = 0.0;
-  int node = h;
-#pragma nounroll
-  for (int it = 0; it <= PK2_NGRAM_MAX_ORDER; ++it) {
-    const int end = p.n_child[node + 1];
-    int lo = p.n_child[node], hi = end;
-    while (lo < hi) {
-      const int mid = (lo + hi) >> 1;
-      if (p.n_word[mid] < w) lo = mid + 1; else hi = mid;
-    }
-    if (lo < end && p.n_word[lo] == w) { cost = acc + (double)p.n_cost[lo]; next = p.n_next[lo]; return true; }
-    if (node == 0) break;
-    acc += (double)p.n_backoff[node];
-    node = p.n_bo[node];
-  }
-  cost = 0.0; next = 0;
-  return false;
-}
-
-constexpr u64 kHashEmpty = 0x243F6A8885A308D3ull;
-__device__ __forceinline__ u64 cb_mix(u64 h, int c) {      // the hash of prefix + c from the hash of the prefix (splitmix64's finish)
-  u64 z = h ^ ((u64)(unsigned)(c + 1) * 0x9E3779B97F4A7C15ull);
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-
-__device__ __forceinline__ void cb_sync_global() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-  __syncthreads();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-}
-
 // ---- ctcb_search: grid (N), cb_lds(B, K).bytes of dynamic LDS.
 __global__ __launch_bounds__(kThreads) void ctcb_search(const CbParams p) {
   extern __shared__ __align__(16) unsigned char lds[];
   __shared__ int hist[256];
   __shared__ u64 wmax[kWaves];
   __shared__ unsigned wtot[kWaves];
-  __shared__ int sel_digit, sel_need, sel_cnt;
+  __shared__ int sel[3];
   const int n = blockIdx.x, tx = threadIdx.x, lane = tx & 63, wave = tx >> 6;
   const int B = p.B, K = p.K, RW = cb_row_words(K), T = min(p.lengths[n], p.Tpad);
   const CbLds L = cb_lds(B, K);
@@ -275,7 +219,7 @@ __global__ __launch_bounds__(kThreads) void ctcb_search(const CbParams p) {
       bool ok = true;
       if (p.has_lm) {
         double cost;
-        ok = cb_lm_arc(p, lms[co + i], p.lm_ids ? p.lm_ids[c] : c, cost, hn);
+        ok = ngram_arc(p.lm, lms[co + i], p.lm_ids ? p.lm_ids[c] : c, cost, hn);
         f = exp(-p.lm_weight * cost + p.bonus);
       }
       const double mass = pb[co + i] + (c != last[co + i] ? pnb[co + i] : 0.0);
@@ -305,7 +249,10 @@ __global__ __launch_bounds__(kThreads) void ctcb_search(const CbParams p) {
       key[tx] = (u64)__double_as_longlong(pbn + pnbn);
     }
     __syncthreads();
-    // 4: the `want`-th largest total.  A thread owns cpt consecutive candidates, so that the scan of step 5 is in candidate order
+    // 4: the B largest totals (a redirected or zero-mass extension has key 0: counted, never kept).  A thread owns cpt
+    // consecutive candidates, so that the slots are in candidate order.  The best total, for the rescale, goes to wmax
+    // ahead of the select and is read behind its barriers: on a frame whose best total is 0 or not finite the select
+    // still runs to its end (integers only, hist is zero again) and the frame breaks behind it
     const int cpt = (M + kThreads - 1) / kThreads, c0 = tx * cpt;
     u64 kq[kMaxCpt], lmax = 0;
 #pragma unroll
@@ -313,38 +260,10 @@ __global__ __launch_bounds__(kThreads) void ctcb_search(const CbParams p) {
       kq[q] = (q < cpt && c0 + q < M) ? key[c0 + q] : 0;
       lmax = kq[q] > lmax ? kq[q] : lmax;
     }
-    lmax = cb_wave_max64(lmax);
+    lmax = wave_max64(lmax);
     if (lane == 0) wmax[wave] = lmax;
-    u64 prefix = 0;
-    int need = min(B, M), fshift = 0;
-    for (int shift = 56; shift >= 0; shift -= 8) {
-#pragma unroll
-      for (int q = 0; q < kMaxCpt; ++q)
-        if (q < cpt && c0 + q < M && (shift == 56 || (kq[q] >> (shift + 8)) == (prefix >> (shift + 8))))
-          atomicAdd(&hist[(int)((kq[q] >> shift) & 255)], 1);
-      __syncthreads();
-      if (wave == 0) {      // lane l: bins 255 - 4 l down to 252 - 4 l; the bin in which the count from the top reaches `need`
-        int h[4], s = 0;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) { h[r] = hist[255 - 4 * lane - r]; hist[255 - 4 * lane - r] = 0; s += h[r]; }
-        const int incl = (int)cb_wave_scan((unsigned)s, lane);
-        int r = need - (incl - s);
-        if (r >= 1 && r <= s) {      // exactly one lane
-          bool found = false;
-#pragma unroll
-          for (int q = 0; q < 4; ++q)
-            if (!found) {
-              if (r <= h[q]) { sel_digit = 255 - 4 * lane - q; sel_need = r; sel_cnt = h[q]; found = true; }
-              else r -= h[q];
-            }
-        }
-      }
-      __syncthreads();
-      prefix |= (u64)sel_digit << shift;
-      need = sel_need;
-      fshift = shift;
-      if (sel_cnt == need) break;      // the bin is taken whole: no need to order it
-    }
+    int slot[kMaxCpt];
+    const int kept = beam_select<kMaxCpt>(kq, c0, cpt, M, B, hist, wtot, sel, lane, wave, slot);
     u64 best = wmax[0];
 #pragma unroll
     for (int w = 1; w < kWaves; ++w) best = wmax[w] > best ? wmax[w] : best;
@@ -353,56 +272,34 @@ __global__ __launch_bounds__(kThreads) void ctcb_search(const CbParams p) {
     eb = min(max(eb, 1), 2045);
     const double scale = __longlong_as_double((long long)(2046 - eb) << 52);      // 2^-(eb - 1023)
     expo += eb - 1023;
-    // 5: slots by one scan of (equal << 16 | greater) in candidate order, then the survivors into the other buffer
-    const u64 tp = prefix >> fshift;
-    unsigned cnt = 0;
+    // 5: the survivors into the other buffer
 #pragma unroll
-    for (int q = 0; q < kMaxCpt; ++q)
-      if (kq[q] != 0) {
-        const u64 hp = kq[q] >> fshift;
-        cnt += hp > tp ? 1u : (hp == tp ? 0x10000u : 0u);
-      }
-    const unsigned incl = cb_wave_scan(cnt, lane);
-    if (lane == 63) wtot[wave] = incl;
-    __syncthreads();
-    unsigned before = incl - cnt, total = 0;
-#pragma unroll
-    for (int w = 0; w < kWaves; ++w) {
-      if (w < wave) before += wtot[w];
-      total += wtot[w];
-    }
-    int G = (int)(before & 0xFFFF), E = (int)(before >> 16);
-#pragma unroll
-    for (int q = 0; q < kMaxCpt; ++q)
-      if (kq[q] != 0) {
-        const u64 hp = kq[q] >> fshift;
-        int s = -1;
-        if (hp > tp) { s = G + min(E, need); ++G; }
-        else if (hp == tp) { if (E < need) s = G + E; ++E; }
-        if (s >= 0 && s < B) {      // (the select keeps min(B, M) at most: s < B)
-          const int idx = c0 + q;
-          if (idx < nb) {
-            pb[no + s] = stay_pb[idx] * scale; pnb[no + s] = stay_pnb[idx] * scale;
-            hash[no + s] = hash[co + idx]; phash[no + s] = phash[co + idx]; node[no + s] = node[co + idx];
-            last[no + s] = last[co + idx]; lms[no + s] = lms[co + idx]; len[no + s] = len[co + idx];
-          } else {
-            const int e = idx - nb, i = e / K, k = e - i * K;
-            const int c = __float_as_int(row[kRowHead + 2 * k]);
-            pb[no + s] = 0.0; pnb[no + s] = __longlong_as_double((long long)kq[q]) * scale;
-            hash[no + s] = cb_mix(hash[co + i], c); phash[no + s] = hash[co + i]; node[no + s] = 1 + t * B + s;
-            last[no + s] = c; lms[no + s] = extlm[e]; len[no + s] = len[co + i] + 1;
-            bp[(size_t)t * B + s] = make_int2(node[co + i], c);
-          }
+    for (int q = 0; q < kMaxCpt; ++q) {
+      const int s = slot[q];
+      if (s >= 0) {
+        const int idx = c0 + q;
+        if (idx < nb) {
+          pb[no + s] = stay_pb[idx] * scale; pnb[no + s] = stay_pnb[idx] * scale;
+          hash[no + s] = hash[co + idx]; phash[no + s] = phash[co + idx]; node[no + s] = node[co + idx];
+          last[no + s] = last[co + idx]; lms[no + s] = lms[co + idx]; len[no + s] = len[co + idx];
+        } else {
+          const int e = idx - nb, i = e / K, k = e - i * K;
+          const int c = __float_as_int(row[kRowHead + 2 * k]);
+          pb[no + s] = 0.0; pnb[no + s] = __longlong_as_double((long long)kq[q]) * scale;
+          hash[no + s] = beam_mix(hash[co + i], c); phash[no + s] = hash[co + i]; node[no + s] = 1 + t * B + s;
+          last[no + s] = c; lms[no + s] = extlm[e]; len[no + s] = len[co + i] + 1;
+          bp[(size_t)t * B + s] = make_int2(node[co + i], c);
         }
       }
+    }
     if (t + 1 < T && tx < RW) rowbuf[((t + 1) & 1) * RW + tx] = nxt;
-    nb = min(B, (int)(total & 0xFFFF) + min((int)(total >> 16), need));
+    nb = kept;
     cur ^= 1;
     __syncthreads();
   }
 
   // tail: scores, their order (ties keep the beam's), the token sequences from the back-pointers
-  cb_sync_global();
+  block_sync_global();
   const int co = cur * B;
   double sc = -INFINITY;
   if (tx < nb) {
@@ -410,36 +307,12 @@ __global__ __launch_bounds__(kThreads) void ctcb_search(const CbParams p) {
     if (p.has_lm && p.use_eos) {
       double cost;
       int hn;
-      cb_lm_arc(p, lms[co + tx], p.lm_eos, cost, hn);
+      ngram_arc(p.lm, lms[co + tx], p.lm_eos, cost, hn);
       sc += -(p.lm_weight * cost);
     }
   }
-  if (tx < B) stay_pb[tx] = sc;
-  __syncthreads();
-  if (tx < B) {
-    int rank = 0;
-    for (int i = 0; i < B; ++i) {
-      const double o = stay_pb[i];
-      rank += (o > sc || (o == sc && i < tx)) ? 1 : 0;
-    }
-    const int len_j = tx < nb ? len[co + tx] : 0;
-    p.out_scores[(size_t)n * B + rank] = sc;
-    p.out_lens[(size_t)n * B + rank] = tx < nb ? len_j : -1;
-    src[rank] = len_j;
-    int32_t* o = p.out_tokens + ((size_t)n * B + rank) * p.Tpad;
-    int nd = tx < nb ? node[co + tx] : 0;
-    for (int d = len_j - 1; d >= 0 && nd > 0; --d) {
-      const int2 e = bp[nd - 1];
-      o[d] = e.y;
-      nd = e.x;
-    }
-  }
   if (tx == 0) p.out_status[n] = numeric ? PK2_CTC_NUMERIC : PK2_CTC_OK;
-  __syncthreads();
-  for (int64_t i = tx; i < (int64_t)B * p.Tpad; i += kThreads) {
-    const int r = (int)(i / p.Tpad), d = (int)(i - (int64_t)r * p.Tpad);
-    if (d >= src[r]) p.out_tokens[(size_t)n * B * p.Tpad + i] = -1;
-  }
+  beam_tail(sc, nb, B, len + co, node + co, bp, p.Tpad, n, stay_pb, src, p.out_tokens, p.out_lens, p.out_scores, tx);
 }
 
 size_t cb_rows_bytes(int64_t N, int64_t T, int K) { return align_up((size_t)(N * T) * cb_row_words(K) * 4, 256); }
@@ -492,8 +365,7 @@ extern "C" int pk2_ctc_beam_search(const int32_t* lengths, const int32_t* length
   p.lengths = lengths_dev; p.x = logits; p.ss = seq_stride; p.fs = frame_stride;
   p.Tpad = T; p.P = num_classes; p.blank = blank; p.B = beam; p.K = std::min(top_tokens, num_classes - 1);
   if (lm) {
-    p.n_word = lm->d_word; p.n_child = lm->d_child; p.n_bo = lm->d_bo; p.n_next = lm->d_next; p.n_cost = lm->d_cost;
-    p.n_backoff = lm->d_backoff; p.lm_start = lm->start; p.lm_eos = lm->eos; p.has_lm = 1; p.use_eos = lm_eos ? 1 : 0;
+    p.lm = ngram_trie(*lm); p.lm_start = lm->start; p.lm_eos = lm->eos; p.has_lm = 1; p.use_eos = lm_eos ? 1 : 0;
     p.lm_ids = lm_ids; p.lm_weight = lm_weight; p.bonus = insertion_bonus;
   }
   p.rows = static_cast<float*>(workspace);

@@ -23,7 +23,7 @@
 
 namespace pk2 {
 
-__device__ __forceinline__ double log_add(double a, double b) {
+__device__ __forceinline__ double fb_log_add(double a, double b) {
   const double m = fmax(a, b);
   if (m == -INFINITY) return m;
   return m + log1p(exp(-fabs(a - b)));
@@ -34,7 +34,7 @@ __device__ __forceinline__ void atomic_log_add(double* addr, double v) {
   unsigned long long old = ldc(a), assumed;
   do {
     assumed = old;
-    const double nv = log_add(__longlong_as_double((long long)assumed), v);
+    const double nv = fb_log_add(__longlong_as_double((long long)assumed), v);
     old = atomicCAS(a, assumed, (unsigned long long)__double_as_longlong(nv));
   } while (old != assumed);
 }
@@ -88,7 +88,7 @@ __device__ __forceinline__ void lds_log_add(double* addr, double v) {
   unsigned long long old = *a, assumed;
   do {
     assumed = old;
-    const double nv = log_add(__longlong_as_double((long long)assumed), v);
+    const double nv = fb_log_add(__longlong_as_double((long long)assumed), v);
     old = atomicCAS(a, assumed, (unsigned long long)__double_as_longlong(nv));
   } while (old != assumed);
 }

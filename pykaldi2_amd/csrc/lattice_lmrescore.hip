@@ -36,8 +36,7 @@ struct LrParams {
   const int64_t *state_off, *arc_off, *level_off_off, *word_off_off;
   const int32_t *src, *dst, *word, *in_off, *level_off, *word_ids, *lm_word;
   const float *graph, *acoustic;
-  const int32_t *n_word, *n_child, *n_bo, *n_next;
-  const float *n_cost, *n_backoff;
+  NgramTrie lm;
   int32_t lm_start, lm_eos, first;
   double scale, expand;
   unsigned long long* work;
@@ -54,35 +53,9 @@ __host__ __device__ inline int64_t lr_work_words(int64_t S, int64_t A, int64_t c
   return 2 * capA + (S + 1 + A + 1 + 3 * capA + 1) / 2;
 }
 
-__device__ __forceinline__ unsigned long long lr_shfl_xor64(unsigned long long v, int m) {
-  const unsigned lo = __shfl_xor((unsigned)v, m, 64), hi = __shfl_xor((unsigned)(v >> 32), m, 64);
-  return ((unsigned long long)hi << 32) | lo;
-}
-
 __device__ __forceinline__ long long lr_shfl_up64(long long v, int o) {
   const unsigned lo = __shfl_up((unsigned)v, o, 64), hi = __shfl_up((unsigned)((unsigned long long)v >> 32), o, 64);
   return (long long)(((unsigned long long)hi << 32) | lo);
-}
-
-// cost and next state of word w from LM state h (arc(h, w)); false if w has no unigram
-__device__ __forceinline__ bool lr_lm_arc(const LrParams& p, int h, int w, double& cost, int& next) {
-  double acc = 0.0;
-  int node = h;
-#pragma nounroll
-  for (int it = 0; it <= PK2_NGRAM_MAX_ORDER; ++it) {
-    const int end = p.n_child[node + 1];
-    int lo = p.n_child[node], hi = end;
-    while (lo < hi) {
-      const int mid = (lo + hi) >> 1;
-      if (p.n_word[mid] < w) lo = mid + 1; else hi = mid;
-    }
-    if (lo < end && p.n_word[lo] == w) { cost = acc + (double)p.n_cost[lo]; next = p.n_next[lo]; return true; }
-    if (node == 0) break;
-    acc += (double)p.n_backoff[node];
-    node = p.n_bo[node];
-  }
-  cost = 0.0; next = 0;
-  return false;
 }
 
 // Inclusive scan in place of v[0..n) (values >= 0) on top of `carry`, by the whole workgroup; values beyond int32 are
@@ -231,10 +204,10 @@ __global__ void __launch_bounds__(kLrThreads) lr_kernel(LrParams p) {
       double cost = 0.0;
       int hn = h;
       if (last) {
-        if (!lr_lm_arc(p, h, p.lm_eos, cost, hn)) fail = 1;
+        if (!ngram_arc(p.lm, h, p.lm_eos, cost, hn)) fail = 1;
         hn = 0;
       } else if (w != 0) {
-        if (!lr_lm_arc(p, h, L.lm_word[w], cost, hn)) fail = 1;
+        if (!ngram_arc(p.lm, h, L.lm_word[w], cost, hn)) fail = 1;
       }
       L.tmp[x].g = (float)((double)L.graph[a] + p.scale * cost);
       L.tmp[x].hn = hn;
@@ -256,7 +229,7 @@ __global__ void __launch_bounds__(kLrThreads) lr_kernel(LrParams p) {
         for (int k = 2; k <= 64; k <<= 1) {
 #pragma nounroll
           for (int j = k >> 1; j > 0; j >>= 1) {
-            const unsigned long long other = lr_shfl_xor64(key, j);
+            const unsigned long long other = shfl_xor64(key, j);
             const bool keep_min = ((lane & j) == 0) == ((lane & k) == 0);
             key = (other < key) == keep_min ? other : key;
           }
@@ -434,8 +407,7 @@ extern "C" int pk2_wordlat_lmrescore(const void* h_lat, int32_t first, int32_t c
   p.state_off = h->d_state_off; p.arc_off = h->d_arc_off; p.level_off_off = h->d_level_off_off; p.word_off_off = h->d_word_off_off;
   p.src = h->d_src; p.dst = h->d_dst; p.word = h->d_word; p.in_off = h->d_in_off; p.level_off = h->d_level_off;
   p.word_ids = h->d_word_ids; p.lm_word = lm_word; p.graph = h->d_graph; p.acoustic = h->d_acoustic;
-  p.n_word = lm->d_word; p.n_child = lm->d_child; p.n_bo = lm->d_bo; p.n_next = lm->d_next; p.n_cost = lm->d_cost;
-  p.n_backoff = lm->d_backoff; p.lm_start = lm->start; p.lm_eos = lm->eos; p.first = first; p.scale = scale; p.expand = expand;
+  p.lm = ngram_trie(*lm); p.lm_start = lm->start; p.lm_eos = lm->eos; p.first = first; p.scale = scale; p.expand = expand;
   p.work = static_cast<unsigned long long*>(work);
   p.o_nstates = out_nstates; p.o_narcs = out_narcs; p.status = status; p.states = states; p.arcs = arcs;
   hipLaunchKernelGGL(lr_kernel, dim3(count), dim3(kLrThreads), 0, static_cast<hipStream_t>(stream), p);

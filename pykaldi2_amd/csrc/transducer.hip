@@ -210,12 +210,6 @@ __global__ __launch_bounds__(kMmThreads) void td_product(const int32_t* __restri
   }
 }
 
-__device__ __forceinline__ double td_logadd(double a, double b) {
-  const double m = fmax(a, b);
-  if (!(m > -INFINITY)) return m;      // both -inf (or NaN, which then shows in log p)
-  return m + log1p(exp(-fabs(a - b)));
-}
-
 // ---- td_lattice: grid (2, N), blockDim = the batch's largest U + 1 rounded up to whole waves (a lane's arithmetic does not
 // depend on it).  blockIdx.x = 0: alpha, loss and status; 1: beta.
 __global__ __launch_bounds__(1024) void td_lattice(const int32_t* __restrict__ pk, float* __restrict__ ws, double* __restrict__ loss,
@@ -246,7 +240,7 @@ __global__ __launch_bounds__(1024) void td_lattice(const int32_t* __restrict__ p
       double left = __shfl_up(right, 1, 64);
       if (lane == 0) left = (wave > 0 && dg > 0) ? bnd[(dg - 1) & 1][wave - 1] : NEG;
       if (u < U1 && t >= 0 && t < T) {
-        a = dg == 0 ? 0.0 : td_logadd(up, left);
+        a = dg == 0 ? 0.0 : pk2::log_add(up, left);
         al[(size_t)t * U1 + u] = a;
         up = a + (double)yc;
         right = u < U ? a + (double)xc : NEG;
@@ -275,7 +269,7 @@ __global__ __launch_bounds__(1024) void td_lattice(const int32_t* __restrict__ p
       if (lane == 63) right = (wave + 1 < nw && dg < D - 1) ? bnd[(dg + 1) & 1][wave + 1] : NEG;
       if (u < U1 && t >= 0 && t < T) {
         const double below = t == T - 1 ? (u == U ? 0.0 : NEG) : b;      // beta[t+1, u]
-        b = td_logadd((double)yc + below, u < U ? (double)xc + right : NEG);
+        b = pk2::log_add((double)yc + below, u < U ? (double)xc + right : NEG);
         be[(size_t)t * U1 + u] = b;
       } else {
         b = NEG;

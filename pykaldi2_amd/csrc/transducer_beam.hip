@@ -27,28 +27,30 @@
 //   2 row pass, a wave per hypothesis: online max and sum, lp(blank), and unless r = R, K rounds of a wave arg-max on
 //     the key (ordered logit bits, ~column) below the last winner (ctcb_rows' scheme)                              [1]
 //   3 a wave per hypothesis looks its prefix up in Out; every thread forms its candidate (slot i, rank k)          [1]
-//   4 wave 0 merges or appends the blank moves, while all threads run the radix select of the beam-th largest
-//     candidate on the ordered bits of the doubles, 8 bits a pass from the top, LDS integer histogram       [2 a pass]
-//   5 one packed scan (greater | equal) in candidate order gives every survivor its slot in the other beam buffer;
-//     a new prefix writes (parent node, token) to the back-pointer table                                           [2]
+//   4 wave 0 merges or appends the blank moves, while all threads run tb_select, one candidate a thread: the radix
+//     select of the beam-th largest candidate on the ordered bits of the doubles, 8 bits a pass from the top, LDS
+//     integer histogram (ctc_beam.hip's beam_select with one candidate a thread measured 0.4 to 0.8 % slower here
+//     on the additive head, profiles/beam_shared_ab.txt: this search keeps its own)                         [2 a pass]
+//     then one packed scan (greater | equal) in candidate order gives every survivor its slot                      [1]
+//   5 the survivors go to the other beam buffer; a new prefix writes (parent node, token) to the back-pointer table [1]
 // The frame ends with the same select over Out (at most beam (R + 1) <= 1024 entries, one per thread).  The beam lives in
 // LDS, double-buffered, as arrays over the slots: score, hash, length, trie node, last token (a parent's hash is not kept:
-// only Out merges, and by the prefix's own identity).  The tail ranks the finals by counting and walks the back-pointers.
+// only Out merges, and by the prefix's own identity).  The tail is beam_tail (beam_dev.h): it ranks the finals by counting
+// and walks the back-pointers.
 #include <algorithm>
 #include <cmath>
 
-#include "common.h"
+#include "beam_dev.h"
 
 #pragma clang fp contract(off)
 
 namespace pk2 {
 namespace {
 
-typedef unsigned long long u64;
 typedef float tb_f16 __attribute__((ext_vector_type(16)));
 
-constexpr int kThreads = 1024;
-constexpr int kWaves = kThreads / 64;
+constexpr int kThreads = kBeamThreads;
+constexpr int kWaves = kBeamWaves;
 constexpr int kTile = 32;           // rows and columns of the MFMA tile
 constexpr int kHPad = 4;            // floats behind a row of H
 static_assert(PK2_TRANSDUCER_BEAM_MAX == kTile, "a round's hypotheses are the rows of one MFMA tile");
@@ -85,54 +87,10 @@ __host__ __device__ inline TbLds tb_lds(size_t B, size_t K, size_t R, size_t Jp)
   return l;
 }
 
-__device__ __forceinline__ u64 tb_shfl_xor64(u64 v, int m) {
-  const unsigned lo = __shfl_xor((unsigned)v, m, 64), hi = __shfl_xor((unsigned)(v >> 32), m, 64);
-  return ((u64)hi << 32) | lo;
-}
-__device__ __forceinline__ u64 tb_wave_max64(u64 v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) { const u64 w = tb_shfl_xor64(v, o); v = w > v ? w : v; }
-  return v;
-}
 __device__ __forceinline__ int tb_wave_max_int(int v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
   return v;
-}
-__device__ __forceinline__ unsigned tb_wave_scan(unsigned v, int lane) {      // inclusive
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) { const unsigned w = __shfl_up(v, o, 64); if (lane >= o) v += w; }
-  return v;
-}
-
-// (logit, column) as one key: a larger logit is a larger key, and of equal logits the lower column
-__device__ __forceinline__ u64 tb_key(float v, int col) {
-  const unsigned b = __float_as_uint(v), u = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-  return ((u64)u << 32) | (0xFFFFFFFFu - (unsigned)col);
-}
-// a double's bits in the order of the doubles
-__device__ __forceinline__ u64 tb_ordered(double v) {
-  const u64 b = (u64)__double_as_longlong(v);
-  return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-__device__ __forceinline__ double tb_logadd(double a, double b) {
-  const double m = fmax(a, b), n = fmin(a, b);
-  if (m == -INFINITY) return m;
-  return m + log1p(exp(n - m));
-}
-
-constexpr u64 kHashEmpty = 0x243F6A8885A308D3ull;
-__device__ __forceinline__ u64 tb_mix(u64 h, int c) {      // the hash of prefix + c from the hash of the prefix (splitmix64's finish)
-  u64 z = h ^ ((u64)(unsigned)(c + 1) * 0x9E3779B97F4A7C15ull);
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
-
-__device__ __forceinline__ void tb_sync_global() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-  __syncthreads();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
 }
 
 // The slot of this thread's candidate among the `want` largest keys of the `count` valid ones, survivors in thread order, or -1;
@@ -149,7 +107,7 @@ __device__ __forceinline__ int tb_select(bool valid, u64 key, int count, int wan
       int h[4], s = 0;
 #pragma unroll
       for (int r = 0; r < 4; ++r) { h[r] = hist[255 - 4 * lane - r]; hist[255 - 4 * lane - r] = 0; s += h[r]; }
-      const int incl = (int)tb_wave_scan((unsigned)s, lane);
+      const int incl = (int)wave_scan((unsigned)s, lane);
       int r = need - (incl - s);
       if (r >= 1 && r <= s) {      // exactly one lane
         bool found = false;
@@ -169,7 +127,7 @@ __device__ __forceinline__ int tb_select(bool valid, u64 key, int count, int wan
   }
   const u64 tp = prefix >> fshift, hp = key >> fshift;
   const unsigned cnt = !valid ? 0u : (hp > tp ? 1u : (hp == tp ? 0x10000u : 0u));
-  const unsigned incl = tb_wave_scan(cnt, lane);
+  const unsigned incl = wave_scan(cnt, lane);
   if (lane == 63) wtot[wave] = incl;
   __syncthreads();
   unsigned before = incl - cnt, total = 0;
@@ -274,7 +232,7 @@ __global__ __launch_bounds__(kThreads) void tb_search(const TbParams p) {
             if (row < nb) zl[(size_t)row * p.Vs + tile * kTile + cl] = acc[v];
           }
         }
-        tb_sync_global();
+        block_sync_global();
       }
       // 2: the row pass
       for (int i = wave; i < nb; i += kWaves) {
@@ -302,12 +260,12 @@ __global__ __launch_bounds__(kThreads) void tb_search(const TbParams p) {
         for (int k = 0; k < K; ++k) {
           u64 best = 0;
           for (int v = lane; v < V; v += 64) {
-            const u64 key = tb_key(z(v), v);
+            const u64 key = beam_key(z(v), v);
             if (v != p.blank && key < prev && key > best) best = key;
           }
-          best = tb_wave_max64(best);
+          best = wave_max64(best);
           prev = best;
-          int col = (int)(0xFFFFFFFFu - (unsigned)best);
+          int col = beam_key_col(best);
           if (col < 0 || col >= V) col = p.blank;      // (K <= V - 1 columns exist: not taken)
           if (lane == 0) {
             tokc[i * K + k] = col;
@@ -339,7 +297,7 @@ __global__ __launch_bounds__(kThreads) void tb_search(const TbParams p) {
         const double v = score[co + lane] + (double)lpb[lane];
         const int mt = match[lane];
         if (mt >= 0) {
-          o_score[mt] = tb_logadd(o_score[mt], v);
+          o_score[mt] = log_add(o_score[mt], v);
         } else {
           const int e = nout + __popcll(freshmask & ((1ull << lane) - 1ull));
           o_score[e] = v; o_hash[e] = hash[co + lane]; o_node[e] = node[co + lane]; o_last[e] = last[co + lane]; o_len[e] = len[co + lane];
@@ -349,10 +307,10 @@ __global__ __launch_bounds__(kThreads) void tb_search(const TbParams p) {
       if (r == R) break;
       // 5: the beam-th largest candidate, the survivors into the other buffer
       int kept;
-      const int s = tb_select(valid, tb_ordered(cs), ncand, B, hist, wtot, sel, lane, wave, kept);
+      const int s = tb_select(valid, beam_ordered(cs), ncand, B, hist, wtot, sel, lane, wave, kept);
       if (s >= 0) {
         const int c = tokc[tx], nd = 1 + (t * R + r) * B + s;
-        score[no + s] = cs; hash[no + s] = tb_mix(hash[co + ci], c); node[no + s] = nd; last[no + s] = c; len[no + s] = len[co + ci] + 1;
+        score[no + s] = cs; hash[no + s] = beam_mix(hash[co + ci], c); node[no + s] = nd; last[no + s] = c; len[no + s] = len[co + ci] + 1;
         bp[nd - 1] = make_int2(node[co + ci], c);
       }
       nb = kept;
@@ -366,7 +324,7 @@ __global__ __launch_bounds__(kThreads) void tb_search(const TbParams p) {
       const int no = (cur ^ 1) * B;
       const bool valid = tx < nout;
       int kept;
-      const int s = tb_select(valid, tb_ordered(valid ? o_score[tx] : 0.0), nout, B, hist, wtot, sel, lane, wave, kept);
+      const int s = tb_select(valid, beam_ordered(valid ? o_score[tx] : 0.0), nout, B, hist, wtot, sel, lane, wave, kept);
       if (s >= 0) {
         score[no + s] = o_score[tx]; hash[no + s] = o_hash[tx]; node[no + s] = o_node[tx]; last[no + s] = o_last[tx]; len[no + s] = o_len[tx];
       }
@@ -379,36 +337,12 @@ __global__ __launch_bounds__(kThreads) void tb_search(const TbParams p) {
   }
 
   // tail: the order of the scores (ties keep the beam's), the token sequences from the back-pointers
-  tb_sync_global();
-  const int co = cur * B, TR = p.Tpad * R;
+  block_sync_global();
+  const int co = cur * B;
   if (numeric) nb = 0;
   const double sc = tx < nb ? score[co + tx] : -INFINITY;
-  if (tx < B) o_score[tx] = sc;
-  __syncthreads();
-  if (tx < B) {
-    int rank = 0;
-    for (int i = 0; i < B; ++i) {
-      const double o = o_score[i];
-      rank += (o > sc || (o == sc && i < tx)) ? 1 : 0;
-    }
-    const int len_j = tx < nb ? len[co + tx] : 0;
-    p.out_scores[(size_t)n * B + rank] = sc;
-    p.out_lens[(size_t)n * B + rank] = tx < nb ? len_j : -1;
-    o_len[rank] = len_j;
-    int32_t* o = p.out_tokens + ((size_t)n * B + rank) * TR;
-    int nd = tx < nb ? node[co + tx] : 0;
-    for (int d = len_j - 1; d >= 0 && nd > 0; --d) {
-      const int2 e = bp[nd - 1];
-      o[d] = e.y;
-      nd = e.x;
-    }
-  }
   if (tx == 0) p.out_status[n] = numeric ? PK2_TRANSDUCER_NUMERIC : PK2_TRANSDUCER_OK;
-  __syncthreads();
-  for (int64_t i = tx; i < (int64_t)B * TR; i += kThreads) {
-    const int r = (int)(i / TR), d = (int)(i - (int64_t)r * TR);
-    if (d >= o_len[r]) p.out_tokens[(size_t)n * B * TR + i] = -1;
-  }
+  beam_tail(sc, nb, B, len + co, node + co, bp, p.Tpad * R, n, o_score, o_len, p.out_tokens, p.out_lens, p.out_scores, tx);
 }
 
 size_t tb_logit_bytes(int64_t N, int V, int J) { return J > 0 ? align_up((size_t)N * kTile * align_up((size_t)V, kTile) * 4, 256) : 0; }

@@ -180,12 +180,6 @@ __global__ __launch_bounds__(256) void tp_rows(const int32_t* __restrict__ pk, T
   }
 }
 
-__device__ __forceinline__ double tp_logadd(double a, double b) {
-  const double m = fmax(a, b);
-  if (!(m > -INFINITY)) return m;      // both -inf (or NaN, which then shows in log p)
-  return m + log1p(exp(-fabs(a - b)));
-}
-
 // begin[0] = 0, steps in [0, S-1], begin[T-1] + S - 1 >= U, nothing negative: by the whole wave.
 __device__ __forceinline__ bool tp_band_ok(const int32_t* bg, int T, int U, int S, int lane) {
   bool bad = false;
@@ -244,7 +238,7 @@ __global__ __launch_bounds__(64) void tp_lattice(const int32_t* __restrict__ pk,
       pubt = -2;
       if (diag == dg) {
         const int u = bt + s;
-        const double a = (t == 0 && u == 0) ? 0.0 : tp_logadd(nbt == t - 1 ? nb : NEG, right);
+        const double a = (t == 0 && u == 0) ? 0.0 : pk2::log_add(nbt == t - 1 ? nb : NEG, right);
         al[(size_t)t * S + s] = a;
         pub = a + (double)yn;
         pubt = t;
@@ -290,7 +284,7 @@ __global__ __launch_bounds__(64) void tp_lattice(const int32_t* __restrict__ pk,
       if (diag == dg) {
         const int u = bt + s;
         const double below = t == T - 1 ? (u == U ? 0.0 : NEG) : (nbt == t + 1 ? nb : NEG);
-        const double b = tp_logadd((double)yn + below, (double)xn + own);
+        const double b = pk2::log_add((double)yn + below, (double)xn + own);
         be[(size_t)t * S + s] = b;
         pub = b;
         pubt = t;

@@ -14,7 +14,7 @@ range an utterance may come back with status 3 (CTC_NUMERIC): loss 0 and gradien
 import numpy as np
 import torch
 
-from . import _lib
+from . import _beam, _lib
 from .chain import _workspace
 
 CTC_OK, CTC_NO_PATH, CTC_NUMERIC = 0, 2, 3      # PK2_CTC_OK / PK2_CTC_NO_PATH / PK2_CTC_NUMERIC
@@ -94,10 +94,8 @@ def _beam_args(lengths, N, T, P, blank, beam, top_tokens, lm, lm_ids):
         raise ValueError("ctc: %d lengths for %d utterances of at most %d frames" % (lengths.shape[0], N, T))
     if N < 1 or P < 2 or not 0 <= blank < P:
         raise ValueError("ctc: %d utterances, blank %d of %d columns" % (N, blank, P))
-    if isinstance(beam, bool) or int(beam) != beam or not 1 <= beam <= MAX_BEAM:
-        raise ValueError("ctc: beam %r outside 1..%d" % (beam, MAX_BEAM))
-    if isinstance(top_tokens, bool) or int(top_tokens) != top_tokens or not 1 <= top_tokens <= MAX_TOP_TOKENS:
-        raise ValueError("ctc: top_tokens %r outside 1..%d" % (top_tokens, MAX_TOP_TOKENS))
+    _beam.limit(beam, MAX_BEAM, "beam", "ctc")
+    _beam.limit(top_tokens, MAX_TOP_TOKENS, "top_tokens", "ctc")
     if lm is None:
         if lm_ids is not None:
             raise ValueError("ctc: lm_ids without an LM")
@@ -151,10 +149,7 @@ def beam_search_raw(logits, lengths, blank=0, beam=16, top_tokens=16, lm=None, l
 def beam_search(logits, lengths, nbest=1, **kw):
     """beam_search_raw and ONE copy to the host: per utterance a list of at most nbest (token list, score), best first."""
     tokens, lens, scores, _ = beam_search_raw(logits, lengths, **kw)
-    N, B, T = tokens.shape
-    flat = torch.cat([tokens.reshape(N, -1).double(), lens.double(), scores], dim=1).cpu().numpy()      # (int32 is exact in float64)
-    tok, ln, sc = flat[:, :B * T].reshape(N, B, T).astype(np.int64), flat[:, B * T:B * T + B].astype(np.int64), flat[:, B * T + B:]
-    return [[(tok[n, r, :ln[n, r]].tolist(), float(sc[n, r])) for r in range(min(nbest, B)) if ln[n, r] >= 0] for n in range(N)]
+    return _beam.nbest_lists(tokens, lens, scores, nbest)
 
 
 def greedy_decode(logits, lengths, blank=0, time_major=False):

@@ -30,7 +30,7 @@ Beam search for either head (csrc/transducer_beam.hip), one laun
 import numpy as np
 import torch
 
-from . import _lib
+from . import _beam, _lib
 from .chain import _workspace
 
 TRANSDUCER_OK, TRANSDUCER_NUMERIC = 0, 3      # PK2_TRANSDUCER_OK / PK2_TRANSDUCER_NUMERIC
@@ -285,12 +285,6 @@ def greedy_decode(am, lengths, table, blank=0, max_symbols=8, time_major=False):
     return [flat[n, :flat[n, -1]].tolist() for n in range(flat.shape[0])]
 
 
-def _limit(value, hi, name):
-    if isinstance(value, bool) or int(value) != value or not 1 <= value <= hi:
-        raise ValueError("transducer: %s %r outside 1..%d" % (name, value, hi))
-    return int(value)
-
-
 def beam_search_raw(am_or_enc, lengths, table_or_pred, blank=0, beam=4, top_tokens=8, max_symbols=2, joiner=None, time_major=False):
     """Transducer beam search with a stateless predictor of context 1 on the device (csrc/transducer_beam.hip):
     one launch, nothing read back.  Time-synchronous; per frame at most max_symbols (1..31) rounds in which every hypothesis
@@ -329,8 +323,9 @@ def beam_search_raw(am_or_enc, lengths, table_or_pred, blank=0, beam=4, top_toke
             raise ValueError("transducer: w_out %s / b_out %s do not go with enc %s and pred %s"
                              % (tuple(w.shape), tuple(b.shape), tuple(am_or_enc.shape), tuple(rows.shape)))
         w, b = w.detach(), b.detach().contiguous()
-    beam, top_tokens = _limit(beam, MAX_BEAM, "beam"), _limit(top_tokens, MAX_BEAM_TOKENS, "top_tokens")
-    max_symbols = _limit(max_symbols, MAX_BEAM_SYMBOLS, "max_symbols")
+    beam = _beam.limit(beam, MAX_BEAM, "beam", "transducer")
+    top_tokens = _beam.limit(top_tokens, MAX_BEAM_TOKENS, "top_tokens", "transducer")
+    max_symbols = _beam.limit(max_symbols, MAX_BEAM_SYMBOLS, "max_symbols", "transducer")
     lengths = np.asarray(lengths, dtype=np.int64).reshape(-1)
     if N < 1 or lengths.shape[0] != N or lengths.min() < 0 or lengths.max() > T:
         raise ValueError("transducer: %d lengths for %d utterances of at most %d frames" % (lengths.shape[0], N, T))
@@ -358,7 +353,4 @@ def beam_search_raw(am_or_enc, lengths, table_or_pred, blank=0, beam=4, top_toke
 def beam_search(am_or_enc, lengths, table_or_pred, nbest=1, **kw):
     """beam_search_raw and ONE copy to the host: per utterance a list of at most nbest (token list, score), best first."""
     tokens, lens, scores, _ = beam_search_raw(am_or_enc, lengths, table_or_pred, **kw)
-    N, B, T = tokens.shape
-    flat = torch.cat([tokens.reshape(N, -1).double(), lens.double(), scores], dim=1).cpu().numpy()      # (int32 is exact in float64)
-    tok, ln, sc = flat[:, :B * T].reshape(N, B, T).astype(np.int64), flat[:, B * T:B * T + B].astype(np.int64), flat[:, B * T + B:]
-    return [[(tok[n, r, :ln[n, r]].tolist(), float(sc[n, r])) for r in range(min(nbest, B)) if ln[n, r] >= 0] for n in range(N)]
+    return _beam.nbest_lists(tokens, lens, scores, nbest)
